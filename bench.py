@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- edited images/sec of the direct-inversion + Prompt-to-Prompt hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                           (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 One "step" = one complete `P2PEditor("directinversion+p2p", ...)` edit of one 512x512 image per rank, FAITHFUL schedule of the
 reference (models/p2p_editor.py:415-479): VAE encode, the discarded VAE decode, 50 B=1 DDIM-inversion UNet calls, 50 B=4
@@ -13,7 +14,14 @@ Weights are seeded-synthetic SD-1.x (no checkpoint exists offline), input image 
 Multi-GPU: images are independent -> each rank edits its own image (weak scaling, no data-path collective); the only
 collective is the start-up RCCL broadcast of the packed weight arena from rank 0 (untimed set-up).
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps and prints the headline line.  --dump-outputs DIR writes, after the timed steps,
+what the last timed step returned to its caller (the 4-panel uint8 image, as float32) to DIR/panel.npy (DIR/panel_rank<r>.npy on
+rank r > 0); inputs and weights are seeded, so the same arguments give the same inputs in every run.
+
+Extra objects in the JSON line, measured only with --full (outside the timed region, but for clock's side-thread sampler):
+  clock         an MFMA-only clock probe before and after the timed region, the part's sclk / power / temperature during it.
+  phases, pruned_schedule, null_text, batched, pipelined, in_flight   the same edit timed loop by loop, and the other schedules /
+                methods / launch shapes (--no-extras skips all but phases).
   roofline      dominant kernel class (the MFMA implicit-GEMM conv/linear kernel): algorithmic FLOPs / summed per-launch HIP-event
                 durations, measured by bracketing every launch of one full edit with events on the library's stream.
   cpu_baseline  the CPU oracle (a port of the reference's fp32 PyTorch path, oracle/) timed on this host: one B=1 and one B=4
@@ -102,6 +110,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: clock, roofline, phases, the extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's panel to DIR/panel.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the pruned-schedule and batched extras (short profiling runs)")
     ap.add_argument("--dry-run", action="store_true", help="process-launch / rendezvous plumbing only, on CPU with gloo (tests)")
@@ -171,7 +182,7 @@ def main():
 
     # synthetic inputs are generated before the timed region (the hot path starts at the decoded RGB image, as in the reference)
     n_pre = args.warmup + args.steps
-    images = {i: synthetic_image(1000 * rank + i) for i in list(range(n_pre)) + [999]}
+    images = {i: synthetic_image(1000 * rank + i) for i in list(range(n_pre)) + ([999] if args.full else [])}
 
     def one_edit(i):
         img = images[i]
@@ -200,8 +211,8 @@ def main():
         except Exception as e:      # the probe must never take the headline line down
             return {"error": "%s: %s" % (type(e).__name__, e)}
 
-    clock = {"mfma_probe_before": mfma_probe()} if rank == 0 else None
-    sampler = ClockSampler(local_rank) if rank == 0 else None
+    clock = {"mfma_probe_before": mfma_probe()} if rank == 0 and args.full else None
+    sampler = ClockSampler(local_rank) if rank == 0 and args.full else None
     barrier()
     eng.reset_counters()
     if sampler is not None:
@@ -223,6 +234,9 @@ def main():
         dt = float(tt.item())
     ctr = eng.counters()
     assert panel.size == (2048, 512)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "panel.npy" if rank == 0 else "panel_rank%d.npy" % rank), np.asarray(panel, dtype=np.float32))
 
     def executed_flops(c):
         """algorithmic FLOPs actually executed: forwards that read the text K/V cache do not project the context"""
@@ -235,7 +249,7 @@ def main():
 
     # per-kernel-class roofline: one more full edit with every launch bracketed by HIP events (rank 0, outside the timed region)
     roofline, classes = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         import csv, tempfile
         dump = os.path.join(tempfile.gettempdir(), "pnpi_bench_launches_%d.csv" % os.getpid())
         os.environ["PNPI_PROFILE_DUMP"] = dump          # one record per launch: class, shape, HIP-event time, kernel template
@@ -318,7 +332,7 @@ def main():
     # the two loops of one more edit timed on their own (rank 0, outside the timed region): the 50 one-row DDIM-inversion forwards and the
     # 50 twelve-row lock-step steps of the dual-branch loop north_star's 40 % target is stated on (models/p2p/p2p_guidance_forward.py:135-173)
     phases = None
-    if rank == 0 and args.schedule == "lockstep":
+    if rank == 0 and args.schedule == "lockstep" and args.full:
         phases = loop_phases(lambda: one_edit(999), 1)
         if phases is not None:      # the names round 4's line used
             phases["one_row_forward_ms"] = phases["inversion_forward_ms"]
@@ -326,7 +340,7 @@ def main():
 
     # extra (never `value`): the pruned-equivalent schedule of SURVEY Note D, FLOPs from the library's counters
     pruned = None
-    if args.schedule == "lockstep" and not args.no_extras:
+    if args.schedule == "lockstep" and args.full and not args.no_extras:
         editor.schedule = "pruned"
         one_edit(999)
         barrier()
@@ -349,7 +363,7 @@ def main():
     # the unconditional embedding (up to 10 Adam iterations, each a recording UNet forward + the reverse walk to the 77 x 768 embedding),
     # then the two guidance passes with the per-step embeddings.  FLOPs are the library's executed counters (backward launches included).
     null_text = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         try:
             ed_nt = P2PEditor(["null-text-inversion+p2p"], "cuda:%d" % local_rank, num_ddim_steps=args.ddim_steps, pipeline=pipe)
             barrier()
@@ -390,7 +404,7 @@ def main():
             null_text = {"error": "%s: %s" % (type(e).__name__, e)}
 
     batched = None
-    if args.batch_images > 1 and args.schedule == "lockstep" and not args.no_extras:
+    if args.batch_images > 1 and args.schedule == "lockstep" and args.full and not args.no_extras:
         nb = args.batch_images
         batch_images = {i: [synthetic_image(5000 + 1000 * rank + nb * i + j) for j in range(nb)] for i in (0, 1)}
 
@@ -452,7 +466,7 @@ def main():
     # extra (never `value`): sweep throughput with the NEXT image's inversion on a second context / HIP stream under this image's
     # lock-step loop (P2PEditor.edit_stream_directinversion); same kernels, same panels
     pipelined = None
-    if args.schedule == "lockstep" and not args.no_extras:
+    if args.schedule == "lockstep" and args.full and not args.no_extras:
         try:
             def items(lo, n):
                 return [(synthetic_image(9000 + 1000 * rank + lo + j), PROMPT_SRC, PROMPT_TGT, (("cat",), ("dog",)), {"words": ("dog",), "values": (2,)})
@@ -480,7 +494,7 @@ def main():
     # extra (never `value`): the headline method with three images in flight (P2PEditor.edit_stream_in_flight: image i on library context
     # i % 3 of this GPU, own HIP stream and worker thread each; same kernels, same panels) -- the sweep mode of run_editing_p2p.py
     in_flight = None
-    if args.schedule == "lockstep" and not args.no_extras:
+    if args.schedule == "lockstep" and args.full and not args.no_extras:
         try:
             nf = 3
             mk = lambda lo, n: [(synthetic_image(12000 + 1000 * rank + lo + j), PROMPT_SRC, PROMPT_TGT, (("cat",), ("dog",)), {"words": ("dog",), "values": (2,)})
@@ -511,10 +525,10 @@ def main():
         # launches of a full run; same kernels, same launch shapes, same 1 : 1 mix of one-row and twelve-row forwards), reduced by
         # tools/pmc_summary.py and committed under profiles/ with the source hash of the kernels they were measured on.  A summary made
         # from other kernel sources than the running tree is NOT reported (traffic: null + the reason).
-        from pnpinversion_amd.build import source_hash
-        prof = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-        sha = source_hash()
         if roofline is not None:
+            from pnpinversion_amd.build import source_hash
+            prof = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
+            sha = source_hash()
             roofline["source_sha16"] = sha
             tag = roofline["kernel"].replace(" ", "")           # igemm_pp_kernel<192,320,1,4,0>
             rounds = ("round6", "round5", "round4")
@@ -554,14 +568,14 @@ def main():
                         roofline["rocprof"] = {"avg_launch_us": us, "calls": int(row["Calls"]),
                                                "achieved": roofline["alg_flop_per_launch"] / us / 1e6,
                                                "frac": roofline["alg_flop_per_launch"] / us / 1e6 / MFMA_PEAK_TFLOPS,
-                                               "source": "profiles/%s_bench_kernel_stats.csv: rocprofv3 --kernel-trace --stats of `bench.py --steps 2 "
+                                               "source": "profiles/%s_bench_kernel_stats.csv: rocprofv3 --kernel-trace --stats of `bench.py --full --steps 2 "
                                                          "--warmup 1 --no-extras --no-cpu-baseline` (faithful edits only; same kernel sources, %s)" % (r, sha)}
                         break
                 break
         # the same fractions against what the matrix pipes of THIS box sustain (information only; `frac` stays against the nominal peak):
         # nominal peak x (MFMA-only probe clock / 2.4 GHz nominal)
         try:
-            ghz = [clock[k]["effective_ghz"] for k in ("mfma_probe_before", "mfma_probe_after") if "effective_ghz" in clock.get(k, {})]
+            ghz = [clock[k]["effective_ghz"] for k in ("mfma_probe_before", "mfma_probe_after") if "effective_ghz" in clock.get(k, {})] if clock else []
             if ghz and roofline is not None:
                 sustained = MFMA_PEAK_TFLOPS * (sum(ghz) / len(ghz)) / 2.4
                 roofline["peak_at_mfma_probe_clock"] = sustained
@@ -587,8 +601,9 @@ def main():
             "bcast_ms": bcast.get("ms"), "bcast_mb": (bcast.get("bytes", 0) / 1e6) if bcast else None,   # the start-up weight broadcast (untimed set-up)
             "whole_path_tflops_per_gpu": per_rank_flops / dt / 1e12,
             "whole_path_mfma_frac": per_rank_flops / dt / 1e12 / MFMA_PEAK_TFLOPS,
-            "roofline": roofline, "phases": phases, "clock": clock,
         }
+        if args.full:
+            out.update(roofline=roofline, phases=phases, clock=clock)
         if pruned is not None:
             out["pruned_schedule"] = pruned
         if batched is not None:
@@ -599,7 +614,7 @@ def main():
             out["in_flight"] = in_flight
         if null_text is not None:
             out["null_text"] = null_text
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (bounded sample, see cpu_baseline)
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (bounded sample, see cpu_baseline)
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out))
     if dist is not None:

@@ -3,6 +3,8 @@ CPU with the seeded synthetic weights.  Run in the build container only:   pytho
 
 Fixtures (the reference has no tests / golden vectors of its own for this path -- SURVEY.md 8c -- so these pin the oracle):
   host_tables.json     get_word_inds / refinement + replacement mappers / alpha schedule / equalizer / LocalBlend selectors
+  host_tables_random.npz   the same tables for 60 seeded random prompt pairs
+  foreign_controllers.npz  the attributes of the reference's own controller objects that the native UNet reads into kernel descriptors
   unet_tiny.npz        my_diffusers UNet2DConditionModel + the reference's hooked attention, TINY16, B=4
   vae_tiny.npz         my_diffusers AutoencoderKL encode mean / decode, TINY16
   unet_sd1.npz         full-width SD-1.x UNet, B=1
@@ -86,6 +88,101 @@ def host_tables():
         out.append(e)
     json.dump(out, open(os.path.join(OUT, "host_tables.json"), "w"))
     print("host_tables.json", len(out))
+
+
+def _np(t):
+    return torch.as_tensor(t).detach().cpu().numpy()
+
+
+def host_tables_random():
+    """60 seeded random prompt pairs (substitutions, insertions, deletions, repeated words, different lengths) through the
+    reference's seq_aligner / get_word_inds / get_time_words_attention_alpha / get_equalizer / LocalBlend.  Keys "<case>/<table>"."""
+    ref_shim.install()
+    from models.p2p import seq_aligner
+    from models.p2p.attention_control import LocalBlend, get_equalizer
+    from utils.utils import get_time_words_attention_alpha, get_word_inds
+    tok = WordTokenizer()
+    vocab = "a the cat dog sitting on wooden red chair photo of mountain snowy watercolor big small tree and with elephant walking".split()
+    rng = np.random.default_rng(1234)
+    out = {}
+    for case in range(60):
+        src = [vocab[i] for i in rng.integers(0, len(vocab), rng.integers(3, 12))]
+        tgt = list(src)
+        for _ in range(rng.integers(1, 4)):                      # 1-3 edits
+            op, pos = rng.integers(0, 3), int(rng.integers(0, len(tgt)))
+            w = vocab[int(rng.integers(0, len(vocab)))]
+            if op == 0:
+                tgt[pos] = w
+            elif op == 1:
+                tgt.insert(pos, w)
+            elif len(tgt) > 2:
+                del tgt[pos]
+        ps, pt = " ".join(src), " ".join(tgt)
+        w0, w1 = src[int(rng.integers(0, len(src)))], tgt[int(rng.integers(0, len(tgt)))]
+        e = {"src": ps, "tgt": pt, "w0": w0, "w1": w1}
+        m, a = seq_aligner.get_refinement_mapper([ps, pt], tok)
+        e["refine_mapper"], e["refine_alphas"] = _np(m), _np(a)
+        if len(src) == len(tgt):
+            e["replace_mapper"] = _np(seq_aligner.get_replacement_mapper([ps, pt], tok))
+        e["word_inds_src"] = get_word_inds(ps, w0, tok)
+        for i, (steps, cr) in enumerate(((50, {"default_": 0.4}), (7, {"default_": 0.8, w1: (0.1, 0.5)}))):
+            e["cross_alpha_%d" % i] = _np(get_time_words_attention_alpha([ps, pt], steps, dict(cr), tok))
+        e["equalizer"] = _np(get_equalizer(pt, (w1,), (2.5,), tokenizer=tok))
+        with ref_shim.cuda_to_cpu():
+            lb = LocalBlend([ps, pt], ((w0,), (w1,)), tokenizer=tok, num_ddim_steps=50)
+        e["lb_alpha"], e["lb_start"] = _np(lb.alpha_layers.reshape(-1)), lb.start_blend
+        out.update({"%02d/%s" % (case, k): np.asarray(v) for k, v in e.items()})
+    np.savez_compressed(os.path.join(OUT, "host_tables_random.npz"), **out)
+    print("host_tables_random.npz", len(out))
+
+
+def foreign_controllers():
+    """The attributes ForeignControllerAdapter reads off the reference's own AttentionReplace / Refine / Reweight (+ LocalBlend, with and
+    without substruct_words) objects for the cat -> dog pair, and the site count its register_attention_control finds on NativeUNet.
+    Keys "<object>/<attribute>", LocalBlend's as "<object>/lb_<attribute>"."""
+    ref_shim.install()
+    import types
+    from models.p2p import attention_control as ref_ac
+    from pnpinversion_amd.pipeline import NativeUNet
+
+    class _Eng:
+        cfg = SD1
+
+        def set_attention_callback(self, fn):
+            pass
+    tok = WordTokenizer()
+    prompts = ["a cat sitting on a wooden chair", "a dog sitting on a wooden chair"]
+    kw = dict(cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6)
+    with ref_shim.cuda_to_cpu():
+        refine = ref_ac.AttentionRefine(prompts, 50, tokenizer=tok, **kw)
+        objs = {
+            "replace": ref_ac.AttentionReplace(prompts, 50, tokenizer=tok, **kw),
+            "refine": refine,
+            "reweight": ref_ac.AttentionReweight(prompts, 50, equalizer=ref_ac.get_equalizer(prompts[1], ("dog",), (2,), tokenizer=tok),
+                                                 controller=refine, **kw),
+            "refine_lb": ref_ac.AttentionRefine(prompts, 50, tokenizer=tok, **kw, local_blend=ref_ac.LocalBlend(
+                prompts, (("cat",), ("dog",)), tokenizer=tok, num_ddim_steps=50)),
+            "refine_lb_sub": ref_ac.AttentionRefine(prompts, 50, tokenizer=tok, **kw, local_blend=ref_ac.LocalBlend(
+                prompts, (("cat",), ("dog",)), substruct_words=(("chair",), ("wooden",)), th=(0.3, 0.45), tokenizer=tok, num_ddim_steps=50)),
+        }
+    out = {}
+    for name, c in objs.items():
+        ref_ac.register_attention_control(types.SimpleNamespace(unet=NativeUNet(_Eng()), tokenizer=tok, device="cpu"), c)
+        e = {"class": type(c).__name__, "num_att_layers": c.num_att_layers, "cross_replace_alpha": _np(c.cross_replace_alpha),
+             "num_self_replace": list(c.num_self_replace)}
+        for k in ("mapper", "alphas", "equalizer"):
+            if hasattr(c, k):
+                e[k] = _np(getattr(c, k))
+        if getattr(c, "prev_controller", None) is not None:
+            e["prev_controller"] = [k for k, v in objs.items() if v is c.prev_controller][0]
+        lb = getattr(c, "local_blend", None)
+        if lb is not None:
+            e.update(lb_alpha_layers=_np(lb.alpha_layers), lb_start_blend=lb.start_blend, lb_th=list(lb.th), lb_counter=lb.counter)
+            if getattr(lb, "substruct_layers", None) is not None:
+                e["lb_substruct_layers"] = _np(lb.substruct_layers)
+        out.update({"%s/%s" % (name, k): np.asarray(v) for k, v in e.items()})
+    np.savez_compressed(os.path.join(OUT, "foreign_controllers.npz"), **out)
+    print("foreign_controllers.npz", len(out))
 
 
 def model_goldens():
@@ -827,6 +924,8 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["host", "models", "e2e", "variants", "masactrl", "proximal", "clip", "dispatch"]
     if "host" in which:
         host_tables()
+        host_tables_random()
+        foreign_controllers()
     if "models" in which:
         model_goldens()
     if "e2e" in which:

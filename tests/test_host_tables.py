@@ -6,6 +6,7 @@ import os
 
 import numpy as np
 import pytest
+import torch
 
 from pnpinversion_amd.p2p import attention_control as ac
 from pnpinversion_amd.p2p import seq_aligner
@@ -149,52 +150,38 @@ def test_clip_bpe_tokenizer_matches_transformers():
     assert get_word_inds("a cat sitting on the wooden chair", "cat", mine).tolist() == get_word_inds("a cat sitting on the wooden chair", "cat", ref).tolist() == [2]
 
 
-def test_random_prompt_pairs_against_the_live_reference():
-    """Where /root/reference is present (the build container; the GPU box has only the committed goldens above): 60 seeded random
-    prompt pairs -- substitutions, insertions, deletions, repeated words, different lengths -- through the reference's own
-    seq_aligner / get_time_words_attention_alpha / get_equalizer / LocalBlend and through the product's, bit for bit."""
-    from oracle import ref_shim
-    if not ref_shim.available():
-        pytest.skip("reference tree not on this machine")
-    ref_shim.install()
-    from models.p2p import seq_aligner as ref_sa
-    from models.p2p.attention_control import LocalBlend as RefLB, get_equalizer as ref_eq
-    from utils.utils import get_time_words_attention_alpha as ref_alpha, get_word_inds as ref_inds
-    import torch
+def _same(got, want):
+    """a product table against the reference's, value for value and in shape"""
+    got = torch.as_tensor(got).detach().cpu().numpy()
+    return got.shape == want.shape and np.array_equal(got, want)
+
+
+def test_random_prompt_pairs_match_the_reference():
+    """60 seeded random prompt pairs -- substitutions, insertions, deletions, repeated words, different lengths -- through the product's
+    seq_aligner / get_time_words_attention_alpha / get_equalizer / LocalBlend, bit for bit against the tables the reference's own
+    functions produced for them (tests/golden/host_tables_random.npz, oracle/make_golden.py)."""
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "host_tables_random.npz"))
+    cases = sorted({k.split("/")[0] for k in g.files})
+    assert len(cases) == 60
     tok = WordTokenizer()
-    vocab = "a the cat dog sitting on wooden red chair photo of mountain snowy watercolor big small tree and with elephant walking".split()
-    rng = np.random.default_rng(1234)
     n_replace = 0
-    for case in range(60):
-        src = [vocab[i] for i in rng.integers(0, len(vocab), rng.integers(3, 12))]
-        tgt = list(src)
-        for _ in range(rng.integers(1, 4)):                      # 1-3 edits
-            op, pos = rng.integers(0, 3), int(rng.integers(0, len(tgt)))
-            w = vocab[int(rng.integers(0, len(vocab)))]
-            if op == 0:
-                tgt[pos] = w
-            elif op == 1:
-                tgt.insert(pos, w)
-            elif len(tgt) > 2:
-                del tgt[pos]
-        ps, pt = " ".join(src), " ".join(tgt)
+    for c in cases:
+        e = lambda k: g["%s/%s" % (c, k)]          # noqa: E731
+        ps, pt, w0, w1 = (str(e(k)) for k in ("src", "tgt", "w0", "w1"))
         m, a = seq_aligner.get_refinement_mapper([ps, pt], tok)
-        rm, ra = ref_sa.get_refinement_mapper([ps, pt], tok)
-        assert torch.equal(torch.as_tensor(m), rm) and torch.equal(torch.as_tensor(a), ra), (ps, pt)
-        if len(src) == len(tgt):
+        assert _same(m, e("refine_mapper")) and _same(a, e("refine_alphas")), (ps, pt)
+        if len(ps.split(" ")) == len(pt.split(" ")):
             n_replace += 1
-            assert torch.equal(torch.as_tensor(seq_aligner.get_replacement_mapper([ps, pt], tok)), ref_sa.get_replacement_mapper([ps, pt], tok)), (ps, pt)
-        w0, w1 = src[int(rng.integers(0, len(src)))], tgt[int(rng.integers(0, len(tgt)))]
-        assert get_word_inds(ps, w0, tok).tolist() == ref_inds(ps, w0, tok).tolist()
-        for steps, frac in ((50, 0.4), (7, {"default_": 0.8, w1: (0.1, 0.5)})):
+            assert _same(seq_aligner.get_replacement_mapper([ps, pt], tok), e("replace_mapper")), (ps, pt)
+        else:
+            assert "%s/replace_mapper" % c not in g.files
+        assert get_word_inds(ps, w0, tok).tolist() == e("word_inds_src").tolist()
+        for i, (steps, frac) in enumerate(((50, 0.4), (7, {"default_": 0.8, w1: (0.1, 0.5)}))):
             cr = frac if isinstance(frac, dict) else {"default_": frac}
-            got = get_time_words_attention_alpha([ps, pt], steps, cr, tok)
-            assert torch.equal(torch.as_tensor(got), ref_alpha([ps, pt], steps, dict(cr), tok)), (ps, pt, steps)
-        assert torch.equal(torch.as_tensor(ac.get_equalizer(pt, (w1,), (2.5,), tokenizer=tok)), ref_eq(pt, (w1,), (2.5,), tokenizer=tok))
-        with ref_shim.cuda_to_cpu():
-            rlb = RefLB([ps, pt], ((w0,), (w1,)), tokenizer=tok, num_ddim_steps=50)
+            assert _same(get_time_words_attention_alpha([ps, pt], steps, cr, tok), e("cross_alpha_%d" % i)), (ps, pt, steps)
+        assert _same(ac.get_equalizer(pt, (w1,), (2.5,), tokenizer=tok), e("equalizer"))
         lb = ac.LocalBlend([ps, pt], ((w0,), (w1,)), tokenizer=tok, num_ddim_steps=50)
-        assert torch.equal(torch.as_tensor(lb.alpha_layers).reshape(-1), rlb.alpha_layers.reshape(-1).cpu()) and lb.start_blend == rlb.start_blend
+        assert _same(torch.as_tensor(lb.alpha_layers).reshape(-1), e("lb_alpha")) and lb.start_blend == int(e("lb_start"))
     assert n_replace >= 5
 
 
@@ -209,19 +196,70 @@ class _FakeEngine:
         self.callback = fn
 
 
-def test_the_references_own_register_attention_control_hooks_the_native_unet():
-    """SURVEY 8b level 1 with the reference's UNMODIFIED code (build container only): models/p2p/attention_control.register_attention_control
-    walks NativeUNet.named_children(), finds the 32 markers of class `CrossAttention` (:62-81), assigns their .forward -- and the native UNet
-    ends up with the controller the closure carries: a kernel descriptor for the reference's own AttentionReplace / Refine / Reweight objects
-    (read off their attributes, bit-identical to this package's classes; with LocalBlend -- substruct words included -- the instance's
-    step_callback is pointed at the native blend), nothing for controller=None."""
-    from oracle import ref_shim
-    if not ref_shim.available():
-        pytest.skip("reference tree not on this machine")
-    ref_shim.install()
+def _register_like_the_reference(model, controller):
+    """models/p2p/attention_control.py:12-81 in brief: None becomes a DummyController; every `CrossAttention` module under the UNet's down /
+    up / mid children gets a forward (reading its to_out first) that closes over `controller`; the count lands in num_att_layers."""
+    class DummyController:
+        def __call__(self, *args):
+            return args[0]
+
+    def ca_forward(self, place_in_unet):
+        to_out = self.to_out[0] if isinstance(self.to_out, torch.nn.ModuleList) else self.to_out   # noqa: F841
+
+        def forward(x, context=None, mask=None, **kwargs):
+            return controller(x, context is not None, place_in_unet)
+        return forward
+
+    def rec(net_, count, place):
+        if net_.__class__.__name__ == "CrossAttention":
+            net_.forward = ca_forward(net_, place)
+            return count + 1
+        for ch in net_.children():
+            count = rec(ch, count, place)
+        return count
+    if controller is None:
+        controller = DummyController()
+    n = 0
+    for name, net in model.unet.named_children():
+        for place in ("down", "up", "mid"):
+            if place in name:
+                n += rec(net, 0, place)
+                break
+    controller.num_att_layers = n
+
+
+def _reference_controllers():
+    """Stand-ins for the reference's own controller objects of the cat -> dog pair: objects of the reference's class names carrying the
+    attributes its AttentionReplace / Refine / Reweight / LocalBlend hold (tests/golden/foreign_controllers.npz, recorded from the
+    reference's objects by oracle/make_golden.py, with the site count its register_attention_control found on NativeUNet)."""
     import types
-    import torch
-    from models.p2p import attention_control as ref_ac
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "foreign_controllers.npz"))
+    out, sites = {}, {}
+    for name in ("replace", "refine", "reweight", "refine_lb", "refine_lb_sub"):       # a Reweight's previous controller comes first
+        e = {k.split("/", 1)[1]: g[k] for k in g.files if k.split("/")[0] == name}
+        c = type(str(e["class"]), (), {})()
+        c.cross_replace_alpha, c.num_self_replace = torch.from_numpy(e["cross_replace_alpha"]), tuple(int(x) for x in e["num_self_replace"])
+        c.cur_step, c.local_blend = 0, None
+        for k in ("mapper", "alphas", "equalizer"):
+            if k in e:
+                setattr(c, k, torch.from_numpy(e[k]))
+        if "prev_controller" in e:
+            c.prev_controller = out[str(e["prev_controller"])]
+        if "lb_alpha_layers" in e:
+            c.local_blend = types.SimpleNamespace(alpha_layers=torch.from_numpy(e["lb_alpha_layers"]), start_blend=int(e["lb_start_blend"]),
+                                                  th=tuple(float(x) for x in e["lb_th"]), counter=int(e["lb_counter"]),
+                                                  substruct_layers=torch.from_numpy(e["lb_substruct_layers"]) if "lb_substruct_layers" in e else None)
+        out[name], sites[name] = c, int(e["num_att_layers"])
+    return out, sites
+
+
+def test_the_references_controller_objects_hook_the_native_unet():
+    """SURVEY 8b level 1 with the reference's controller objects (stand-ins with their recorded attributes, see _reference_controllers)
+    registered the reference's way: the registration walks NativeUNet.named_children(), finds the 32 markers of class `CrossAttention`,
+    assigns their .forward -- and the native UNet ends up with the controller the closure carries: a kernel descriptor for the
+    reference's AttentionReplace / Refine / Reweight objects (read off their attributes, bit-identical to this package's classes; with
+    LocalBlend -- substruct words included -- the instance's step_callback is pointed at the native blend), nothing for controller=None."""
+    import types
     from pnpinversion_amd.config import SD1
     from pnpinversion_amd.pipeline import NativeUNet
     tok = WordTokenizer()
@@ -229,25 +267,17 @@ def test_the_references_own_register_attention_control_hooks_the_native_unet():
     model = types.SimpleNamespace(unet=NativeUNet(eng), tokenizer=tok, device="cpu")
     names = [n for n, _ in model.unet.named_children()]
     assert any("down" in n for n in names) and any("mid" in n for n in names) and any("up" in n for n in names)
+    ref, ref_sites = _reference_controllers()
+    ref_replace, ref_refine, ref_rw, ref_lb, ref_lb_sub = (ref[k] for k in ("replace", "refine", "reweight", "refine_lb", "refine_lb_sub"))
+    assert set(ref_sites.values()) == {32}                              # the reference's own registration counted 32 sites
 
     # controller=None: the reference's DummyController is counted up to 32 and means "no controller"
-    ref_ac.register_attention_control(model, None)
+    _register_like_the_reference(model, None)
     assert model.unet.controller is None
 
     ps, pt = "a cat sitting on a wooden chair", "a dog sitting on a wooden chair"
     prompts = [ps, pt]
-    with ref_shim.cuda_to_cpu():
-        ref_replace = ref_ac.AttentionReplace(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok)
-        ref_refine = ref_ac.AttentionRefine(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok)
-        eq = ref_ac.get_equalizer(pt, ("dog",), (2,), tokenizer=tok)
-        ref_rw = ref_ac.AttentionReweight(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, equalizer=eq,
-                                          controller=ref_refine)          # (the reference's Reweight takes no tokenizer, :347-355)
-        ref_lb = ref_ac.AttentionRefine(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok,
-                                        local_blend=ref_ac.LocalBlend(prompts, (("cat",), ("dog",)), tokenizer=tok, num_ddim_steps=50))
-        ref_lb_sub = ref_ac.AttentionRefine(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok,
-                                            local_blend=ref_ac.LocalBlend(prompts, (("cat",), ("dog",)), substruct_words=(("chair",), ("wooden",)),
-                                                                          th=(0.3, 0.45), tokenizer=tok, num_ddim_steps=50))
-        ref_store = ref_ac.AttentionStore()
+    ref_store = type("AttentionStore", (), {})()
     mine_replace = ac.AttentionReplace(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok)
     mine_refine = ac.AttentionRefine(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok)
     mine_rw = ac.AttentionReweight(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6,
@@ -259,8 +289,8 @@ def test_the_references_own_register_attention_control_hooks_the_native_unet():
         assert a.self_range == b.self_range and a.lb_alpha is None and b.lb_alpha is None
 
     for ref_c, mine in ((ref_replace, mine_replace), (ref_refine, mine_refine), (ref_rw, mine_rw)):
-        ref_ac.register_attention_control(model, ref_c)
-        assert ref_c.num_att_layers == 32                                   # the reference counted 32 sites
+        _register_like_the_reference(model, ref_c)
+        assert ref_c.num_att_layers == 32
         got = model.unet.controller
         assert isinstance(got, ac.ForeignControllerAdapter) and got.wrapped is ref_c and not ac.is_callback_controller(got)
         same_tables(got.tables(), mine.tables())
@@ -282,7 +312,7 @@ def test_the_references_own_register_attention_control_hooks_the_native_unet():
         mine = ac.AttentionRefine(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok,
                                   local_blend=ac.LocalBlend(prompts, (("cat",), ("dog",)), substruct_words=sub, th=th, tokenizer=tok,
                                                             num_ddim_steps=50))
-        ref_ac.register_attention_control(bmodel, ref_c)
+        _register_like_the_reference(bmodel, ref_c)
         got = bmodel.unet.controller
         assert isinstance(got, ac.ForeignControllerAdapter) and got.wrapped is ref_c and not ac.is_callback_controller(got)
         a, b = got.tables(), mine.tables()
@@ -305,10 +335,10 @@ def test_the_references_own_register_attention_control_hooks_the_native_unet():
         ac.AttentionRefine(prompts, 50, cross_replace_steps={"default_": 0.4}, self_replace_steps=0.6, tokenizer=tok,
                            local_blend=ac.LocalBlend(prompts, (("cat",), ("dog",)), tokenizer=tok, num_ddim_steps=50)).step_callback(x)
     # a plain AttentionStore: no edit (its step bookkeeping still runs on the reference's object)
-    ref_ac.register_attention_control(model, ref_store)
+    _register_like_the_reference(model, ref_store)
     assert model.unet.controller.tables() is None and model.unet.controller.wrapped is ref_store
     # this package's own classes through the reference's function: unchanged
-    ref_ac.register_attention_control(model, mine_rw)
+    _register_like_the_reference(model, mine_rw)
     assert model.unet.controller is mine_rw and mine_rw.num_att_layers == 32
     # a hook that is not the reference's protocol is refused, not ignored
     site = next(iter(next(iter(model.unet.named_children()))[1].children()))
@@ -322,26 +352,6 @@ def test_native_unet_attention_site_markers_without_the_reference():
     from pnpinversion_amd.config import SD1, SMALL64_LB
     from pnpinversion_amd.pipeline import NativeUNet
 
-    def register(model, controller):           # models/p2p/attention_control.py:12-81, condensed
-        def ca_forward(self, place_in_unet):
-            def forward(x, context=None, mask=None, **kwargs):
-                return controller(x, context is not None, place_in_unet)
-            return forward
-
-        def rec(net_, count, place):
-            if net_.__class__.__name__ == "CrossAttention":
-                net_.forward = ca_forward(net_, place)
-                return count + 1
-            for ch in net_.children():
-                count = rec(ch, count, place)
-            return count
-        n = 0
-        for name, net in model.unet.named_children():
-            for place in ("down", "up", "mid"):
-                if place in name:
-                    n += rec(net, 0, place)
-        controller.num_att_layers = n
-
     class Probe:
         def __call__(self, attn, is_cross, place):
             return attn
@@ -351,7 +361,7 @@ def test_native_unet_attention_site_markers_without_the_reference():
         unet = NativeUNet(eng)
         model = types.SimpleNamespace(unet=unet)
         p = Probe()
-        register(model, p)
+        _register_like_the_reference(model, p)
         assert p.num_att_layers == want == unet.num_att_layers and unet.controller is p and ac.is_callback_controller(p)
         sites = [s for _, cont in unet.named_children() for s in cont.children()]
         assert [s.is_cross for s in sites] == [False, True] * (want // 2) and [s.index for s in sites] == list(range(want))

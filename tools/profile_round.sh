@@ -9,10 +9,10 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$R"
 set -x
-timeout 400 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- python bench.py --steps 2 --warmup 1 --no-extras --no-cpu-baseline > "$OUT/bench_under_trace.json" 2> "$OUT/kt.err"
+timeout 400 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline > "$OUT/bench_under_trace.json" 2> "$OUT/kt.err"
 tail -c 600 "$OUT/bench_under_trace.json"
 find "$OUT/kt" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/kernel_stats.csv"
-python -c "import json; from pnpinversion_amd.build import source_hash; json.dump({'source_sha16': source_hash(), 'command': 'rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-extras --no-cpu-baseline'}, open('$OUT/kernel_stats.meta.json', 'w'))"
+python -c "import json; from pnpinversion_amd.build import source_hash; json.dump({'source_sha16': source_hash(), 'command': 'rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline'}, open('$OUT/kernel_stats.meta.json', 'w'))"
 head -12 "$OUT/kernel_stats.csv"
 # BASELINE config 3's launch shape (8 images per set of launches: 8-row inversion, 96-row lock-step forwards) under the same tracer
 timeout 400 rocprofv3 --kernel-trace --stats -d "$OUT/kt96" -o kt96 --output-format csv -- python tools/batched_only.py 8 50 1 > "$OUT/batched_under_trace.json" 2> "$OUT/kt96.err"
@@ -23,7 +23,7 @@ find "$OUT/kt96" -name "*kernel_trace.csv" -delete
 # interception once a process has launched some tens of thousands of kernels (a full edit is ~50 000 launches, plus the event-bracketed
 # profiling edit; tools/fwd_only.py with 1 600 never tripped it).  Same kernels, same launch shapes, same 1 : 1 mix of one-row and
 # twelve-row forwards -- per-launch averages are what the summary keeps.
-SHORT="python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras --ddim-steps 2"
+SHORT="python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras --ddim-steps 2"
 export PMC_SOURCE="rocprofv3 --pmc passes (one counter set per run) of: $SHORT"
 timeout 500 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch --output-format csv -- $SHORT > "$OUT/fetch.log" 2>&1
 timeout 500 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o write --output-format csv -- $SHORT > "$OUT/write.log" 2>&1
