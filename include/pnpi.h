@@ -287,6 +287,43 @@ int pnpi_direct_edit_pruned(pnpi_ctx* ctx, const float* ddim_latents, int nimg, 
                             const pnpi_ctrl_desc* ctrl_host /* nullable or [nimg] */, int nsteps, const int* timesteps_host,
                             float guidance_scale, float* latents_out);
 
+/* ---- edit-friendly DDPM inversion (models/edit_friendly_ddm/inversion_utils.py, eta > 0) ------------------------------------------
+ * Latents fp32 [.][4][h][w], E = 4*h*w.  The per-step scalars are the reference's 0-dim fp32 expressions in its order (get_variance
+ * :91-98, :157-168, :190-206); every element-wise op is rounded separately as in eager PyTorch, so the level-1 kernels are bit-exact
+ * against the reference's formulas given the same eps.
+ * One deviation: at a step whose variance is exactly 0 (t = 0 when ab_prev == ab[t], i.e. set_alpha_to_one=False) the reference divides
+ * by zero and its xts[0] is NaN; here z = 0 and xts[0] keeps x0.  Neither value is read by anything (zs[0] is zeroed at :173-174). */
+/* the host scalars of one step, no context: out6 = [sqrt(ab_t), sqrt(1-ab_t), sqrt(ab_prev), sqrt(1-ab_prev-eta*var), eta*sqrt(var), var]
+ * with ab_prev = alphas_cumprod[t - step_ratio] (final_alpha below 0) */
+int pnpi_ef_step_scalars(const float* alphas_cumprod, int n, float final_alpha, int t, int step_ratio, float eta, float* out6);
+/* sample_xts_from_x0 (:31-55): xts_out[1 + k] = x0 * sqrt(ab[t]) + noise[k] * sqrt(1 - ab[t]) for the k-th draw, t = timesteps_host[nsteps-1-k]
+ * (the reference draws in reversed(timesteps) order).  noise [nsteps][nimg][E], xts_out [nsteps+1][nimg][E]; level 0 is not written. */
+int pnpi_ef_sample_xts(pnpi_ctx* ctx, const float* x0, int nimg, const float* noise, size_t row_elems, int nsteps,
+                       const int* timesteps_host, float* xts_out);
+/* one step of inversion_forward_process (:151-171): eps [nimg][2][E] (uncond, cond; cfg != 0) or [nimg][1][E] (cfg == 0: prompt ""),
+ * xt = xts[idx+1], xprev = xts[idx] (overwritten with the corrected mu + sigma z), z_out = zs[idx].  eta <= 0 is PNPI_EINVAL. */
+int pnpi_ef_noise_map(pnpi_ctx* ctx, const float* eps, int cfg, float cfg_scale, const float* xt, float* xprev, float* z_out, int nimg,
+                      size_t row_elems, int t, int step_ratio, float eta);
+/* reverse_step (:179-208) after the per-row CFG of :254-258: eps [nimg][2P][E] (P uncond rows, then P cond rows), x / out [nimg][P][E]
+ * (may alias), z [nimg][E] (one noise map per image, every prompt row), cfg_scales_host [P], P = nprompts in {1, 2}.  eta <= 0 adds no
+ * noise (:203). */
+int pnpi_ef_reverse_step(pnpi_ctx* ctx, const float* eps, const float* x, const float* z, int nimg, int nprompts, size_t row_elems,
+                         const float* cfg_scales_host, int t, int step_ratio, float eta, float* out);
+/* inversion_forward_process(model, x0, etas, prompt, cfg_scale) (:100-176), device-resident: xts_out [nsteps+1][nimg][E] (level 0 = x0),
+ * zs_out [nsteps][nimg][E] (zs[0] = 0).  noise [nsteps][nimg][E] = the draws in the reference's order; etas_host [nsteps] indexed like
+ * the reference's etas[idx] (all > 0).  One UNet launch of nimg x [uncond, cond] rows per step (uncond only when ctx_cond is NULL). */
+int pnpi_ef_invert(pnpi_ctx* ctx, const float* x0, int nimg, const float* noise, const float* ctx_uncond /*[nimg][77][768]*/,
+                   const float* ctx_cond /*[nimg][77][768], nullable: prompt ""*/, float cfg_scale, const float* etas_host, int nsteps,
+                   const int* timesteps_host, float* xts_out, float* zs_out);
+/* inversion_reverse_process(model, xT, etas, prompts, cfg_scales, zs, controller) (:210-262), device-resident, over the last nsteps_run of
+ * the nsteps_total timesteps: step k uses zs[nsteps_run-1-k] and etas_host[nsteps_run-1-k] (etas_host [nsteps_total]).
+ * xT [nimg][E] (every prompt row starts there), zs [nsteps_run][nimg][E], context [nimg][2*nprompts][77][768] (nprompts uncond rows, then
+ * nprompts cond rows), cfg_scales_host [nprompts], ctrl_host nullable or [nimg] (needs nprompts == 2, no LocalBlend; step index from 0),
+ * latents_out [nimg][nprompts][E].  One UNet launch of 2 * nprompts * nimg rows per step. */
+int pnpi_ef_edit(pnpi_ctx* ctx, const float* xT, const float* zs, int nimg, int nprompts, const float* context,
+                 const float* cfg_scales_host, const pnpi_ctrl_desc* ctrl_host, const float* etas_host, int nsteps_run, int nsteps_total,
+                 const int* timesteps_host, float* latents_out);
+
 /* ---- kernel-level entry points (used by tests/ and bench.py to exercise single kernels) ------------------------- */
 int pnpi_op_conv(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nhwc_f16, int C1, int C2, int B, int H, int W,
                  int ksize, int stride, int pad, int upsample, int Ho, int Wo, const void* w_f16 /*[N][k*k*(C1+C2)]*/,

@@ -136,6 +136,13 @@ SYMBOLS = {
                                 _vp, _vp, _vp, _i, _i]),
     "pnpi_op_local_blend": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _i]),
     "pnpi_op_local_blend_sub": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _i]),
+    # edit-friendly DDPM inversion (models/edit_friendly_ddm/inversion_utils.py)
+    "pnpi_ef_step_scalars": (_i, [_fp, _i, _f, _i, _i, _f, _fp]),                              # get_variance :91-98 + :157-168, :190-206
+    "pnpi_ef_sample_xts": (_i, [_vp, _vp, _i, _vp, _sz, _i, _ip, _vp]),                        # sample_xts_from_x0 :31-55
+    "pnpi_ef_noise_map": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _i, _sz, _i, _i, _f]),         # inversion_forward_process :151-171
+    "pnpi_ef_reverse_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _sz, _fp, _i, _i, _f, _vp]),     # :254-258 + reverse_step :179-208
+    "pnpi_ef_invert": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _f, _fp, _i, _ip, _vp, _vp]),         # inversion_forward_process :100-176
+    "pnpi_ef_edit": (_i, [_vp, _vp, _vp, _i, _i, _vp, _fp, C.POINTER(CtrlDesc), _fp, _i, _i, _ip, _vp]),  # inversion_reverse_process :210-262
 }
 
 _lib = None

@@ -990,6 +990,160 @@ int pnpi_direct_edit_pruned(pnpi_ctx* c, const float* lat_all, int nimg, const f
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------- edit-friendly DDPM inversion
+// models/edit_friendly_ddm/inversion_utils.py (eta > 0: the forward process stores one noise map per step, the reverse process replays
+// them).  Scalars: ef_step_scalars (step.hip), the reference's 0-dim fp32 expressions in its order.
+int pnpi_ef_step_scalars(const float* alphas_cumprod, int n, float final_alpha, int t, int step_ratio, float eta, float* out6) {
+  if (!alphas_cumprod || !out6 || t < 0 || t >= n || step_ratio <= 0) return PNPI_EINVAL;
+  const int tp = t - step_ratio;
+  ef_step_scalars(alphas_cumprod[t], tp >= 0 ? alphas_cumprod[tp] : final_alpha, eta, out6);
+  return 0;
+}
+static int ef_scalars(pnpi_ctx* c, int t, int ratio, float eta, float* sc) {
+  if (!c->sched_set) return fail(c, PNPI_ESTATE, "pnpi_set_scheduler not called");
+  if (t < 0 || t >= (int)c->ac.size() || ratio <= 0) return fail(c, PNPI_EINVAL, "timestep out of range");
+  return pnpi_ef_step_scalars(c->ac.data(), (int)c->ac.size(), c->final_alpha, t, ratio, eta, sc);
+}
+// (sqrt(ab[t]), sqrt(1 - ab[t])) of level 1 + k, k in draw order (timestep ts[nsteps - 1 - k]), uploaded to the controller arena
+static int ef_levels(pnpi_ctx* c, int nsteps, const int* ts, float** dst) {
+  if (!c->sched_set) return fail(c, PNPI_ESTATE, "pnpi_set_scheduler not called");
+  std::vector<float> lev(2 * (size_t)nsteps);
+  for (int k = 0; k < nsteps; ++k) {
+    const int t = ts[nsteps - 1 - k];
+    if (t < 0 || t >= (int)c->ac.size()) return fail(c, PNPI_EINVAL, "timestep out of range");
+    lev[2 * k] = sqrtf(c->ac[t]);
+    lev[2 * k + 1] = sqrtf(1.0f - c->ac[t]);
+  }
+  *dst = misc_f(c, lev.size());
+  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
+  return upload(c, *dst, lev.data(), lev.size() * sizeof(float));
+}
+
+int pnpi_ef_sample_xts(pnpi_ctx* c, const float* x0, int nimg, const float* noise, size_t row_elems, int nsteps, const int* ts, float* xts_out) {
+  if (!c || !x0 || !noise || !ts || !xts_out || nimg <= 0 || nsteps <= 0 || row_elems == 0) return PNPI_EINVAL;
+  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
+  float* lev;
+  CKP(ef_levels(c, nsteps, ts, &lev));
+  CK(launch_ef_sample_xts(x0, noise, lev, nsteps, (size_t)nimg * row_elems, xts_out, c->st));
+  return 0;
+}
+
+int pnpi_ef_noise_map(pnpi_ctx* c, const float* eps, int cfg, float cfg_scale, const float* xt, float* xprev, float* z_out, int nimg,
+                      size_t row_elems, int t, int step_ratio, float eta) {
+  if (!c || !eps || !xt || !xprev || !z_out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
+  if (!(eta > 0.f)) return fail(c, PNPI_EINVAL, "edit-friendly inversion needs eta > 0 (eta = 0 stores no noise maps)");
+  float sc[6]; CKP(ef_scalars(c, t, step_ratio, eta, sc));
+  CK(launch_ef_noise_map(eps, cfg ? 1 : 0, cfg_scale, xt, xprev, z_out, nimg, row_elems, sc, c->st));
+  return 0;
+}
+
+int pnpi_ef_reverse_step(pnpi_ctx* c, const float* eps, const float* x, const float* z, int nimg, int nprompts, size_t row_elems,
+                         const float* cfg_scales_host, int t, int step_ratio, float eta, float* out) {
+  if (!c || !eps || !x || !z || !cfg_scales_host || !out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
+  if (nprompts != 1 && nprompts != 2) return fail(c, PNPI_EINVAL, "nprompts must be 1 or 2");
+  float sc[6]; CKP(ef_scalars(c, t, step_ratio, eta, sc));
+  CK(launch_ef_reverse_step(eps, x, z, nimg, nprompts, row_elems, cfg_scales_host[0], cfg_scales_host[nprompts - 1], sc, eta > 0.f ? 1 : 0,
+                            out, c->st));
+  return 0;
+}
+
+/* inversion_forward_process (inversion_utils.py:100-176) for nimg images: xts from x0 and the caller's draws, then for t = ts[0] .. ts[nsteps-1]
+ * (idx = nsteps-1 .. 0) one UNet launch of the rows [img][uncond, cond] (uncond only when ctx_cond is NULL: prompt "") on xts[idx+1], and the
+ * noise map / corrected xts[idx] of that step.  zs[0] is zeroed at the end (:173-174). */
+int pnpi_ef_invert(pnpi_ctx* c, const float* x0, int nimg, const float* noise, const float* ctx_uncond, const float* ctx_cond, float cfg_scale,
+                   const float* etas_host, int nsteps, const int* ts, float* xts_out, float* zs_out) {
+  if (!c || !x0 || !noise || !ctx_uncond || !etas_host || !ts || !xts_out || !zs_out || nimg <= 0 || nsteps <= 0) return PNPI_EINVAL;
+  for (int k = 0; k < nsteps; ++k)
+    if (!(etas_host[k] > 0.f)) return fail(c, PNPI_EINVAL, "edit-friendly inversion needs eta > 0 at every step");
+  CKP(check_loop_ready(c));
+  const pnpi_model_config& g = c->cfg;
+  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
+  const int ratio = g.n_train_timesteps / nsteps, rpi = ctx_cond ? 2 : 1, rows = rpi * nimg;
+  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "nimg * (1 + has_cond) exceeds max_unet_rows");
+  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
+  float* eps = misc_f(c, (size_t)rows * E);
+  float* in = misc_f(c, (size_t)rows * E);
+  float* ctx2 = misc_f(c, (size_t)rows * CE);
+  std::vector<int> inmap(rows);
+  for (int r = 0; r < rows; ++r) inmap[r] = r / rpi;
+  int* d_inmap;
+  CKP(upload_ints(c, inmap, &d_inmap));
+  float* lev;
+  CKP(ef_levels(c, nsteps, ts, &lev));
+  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
+  for (int i = 0; i < nimg; ++i) {   // rows [img][uncond, cond]
+    CKH(hipMemcpyAsync(ctx2 + (size_t)(rpi * i) * CE, ctx_uncond + (size_t)i * CE, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+    if (ctx_cond)
+      CKH(hipMemcpyAsync(ctx2 + (size_t)(rpi * i + 1) * CE, ctx_cond + (size_t)i * CE, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  }
+  const size_t L = (size_t)nimg * E;
+  CKH(hipMemcpyAsync(xts_out, x0, L * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  CK(launch_ef_sample_xts(x0, noise, lev, nsteps, L, xts_out, c->st));
+  LoopKV kv(c);
+  CKP(kv.begin(ctx2, rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i], idx = nsteps - 1 - i;
+    const float* xt = xts_out + (size_t)(idx + 1) * L;
+    CK(launch_gather_rows_f32(xt, d_inmap, rows, E, in, c->st));
+    int r = unet_fwd(c, in, rows, t, ctx2, false, 0, eps);
+    if (r) return r;
+    float sc[6]; CKP(ef_scalars(c, t, ratio, etas_host[idx], sc));
+    CK(launch_ef_noise_map(eps, ctx_cond ? 1 : 0, cfg_scale, xt, xts_out + (size_t)idx * L, zs_out + (size_t)idx * L, nimg, E, sc, c->st));
+  }
+  CKH(hipMemsetAsync(zs_out, 0, L * sizeof(float), c->st));
+  return 0;
+}
+
+/* inversion_reverse_process (inversion_utils.py:210-262) with stored noise maps, nimg images x nprompts prompt rows: the last nsteps_run of the
+ * nsteps_total timesteps, step k (0-based) at t = ts[nsteps_total - nsteps_run + k] replays zs[nsteps_run-1-k] with etas[nsteps_run-1-k].
+ * One UNet launch of 2 * nprompts * nimg rows per step, per image [uncond_0 .. uncond_{P-1}, cond_0 .. cond_{P-1}] (the reference's uncond and
+ * cond calls); with two prompts that is the controller layout [uncond_src, uncond_tgt, cond_src, cond_tgt], and the controller's step index
+ * runs from 0 (the edit pass's own cur_step). */
+int pnpi_ef_edit(pnpi_ctx* c, const float* xT, const float* zs, int nimg, int nprompts, const float* context, const float* cfg_scales_host,
+                 const pnpi_ctrl_desc* ctrl_host, const float* etas_host, int nsteps_run, int nsteps_total, const int* ts, float* latents_out) {
+  if (!c || !xT || !zs || !context || !cfg_scales_host || !etas_host || !ts || !latents_out || nimg <= 0) return PNPI_EINVAL;
+  if (nprompts != 1 && nprompts != 2) return fail(c, PNPI_EINVAL, "nprompts must be 1 or 2");
+  if (nsteps_run <= 0 || nsteps_run > nsteps_total) return fail(c, PNPI_EINVAL, "need 0 < nsteps_run <= nsteps_total");
+  if (ctrl_host && nprompts != 2) return fail(c, PNPI_EINVAL, "an attention controller needs two prompts (source, target)");
+  if (ctrl_host)
+    for (int i = 0; i < nimg; ++i)
+      if (ctrl_host[i].lb_enabled) return fail(c, PNPI_EINVAL, "LocalBlend is not supported by the edit-friendly edit");
+  CKP(check_loop_ready(c));
+  const pnpi_model_config& g = c->cfg;
+  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size;
+  const int ratio = g.n_train_timesteps / nsteps_total, P = nprompts, rows = 2 * P * nimg;
+  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "2 * nprompts * nimg exceeds max_unet_rows");
+  if (ctrl_host) CKP(setup_ctrl(c, ctrl_host, nimg, rows));
+  else CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
+  float* lat = misc_f(c, (size_t)nimg * P * E);
+  float* in = misc_f(c, (size_t)rows * E);
+  float* eps = misc_f(c, (size_t)rows * E);
+  std::vector<int> expand(nimg * P), inmap(rows);
+  for (int i = 0; i < nimg; ++i) {
+    for (int p = 0; p < P; ++p) expand[P * i + p] = i;
+    for (int k = 0; k < 2 * P; ++k) inmap[2 * P * i + k] = P * i + (k % P);
+  }
+  int *d_expand, *d_inmap;
+  CKP(upload_ints(c, expand, &d_expand));
+  CKP(upload_ints(c, inmap, &d_inmap));
+  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
+  CK(launch_gather_rows_f32(xT, d_expand, nimg * P, E, lat, c->st));      // xT.expand(batch_size, ...) (:240)
+  LoopKV kv(c);
+  CKP(kv.begin(context, rows));
+  for (int k = 0; k < nsteps_run; ++k) {
+    const int t = ts[nsteps_total - nsteps_run + k], idx = nsteps_run - 1 - k;
+    CK(launch_gather_rows_f32(lat, d_inmap, rows, E, in, c->st));
+    int r = unet_fwd(c, in, rows, t, context, ctrl_host != nullptr, k, eps);
+    if (r) return r;
+    const float eta = etas_host[idx];
+    float sc[6]; CKP(ef_scalars(c, t, ratio, eta, sc));
+    CK(launch_ef_reverse_step(eps, lat, zs + (size_t)idx * nimg * E, nimg, P, E, cfg_scales_host[0], cfg_scales_host[P - 1], sc,
+                              eta > 0.f ? 1 : 0, lat, c->st));
+  }
+  CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * P * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------- kernel-level ops
 int pnpi_op_conv(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int H, int W, int ksize, int stride, int pad,
                  int ups, int Ho, int Wo, const void* w, const float* bias, const void* res, int N, void* out, int force_cfg,

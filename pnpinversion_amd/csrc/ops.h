@@ -182,6 +182,13 @@ int launch_quantile_abs_diff(const float* eps, int nimg, int rows_per_img, size_
 int launch_fill_f32(float* p, int n, float v, hipStream_t st);
 int launch_local_blend(const float* lb_acc, int nslots, int map_hw, int lat_hw, int C, float th, float* latents,
                        int nimg, hipStream_t st, int planes = 2, float th_sub = 0.3f);   // planes 4: planes 2, 3 are the substruct maps (no pooling, th_sub)
+// edit-friendly DDPM (eta > 0, stored noise maps).  sc: the 6 host scalars of ef_step_scalars [sa_t, sb_t, sa_p, dcoef, sigma, var]
+void ef_step_scalars(float ab_t, float ab_p, float eta, float* out);
+int launch_ef_sample_xts(const float* x0, const float* noise, const float* lev_dev, int nlev, size_t per_lev, float* xts, hipStream_t st);
+int launch_ef_noise_map(const float* eps, int cfg, float g, const float* xt, float* xprev, float* z_out, int nimg, size_t E, const float* sc,
+                        hipStream_t st);
+int launch_ef_reverse_step(const float* eps, const float* x, const float* z, int nimg, int P, size_t E, float g0, float g1, const float* sc,
+                           int add_noise, float* out, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
 // Activation-gradient kernels of the null-text path (bwd.hip)

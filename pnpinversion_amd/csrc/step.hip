@@ -301,3 +301,108 @@ int launch_local_blend(const float* lb_acc, int nslots, int map_hw, int lat_hw, 
   local_blend_kernel<<<nimg, 256, lds, st>>>(lb_acc, nslots, map_hw, lat_hw, C, th, latents, planes, th_sub);
   return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------- edit-friendly DDPM (eta > 0)
+// Reference: models/edit_friendly_ddm/inversion_utils.py -- sample_xts_from_x0 :31-55, inversion_forward_process :151-171,
+// get_variance :91-98, reverse_step :179-208.  The per-step scalars are the reference's 0-dim fp32 torch ops, evaluated here on the host
+// in the same order (this file is compiled without FMA contraction, host code included):
+//   ab_p  = ab[t - ratio] (final_alpha_cumprod below 0)
+//   var   = ((1 - ab_p) / (1 - ab_t)) * (1 - ab_t / ab_p)
+//   dcoef = ((1 - ab_p) - eta * var) ** 0.5        sigma = eta * var ** 0.5
+// out: [sa_t, sb_t, sa_p, dcoef, sigma, var]
+void ef_step_scalars(float ab_t, float ab_p, float eta, float* out) {
+  const float bt = 1.0f - ab_t, bp = 1.0f - ab_p;
+  const float var = (bp / bt) * (1.0f - ab_t / ab_p);
+  out[0] = sqrtf(ab_t);
+  out[1] = sqrtf(bt);
+  out[2] = sqrtf(ab_p);
+  out[3] = sqrtf(bp - eta * var);
+  out[4] = eta * sqrtf(var);
+  out[5] = var;
+}
+
+// xts[1 + k][img] = x0[img] * sqrt(ab[t_k]) + noise[k][img] * sqrt(1 - ab[t_k])   (inversion_utils.py:53), k = 0 .. nlev-1 in draw order.
+// lev: [nlev][2] = (sqrt(ab), sqrt(1 - ab)) per level.  xts[0] is not written.
+__global__ void ef_sample_xts_kernel(const float* __restrict__ x0, const float* __restrict__ noise, const float* __restrict__ lev, int nlev,
+                                     size_t per_lev, float* __restrict__ xts) {
+  const size_t total = (size_t)nlev * per_lev;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int k = (int)(i / per_lev);
+    const size_t r = i - (size_t)k * per_lev;
+    xts[per_lev + i] = __fadd_rn(__fmul_rn(x0[r], lev[2 * k]), __fmul_rn(noise[i], lev[2 * k + 1]));
+  }
+}
+int launch_ef_sample_xts(const float* x0, const float* noise, const float* lev_dev, int nlev, size_t per_lev, float* xts, hipStream_t st) {
+  size_t total = (size_t)nlev * per_lev;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  ef_sample_xts_kernel<<<blocks, 256, 0, st>>>(x0, noise, lev_dev, nlev, per_lev, xts);
+  return (int)hipGetLastError();
+}
+
+// One step of inversion_forward_process (:151-171) for nimg images.  eps: [nimg][2][E] (uncond, cond) when cfg, else [nimg][1][E];
+// xt = xts[idx+1], xprev = xts[idx] (read, then overwritten with the corrected value), z_out = zs[idx]:
+//   e = eu + g * (ec - eu);  x0 = (xt - sb_t e) / sa_t;  mu = sa_p x0 + dcoef e;  z = (xprev - mu) / sigma;  xprev = mu + sigma z
+// var_zero (the t = 0 step, ab_p == ab_t): z = 0 and xprev is left as sampled.  The reference divides by zero there and its xts[0] is
+// NaN; nothing reads either (zs[0] is zeroed at :173-174).
+__global__ void ef_noise_map_kernel(const float* __restrict__ eps, int cfg, float g, const float* __restrict__ xt, float* __restrict__ xprev,
+                                    float* __restrict__ z_out, int nimg, size_t E, float sa_t, float sb_t, float sa_p, float dcoef, float sigma,
+                                    int var_zero) {
+  const size_t total = (size_t)nimg * E;
+  const int rpi = cfg ? 2 : 1;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / E, e_idx = i - img * E;
+    const float eu = eps[(img * rpi) * E + e_idx];
+    const float e = cfg ? __fadd_rn(eu, __fmul_rn(g, __fsub_rn(eps[(img * rpi + 1) * E + e_idx], eu))) : eu;
+    const float x0 = __fdiv_rn(__fsub_rn(xt[i], __fmul_rn(sb_t, e)), sa_t);
+    const float mu = __fadd_rn(__fmul_rn(sa_p, x0), __fmul_rn(dcoef, e));
+    if (var_zero) {
+      z_out[i] = 0.f;
+    } else {
+      const float z = __fdiv_rn(__fsub_rn(xprev[i], mu), sigma);
+      z_out[i] = z;
+      xprev[i] = __fadd_rn(mu, __fmul_rn(sigma, z));
+    }
+  }
+}
+int launch_ef_noise_map(const float* eps, int cfg, float g, const float* xt, float* xprev, float* z_out, int nimg, size_t E, const float* sc,
+                        hipStream_t st) {
+  size_t total = (size_t)nimg * E;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  if (blocks < 1) blocks = 1;
+  ef_noise_map_kernel<<<blocks, 256, 0, st>>>(eps, cfg, g, xt, xprev, z_out, nimg, E, sc[0], sc[1], sc[2], sc[3], sc[4], sc[5] == 0.0f);
+  return (int)hipGetLastError();
+}
+
+// One reverse_step (:179-208) after the per-row CFG of inversion_reverse_process (:254-258), P prompt rows per image:
+// eps: [nimg][2P][E] (P uncond rows, then P cond rows), x / out: [nimg][P][E] (may alias), z: [nimg][E] (one noise map per image, expanded
+// over its prompt rows as at :252), g0 / g1: the guidance scale of prompt row 0 / 1.
+//   e = eu + g_r (ec - eu);  x0 = (x - sb_t e) / sa_t;  prev = sa_p x0 + dcoef e;  prev += sigma z   (only when eta > 0, :203-206)
+__global__ void ef_reverse_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, int nimg, int P, size_t E,
+                                       float g0, float g1, float sa_t, float sb_t, float sa_p, float dcoef, float sigma, int add_noise,
+                                       float* out) {
+  const size_t total = (size_t)nimg * P * E;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e_idx = i % E, ir = i / E;
+    const int r = (int)(ir % P);
+    const size_t img = ir / P;
+    const float eu = eps[(img * 2 * P + r) * E + e_idx], ec = eps[(img * 2 * P + P + r) * E + e_idx];
+    const float e = __fadd_rn(eu, __fmul_rn(r == 0 ? g0 : g1, __fsub_rn(ec, eu)));
+    const float x0 = __fdiv_rn(__fsub_rn(x[i], __fmul_rn(sb_t, e)), sa_t);
+    float prev = __fadd_rn(__fmul_rn(sa_p, x0), __fmul_rn(dcoef, e));
+    if (add_noise) prev = __fadd_rn(prev, __fmul_rn(sigma, z[img * E + e_idx]));
+    out[i] = prev;
+  }
+}
+int launch_ef_reverse_step(const float* eps, const float* x, const float* z, int nimg, int P, size_t E, float g0, float g1, const float* sc,
+                           int add_noise, float* out, hipStream_t st) {
+  if (P != 1 && P != 2) return -3;
+  size_t total = (size_t)nimg * P * E;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  if (blocks < 1) blocks = 1;
+  ef_reverse_step_kernel<<<blocks, 256, 0, st>>>(eps, x, z, nimg, P, E, g0, g1, sc[0], sc[1], sc[2], sc[3], sc[4], add_noise, out);
+  return (int)hipGetLastError();
+}

@@ -564,3 +564,103 @@ class NativeEngine:
                    float(quantile), C.byref(rd) if rd is not None else None, _p(out))
         self._keep = (xT, ctx, nl, ts, arr, ctrls, ref, rd)
         return out
+
+    # ---- edit-friendly DDPM inversion (models/edit_friendly_ddm/inversion_utils.py, eta > 0)
+    @staticmethod
+    def _etas(etas, n):
+        """the reference's `etas`: a number (repeated, :121-122 / :231) or a per-step list indexed by idx"""
+        if isinstance(etas, (int, float)):
+            etas = [etas] * n
+        e = np.ascontiguousarray(np.asarray(etas, dtype=np.float32))
+        if e.shape != (n,):
+            raise ValueError("etas: one value per inference step (%d), got shape %s" % (n, e.shape))
+        return e, e.ctypes.data_as(C.POINTER(C.c_float))
+
+    def ef_step_scalars(self, t, ratio, eta):
+        """host scalars of one step: (sqrt(ab_t), sqrt(1-ab_t), sqrt(ab_prev), sqrt(1-ab_prev-eta*var), eta*sqrt(var), var)"""
+        return ef_step_scalars(self.lib, self.ac, self.final_alpha, t, ratio, eta)
+
+    def ef_sample_xts(self, x0, noise, timesteps):
+        """sample_xts_from_x0 (:31-55): x0 [nimg,4,h,w], noise [nsteps, nimg, 4, h, w] in draw order -> xts [nsteps+1, nimg, 4, h, w]"""
+        x, nz = self._f32(x0), self._f32(noise)
+        n, nimg = len(timesteps), x.shape[0]
+        assert nz.shape == (n, *x.shape)
+        out = torch.empty(n + 1, *x.shape, device=self.device)
+        out[0] = x
+        ts, tsp = self._ts(timesteps)
+        self._call("pnpi_ef_sample_xts", _p(x), nimg, _p(nz), x[0].numel(), n, tsp, _p(out))
+        self._keep = (x, nz, ts)
+        return out
+
+    def ef_noise_map(self, eps, xt, xprev, t, ratio, eta, cfg_scale=None):
+        """One forward-process step (:151-171).  eps [nimg, 2, 4, h, w] (uncond, cond) with cfg_scale, or [nimg, 1, ...] without;
+        xt = xts[idx+1], xprev = xts[idx] [nimg, 4, h, w] -> (z, corrected xprev), new tensors."""
+        e, x = self._f32(eps), self._f32(xt)
+        xp = self._f32(xprev).clone()
+        nimg = x.shape[0]
+        z = torch.empty_like(x)
+        self._call("pnpi_ef_noise_map", _p(e), 1 if cfg_scale is not None else 0, float(cfg_scale or 0.0), _p(x), _p(xp), _p(z), nimg,
+                   x[0].numel(), int(t), int(ratio), float(eta))
+        self._keep = (e, x)
+        return z, xp
+
+    def ef_reverse_step(self, eps, x, z, t, ratio, eta, cfg_scales):
+        """CFG per prompt row + reverse_step (:179-208, :254-258): eps [nimg, 2P, 4, h, w], x [nimg, P, 4, h, w], z [nimg, 4, h, w]"""
+        e, xs, zz = self._f32(eps), self._f32(x), self._f32(z)
+        nimg, P = xs.shape[:2]
+        sc = np.ascontiguousarray(np.asarray(cfg_scales, dtype=np.float32))
+        assert sc.shape == (P,) and e.shape[1] == 2 * P
+        out = torch.empty_like(xs)
+        self._call("pnpi_ef_reverse_step", _p(e), _p(xs), _p(zz), nimg, P, xs[0, 0].numel(), sc.ctypes.data_as(C.POINTER(C.c_float)), int(t),
+                   int(ratio), float(eta), _p(out))
+        self._keep = (e, xs, zz, sc)
+        return out
+
+    def ef_invert(self, x0, noise, ctx_uncond, ctx_cond, cfg_scale, etas, timesteps):
+        """inversion_forward_process (:100-176) for nimg images, device-resident (pnpi_ef_invert).  x0 [nimg,4,h,w], noise
+        [nsteps, nimg, 4, h, w] (the draws in the reference's order), ctx_* [nimg, 77, D] (ctx_cond None: prompt "").
+        -> (xts [nsteps+1, nimg, 4, h, w], zs [nsteps, nimg, 4, h, w])"""
+        x, nz, cu = self._f32(x0), self._f32(noise), self._f32(ctx_uncond)
+        cc = self._f32(ctx_cond) if ctx_cond is not None else None
+        n, nimg = len(timesteps), x.shape[0]
+        if nz.shape != (n, *x.shape):
+            raise ValueError("noise must be [nsteps, nimg, 4, h, w] = %s, got %s" % ((n, *x.shape), tuple(nz.shape)))
+        e, ep = self._etas(etas, n)
+        ts, tsp = self._ts(timesteps)
+        xts = torch.empty(n + 1, *x.shape, device=self.device)
+        zs = torch.empty(n, *x.shape, device=self.device)
+        self._call("pnpi_ef_invert", _p(x), nimg, _p(nz), _p(cu), _p(cc), float(cfg_scale), ep, n, tsp, _p(xts), _p(zs))
+        self._keep = (x, nz, cu, cc, e, ts)
+        return xts, zs
+
+    def ef_edit(self, xT, zs, context, cfg_scales, ctrls, etas, timesteps):
+        """inversion_reverse_process (:210-262) with stored noise maps, device-resident (pnpi_ef_edit).  xT [nimg,4,h,w],
+        zs [nsteps_run, nimg, 4, h, w] (the first nsteps_run maps), context [nimg, 2P, 77, D] (P uncond rows, then P cond rows),
+        cfg_scales [P], ctrls None | [nimg] ControllerTables (P == 2), etas: number or [len(timesteps)], timesteps: the full schedule.
+        -> latents [nimg, P, 4, h, w]"""
+        x, z, ctx = self._f32(xT), self._f32(zs), self._f32(context)
+        nimg, P = x.shape[0], ctx.shape[1] // 2
+        n_run, n_tot = z.shape[0], len(timesteps)
+        if z.shape[1:] != x.shape or ctx.shape[:2] != (nimg, 2 * P):
+            raise ValueError("zs [nsteps_run, nimg, 4, h, w] and context [nimg, 2 * nprompts, 77, D] expected")
+        sc = np.ascontiguousarray(np.asarray(cfg_scales, dtype=np.float32))
+        if sc.shape != (P,):
+            raise ValueError("one guidance scale per prompt row (%d), got %s" % (P, sc.shape))
+        e, ep = self._etas(etas, n_tot)
+        ts, tsp = self._ts(timesteps)
+        arr = _desc_array(ctrls)
+        out = torch.empty(nimg, P, *x.shape[1:], device=self.device)
+        self._call("pnpi_ef_edit", _p(x), _p(z), nimg, P, _p(ctx), sc.ctypes.data_as(C.POINTER(C.c_float)), arr, ep, n_run, n_tot, tsp, _p(out))
+        self._keep = (x, z, ctx, sc, e, ts, arr, ctrls)
+        return out
+
+
+def ef_step_scalars(lib, alphas_cumprod, final_alpha, t, ratio, eta):
+    """pnpi_ef_step_scalars without a context (host only, no GPU): the six fp32 scalars of one edit-friendly step."""
+    ac = np.ascontiguousarray(np.asarray(alphas_cumprod, dtype=np.float32))
+    out = np.zeros(6, dtype=np.float32)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))       # noqa: E731
+    st = lib.pnpi_ef_step_scalars(fp(ac), len(ac), float(final_alpha), int(t), int(ratio), float(eta), fp(out))
+    if st != 0:
+        raise _capi.PnpiError(st, "pnpi_ef_step_scalars: invalid arguments")
+    return out
