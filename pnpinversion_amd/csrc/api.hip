@@ -1,12 +1,13 @@
 // libpnpi: C-ABI entry points + the static SD-1.x UNet / VAE graph executor and the device-resident DI / P2P loops.
 // See include/pnpi.h for the reference interface each entry point replaces.
-// One translation unit in six files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the level-2 loops, the
-// null-text optimisation, kernel-level test hooks) includes, in order,
+// One translation unit in seven files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the CLIP text encoder,
+// kernel-level test hooks) includes, in order,
 //   api_weights.inc   weight slots of the packed arena and the model builder
 //   api_graph.inc     profiling records, activation tape, op wrappers, ResNet / transformer blocks, unet_fwd
 //   api_backward.inc  reverse walk over the tape (gradient w.r.t. the unconditional embedding)
 //   api_vae.inc       AutoencoderKL encoder / decoder graph
 //   api_ctrl.inc      per-loop text K / V cache, controller descriptor -> device tables
+//   api_loops.inc     (last) the loop scaffold and the level-2 loops: DDIM / direct inversion, edit loops, edit-friendly DDPM, null-text
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -602,12 +603,17 @@ int pnpi_cfg_ddim_prev(pnpi_ctx* c, const float* eps, const float* x, int nimg, 
   if (prox < 0 || prox > 2 || (prox && !prox_threshold)) return fail(c, PNPI_EINVAL, "prox must be 0, or 1 / 2 with a threshold");
   float af, at; CKP(alphas_for(c, t, ratio, false, &af, &at));
   CKP(recon_check(c, recon));
-  const float* rref = prox ? recon_ref_at(recon, t) : nullptr;
-  const float* rinv = (prox && recon_inv_at(recon, t)) ? recon->inv_x_stars : nullptr;     // level 1: the caller points inv_x_stars at this step's x*_{t-1} [nimg][...]
-  const bool rc = rref || rinv;
-  const int S = c->cfg.sample_size;
-  CK(launch_cfg_ddim_prev(eps, x, nimg, rpi, row_elems, gs, af, at, noise_loss, offset_rows, target, offset_scale, offset_out, x_out, c->st,
-                          prox_threshold, prox, rref, rc ? recon->recon_lr : 0.f, rc ? recon->dilate_mask : 0, S, S, rinv));
+  CfgStepP s;
+  s.eps = eps; s.x = x; s.x_out = x_out; s.nimg = nimg; s.rows_per_img = rpi; s.row_elems = row_elems; s.gscale = gs; s.a_t = af; s.a_prev = at;
+  s.noise_loss = noise_loss; s.offset_rows = offset_rows; s.target = target; s.offset_scale = offset_scale; s.offset_out = offset_out;
+  s.prox_thr = prox_threshold; s.prox_mode = prox;
+  if (prox) {
+    s.recon_ref = recon_ref_at(recon, t);
+    if (recon_inv_at(recon, t)) s.inv_ref = recon->inv_x_stars;     // level 1: the caller points inv_x_stars at this step's x*_{t-1} [nimg][...]
+  }
+  if (s.recon_ref || s.inv_ref) { s.recon_lr = recon->recon_lr; s.dilate = recon->dilate_mask; }
+  s.lat_h = s.lat_w = c->cfg.sample_size;
+  CK(launch_cfg_ddim_prev(s, c->st));
   return 0;
 }
 
@@ -670,491 +676,22 @@ int pnpi_text_encode(pnpi_ctx* c, const int32_t* input_ids, int n, float* hidden
   return clip_fwd(c, (const int*)input_ids, n, hidden_out);
 }
 
-// ---- level 2 loops. Scratch for the loops lives at the top of the controller arena (after the controller tables).
-// The loops' text context is constant over their steps: project K / V once, then every forward of the loop reads the cache.
-struct LoopKV {
-  pnpi_ctx* c;
-  bool armed = false;
-  explicit LoopKV(pnpi_ctx* c_) : c(c_) {}
-  int begin(const float* context, int rows) {
-    if (!g_text_kv) return 0;
-    int r = text_kv_precompute(c, context, rows);
-    if (r) return r;
-    c->tkv.use = true;
-    armed = true;
-    return 0;
-  }
-  // a loop's projections belong to the loop's context: dropped at its end, so that a later pnpi_unet_forward(context = NULL) can
-  // never silently read them (it fails and names pnpi_text_kv_precompute instead)
-  ~LoopKV() { if (armed) { c->tkv.use = false; c->tkv.rows = 0; } }
-};
-int pnpi_ddim_invert(pnpi_ctx* c, const float* z0, int nimg, const float* ctx_cond, int nsteps, const int* ts, float* all) {
-  if (!c || !z0 || !ctx_cond || !ts || !all || nsteps <= 0) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size;
-  const int ratio = g.n_train_timesteps / nsteps;
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  float* eps = misc_f(c, (size_t)nimg * E);
-  CKH(hipMemcpyAsync(all, z0, (size_t)nimg * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  LoopKV kv(c);
-  CKP(kv.begin(ctx_cond, nimg));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[nsteps - i - 1];
-    const float* cur = all + (size_t)i * nimg * E;
-    int r = unet_fwd(c, cur, nimg, t, ctx_cond, false, 0, eps);
-    if (r) return r;
-    float af, at; CKP(alphas_for(c, t, ratio, true, &af, &at));
-    CK(launch_ddim_move(cur, eps, af, at, (size_t)nimg * E, all + (size_t)(i + 1) * nimg * E, c->st));
-  }
-  return 0;
-}
-
-static int upload_ints(pnpi_ctx* c, const std::vector<int>& v, int** dst);
-
-/* DirectInversion.ddim_with_guidance_scale_loop (inversion.py:334-347): inversion under classifier-free guidance.  The reference
- * makes two B=1 UNet calls per step (uncond, cond); here they are the two rows of one launch. */
-int pnpi_ddim_invert_cfg(pnpi_ctx* c, const float* z0, int nimg, const float* ctx_uncond, const float* ctx_cond, float gs, int nsteps,
-                         const int* ts, float* all) {
-  if (!c || !z0 || !ctx_uncond || !ctx_cond || !ts || !all || nsteps <= 0) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  const int ratio = g.n_train_timesteps / nsteps, rows = 2 * nimg;
-  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "nimg * 2 exceeds max_unet_rows");
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  float* eps = misc_f(c, (size_t)rows * E);
-  float* in = misc_f(c, (size_t)rows * E);
-  float* ctx2 = misc_f(c, (size_t)rows * CE);
-  std::vector<int> inmap(rows);
-  for (int i = 0; i < nimg; ++i) { inmap[2 * i] = i; inmap[2 * i + 1] = i; }
-  int* d_inmap;
-  CKP(upload_ints(c, inmap, &d_inmap));
-  for (int i = 0; i < nimg; ++i) {   // rows [img][uncond, cond]
-    CKH(hipMemcpyAsync(ctx2 + (size_t)(2 * i) * CE, ctx_uncond + (size_t)i * CE, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-    CKH(hipMemcpyAsync(ctx2 + (size_t)(2 * i + 1) * CE, ctx_cond + (size_t)i * CE, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  }
-  CKH(hipMemcpyAsync(all, z0, (size_t)nimg * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  LoopKV kv(c);
-  CKP(kv.begin(ctx2, rows));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[nsteps - i - 1];
-    const float* cur = all + (size_t)i * nimg * E;
-    CK(launch_gather_rows_f32(cur, d_inmap, rows, E, in, c->st));
-    int r = unet_fwd(c, in, rows, t, ctx2, false, 0, eps);
-    if (r) return r;
-    float af, at; CKP(alphas_for(c, t, ratio, true, &af, &at));
-    // noise = eps_u + gs * (eps_c - eps_u); next_step (the same fused kernel as the denoising direction, other alphas)
-    CK(launch_cfg_ddim_prev(eps, cur, nimg, 1, E, gs, af, at, nullptr, 0, nullptr, 1.f, nullptr, all + (size_t)(i + 1) * nimg * E, c->st));
-  }
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  return 0;
-}
-
-static int upload_ints(pnpi_ctx* c, const std::vector<int>& v, int** dst) {
-  *dst = (int*)c->ctrl_arena.alloc(v.size() * sizeof(int));
-  return upload(c, *dst, v.data(), v.size() * sizeof(int));
-}
-
-int pnpi_offset_calculate(pnpi_ctx* c, const float* lat_all, int nimg, const float* context4, int nsteps, const int* ts, float gs,
-                          const float* offset_scale_host, float* noise_loss_out) {
-  if (!c || !lat_all || !context4 || !ts || !noise_loss_out || nsteps <= 0) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size;
-  const int ratio = g.n_train_timesteps / nsteps, rows = 4 * nimg;
-  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "nimg * 4 exceeds max_unet_rows");
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  float* cur = misc_f(c, (size_t)nimg * 2 * E);
-  float* in = misc_f(c, (size_t)rows * E);
-  float* eps = misc_f(c, (size_t)rows * E);
-  std::vector<int> expand(nimg * 2), inmap(rows);
-  for (int i = 0; i < nimg; ++i) { expand[2 * i] = i; expand[2 * i + 1] = i; for (int k = 0; k < 4; ++k) inmap[4 * i + k] = 2 * i + (k & 1); }
-  int *d_expand, *d_inmap;
-  CKP(upload_ints(c, expand, &d_expand));
-  CKP(upload_ints(c, inmap, &d_inmap));
-  CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, nimg * 2, E, cur, c->st));
-  LoopKV kv(c);
-  CKP(kv.begin(context4, rows));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[i];
-    CK(launch_gather_rows_f32(cur, d_inmap, rows, E, in, c->st));
-    int r = unet_fwd(c, in, rows, t, context4, false, 0, eps);
-    if (r) return r;
-    float af, at; CKP(alphas_for(c, t, ratio, false, &af, &at));
-    const float* target = lat_all + (size_t)(nsteps - i - 1) * nimg * E;
-    CK(launch_cfg_ddim_prev(eps, cur, nimg, 2, E, gs, af, at, nullptr, 0, target, offset_scale_host ? offset_scale_host[i] : 1.f,
-                            noise_loss_out + (size_t)i * nimg * 2 * E, cur, c->st));
-  }
-  return 0;
-}
-
-// uncond_steps (nullable): [nsteps][nimg][77][768] per-step unconditional embeddings (null-text inversion).  p2p_guidance_forward uses the
-// step's embedding for every unconditional row of the image (p2p_guidance_forward.py:56-57); uncond_first_only = the single-branch variant
-// (:92: the first row only).  The text K / V are then projected once per STEP instead of once per loop.
-static int edit_loop_impl(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const float* noise_loss, int offset_rows,
-                          const pnpi_ctrl_desc* ctrl_host, int nsteps, const int* ts, float gs, int prox, float quantile,
-                          const pnpi_recon_desc* recon, float* latents_out, const float* uncond_steps, int uncond_first_only) {
-  if (!c || !x_T || !context4 || !ts || !latents_out || nsteps <= 0) return PNPI_EINVAL;
-  CKP(recon_check(c, recon));
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size;
-  const int ratio = g.n_train_timesteps / nsteps, rows = 4 * nimg;
-  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "nimg * 4 exceeds max_unet_rows");
-  if (ctrl_host) CKP(setup_ctrl(c, ctrl_host, nimg, rows));
-  else CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  const bool use_ctrl = ctrl_host != nullptr;
-  if (prox < 0 || prox > 2) return fail(c, PNPI_EINVAL, "prox must be 0 (none), 1 (l0) or 2 (l1)");
-  float* lat = misc_f(c, (size_t)nimg * 2 * E);
-  float* in = misc_f(c, (size_t)rows * E);
-  float* eps = misc_f(c, (size_t)rows * E);
-  float* thr = misc_f(c, (size_t)nimg);
-  std::vector<int> expand(nimg * 2), inmap(rows);
-  for (int i = 0; i < nimg; ++i) { expand[2 * i] = i; expand[2 * i + 1] = i; for (int k = 0; k < 4; ++k) inmap[4 * i + k] = 2 * i + (k & 1); }
-  int *d_expand, *d_inmap;
-  CKP(upload_ints(c, expand, &d_expand));
-  CKP(upload_ints(c, inmap, &d_inmap));
-  CK(launch_gather_rows_f32(x_T, d_expand, nimg * 2, E, lat, c->st));
-  if (prox && !(quantile > 0.f)) CK(launch_fill_f32(thr, nimg, -quantile, c->st));   // negative quantile = fixed threshold (:43-44)
-  const size_t CE = (size_t)g.ctx_len * g.cross_dim;
-  float* ctx_step = nullptr;
-  if (uncond_steps) {
-    ctx_step = misc_f(c, (size_t)rows * CE);
-    CKH(hipMemcpyAsync(ctx_step, context4, (size_t)rows * CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  }
-  LoopKV kv(c);
-  if (!uncond_steps) CKP(kv.begin(context4, rows));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[i];
-    const float* ctx_i = context4;
-    if (uncond_steps) {
-      for (int im = 0; im < nimg; ++im) {
-        const float* u = uncond_steps + ((size_t)i * nimg + im) * CE;
-        CKH(hipMemcpyAsync(ctx_step + (size_t)(4 * im) * CE, u, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-        if (!uncond_first_only) CKH(hipMemcpyAsync(ctx_step + (size_t)(4 * im + 1) * CE, u, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-      }
-      ctx_i = ctx_step;
-      CKP(kv.begin(ctx_i, rows));
-    }
-    CK(launch_gather_rows_f32(lat, d_inmap, rows, E, in, c->st));
-    int r = unet_fwd(c, in, rows, t, ctx_i, use_ctrl, i, eps);
-    if (r) return r;
-    float af, at; CKP(alphas_for(c, t, ratio, false, &af, &at));
-    const float* nl = noise_loss ? noise_loss + (size_t)i * nimg * 2 * E : nullptr;
-    if (prox && quantile > 0.f) CK(launch_quantile_abs_diff(eps, nimg, 2, E, quantile, thr, c->st));
-    const float* rref = prox ? recon_ref_at(recon, t) : nullptr;
-    // inversion guidance: x_stars[len(x_stars) - i - 2] (proximal_guidance_forward.py:75), one latent per image for both of its rows
-    const float* inv = (prox && recon_inv_at(recon, t)) ? recon->inv_x_stars + (size_t)(nsteps - 1 - i) * nimg * E : nullptr;
-    const bool rc = rref || inv;
-    CK(launch_cfg_ddim_prev(eps, lat, nimg, 2, E, gs, af, at, nl, offset_rows, nullptr, 1.f, nullptr, lat, c->st, prox ? thr : nullptr, prox,
-                            rref, rc ? recon->recon_lr : 0.f, rc ? recon->dilate_mask : 0, g.sample_size, g.sample_size, inv));
-    if (use_ctrl) CKP(apply_local_blend(c, lat, i));
-  }
-  CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * 2 * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  return 0;
-}
-int pnpi_edit_loop(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const float* noise_loss, int offset_rows,
-                   const pnpi_ctrl_desc* ctrl_host, int nsteps, const int* ts, float gs, int prox, float quantile,
-                   const pnpi_recon_desc* recon, float* latents_out) {
-  return edit_loop_impl(c, x_T, nimg, context4, noise_loss, offset_rows, ctrl_host, nsteps, ts, gs, prox, quantile, recon, latents_out, nullptr, 0);
-}
-int pnpi_edit_loop_uncond_steps(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const pnpi_ctrl_desc* ctrl_host, int nsteps,
-                                const int* ts, float gs, int prox, float quantile, const float* uncond_steps, int uncond_first_only,
-                                float* latents_out) {
-  if (!uncond_steps) return PNPI_EINVAL;
-  return edit_loop_impl(c, x_T, nimg, context4, nullptr, 1, ctrl_host, nsteps, ts, gs, prox, quantile, nullptr, latents_out, uncond_steps,
-                        uncond_first_only);
-}
-
-// the same with reconstruction guidance (null-text-inversion+proximal-guidance, use_reconstruction_guidance=True: p2p_editor.py:620-627)
-int pnpi_edit_loop_uncond_steps_recon(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const pnpi_ctrl_desc* ctrl_host, int nsteps,
-                                      const int* ts, float gs, int prox, float quantile, const float* uncond_steps, int uncond_first_only,
-                                      const pnpi_recon_desc* recon, float* latents_out) {
-  if (!uncond_steps) return PNPI_EINVAL;
-  return edit_loop_impl(c, x_T, nimg, context4, nullptr, 1, ctrl_host, nsteps, ts, gs, prox, quantile, recon, latents_out, uncond_steps,
-                        uncond_first_only);
-}
-
-/* offset_calculate + npass guidance-forward passes of P2PEditor.edit_image_directinversion (p2p_editor.py:99-160) advanced in
- * lock step: every pass walks the same timesteps and pass p's step i needs only noise_loss[i], which the offset pass produces
- * at the same step -- so one UNet launch per step serves all (1 + npass) * 4 * nimg rows. */
-int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* context4, int npass, const pnpi_ctrl_desc* ctrl_host,
-                     int offset_rows, int nsteps, const int* ts, float gs, const float* offset_scale_host, float* noise_loss_out,
-                     float* latents_out) {
-  if (!c || !lat_all || !context4 || !ts || !noise_loss_out || !latents_out || nsteps <= 0 || npass <= 0 || nimg <= 0) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size;
-  const size_t CE = (size_t)g.ctx_len * g.cross_dim;
-  const int ratio = g.n_train_timesteps / nsteps, NI = (1 + npass) * nimg, rows = 4 * NI;
-  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "(1 + npass) * nimg * 4 exceeds max_unet_rows");
-  std::vector<pnpi_ctrl_desc> cds(NI);
-  memset(cds.data(), 0, cds.size() * sizeof(pnpi_ctrl_desc));      // the offset pass (pseudo-images 0..nimg-1) runs no controller
-  if (ctrl_host) for (int i = 0; i < npass * nimg; ++i) cds[nimg + i] = ctrl_host[i];
-  CKP(setup_ctrl(c, cds.data(), NI, rows));
-  float* lat = misc_f(c, (size_t)NI * 2 * E);
-  float* in = misc_f(c, (size_t)rows * E);
-  float* eps = misc_f(c, (size_t)rows * E);
-  float* ctxrep = misc_f(c, (size_t)rows * CE);
-  std::vector<int> expand(NI * 2), inmap(rows), ctxmap(rows);
-  for (int q = 0; q < NI; ++q) {
-    const int img = q % nimg;
-    expand[2 * q] = img; expand[2 * q + 1] = img;
-    for (int k = 0; k < 4; ++k) { inmap[4 * q + k] = 2 * q + (k & 1); ctxmap[4 * q + k] = 4 * img + k; }
-  }
-  int *d_expand, *d_inmap, *d_ctxmap;
-  CKP(upload_ints(c, expand, &d_expand));
-  CKP(upload_ints(c, inmap, &d_inmap));
-  CKP(upload_ints(c, ctxmap, &d_ctxmap));
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, NI * 2, E, lat, c->st));
-  CK(launch_gather_rows_f32(context4, d_ctxmap, rows, CE, ctxrep, c->st));
-  LoopKV kv(c);
-  CKP(kv.begin(ctxrep, rows));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[i];
-    CK(launch_gather_rows_f32(lat, d_inmap, rows, E, in, c->st));
-    int r = unet_fwd(c, in, rows, t, ctxrep, true, i, eps);
-    if (r) return r;
-    float af, at; CKP(alphas_for(c, t, ratio, false, &af, &at));
-    const float* target = lat_all + (size_t)(nsteps - i - 1) * nimg * E;
-    float* nl = noise_loss_out + (size_t)i * nimg * 2 * E;
-    CK(launch_cfg_ddim_prev(eps, lat, nimg, 2, E, gs, af, at, nullptr, 0, target, offset_scale_host ? offset_scale_host[i] : 1.f, nl, lat, c->st));
-    for (int p = 1; p <= npass; ++p) {
-      float* lp = lat + (size_t)p * nimg * 2 * E;
-      CK(launch_cfg_ddim_prev(eps + (size_t)p * nimg * 4 * E, lp, nimg, 2, E, gs, af, at, nl, offset_rows, nullptr, 1.f, nullptr, lp, c->st));
-    }
-    CKP(apply_local_blend(c, lat, i));
-  }
-  CKH(hipMemcpyAsync(latents_out, lat + (size_t)nimg * 2 * E, (size_t)npass * nimg * 2 * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  return 0;
-}
-
-/* The pruned-equivalent schedule of SURVEY.md Note D (algebra, not approximation): in direct-inversion mode the source latent after
- * every step is prev + (x*_{t-1} - prev) == x*_{t-1}, and no controller ever touches the unconditional rows or the conditional
- * source row's output.  So the offset pass and the reconstruction pass are redundant, the source latent can be ASSIGNED from the
- * stored trajectory, and the unconditional-source row is dead: one 3-row launch per step and image
- * [uncond_tgt, cond_src (attention maps only), cond_tgt] instead of 12.  200 sample-forwards per image instead of 650.
- * context4 rows as everywhere: [unc_src, unc_tgt, cond_src, cond_tgt] per image (row 0 is not used). */
-int pnpi_direct_edit_pruned(pnpi_ctx* c, const float* lat_all, int nimg, const float* context4, const pnpi_ctrl_desc* ctrl_host,
-                            int nsteps, const int* ts, float gs, float* latents_out) {
-  if (!c || !lat_all || !context4 || !ts || !latents_out || nsteps <= 0 || nimg <= 0) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  const int ratio = g.n_train_timesteps / nsteps, rows = 3 * nimg;
-  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "3 * nimg exceeds max_unet_rows");
-  std::vector<pnpi_ctrl_desc> none(nimg);
-  memset(none.data(), 0, none.size() * sizeof(pnpi_ctrl_desc));
-  CKP(setup_ctrl(c, ctrl_host ? ctrl_host : none.data(), nimg, rows, 3, 1, 2));
-  float* lat = misc_f(c, (size_t)nimg * 2 * E);      // [img][src, tgt]
-  float* in = misc_f(c, (size_t)rows * E);
-  float* eps = misc_f(c, (size_t)rows * E);
-  float* eps2 = misc_f(c, (size_t)nimg * 2 * E);     // [img][unc_tgt, cond_tgt]
-  float* xt = misc_f(c, (size_t)nimg * E);
-  float* ctx3 = misc_f(c, (size_t)rows * CE);
-  std::vector<int> expand(nimg * 2), inmap(rows), ctxmap(rows), epsmap(nimg * 2), tgtmap(nimg);
-  for (int i = 0; i < nimg; ++i) {
-    expand[2 * i] = i; expand[2 * i + 1] = i;
-    inmap[3 * i] = 2 * i + 1; inmap[3 * i + 1] = 2 * i; inmap[3 * i + 2] = 2 * i + 1;
-    ctxmap[3 * i] = 4 * i + 1; ctxmap[3 * i + 1] = 4 * i + 2; ctxmap[3 * i + 2] = 4 * i + 3;
-    epsmap[2 * i] = 3 * i; epsmap[2 * i + 1] = 3 * i + 2;
-    tgtmap[i] = 2 * i + 1;
-  }
-  int *d_expand, *d_inmap, *d_ctxmap, *d_epsmap, *d_tgtmap;
-  CKP(upload_ints(c, expand, &d_expand)); CKP(upload_ints(c, inmap, &d_inmap)); CKP(upload_ints(c, ctxmap, &d_ctxmap));
-  CKP(upload_ints(c, epsmap, &d_epsmap)); CKP(upload_ints(c, tgtmap, &d_tgtmap));
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, nimg * 2, E, lat, c->st));      // both rows start from x*_T
-  CK(launch_gather_rows_f32(context4, d_ctxmap, rows, CE, ctx3, c->st));
-  LoopKV kv(c);
-  CKP(kv.begin(ctx3, rows));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[i];
-    CK(launch_gather_rows_f32(lat, d_inmap, rows, E, in, c->st));
-    int r = unet_fwd(c, in, rows, t, ctx3, true, i, eps);
-    if (r) return r;
-    float af, at; CKP(alphas_for(c, t, ratio, false, &af, &at));
-    CK(launch_gather_rows_f32(eps, d_epsmap, nimg * 2, E, eps2, c->st));
-    CK(launch_gather_rows_f32(lat, d_tgtmap, nimg, E, xt, c->st));
-    CK(launch_cfg_ddim_prev(eps2, xt, nimg, 1, E, gs, af, at, nullptr, 0, nullptr, 1.f, nullptr, xt, c->st));
-    // source latent := x*_{t-1} (assigned, not reconstructed); target latent := the step's result
-    const float* target = lat_all + (size_t)(nsteps - i - 1) * nimg * E;
-    CKH(hipMemcpy2DAsync(lat, 2 * E * sizeof(float), target, E * sizeof(float), E * sizeof(float), nimg, hipMemcpyDeviceToDevice, c->st));
-    CKH(hipMemcpy2DAsync(lat + E, 2 * E * sizeof(float), xt, E * sizeof(float), E * sizeof(float), nimg, hipMemcpyDeviceToDevice, c->st));
-    CKP(apply_local_blend(c, lat, i));
-  }
-  CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * 2 * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------- edit-friendly DDPM inversion
-// models/edit_friendly_ddm/inversion_utils.py (eta > 0: the forward process stores one noise map per step, the reverse process replays
-// them).  Scalars: ef_step_scalars (step.hip), the reference's 0-dim fp32 expressions in its order.
-int pnpi_ef_step_scalars(const float* alphas_cumprod, int n, float final_alpha, int t, int step_ratio, float eta, float* out6) {
-  if (!alphas_cumprod || !out6 || t < 0 || t >= n || step_ratio <= 0) return PNPI_EINVAL;
-  const int tp = t - step_ratio;
-  ef_step_scalars(alphas_cumprod[t], tp >= 0 ? alphas_cumprod[tp] : final_alpha, eta, out6);
-  return 0;
-}
-static int ef_scalars(pnpi_ctx* c, int t, int ratio, float eta, float* sc) {
-  if (!c->sched_set) return fail(c, PNPI_ESTATE, "pnpi_set_scheduler not called");
-  if (t < 0 || t >= (int)c->ac.size() || ratio <= 0) return fail(c, PNPI_EINVAL, "timestep out of range");
-  return pnpi_ef_step_scalars(c->ac.data(), (int)c->ac.size(), c->final_alpha, t, ratio, eta, sc);
-}
-// (sqrt(ab[t]), sqrt(1 - ab[t])) of level 1 + k, k in draw order (timestep ts[nsteps - 1 - k]), uploaded to the controller arena
-static int ef_levels(pnpi_ctx* c, int nsteps, const int* ts, float** dst) {
-  if (!c->sched_set) return fail(c, PNPI_ESTATE, "pnpi_set_scheduler not called");
-  std::vector<float> lev(2 * (size_t)nsteps);
-  for (int k = 0; k < nsteps; ++k) {
-    const int t = ts[nsteps - 1 - k];
-    if (t < 0 || t >= (int)c->ac.size()) return fail(c, PNPI_EINVAL, "timestep out of range");
-    lev[2 * k] = sqrtf(c->ac[t]);
-    lev[2 * k + 1] = sqrtf(1.0f - c->ac[t]);
-  }
-  *dst = misc_f(c, lev.size());
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  return upload(c, *dst, lev.data(), lev.size() * sizeof(float));
-}
-
-int pnpi_ef_sample_xts(pnpi_ctx* c, const float* x0, int nimg, const float* noise, size_t row_elems, int nsteps, const int* ts, float* xts_out) {
-  if (!c || !x0 || !noise || !ts || !xts_out || nimg <= 0 || nsteps <= 0 || row_elems == 0) return PNPI_EINVAL;
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  float* lev;
-  CKP(ef_levels(c, nsteps, ts, &lev));
-  CK(launch_ef_sample_xts(x0, noise, lev, nsteps, (size_t)nimg * row_elems, xts_out, c->st));
-  return 0;
-}
-
-int pnpi_ef_noise_map(pnpi_ctx* c, const float* eps, int cfg, float cfg_scale, const float* xt, float* xprev, float* z_out, int nimg,
-                      size_t row_elems, int t, int step_ratio, float eta) {
-  if (!c || !eps || !xt || !xprev || !z_out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
-  if (!(eta > 0.f)) return fail(c, PNPI_EINVAL, "edit-friendly inversion needs eta > 0 (eta = 0 stores no noise maps)");
-  float sc[6]; CKP(ef_scalars(c, t, step_ratio, eta, sc));
-  CK(launch_ef_noise_map(eps, cfg ? 1 : 0, cfg_scale, xt, xprev, z_out, nimg, row_elems, sc, c->st));
-  return 0;
-}
-
-int pnpi_ef_reverse_step(pnpi_ctx* c, const float* eps, const float* x, const float* z, int nimg, int nprompts, size_t row_elems,
-                         const float* cfg_scales_host, int t, int step_ratio, float eta, float* out) {
-  if (!c || !eps || !x || !z || !cfg_scales_host || !out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
-  if (nprompts != 1 && nprompts != 2) return fail(c, PNPI_EINVAL, "nprompts must be 1 or 2");
-  float sc[6]; CKP(ef_scalars(c, t, step_ratio, eta, sc));
-  CK(launch_ef_reverse_step(eps, x, z, nimg, nprompts, row_elems, cfg_scales_host[0], cfg_scales_host[nprompts - 1], sc, eta > 0.f ? 1 : 0,
-                            out, c->st));
-  return 0;
-}
-
-/* inversion_forward_process (inversion_utils.py:100-176) for nimg images: xts from x0 and the caller's draws, then for t = ts[0] .. ts[nsteps-1]
- * (idx = nsteps-1 .. 0) one UNet launch of the rows [img][uncond, cond] (uncond only when ctx_cond is NULL: prompt "") on xts[idx+1], and the
- * noise map / corrected xts[idx] of that step.  zs[0] is zeroed at the end (:173-174). */
-int pnpi_ef_invert(pnpi_ctx* c, const float* x0, int nimg, const float* noise, const float* ctx_uncond, const float* ctx_cond, float cfg_scale,
-                   const float* etas_host, int nsteps, const int* ts, float* xts_out, float* zs_out) {
-  if (!c || !x0 || !noise || !ctx_uncond || !etas_host || !ts || !xts_out || !zs_out || nimg <= 0 || nsteps <= 0) return PNPI_EINVAL;
-  for (int k = 0; k < nsteps; ++k)
-    if (!(etas_host[k] > 0.f)) return fail(c, PNPI_EINVAL, "edit-friendly inversion needs eta > 0 at every step");
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  const int ratio = g.n_train_timesteps / nsteps, rpi = ctx_cond ? 2 : 1, rows = rpi * nimg;
-  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "nimg * (1 + has_cond) exceeds max_unet_rows");
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  float* eps = misc_f(c, (size_t)rows * E);
-  float* in = misc_f(c, (size_t)rows * E);
-  float* ctx2 = misc_f(c, (size_t)rows * CE);
-  std::vector<int> inmap(rows);
-  for (int r = 0; r < rows; ++r) inmap[r] = r / rpi;
-  int* d_inmap;
-  CKP(upload_ints(c, inmap, &d_inmap));
-  float* lev;
-  CKP(ef_levels(c, nsteps, ts, &lev));
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  for (int i = 0; i < nimg; ++i) {   // rows [img][uncond, cond]
-    CKH(hipMemcpyAsync(ctx2 + (size_t)(rpi * i) * CE, ctx_uncond + (size_t)i * CE, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-    if (ctx_cond)
-      CKH(hipMemcpyAsync(ctx2 + (size_t)(rpi * i + 1) * CE, ctx_cond + (size_t)i * CE, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  }
-  const size_t L = (size_t)nimg * E;
-  CKH(hipMemcpyAsync(xts_out, x0, L * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  CK(launch_ef_sample_xts(x0, noise, lev, nsteps, L, xts_out, c->st));
-  LoopKV kv(c);
-  CKP(kv.begin(ctx2, rows));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[i], idx = nsteps - 1 - i;
-    const float* xt = xts_out + (size_t)(idx + 1) * L;
-    CK(launch_gather_rows_f32(xt, d_inmap, rows, E, in, c->st));
-    int r = unet_fwd(c, in, rows, t, ctx2, false, 0, eps);
-    if (r) return r;
-    float sc[6]; CKP(ef_scalars(c, t, ratio, etas_host[idx], sc));
-    CK(launch_ef_noise_map(eps, ctx_cond ? 1 : 0, cfg_scale, xt, xts_out + (size_t)idx * L, zs_out + (size_t)idx * L, nimg, E, sc, c->st));
-  }
-  CKH(hipMemsetAsync(zs_out, 0, L * sizeof(float), c->st));
-  return 0;
-}
-
-/* inversion_reverse_process (inversion_utils.py:210-262) with stored noise maps, nimg images x nprompts prompt rows: the last nsteps_run of the
- * nsteps_total timesteps, step k (0-based) at t = ts[nsteps_total - nsteps_run + k] replays zs[nsteps_run-1-k] with etas[nsteps_run-1-k].
- * One UNet launch of 2 * nprompts * nimg rows per step, per image [uncond_0 .. uncond_{P-1}, cond_0 .. cond_{P-1}] (the reference's uncond and
- * cond calls); with two prompts that is the controller layout [uncond_src, uncond_tgt, cond_src, cond_tgt], and the controller's step index
- * runs from 0 (the edit pass's own cur_step). */
-int pnpi_ef_edit(pnpi_ctx* c, const float* xT, const float* zs, int nimg, int nprompts, const float* context, const float* cfg_scales_host,
-                 const pnpi_ctrl_desc* ctrl_host, const float* etas_host, int nsteps_run, int nsteps_total, const int* ts, float* latents_out) {
-  if (!c || !xT || !zs || !context || !cfg_scales_host || !etas_host || !ts || !latents_out || nimg <= 0) return PNPI_EINVAL;
-  if (nprompts != 1 && nprompts != 2) return fail(c, PNPI_EINVAL, "nprompts must be 1 or 2");
-  if (nsteps_run <= 0 || nsteps_run > nsteps_total) return fail(c, PNPI_EINVAL, "need 0 < nsteps_run <= nsteps_total");
-  if (ctrl_host && nprompts != 2) return fail(c, PNPI_EINVAL, "an attention controller needs two prompts (source, target)");
-  if (ctrl_host)
-    for (int i = 0; i < nimg; ++i)
-      if (ctrl_host[i].lb_enabled) return fail(c, PNPI_EINVAL, "LocalBlend is not supported by the edit-friendly edit");
-  CKP(check_loop_ready(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size;
-  const int ratio = g.n_train_timesteps / nsteps_total, P = nprompts, rows = 2 * P * nimg;
-  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, "2 * nprompts * nimg exceeds max_unet_rows");
-  if (ctrl_host) CKP(setup_ctrl(c, ctrl_host, nimg, rows));
-  else CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  float* lat = misc_f(c, (size_t)nimg * P * E);
-  float* in = misc_f(c, (size_t)rows * E);
-  float* eps = misc_f(c, (size_t)rows * E);
-  std::vector<int> expand(nimg * P), inmap(rows);
-  for (int i = 0; i < nimg; ++i) {
-    for (int p = 0; p < P; ++p) expand[P * i + p] = i;
-    for (int k = 0; k < 2 * P; ++k) inmap[2 * P * i + k] = P * i + (k % P);
-  }
-  int *d_expand, *d_inmap;
-  CKP(upload_ints(c, expand, &d_expand));
-  CKP(upload_ints(c, inmap, &d_inmap));
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  CK(launch_gather_rows_f32(xT, d_expand, nimg * P, E, lat, c->st));      // xT.expand(batch_size, ...) (:240)
-  LoopKV kv(c);
-  CKP(kv.begin(context, rows));
-  for (int k = 0; k < nsteps_run; ++k) {
-    const int t = ts[nsteps_total - nsteps_run + k], idx = nsteps_run - 1 - k;
-    CK(launch_gather_rows_f32(lat, d_inmap, rows, E, in, c->st));
-    int r = unet_fwd(c, in, rows, t, context, ctrl_host != nullptr, k, eps);
-    if (r) return r;
-    const float eta = etas_host[idx];
-    float sc[6]; CKP(ef_scalars(c, t, ratio, eta, sc));
-    CK(launch_ef_reverse_step(eps, lat, zs + (size_t)idx * nimg * E, nimg, P, E, cfg_scales_host[0], cfg_scales_host[P - 1], sc,
-                              eta > 0.f ? 1 : 0, lat, c->st));
-  }
-  CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * P * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------- kernel-level ops
-int pnpi_op_conv(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int H, int W, int ksize, int stride, int pad,
-                 int ups, int Ho, int Wo, const void* w, const float* bias, const void* res, int N, void* out, int force_cfg,
-                 int force_split) {
+static int conv_hook(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int H, int W, int ksize, int stride, int pad, int ups,
+                     int Ho, int Wo, const void* w, const float* bias, const void* res, int N, void* out, int force_cfg, int force_split,
+                     float* stats_out, int* tile_rows_out) {
   GemmP p; gemm_defaults(p);
   p.x1 = (const half_t*)x1; p.x2 = (const half_t*)x2; p.C1 = C1; p.C2 = C2; p.ldx1 = C1; p.ldx2 = C2;
   p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.ksize = ksize; p.stride = stride; p.pad = pad; p.ups = ups;
   p.K = ksize * ksize * (C1 + C2); p.w = (const half_t*)w; p.ldw = p.K; p.M = B * Ho * Wo; p.N = N;
-  p.bias = bias; p.res = (const half_t*)res; p.ldres = N; p.out = (half_t*)out; p.ldo = N;
-  CK(launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, force_cfg, force_split));
+  p.bias = bias; p.res = (const half_t*)res; p.ldres = N; p.out = (half_t*)out; p.ldo = N; p.stats = stats_out;
+  CK(launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, force_cfg, force_split, nullptr, tile_rows_out));
   return 0;
+}
+int pnpi_op_conv(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int H, int W, int ksize, int stride, int pad,
+                 int ups, int Ho, int Wo, const void* w, const float* bias, const void* res, int N, void* out, int force_cfg,
+                 int force_split) {
+  return conv_hook(c, x1, x2, C1, C2, B, H, W, ksize, stride, pad, ups, Ho, Wo, w, bias, res, N, out, force_cfg, force_split, nullptr, nullptr);
 }
 /* conv + the per-(m-tile, channel) GroupNorm partial sums its epilogue produces (the statistics fusion of resnet_fwd): stats_out
  * [ceil(M / tile_rows)][N][2] fp32 = (sum, sum of squares) of the stored fp16 values; *tile_rows_out = rows per m-tile, 0 when the
@@ -1163,13 +700,7 @@ int pnpi_op_conv_stats(pnpi_ctx* c, const void* x1, const void* x2, int C1, int 
                        int ups, int Ho, int Wo, const void* w, const float* bias, const void* res, int N, void* out, int force_cfg,
                        int force_split, float* stats_out, int* tile_rows_out) {
   if (!c || !stats_out || !tile_rows_out) return PNPI_EINVAL;
-  GemmP p; gemm_defaults(p);
-  p.x1 = (const half_t*)x1; p.x2 = (const half_t*)x2; p.C1 = C1; p.C2 = C2; p.ldx1 = C1; p.ldx2 = C2;
-  p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.ksize = ksize; p.stride = stride; p.pad = pad; p.ups = ups;
-  p.K = ksize * ksize * (C1 + C2); p.w = (const half_t*)w; p.ldw = p.K; p.M = B * Ho * Wo; p.N = N;
-  p.bias = bias; p.res = (const half_t*)res; p.ldres = N; p.out = (half_t*)out; p.ldo = N; p.stats = stats_out;
-  CK(launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, force_cfg, force_split, nullptr, tile_rows_out));
-  return 0;
+  return conv_hook(c, x1, x2, C1, C2, B, H, W, ksize, stride, pad, ups, Ho, Wo, w, bias, res, N, out, force_cfg, force_split, stats_out, tile_rows_out);
 }
 /* process-wide kernel tuning knobs (tile-variant A/B inside one process, tests of non-default variants) */
 int pnpi_tile_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split, int* entry_m) {
@@ -1225,226 +756,6 @@ int pnpi_op_softmax_rows(pnpi_ctx* c, void* x, int M, int N, int ld) {
   CK(launch_softmax_rows((half_t*)x, M, N, ld, c->st));
   return 0;
 }
-// ---- differentiable UNet forward (null-text path groundwork)
-static int tape_ensure(pnpi_ctx* c) {
-  if (c->tape) return 0;
-  const pnpi_model_config& g = c->cfg;
-  // The activation arenas were sized at create for max_unet_rows rows of the plain forward (block temporaries released in stack order).
-  // A recording forward of ONE row keeps every temporary: measure it with a dry run and grow the arenas if that is more (set-up time
-  // only -- nothing is allocated in the optimisation loop).  New buffers are allocated BEFORE the old ones are freed and the context's
-  // state changes only after every allocation has succeeded: a failed hipMalloc leaves the context as it was (and without a tape).
-  std::unique_ptr<Tape> T(new Tape());
-  CKH(hipStreamSynchronize(c->st));
-  size_t pp, tp;
-  {
-    const Bump sp = c->persist, stmp = c->temp;
-    Tape* const prev = c->tape;
-    c->persist = Bump(); c->temp = Bump();
-    c->tape = T.get();
-    c->dry = true; T->rec = true;
-    const bool kv = c->tkv.use; c->tkv.use = false;
-    const int r = unet_fwd(c, nullptr, 1, 0, nullptr, false, 0, nullptr);
-    c->dry = false; T->rec = false; c->tkv.use = kv;
-    pp = align_up(c->persist.peak + (1 << 20), 4096); tp = align_up(c->temp.peak + (1 << 20), 4096);
-    c->persist = sp; c->temp = stmp; c->tape = prev;
-    if (r) return r;
-  }
-  // gradients + dgrad scratch of one UNet row: about 2.8x the recorded activations at SD-1.x width (1.1 of 0.4 GB); 6x with a 64 MB floor
-  const size_t gcap = align_up(std::max((size_t)64 << 20, 6 * (pp + tp)), 4096);
-  char *gbase = nullptr, *nper = nullptr, *ntmp = nullptr;
-  float* dctx = nullptr;
-  auto undo = [&]() { if (gbase) (void)hipFree(gbase); if (nper) (void)hipFree(nper); if (ntmp) (void)hipFree(ntmp); if (dctx) (void)hipFree(dctx); };
-  hipError_t e = hipMalloc((void**)&gbase, gcap);
-  if (e == hipSuccess) e = hipMalloc((void**)&dctx, (size_t)g.ctx_len * g.cross_dim * sizeof(float));
-  if (e == hipSuccess && pp > c->persist.cap) e = hipMalloc((void**)&nper, pp);
-  if (e == hipSuccess && tp > c->temp.cap) e = hipMalloc((void**)&ntmp, tp);
-  if (e != hipSuccess) { undo(); const std::string msg = std::string("null-text tape: ") + hipGetErrorString(e); return fail(c, PNPI_EHIP, msg.c_str()); }
-  if (nper) { (void)hipFree(c->persist.base); c->persist.base = nper; c->persist.cap = pp; }
-  if (ntmp) { (void)hipFree(c->temp.base); c->temp.base = ntmp; c->temp.cap = tp; }
-  c->persist.reset(); c->temp.reset(); c->persist.overflow = false; c->temp.overflow = false;
-  T->garena.base = gbase; T->garena.cap = gcap; T->d_ctx = dctx;
-  c->tape = T.release();
-  return 0;
-}
-// eps = UNet(latents, t, context) for ONE row, and d_context = (d loss / d eps)^T (d eps / d context) for the given d loss / d eps
-// (fp32, the layout of eps; pre-multiplied by the caller's power-of-two loss scale -- activations' gradients travel in fp16).
-int pnpi_unet_context_grad(pnpi_ctx* c, const float* latents, int t, const float* context, const float* d_eps, float* eps_out, float* d_context_out) {
-  if (!c || !latents || !context || !d_eps || !d_context_out) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  CKP(tape_ensure(c));
-  Tape& T = *c->tape;
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  float* eps = eps_out ? eps_out : misc_f(c, E);
-  T.ops.clear(); T.grads.clear(); T.garena.reset(); T.garena.overflow = false;
-  c->tkv.use = false;
-  T.rec = true;
-  int r = unet_fwd(c, latents, 1, t, context, false, 0, eps);
-  T.rec = false;
-  if (r) return r;
-  half_t* d_out = tape_galloc(c, (size_t)g.sample_size * g.sample_size * 8);
-  if (!d_out) return fail(c, PNPI_ENOMEM, "gradient arena overflow");
-  CK(launch_nchw_f32_to_nhwc_f16(d_eps, 1, g.in_channels, g.sample_size * g.sample_size, 8, d_out, c->st));
-  CKH(hipMemsetAsync(T.d_ctx, 0, CE * sizeof(float), c->st));
-  CKP(tape_backward(c, d_out));
-  CKH(hipMemcpyAsync(d_context_out, T.d_ctx, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  return 0;
-}
-
-// The Adam loop both optimisations share (inversion.py:203-218 and :430-447): eps_c = UNet(lat, t, ctx_cond) once, then up to
-// num_inner_steps x {recording forward with the current embedding `unc`, loss = mse(prev_step(CFG), target) and its gradient, reverse
-// walk to the embedding, Adam (torch.optim.Adam defaults, state fresh per DDIM step)}; the loss is read back for the reference's
-// early-stop test `loss < epsilon + i * 2e-5`.  eps2 = [eps_u | eps_c] (2E floats).  losses_host (nullable): [num_inner_steps].
-struct NullOptBufs { float *eps2, *d_eps, *am, *av, *loss_d; };
-static int null_inner_loop(pnpi_ctx* c, const NullOptBufs& b, const float* lat, int t, int i, float* unc, const float* ctx_cond,
-                           const float* target, float guidance_scale, float a_t, float a_p, int num_inner_steps, float epsilon,
-                           int* its_out, float* losses_host) {
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  const float scale = 4096.f;                                   // loss scale of the fp16 activation gradients (removed before Adam)
-  const double sa_t = sqrt((double)a_t), sb_t = sqrt(1.0 - a_t), sa_p = sqrt((double)a_p), sb_p = sqrt(1.0 - a_p);
-  const float c_x = (float)(sa_p / sa_t), c_e = (float)(sb_p - sa_p * sb_t / sa_t);       // rec = c_x x + c_e eps
-  const float lr = (float)(1e-2 * (1.0 - i / 100.0));
-  int its = 0;
-  c->tkv.use = false;
-  int r = unet_fwd(c, lat, 1, t, ctx_cond, false, 0, b.eps2 + E);
-  if (r) return r;
-  CKH(hipMemsetAsync(b.am, 0, CE * sizeof(float), c->st));
-  CKH(hipMemsetAsync(b.av, 0, CE * sizeof(float), c->st));
-  for (int j = 0; j < num_inner_steps; ++j) {
-    // forward with the tape recording; the loss head needs eps_u first, so forward and backward are two calls of the tape machinery
-    Tape& T = *c->tape;
-    T.ops.clear(); T.grads.clear(); T.garena.reset(); T.garena.overflow = false;
-    T.rec = true;
-    r = unet_fwd(c, lat, 1, t, unc, false, 0, b.eps2);
-    T.rec = false;
-    if (r) return r;
-    CK(launch_null_text_loss(b.eps2, b.eps2 + E, lat, target, (int)E, guidance_scale, c_x, c_e, scale, b.d_eps, b.loss_d, c->st));
-    half_t* d_out = tape_galloc(c, (size_t)g.sample_size * g.sample_size * 8);
-    if (!d_out) return fail(c, PNPI_ENOMEM, "gradient arena overflow");
-    CK(launch_nchw_f32_to_nhwc_f16(b.d_eps, 1, g.in_channels, g.sample_size * g.sample_size, 8, d_out, c->st));
-    CKH(hipMemsetAsync(T.d_ctx, 0, CE * sizeof(float), c->st));
-    CKP(tape_backward(c, d_out));
-    CK(launch_adam_step(unc, b.am, b.av, T.d_ctx, (int)CE, j + 1, lr, 1.f / scale, c->st));
-    float loss_h = 0.f;
-    CKH(hipMemcpyAsync(&loss_h, b.loss_d, sizeof(float), hipMemcpyDeviceToHost, c->st));
-    CKH(hipStreamSynchronize(c->st));
-    if (losses_host) losses_host[j] = loss_h;
-    its = j + 1;
-    c->ctr.unet_backward_rows += 1;
-    if (loss_h < epsilon + i * 2e-5f) break;
-  }
-  *its_out = its;
-  return 0;
-}
-static int null_bufs(pnpi_ctx* c, NullOptBufs& b) {
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  b.eps2 = misc_f(c, 2 * E); b.d_eps = misc_f(c, E); b.am = misc_f(c, CE); b.av = misc_f(c, CE); b.loss_d = misc_f(c, 1);
-  return 0;
-}
-
-// NullInversion.null_optimization (models/p2p/inversion.py:196-225) for one image, device resident.  ddim_latents [nsteps + 1][E] (the
-// inversion trajectory, x*_0 first), ctx_uncond / ctx_cond [77][768]; uncond_out [nsteps][77][768] receives the optimised embedding of
-// every step; then the CFG step with the optimised embedding moves the latent on.  losses_out (nullable, host): [nsteps][num_inner_steps]
-// loss of every Adam iteration (-1 for iterations the early stop skipped).
-int pnpi_null_text_optimize(pnpi_ctx* c, const float* ddim_latents, const float* ctx_uncond, const float* ctx_cond, int nsteps,
-                            const int* ts, float guidance_scale, int num_inner_steps, float epsilon, float* uncond_out, int* iters_out,
-                            float* losses_out) {
-  if (!c || !ddim_latents || !ctx_uncond || !ctx_cond || !ts || !uncond_out || nsteps <= 0 || num_inner_steps < 0) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  CKP(tape_ensure(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  const int ratio = g.n_train_timesteps / nsteps;
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  NullOptBufs b; null_bufs(c, b);
-  float* lat = misc_f(c, E);
-  float* unc = misc_f(c, CE);
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  if (losses_out) for (int k = 0; k < nsteps * num_inner_steps; ++k) losses_out[k] = -1.f;
-  CKH(hipMemcpyAsync(unc, ctx_uncond, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  CKH(hipMemcpyAsync(lat, ddim_latents + (size_t)nsteps * E, E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[i];
-    float a_t, a_p; CKP(alphas_for(c, t, ratio, false, &a_t, &a_p));
-    const float* target = ddim_latents + (size_t)(nsteps - i - 1) * E;
-    int its = 0;
-    if (num_inner_steps > 0)
-      CKP(null_inner_loop(c, b, lat, t, i, unc, ctx_cond, target, guidance_scale, a_t, a_p, num_inner_steps, epsilon, &its,
-                          losses_out ? losses_out + (size_t)i * num_inner_steps : nullptr));
-    if (iters_out) iters_out[i] = its;
-    CKH(hipMemcpyAsync(uncond_out + (size_t)i * CE, unc, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
-    // latent_cur = prev_step(CFG(eps(unc), eps(cond)))   (get_noise_pred with the optimised embedding, inversion.py:221-224)
-    c->tkv.use = false;
-    int r = unet_fwd(c, lat, 1, t, unc, false, 0, b.eps2);
-    if (r) return r;
-    if (num_inner_steps == 0) { r = unet_fwd(c, lat, 1, t, ctx_cond, false, 0, b.eps2 + E); if (r) return r; }
-    CK(launch_cfg_ddim_prev(b.eps2, lat, 1, 1, E, guidance_scale, a_t, a_p, nullptr, 0, nullptr, 1.f, nullptr, lat, c->st));
-  }
-  return 0;
-}
-
-// DirectInversion.null_latent_calculate (models/p2p/inversion.py:419-460, "ablation_null-latent-inversion+p2p") for one (source, target)
-// prompt pair.  context4 rows = [unc_src, unc_tgt, cond_src, cond_tgt].  Per step: the unconditional embeddings are optimised as in
-// null-text inversion -- the reference's loss reads the SOURCE row only (:441), so the target row's embedding has a zero gradient, Adam
-// leaves it where it is, and only the source row needs the recording forward / reverse walk; its conditional prediction is constant over
-// the iterations -- then the step's effect becomes a latent offset for both rows:
-//   noise_loss[i] = prev_step(CFG with the optimised embeddings) - prev_step(CFG with the ORIGINAL ones),  latent_cur = plain + noise_loss[i]
-// (:449-459).  The two 4-row forwards run with rows ordered [unc_src, cond_src, unc_tgt, cond_tgt] (row results do not depend on the
-// order) so that the step kernel sees them as two one-row images.  noise_loss_out [nsteps][2][E].
-int pnpi_null_latent_calculate(pnpi_ctx* c, const float* ddim_latents, const float* context4, int nsteps, const int* ts, float guidance_scale,
-                               int num_inner_steps, float epsilon, float* noise_loss_out, int* iters_out, float* losses_out) {
-  if (!c || !ddim_latents || !context4 || !ts || !noise_loss_out || nsteps <= 0 || num_inner_steps < 0) return PNPI_EINVAL;
-  CKP(check_loop_ready(c));
-  if (c->max_rows < 4) return fail(c, PNPI_EINVAL, "null-latent inversion needs max_unet_rows >= 4");
-  CKP(tape_ensure(c));
-  const pnpi_model_config& g = c->cfg;
-  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
-  const int ratio = g.n_train_timesteps / nsteps;
-  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
-  NullOptBufs b; null_bufs(c, b);
-  float* cur = misc_f(c, 2 * E);          // latent_cur [src, tgt]
-  float* in4 = misc_f(c, 4 * E);          // [src, src, tgt, tgt]
-  float* eps4 = misc_f(c, 4 * E);
-  float* opt = misc_f(c, 2 * E);
-  float* unc = misc_f(c, 2 * CE);         // the embeddings being optimised [src, tgt] (warm-started from step to step)
-  float* ctx4 = misc_f(c, 4 * CE);        // [unc_src, cond_src, unc_tgt, cond_tgt] of the forward at hand
-  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
-  if (losses_out) for (int k = 0; k < nsteps * num_inner_steps; ++k) losses_out[k] = -1.f;
-  const float* cond = context4 + 2 * CE;
-  auto d2d = [&](float* d, const float* s, size_t n) { return hipMemcpyAsync(d, s, n * sizeof(float), hipMemcpyDeviceToDevice, c->st); };
-  CKH(d2d(unc, context4, 2 * CE));
-  CKH(d2d(cur, ddim_latents + (size_t)nsteps * E, E));
-  CKH(d2d(cur + E, ddim_latents + (size_t)nsteps * E, E));
-  CKH(d2d(ctx4 + CE, cond, CE));
-  CKH(d2d(ctx4 + 3 * CE, cond + CE, CE));
-  for (int i = 0; i < nsteps; ++i) {
-    const int t = ts[i];
-    float a_t, a_p; CKP(alphas_for(c, t, ratio, false, &a_t, &a_p));
-    const float* target = ddim_latents + (size_t)(nsteps - i - 1) * E;
-    int its = 0;
-    if (num_inner_steps > 0)
-      CKP(null_inner_loop(c, b, cur, t, i, unc, cond, target, guidance_scale, a_t, a_p, num_inner_steps, epsilon, &its,
-                          losses_out ? losses_out + (size_t)i * num_inner_steps : nullptr));
-    if (iters_out) iters_out[i] = its;
-    CKH(d2d(in4, cur, E)); CKH(d2d(in4 + E, cur, E)); CKH(d2d(in4 + 2 * E, cur + E, E)); CKH(d2d(in4 + 3 * E, cur + E, E));
-    c->tkv.use = false;
-    // with the optimised embeddings -> opt
-    CKH(d2d(ctx4, unc, CE)); CKH(d2d(ctx4 + 2 * CE, unc + CE, CE));
-    int r = unet_fwd(c, in4, 4, t, ctx4, false, 0, eps4);
-    if (r) return r;
-    CK(launch_cfg_ddim_prev(eps4, cur, 2, 1, E, guidance_scale, a_t, a_p, nullptr, 0, nullptr, 1.f, nullptr, opt, c->st));
-    // with the original ones -> plain; loss = opt - plain; latent_cur = plain + loss
-    CKH(d2d(ctx4, context4, CE)); CKH(d2d(ctx4 + 2 * CE, context4 + CE, CE));
-    r = unet_fwd(c, in4, 4, t, ctx4, false, 0, eps4);
-    if (r) return r;
-    CK(launch_cfg_ddim_prev(eps4, cur, 2, 1, E, guidance_scale, a_t, a_p, nullptr, 0, opt, 1.f, noise_loss_out + (size_t)i * 2 * E, cur, c->st));
-  }
-  return 0;
-}
-
 int pnpi_op_attention_bwd(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* v, int ldv, int v_off,
                           const void* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, void* dq, void* dk, void* dv,
                           void* scratch, size_t scratch_bytes) {
@@ -1535,5 +846,7 @@ int pnpi_op_local_blend_sub(pnpi_ctx* c, const float* lb_acc, int nslots, int ma
   CK(launch_local_blend(lb_acc, nslots, map_hw, lat_hw, C, th, latents, nimg, c->st, 4, th_sub));
   return 0;
 }
+
+#include "api_loops.inc"
 
 }  // extern "C"

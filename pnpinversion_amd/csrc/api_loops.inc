@@ -1,0 +1,674 @@
+// api_loops.inc -- part of api.hip (one translation unit: included there, last, inside its extern "C" block; not compiled on its own).
+// the level-2 entry points: whole inversion / editing loops in one C call (DDIM, direct inversion, Prompt-to-Prompt edit loops,
+// edit-friendly DDPM, null-text optimisation)
+// ---------------------------------------------------------------------------------------------------- loop scaffold
+// The loops' text context is constant over their steps: project K / V once, then every forward of the loop reads the cache.
+struct LoopKV {
+  pnpi_ctx* c;
+  bool armed = false;
+  explicit LoopKV(pnpi_ctx* c_) : c(c_) {}
+  int begin(const float* context, int rows) {
+    if (!g_text_kv) return 0;
+    int r = text_kv_precompute(c, context, rows);
+    if (r) return r;
+    c->tkv.use = true;
+    armed = true;
+    return 0;
+  }
+  // a loop's projections belong to the loop's context: dropped at its end, so that a later pnpi_unet_forward(context = NULL) can
+  // never silently read them (it fails and names pnpi_text_kv_precompute instead)
+  ~LoopKV() { if (armed) { c->tkv.use = false; c->tkv.rows = 0; } }
+};
+// What every loop sets up before its first step.  Scratch lives at the top of the controller arena (after the controller tables):
+//   loop_begin    entry checks, E / CE / ratio, the controller tables (setup_ctrl resets the arena)
+//   misc_f ...    the loop's own scratch;  loop_map / loop_maps_cfg: its row maps, built on the host
+//   loop_commit   the step buffers, ONE overflow test before anything is launched on that scratch, one upload of all the maps
+//   loop_unet     a step's prologue: gather the rows of the launch, run the UNet on them
+struct Loop {
+  pnpi_ctx* c;
+  size_t E = 0, CE = 0;                        // floats per latent row / per context row
+  int ratio = 0, rows = 0;                     // scheduler stride; UNet rows per launch
+  float *in = nullptr, *eps = nullptr;         // [rows][E] gathered input (loops with row maps only) and prediction of a step
+  LoopKV kv;
+  std::vector<int> maps;                       // host copy of all row maps, back to back
+  std::vector<std::pair<int**, size_t>> map_dst;
+  explicit Loop(pnpi_ctx* c_) : c(c_), kv(c_) {}
+};
+// cds (nullable): controller descriptors of the nq (pseudo-)images of the launch, rows = rpi * nq
+static int loop_begin(Loop& L, int nsteps, int rows, const char* too_many_rows, const pnpi_ctrl_desc* cds = nullptr, int nq = 0, int rpi = 4,
+                      int src_off = 2, int tgt_off = 3) {
+  pnpi_ctx* c = L.c;
+  CKP(check_loop_ready(c));
+  const pnpi_model_config& g = c->cfg;
+  L.E = (size_t)g.in_channels * g.sample_size * g.sample_size; L.CE = (size_t)g.ctx_len * g.cross_dim;
+  L.ratio = g.n_train_timesteps / nsteps; L.rows = rows;
+  if (rows > c->max_rows) return fail(c, PNPI_EINVAL, too_many_rows);
+  return cds ? setup_ctrl(c, cds, nq, rows, rpi, src_off, tgt_off) : setup_ctrl(c, nullptr, 0, c->max_rows);
+}
+static void loop_map(Loop& L, const std::vector<int>& m, int** dev) {      // *dev is valid after loop_commit
+  L.map_dst.push_back({dev, L.maps.size()});
+  L.maps.insert(L.maps.end(), m.begin(), m.end());
+}
+// nq (pseudo-)images of P latents and 2 P rows [uncond_0 .. uncond_{P-1}, cond_0 .. cond_{P-1}] each; pseudo-image q starts from image
+// q % nimg:  expand: image -> its P latents,  inmap: latents -> rows.  P = 2 is the layout [unc_src, unc_tgt, cond_src, cond_tgt].
+static void loop_maps_cfg(Loop& L, int nq, int nimg, int P, int** d_expand, int** d_inmap) {
+  std::vector<int> expand(nq * P), inmap(nq * 2 * P);
+  for (int q = 0; q < nq; ++q) {
+    for (int p = 0; p < P; ++p) expand[P * q + p] = q % nimg;
+    for (int k = 0; k < 2 * P; ++k) inmap[2 * P * q + k] = P * q + k % P;
+  }
+  loop_map(L, expand, d_expand);
+  loop_map(L, inmap, d_inmap);
+}
+static int loop_commit(Loop& L, bool step_bufs = true) {
+  pnpi_ctx* c = L.c;
+  if (step_bufs) L.eps = misc_f(c, (size_t)L.rows * L.E);
+  if (step_bufs && !L.maps.empty()) L.in = misc_f(c, (size_t)L.rows * L.E);
+  int* d = (int*)c->ctrl_arena.alloc(L.maps.size() * sizeof(int));
+  // Bump::alloc hands out the arena's base on overflow: nothing may be launched on (or uploaded to) such scratch
+  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
+  for (auto& m : L.map_dst) *m.first = d + m.second;
+  return L.maps.empty() ? 0 : upload(c, d, L.maps.data(), L.maps.size() * sizeof(int));
+}
+// inmap == NULL: lat already holds the rows of the launch
+static int loop_unet(Loop& L, const float* lat, const int* inmap, int t, const float* ctx, bool use_ctrl, int step) {
+  pnpi_ctx* c = L.c;
+  if (inmap) { CK(launch_gather_rows_f32(lat, inmap, L.rows, L.E, L.in, c->st)); lat = L.in; }
+  return unet_fwd(c, lat, L.rows, t, ctx, use_ctrl, step, L.eps);
+}
+// dst rows [img][uncond, cond] (ctx_cond == NULL: [img][uncond])
+static int interleave_ctx(pnpi_ctx* c, float* dst, const float* ctx_uncond, const float* ctx_cond, int nimg, size_t CE) {
+  const size_t w = CE * sizeof(float), pitch = (ctx_cond ? 2 : 1) * w;
+  CKH(hipMemcpy2DAsync(dst, pitch, ctx_uncond, w, w, nimg, hipMemcpyDeviceToDevice, c->st));
+  if (ctx_cond) CKH(hipMemcpy2DAsync(dst + CE, pitch, ctx_cond, w, w, nimg, hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+// the plain CFG + DDIM step of a loop: P latents per image, rows [uncond x P, cond x P] of eps
+static CfgStepP cfg_step(const Loop& L, const float* eps, const float* x, int nimg, int P, float gs, float a_from, float a_to, float* x_out) {
+  CfgStepP s;
+  s.eps = eps; s.x = x; s.nimg = nimg; s.rows_per_img = P; s.row_elems = L.E; s.gscale = gs; s.a_t = a_from; s.a_prev = a_to; s.x_out = x_out;
+  return s;
+}
+
+// ---------------------------------------------------------------------------------------------------- DDIM / direct inversion
+int pnpi_ddim_invert(pnpi_ctx* c, const float* z0, int nimg, const float* ctx_cond, int nsteps, const int* ts, float* all) {
+  if (!c || !z0 || !ctx_cond || !ts || !all || nsteps <= 0) return PNPI_EINVAL;
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, nimg, "nimg exceeds max_unet_rows"));
+  CKP(loop_commit(L));
+  const size_t E = L.E;
+  CKH(hipMemcpyAsync(all, z0, (size_t)nimg * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  CKP(L.kv.begin(ctx_cond, nimg));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[nsteps - i - 1];
+    const float* cur = all + (size_t)i * nimg * E;
+    CKP(loop_unet(L, cur, nullptr, t, ctx_cond, false, 0));
+    float af, at; CKP(alphas_for(c, t, L.ratio, true, &af, &at));
+    CK(launch_ddim_move(cur, L.eps, af, at, (size_t)nimg * E, all + (size_t)(i + 1) * nimg * E, c->st));
+  }
+  return 0;
+}
+
+/* DirectInversion.ddim_with_guidance_scale_loop (inversion.py:334-347): inversion under classifier-free guidance.  The reference
+ * makes two B=1 UNet calls per step (uncond, cond); here they are the two rows of one launch. */
+int pnpi_ddim_invert_cfg(pnpi_ctx* c, const float* z0, int nimg, const float* ctx_uncond, const float* ctx_cond, float gs, int nsteps,
+                         const int* ts, float* all) {
+  if (!c || !z0 || !ctx_uncond || !ctx_cond || !ts || !all || nsteps <= 0) return PNPI_EINVAL;
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 2 * nimg, "nimg * 2 exceeds max_unet_rows"));
+  const size_t E = L.E;
+  float* ctx2 = misc_f(c, (size_t)L.rows * L.CE);
+  std::vector<int> inmap(L.rows);
+  for (int r = 0; r < L.rows; ++r) inmap[r] = r / 2;
+  int* d_inmap;
+  loop_map(L, inmap, &d_inmap);
+  CKP(loop_commit(L));
+  CKP(interleave_ctx(c, ctx2, ctx_uncond, ctx_cond, nimg, L.CE));
+  CKH(hipMemcpyAsync(all, z0, (size_t)nimg * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  CKP(L.kv.begin(ctx2, L.rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[nsteps - i - 1];
+    const float* cur = all + (size_t)i * nimg * E;
+    CKP(loop_unet(L, cur, d_inmap, t, ctx2, false, 0));
+    float af, at; CKP(alphas_for(c, t, L.ratio, true, &af, &at));
+    // noise = eps_u + gs * (eps_c - eps_u); next_step (the same fused kernel as the denoising direction, other alphas)
+    CK(launch_cfg_ddim_prev(cfg_step(L, L.eps, cur, nimg, 1, gs, af, at, all + (size_t)(i + 1) * nimg * E), c->st));
+  }
+  return 0;
+}
+
+int pnpi_offset_calculate(pnpi_ctx* c, const float* lat_all, int nimg, const float* context4, int nsteps, const int* ts, float gs,
+                          const float* offset_scale_host, float* noise_loss_out) {
+  if (!c || !lat_all || !context4 || !ts || !noise_loss_out || nsteps <= 0) return PNPI_EINVAL;
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 4 * nimg, "nimg * 4 exceeds max_unet_rows"));
+  const size_t E = L.E;
+  float* cur = misc_f(c, (size_t)nimg * 2 * E);
+  int *d_expand, *d_inmap;
+  loop_maps_cfg(L, nimg, nimg, 2, &d_expand, &d_inmap);
+  CKP(loop_commit(L));
+  CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, nimg * 2, E, cur, c->st));
+  CKP(L.kv.begin(context4, L.rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i];
+    CKP(loop_unet(L, cur, d_inmap, t, context4, false, 0));
+    float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
+    CfgStepP s = cfg_step(L, L.eps, cur, nimg, 2, gs, af, at, cur);
+    s.target = lat_all + (size_t)(nsteps - i - 1) * nimg * E; s.offset_scale = offset_scale_host ? offset_scale_host[i] : 1.f;
+    s.offset_out = noise_loss_out + (size_t)i * nimg * 2 * E;
+    CK(launch_cfg_ddim_prev(s, c->st));
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- edit loops
+// uncond_steps (nullable): [nsteps][nimg][77][768] per-step unconditional embeddings (null-text inversion).  p2p_guidance_forward uses the
+// step's embedding for every unconditional row of the image (p2p_guidance_forward.py:56-57); uncond_first_only = the single-branch variant
+// (:92: the first row only).  The text K / V are then projected once per STEP instead of once per loop.
+static int edit_loop_impl(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const float* noise_loss, int offset_rows,
+                          const pnpi_ctrl_desc* ctrl_host, int nsteps, const int* ts, float gs, int prox, float quantile,
+                          const pnpi_recon_desc* recon, float* latents_out, const float* uncond_steps, int uncond_first_only) {
+  if (!c || !x_T || !context4 || !ts || !latents_out || nsteps <= 0) return PNPI_EINVAL;
+  CKP(recon_check(c, recon));
+  if (prox < 0 || prox > 2) return fail(c, PNPI_EINVAL, "prox must be 0 (none), 1 (l0) or 2 (l1)");
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 4 * nimg, "nimg * 4 exceeds max_unet_rows", ctrl_host, nimg));
+  const size_t E = L.E, CE = L.CE; const int rows = L.rows, S = c->cfg.sample_size;
+  const bool use_ctrl = ctrl_host != nullptr;
+  float* lat = misc_f(c, (size_t)nimg * 2 * E);
+  float* thr = misc_f(c, (size_t)nimg);
+  float* ctx_step = uncond_steps ? misc_f(c, (size_t)rows * CE) : nullptr;
+  int *d_expand, *d_inmap;
+  loop_maps_cfg(L, nimg, nimg, 2, &d_expand, &d_inmap);
+  CKP(loop_commit(L));
+  CK(launch_gather_rows_f32(x_T, d_expand, nimg * 2, E, lat, c->st));
+  if (prox && !(quantile > 0.f)) CK(launch_fill_f32(thr, nimg, -quantile, c->st));   // negative quantile = fixed threshold (:43-44)
+  if (uncond_steps) CKH(hipMemcpyAsync(ctx_step, context4, (size_t)rows * CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  else CKP(L.kv.begin(context4, rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i];
+    const float* ctx_i = context4;
+    if (uncond_steps) {
+      for (int im = 0; im < nimg; ++im) {
+        const float* u = uncond_steps + ((size_t)i * nimg + im) * CE;
+        CKH(hipMemcpyAsync(ctx_step + (size_t)(4 * im) * CE, u, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+        if (!uncond_first_only) CKH(hipMemcpyAsync(ctx_step + (size_t)(4 * im + 1) * CE, u, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+      }
+      ctx_i = ctx_step;
+      CKP(L.kv.begin(ctx_i, rows));
+    }
+    CKP(loop_unet(L, lat, d_inmap, t, ctx_i, use_ctrl, i));
+    float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
+    CfgStepP s = cfg_step(L, L.eps, lat, nimg, 2, gs, af, at, lat);
+    if (noise_loss) { s.noise_loss = noise_loss + (size_t)i * nimg * 2 * E; s.offset_rows = offset_rows; }
+    if (prox) {
+      if (quantile > 0.f) CK(launch_quantile_abs_diff(L.eps, nimg, 2, E, quantile, thr, c->st));
+      s.prox_thr = thr; s.prox_mode = prox;
+      s.recon_ref = recon_ref_at(recon, t);
+      // inversion guidance: x_stars[len(x_stars) - i - 2] (proximal_guidance_forward.py:75), one latent per image for both of its rows
+      if (recon_inv_at(recon, t)) s.inv_ref = recon->inv_x_stars + (size_t)(nsteps - 1 - i) * nimg * E;
+      if (s.recon_ref || s.inv_ref) { s.recon_lr = recon->recon_lr; s.dilate = recon->dilate_mask; s.lat_h = s.lat_w = S; }
+    }
+    CK(launch_cfg_ddim_prev(s, c->st));
+    if (use_ctrl) CKP(apply_local_blend(c, lat, i));
+  }
+  CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * 2 * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+int pnpi_edit_loop(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const float* noise_loss, int offset_rows,
+                   const pnpi_ctrl_desc* ctrl_host, int nsteps, const int* ts, float gs, int prox, float quantile,
+                   const pnpi_recon_desc* recon, float* latents_out) {
+  return edit_loop_impl(c, x_T, nimg, context4, noise_loss, offset_rows, ctrl_host, nsteps, ts, gs, prox, quantile, recon, latents_out, nullptr, 0);
+}
+int pnpi_edit_loop_uncond_steps(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const pnpi_ctrl_desc* ctrl_host, int nsteps,
+                                const int* ts, float gs, int prox, float quantile, const float* uncond_steps, int uncond_first_only,
+                                float* latents_out) {
+  return pnpi_edit_loop_uncond_steps_recon(c, x_T, nimg, context4, ctrl_host, nsteps, ts, gs, prox, quantile, uncond_steps, uncond_first_only, nullptr, latents_out);
+}
+// the same with reconstruction guidance (null-text-inversion+proximal-guidance, use_reconstruction_guidance=True: p2p_editor.py:620-627)
+int pnpi_edit_loop_uncond_steps_recon(pnpi_ctx* c, const float* x_T, int nimg, const float* context4, const pnpi_ctrl_desc* ctrl_host, int nsteps,
+                                      const int* ts, float gs, int prox, float quantile, const float* uncond_steps, int uncond_first_only,
+                                      const pnpi_recon_desc* recon, float* latents_out) {
+  if (!uncond_steps) return PNPI_EINVAL;
+  return edit_loop_impl(c, x_T, nimg, context4, nullptr, 1, ctrl_host, nsteps, ts, gs, prox, quantile, recon, latents_out, uncond_steps,
+                        uncond_first_only);
+}
+
+/* offset_calculate + npass guidance-forward passes of P2PEditor.edit_image_directinversion (p2p_editor.py:99-160) advanced in
+ * lock step: every pass walks the same timesteps and pass p's step i needs only noise_loss[i], which the offset pass produces
+ * at the same step -- so one UNet launch per step serves all (1 + npass) * 4 * nimg rows. */
+int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* context4, int npass, const pnpi_ctrl_desc* ctrl_host,
+                     int offset_rows, int nsteps, const int* ts, float gs, const float* offset_scale_host, float* noise_loss_out,
+                     float* latents_out) {
+  if (!c || !lat_all || !context4 || !ts || !noise_loss_out || !latents_out || nsteps <= 0 || npass <= 0 || nimg <= 0) return PNPI_EINVAL;
+  const int NI = (1 + npass) * nimg;
+  std::vector<pnpi_ctrl_desc> cds(NI);
+  memset(cds.data(), 0, cds.size() * sizeof(pnpi_ctrl_desc));      // the offset pass (pseudo-images 0..nimg-1) runs no controller
+  if (ctrl_host) for (int i = 0; i < npass * nimg; ++i) cds[nimg + i] = ctrl_host[i];
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 4 * NI, "(1 + npass) * nimg * 4 exceeds max_unet_rows", cds.data(), NI));
+  const size_t E = L.E, CE = L.CE; const int rows = L.rows;
+  float* lat = misc_f(c, (size_t)NI * 2 * E);
+  float* ctxrep = misc_f(c, (size_t)rows * CE);
+  std::vector<int> ctxmap(rows);
+  for (int r = 0; r < rows; ++r) ctxmap[r] = 4 * (r / 4 % nimg) + r % 4;
+  int *d_expand, *d_inmap, *d_ctxmap;
+  loop_maps_cfg(L, NI, nimg, 2, &d_expand, &d_inmap);
+  loop_map(L, ctxmap, &d_ctxmap);
+  CKP(loop_commit(L));
+  CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, NI * 2, E, lat, c->st));
+  CK(launch_gather_rows_f32(context4, d_ctxmap, rows, CE, ctxrep, c->st));
+  CKP(L.kv.begin(ctxrep, rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i];
+    CKP(loop_unet(L, lat, d_inmap, t, ctxrep, true, i));
+    float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
+    float* nl = noise_loss_out + (size_t)i * nimg * 2 * E;
+    CfgStepP s = cfg_step(L, L.eps, lat, nimg, 2, gs, af, at, lat);
+    s.target = lat_all + (size_t)(nsteps - i - 1) * nimg * E; s.offset_scale = offset_scale_host ? offset_scale_host[i] : 1.f; s.offset_out = nl;
+    CK(launch_cfg_ddim_prev(s, c->st));
+    for (int p = 1; p <= npass; ++p) {
+      float* lp = lat + (size_t)p * nimg * 2 * E;
+      s = cfg_step(L, L.eps + (size_t)p * nimg * 4 * E, lp, nimg, 2, gs, af, at, lp);
+      s.noise_loss = nl; s.offset_rows = offset_rows;
+      CK(launch_cfg_ddim_prev(s, c->st));
+    }
+    CKP(apply_local_blend(c, lat, i));
+  }
+  CKH(hipMemcpyAsync(latents_out, lat + (size_t)nimg * 2 * E, (size_t)npass * nimg * 2 * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
+/* The pruned-equivalent schedule of SURVEY.md Note D (algebra, not approximation): in direct-inversion mode the source latent after
+ * every step is prev + (x*_{t-1} - prev) == x*_{t-1}, and no controller ever touches the unconditional rows or the conditional
+ * source row's output.  So the offset pass and the reconstruction pass are redundant, the source latent can be ASSIGNED from the
+ * stored trajectory, and the unconditional-source row is dead: one 3-row launch per step and image
+ * [uncond_tgt, cond_src (attention maps only), cond_tgt] instead of 12.  200 sample-forwards per image instead of 650.
+ * context4 rows as everywhere: [unc_src, unc_tgt, cond_src, cond_tgt] per image (row 0 is not used). */
+int pnpi_direct_edit_pruned(pnpi_ctx* c, const float* lat_all, int nimg, const float* context4, const pnpi_ctrl_desc* ctrl_host,
+                            int nsteps, const int* ts, float gs, float* latents_out) {
+  if (!c || !lat_all || !context4 || !ts || !latents_out || nsteps <= 0 || nimg <= 0) return PNPI_EINVAL;
+  std::vector<pnpi_ctrl_desc> none(nimg);
+  memset(none.data(), 0, none.size() * sizeof(pnpi_ctrl_desc));
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 3 * nimg, "3 * nimg exceeds max_unet_rows", ctrl_host ? ctrl_host : none.data(), nimg, 3, 1, 2));
+  const size_t E = L.E, CE = L.CE; const int rows = L.rows;
+  float* lat = misc_f(c, (size_t)nimg * 2 * E);      // [img][src, tgt]
+  float* eps2 = misc_f(c, (size_t)nimg * 2 * E);     // [img][unc_tgt, cond_tgt]
+  float* xt = misc_f(c, (size_t)nimg * E);
+  float* ctx3 = misc_f(c, (size_t)rows * CE);
+  std::vector<int> expand(nimg * 2), inmap(rows), ctxmap(rows), epsmap(nimg * 2), tgtmap(nimg);
+  for (int i = 0; i < nimg; ++i) {
+    expand[2 * i] = i; expand[2 * i + 1] = i;
+    inmap[3 * i] = 2 * i + 1; inmap[3 * i + 1] = 2 * i; inmap[3 * i + 2] = 2 * i + 1;
+    ctxmap[3 * i] = 4 * i + 1; ctxmap[3 * i + 1] = 4 * i + 2; ctxmap[3 * i + 2] = 4 * i + 3;
+    epsmap[2 * i] = 3 * i; epsmap[2 * i + 1] = 3 * i + 2;
+    tgtmap[i] = 2 * i + 1;
+  }
+  int *d_expand, *d_inmap, *d_ctxmap, *d_epsmap, *d_tgtmap;
+  loop_map(L, expand, &d_expand); loop_map(L, inmap, &d_inmap); loop_map(L, ctxmap, &d_ctxmap);
+  loop_map(L, epsmap, &d_epsmap); loop_map(L, tgtmap, &d_tgtmap);
+  CKP(loop_commit(L));
+  CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, nimg * 2, E, lat, c->st));      // both rows start from x*_T
+  CK(launch_gather_rows_f32(context4, d_ctxmap, rows, CE, ctx3, c->st));
+  CKP(L.kv.begin(ctx3, rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i];
+    CKP(loop_unet(L, lat, d_inmap, t, ctx3, true, i));
+    float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
+    CK(launch_gather_rows_f32(L.eps, d_epsmap, nimg * 2, E, eps2, c->st));
+    CK(launch_gather_rows_f32(lat, d_tgtmap, nimg, E, xt, c->st));
+    CK(launch_cfg_ddim_prev(cfg_step(L, eps2, xt, nimg, 1, gs, af, at, xt), c->st));
+    // source latent := x*_{t-1} (assigned, not reconstructed); target latent := the step's result
+    const float* target = lat_all + (size_t)(nsteps - i - 1) * nimg * E;
+    CKH(hipMemcpy2DAsync(lat, 2 * E * sizeof(float), target, E * sizeof(float), E * sizeof(float), nimg, hipMemcpyDeviceToDevice, c->st));
+    CKH(hipMemcpy2DAsync(lat + E, 2 * E * sizeof(float), xt, E * sizeof(float), E * sizeof(float), nimg, hipMemcpyDeviceToDevice, c->st));
+    CKP(apply_local_blend(c, lat, i));
+  }
+  CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * 2 * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- edit-friendly DDPM inversion
+// models/edit_friendly_ddm/inversion_utils.py (eta > 0: the forward process stores one noise map per step, the reverse process replays
+// them).  Scalars: ef_step_scalars (step.hip), the reference's 0-dim fp32 expressions in its order.
+int pnpi_ef_step_scalars(const float* alphas_cumprod, int n, float final_alpha, int t, int step_ratio, float eta, float* out6) {
+  if (!alphas_cumprod || !out6 || t < 0 || t >= n || step_ratio <= 0) return PNPI_EINVAL;
+  const int tp = t - step_ratio;
+  ef_step_scalars(alphas_cumprod[t], tp >= 0 ? alphas_cumprod[tp] : final_alpha, eta, out6);
+  return 0;
+}
+static int ef_scalars(pnpi_ctx* c, int t, int ratio, float eta, float* sc) {
+  if (!c->sched_set) return fail(c, PNPI_ESTATE, "pnpi_set_scheduler not called");
+  if (t < 0 || t >= (int)c->ac.size() || ratio <= 0) return fail(c, PNPI_EINVAL, "timestep out of range");
+  return pnpi_ef_step_scalars(c->ac.data(), (int)c->ac.size(), c->final_alpha, t, ratio, eta, sc);
+}
+// (sqrt(ab[t]), sqrt(1 - ab[t])) of level 1 + k, k in draw order (timestep ts[nsteps - 1 - k]), uploaded to the controller arena
+static int ef_levels(pnpi_ctx* c, int nsteps, const int* ts, float** dst) {
+  if (!c->sched_set) return fail(c, PNPI_ESTATE, "pnpi_set_scheduler not called");
+  std::vector<float> lev(2 * (size_t)nsteps);
+  for (int k = 0; k < nsteps; ++k) {
+    const int t = ts[nsteps - 1 - k];
+    if (t < 0 || t >= (int)c->ac.size()) return fail(c, PNPI_EINVAL, "timestep out of range");
+    lev[2 * k] = sqrtf(c->ac[t]);
+    lev[2 * k + 1] = sqrtf(1.0f - c->ac[t]);
+  }
+  *dst = misc_f(c, lev.size());
+  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "loop arena overflow");
+  return upload(c, *dst, lev.data(), lev.size() * sizeof(float));
+}
+
+int pnpi_ef_sample_xts(pnpi_ctx* c, const float* x0, int nimg, const float* noise, size_t row_elems, int nsteps, const int* ts, float* xts_out) {
+  if (!c || !x0 || !noise || !ts || !xts_out || nimg <= 0 || nsteps <= 0 || row_elems == 0) return PNPI_EINVAL;
+  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
+  float* lev;
+  CKP(ef_levels(c, nsteps, ts, &lev));
+  CK(launch_ef_sample_xts(x0, noise, lev, nsteps, (size_t)nimg * row_elems, xts_out, c->st));
+  return 0;
+}
+
+int pnpi_ef_noise_map(pnpi_ctx* c, const float* eps, int cfg, float cfg_scale, const float* xt, float* xprev, float* z_out, int nimg,
+                      size_t row_elems, int t, int step_ratio, float eta) {
+  if (!c || !eps || !xt || !xprev || !z_out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
+  if (!(eta > 0.f)) return fail(c, PNPI_EINVAL, "edit-friendly inversion needs eta > 0 (eta = 0 stores no noise maps)");
+  float sc[6]; CKP(ef_scalars(c, t, step_ratio, eta, sc));
+  CK(launch_ef_noise_map(eps, cfg ? 1 : 0, cfg_scale, xt, xprev, z_out, nimg, row_elems, sc, c->st));
+  return 0;
+}
+
+int pnpi_ef_reverse_step(pnpi_ctx* c, const float* eps, const float* x, const float* z, int nimg, int nprompts, size_t row_elems,
+                         const float* cfg_scales_host, int t, int step_ratio, float eta, float* out) {
+  if (!c || !eps || !x || !z || !cfg_scales_host || !out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
+  if (nprompts != 1 && nprompts != 2) return fail(c, PNPI_EINVAL, "nprompts must be 1 or 2");
+  float sc[6]; CKP(ef_scalars(c, t, step_ratio, eta, sc));
+  CK(launch_ef_reverse_step(eps, x, z, nimg, nprompts, row_elems, cfg_scales_host[0], cfg_scales_host[nprompts - 1], sc, eta > 0.f ? 1 : 0,
+                            out, c->st));
+  return 0;
+}
+
+/* inversion_forward_process (inversion_utils.py:100-176) for nimg images: xts from x0 and the caller's draws, then for t = ts[0] .. ts[nsteps-1]
+ * (idx = nsteps-1 .. 0) one UNet launch of the rows [img][uncond, cond] (uncond only when ctx_cond is NULL: prompt "") on xts[idx+1], and the
+ * noise map / corrected xts[idx] of that step.  zs[0] is zeroed at the end (:173-174). */
+int pnpi_ef_invert(pnpi_ctx* c, const float* x0, int nimg, const float* noise, const float* ctx_uncond, const float* ctx_cond, float cfg_scale,
+                   const float* etas_host, int nsteps, const int* ts, float* xts_out, float* zs_out) {
+  if (!c || !x0 || !noise || !ctx_uncond || !etas_host || !ts || !xts_out || !zs_out || nimg <= 0 || nsteps <= 0) return PNPI_EINVAL;
+  for (int k = 0; k < nsteps; ++k)
+    if (!(etas_host[k] > 0.f)) return fail(c, PNPI_EINVAL, "edit-friendly inversion needs eta > 0 at every step");
+  const int rpi = ctx_cond ? 2 : 1;
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, rpi * nimg, "nimg * (1 + has_cond) exceeds max_unet_rows"));
+  const size_t E = L.E, N = (size_t)nimg * E;
+  float* ctx2 = misc_f(c, (size_t)L.rows * L.CE);
+  std::vector<int> inmap(L.rows);
+  for (int r = 0; r < L.rows; ++r) inmap[r] = r / rpi;
+  int* d_inmap;
+  loop_map(L, inmap, &d_inmap);
+  float* lev;
+  CKP(ef_levels(c, nsteps, ts, &lev));
+  CKP(loop_commit(L));
+  CKP(interleave_ctx(c, ctx2, ctx_uncond, ctx_cond, nimg, L.CE));
+  CKH(hipMemcpyAsync(xts_out, x0, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  CK(launch_ef_sample_xts(x0, noise, lev, nsteps, N, xts_out, c->st));
+  CKP(L.kv.begin(ctx2, L.rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i], idx = nsteps - 1 - i;
+    const float* xt = xts_out + (size_t)(idx + 1) * N;
+    CKP(loop_unet(L, xt, d_inmap, t, ctx2, false, 0));
+    float sc[6]; CKP(ef_scalars(c, t, L.ratio, etas_host[idx], sc));
+    CK(launch_ef_noise_map(L.eps, ctx_cond ? 1 : 0, cfg_scale, xt, xts_out + (size_t)idx * N, zs_out + (size_t)idx * N, nimg, E, sc, c->st));
+  }
+  CKH(hipMemsetAsync(zs_out, 0, N * sizeof(float), c->st));
+  return 0;
+}
+
+/* inversion_reverse_process (inversion_utils.py:210-262) with stored noise maps, nimg images x nprompts prompt rows: the last nsteps_run of the
+ * nsteps_total timesteps, step k (0-based) at t = ts[nsteps_total - nsteps_run + k] replays zs[nsteps_run-1-k] with etas[nsteps_run-1-k].
+ * One UNet launch of 2 * nprompts * nimg rows per step, per image [uncond_0 .. uncond_{P-1}, cond_0 .. cond_{P-1}] (the reference's uncond and
+ * cond calls); with two prompts that is the controller layout [uncond_src, uncond_tgt, cond_src, cond_tgt], and the controller's step index
+ * runs from 0 (the edit pass's own cur_step). */
+int pnpi_ef_edit(pnpi_ctx* c, const float* xT, const float* zs, int nimg, int nprompts, const float* context, const float* cfg_scales_host,
+                 const pnpi_ctrl_desc* ctrl_host, const float* etas_host, int nsteps_run, int nsteps_total, const int* ts, float* latents_out) {
+  if (!c || !xT || !zs || !context || !cfg_scales_host || !etas_host || !ts || !latents_out || nimg <= 0) return PNPI_EINVAL;
+  if (nprompts != 1 && nprompts != 2) return fail(c, PNPI_EINVAL, "nprompts must be 1 or 2");
+  if (nsteps_run <= 0 || nsteps_run > nsteps_total) return fail(c, PNPI_EINVAL, "need 0 < nsteps_run <= nsteps_total");
+  if (ctrl_host && nprompts != 2) return fail(c, PNPI_EINVAL, "an attention controller needs two prompts (source, target)");
+  if (ctrl_host)
+    for (int i = 0; i < nimg; ++i)
+      if (ctrl_host[i].lb_enabled) return fail(c, PNPI_EINVAL, "LocalBlend is not supported by the edit-friendly edit");
+  const int P = nprompts;
+  Loop L(c);
+  CKP(loop_begin(L, nsteps_total, 2 * P * nimg, "2 * nprompts * nimg exceeds max_unet_rows", ctrl_host, nimg));
+  const size_t E = L.E;
+  float* lat = misc_f(c, (size_t)nimg * P * E);
+  int *d_expand, *d_inmap;
+  loop_maps_cfg(L, nimg, nimg, P, &d_expand, &d_inmap);
+  CKP(loop_commit(L));
+  CK(launch_gather_rows_f32(xT, d_expand, nimg * P, E, lat, c->st));      // xT.expand(batch_size, ...) (:240)
+  CKP(L.kv.begin(context, L.rows));
+  for (int k = 0; k < nsteps_run; ++k) {
+    const int t = ts[nsteps_total - nsteps_run + k], idx = nsteps_run - 1 - k;
+    CKP(loop_unet(L, lat, d_inmap, t, context, ctrl_host != nullptr, k));
+    const float eta = etas_host[idx];
+    float sc[6]; CKP(ef_scalars(c, t, L.ratio, eta, sc));
+    CK(launch_ef_reverse_step(L.eps, lat, zs + (size_t)idx * nimg * E, nimg, P, E, cfg_scales_host[0], cfg_scales_host[P - 1], sc,
+                              eta > 0.f ? 1 : 0, lat, c->st));
+  }
+  CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * P * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- null-text optimisation
+// differentiable UNet forward: one recorded row, reverse walk in api_backward.inc
+static int tape_ensure(pnpi_ctx* c) {
+  if (c->tape) return 0;
+  const pnpi_model_config& g = c->cfg;
+  // The activation arenas were sized at create for max_unet_rows rows of the plain forward (block temporaries released in stack order).
+  // A recording forward of ONE row keeps every temporary: measure it with a dry run and grow the arenas if that is more (set-up time
+  // only -- nothing is allocated in the optimisation loop).  New buffers are allocated BEFORE the old ones are freed and the context's
+  // state changes only after every allocation has succeeded: a failed hipMalloc leaves the context as it was (and without a tape).
+  std::unique_ptr<Tape> T(new Tape());
+  CKH(hipStreamSynchronize(c->st));
+  size_t pp, tp;
+  {
+    const Bump sp = c->persist, stmp = c->temp;
+    Tape* const prev = c->tape;
+    c->persist = Bump(); c->temp = Bump();
+    c->tape = T.get();
+    c->dry = true; T->rec = true;
+    const bool kv = c->tkv.use; c->tkv.use = false;
+    const int r = unet_fwd(c, nullptr, 1, 0, nullptr, false, 0, nullptr);
+    c->dry = false; T->rec = false; c->tkv.use = kv;
+    pp = align_up(c->persist.peak + (1 << 20), 4096); tp = align_up(c->temp.peak + (1 << 20), 4096);
+    c->persist = sp; c->temp = stmp; c->tape = prev;
+    if (r) return r;
+  }
+  // gradients + dgrad scratch of one UNet row: about 2.8x the recorded activations at SD-1.x width (1.1 of 0.4 GB); 6x with a 64 MB floor
+  const size_t gcap = align_up(std::max((size_t)64 << 20, 6 * (pp + tp)), 4096);
+  char *gbase = nullptr, *nper = nullptr, *ntmp = nullptr;
+  float* dctx = nullptr;
+  auto undo = [&]() { if (gbase) (void)hipFree(gbase); if (nper) (void)hipFree(nper); if (ntmp) (void)hipFree(ntmp); if (dctx) (void)hipFree(dctx); };
+  hipError_t e = hipMalloc((void**)&gbase, gcap);
+  if (e == hipSuccess) e = hipMalloc((void**)&dctx, (size_t)g.ctx_len * g.cross_dim * sizeof(float));
+  if (e == hipSuccess && pp > c->persist.cap) e = hipMalloc((void**)&nper, pp);
+  if (e == hipSuccess && tp > c->temp.cap) e = hipMalloc((void**)&ntmp, tp);
+  if (e != hipSuccess) { undo(); const std::string msg = std::string("null-text tape: ") + hipGetErrorString(e); return fail(c, PNPI_EHIP, msg.c_str()); }
+  if (nper) { (void)hipFree(c->persist.base); c->persist.base = nper; c->persist.cap = pp; }
+  if (ntmp) { (void)hipFree(c->temp.base); c->temp.base = ntmp; c->temp.cap = tp; }
+  c->persist.reset(); c->temp.reset(); c->persist.overflow = false; c->temp.overflow = false;
+  T->garena.base = gbase; T->garena.cap = gcap; T->d_ctx = dctx;
+  c->tape = T.release();
+  return 0;
+}
+// eps = UNet(latents, t, context) for ONE row, and d_context = (d loss / d eps)^T (d eps / d context) for the given d loss / d eps
+// (fp32, the layout of eps; pre-multiplied by the caller's power-of-two loss scale -- activations' gradients travel in fp16).
+int pnpi_unet_context_grad(pnpi_ctx* c, const float* latents, int t, const float* context, const float* d_eps, float* eps_out, float* d_context_out) {
+  if (!c || !latents || !context || !d_eps || !d_context_out) return PNPI_EINVAL;
+  CKP(check_loop_ready(c));
+  CKP(tape_ensure(c));
+  Tape& T = *c->tape;
+  const pnpi_model_config& g = c->cfg;
+  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
+  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
+  float* eps = eps_out ? eps_out : misc_f(c, E);
+  T.ops.clear(); T.grads.clear(); T.garena.reset(); T.garena.overflow = false;
+  c->tkv.use = false;
+  T.rec = true;
+  int r = unet_fwd(c, latents, 1, t, context, false, 0, eps);
+  T.rec = false;
+  if (r) return r;
+  half_t* d_out = tape_galloc(c, (size_t)g.sample_size * g.sample_size * 8);
+  if (!d_out) return fail(c, PNPI_ENOMEM, "gradient arena overflow");
+  CK(launch_nchw_f32_to_nhwc_f16(d_eps, 1, g.in_channels, g.sample_size * g.sample_size, 8, d_out, c->st));
+  CKH(hipMemsetAsync(T.d_ctx, 0, CE * sizeof(float), c->st));
+  CKP(tape_backward(c, d_out));
+  CKH(hipMemcpyAsync(d_context_out, T.d_ctx, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
+// The Adam loop both optimisations share (inversion.py:203-218 and :430-447): eps_c = UNet(lat, t, ctx_cond) once, then up to
+// num_inner_steps x {recording forward with the current embedding `unc`, loss = mse(prev_step(CFG), target) and its gradient, reverse
+// walk to the embedding, Adam (torch.optim.Adam defaults, state fresh per DDIM step)}; the loss is read back for the reference's
+// early-stop test `loss < epsilon + i * 2e-5`.  eps2 = [eps_u | eps_c] (2E floats).  losses_host (nullable): [num_inner_steps].
+struct NullOptBufs { float *eps2, *d_eps, *am, *av, *loss_d; };
+static int null_inner_loop(pnpi_ctx* c, const NullOptBufs& b, const float* lat, int t, int i, float* unc, const float* ctx_cond,
+                           const float* target, float guidance_scale, float a_t, float a_p, int num_inner_steps, float epsilon,
+                           int* its_out, float* losses_host) {
+  const pnpi_model_config& g = c->cfg;
+  const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
+  const float scale = 4096.f;                                   // loss scale of the fp16 activation gradients (removed before Adam)
+  const double sa_t = sqrt((double)a_t), sb_t = sqrt(1.0 - a_t), sa_p = sqrt((double)a_p), sb_p = sqrt(1.0 - a_p);
+  const float c_x = (float)(sa_p / sa_t), c_e = (float)(sb_p - sa_p * sb_t / sa_t);       // rec = c_x x + c_e eps
+  const float lr = (float)(1e-2 * (1.0 - i / 100.0));
+  int its = 0;
+  c->tkv.use = false;
+  int r = unet_fwd(c, lat, 1, t, ctx_cond, false, 0, b.eps2 + E);
+  if (r) return r;
+  CKH(hipMemsetAsync(b.am, 0, CE * sizeof(float), c->st));
+  CKH(hipMemsetAsync(b.av, 0, CE * sizeof(float), c->st));
+  for (int j = 0; j < num_inner_steps; ++j) {
+    // forward with the tape recording; the loss head needs eps_u first, so forward and backward are two calls of the tape machinery
+    Tape& T = *c->tape;
+    T.ops.clear(); T.grads.clear(); T.garena.reset(); T.garena.overflow = false;
+    T.rec = true;
+    r = unet_fwd(c, lat, 1, t, unc, false, 0, b.eps2);
+    T.rec = false;
+    if (r) return r;
+    CK(launch_null_text_loss(b.eps2, b.eps2 + E, lat, target, (int)E, guidance_scale, c_x, c_e, scale, b.d_eps, b.loss_d, c->st));
+    half_t* d_out = tape_galloc(c, (size_t)g.sample_size * g.sample_size * 8);
+    if (!d_out) return fail(c, PNPI_ENOMEM, "gradient arena overflow");
+    CK(launch_nchw_f32_to_nhwc_f16(b.d_eps, 1, g.in_channels, g.sample_size * g.sample_size, 8, d_out, c->st));
+    CKH(hipMemsetAsync(T.d_ctx, 0, CE * sizeof(float), c->st));
+    CKP(tape_backward(c, d_out));
+    CK(launch_adam_step(unc, b.am, b.av, T.d_ctx, (int)CE, j + 1, lr, 1.f / scale, c->st));
+    float loss_h = 0.f;
+    CKH(hipMemcpyAsync(&loss_h, b.loss_d, sizeof(float), hipMemcpyDeviceToHost, c->st));
+    CKH(hipStreamSynchronize(c->st));
+    if (losses_host) losses_host[j] = loss_h;
+    its = j + 1;
+    c->ctr.unet_backward_rows += 1;
+    if (loss_h < epsilon + i * 2e-5f) break;
+  }
+  *its_out = its;
+  return 0;
+}
+static NullOptBufs null_bufs(const Loop& L) {
+  pnpi_ctx* c = L.c;
+  return {misc_f(c, 2 * L.E), misc_f(c, L.E), misc_f(c, L.CE), misc_f(c, L.CE), misc_f(c, 1)};
+}
+
+// NullInversion.null_optimization (models/p2p/inversion.py:196-225) for one image, device resident.  ddim_latents [nsteps + 1][E] (the
+// inversion trajectory, x*_0 first), ctx_uncond / ctx_cond [77][768]; uncond_out [nsteps][77][768] receives the optimised embedding of
+// every step; then the CFG step with the optimised embedding moves the latent on.  losses_out (nullable, host): [nsteps][num_inner_steps]
+// loss of every Adam iteration (-1 for iterations the early stop skipped).
+int pnpi_null_text_optimize(pnpi_ctx* c, const float* ddim_latents, const float* ctx_uncond, const float* ctx_cond, int nsteps,
+                            const int* ts, float guidance_scale, int num_inner_steps, float epsilon, float* uncond_out, int* iters_out,
+                            float* losses_out) {
+  if (!c || !ddim_latents || !ctx_uncond || !ctx_cond || !ts || !uncond_out || nsteps <= 0 || num_inner_steps < 0) return PNPI_EINVAL;
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 1, "null-text inversion needs max_unet_rows >= 1"));
+  CKP(tape_ensure(c));
+  const size_t E = L.E, CE = L.CE;
+  const NullOptBufs b = null_bufs(L);
+  float* lat = misc_f(c, E);
+  float* unc = misc_f(c, CE);
+  CKP(loop_commit(L, false));
+  if (losses_out) for (int k = 0; k < nsteps * num_inner_steps; ++k) losses_out[k] = -1.f;
+  CKH(hipMemcpyAsync(unc, ctx_uncond, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  CKH(hipMemcpyAsync(lat, ddim_latents + (size_t)nsteps * E, E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i];
+    float a_t, a_p; CKP(alphas_for(c, t, L.ratio, false, &a_t, &a_p));
+    const float* target = ddim_latents + (size_t)(nsteps - i - 1) * E;
+    int its = 0;
+    if (num_inner_steps > 0)
+      CKP(null_inner_loop(c, b, lat, t, i, unc, ctx_cond, target, guidance_scale, a_t, a_p, num_inner_steps, epsilon, &its,
+                          losses_out ? losses_out + (size_t)i * num_inner_steps : nullptr));
+    if (iters_out) iters_out[i] = its;
+    CKH(hipMemcpyAsync(uncond_out + (size_t)i * CE, unc, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+    // latent_cur = prev_step(CFG(eps(unc), eps(cond)))   (get_noise_pred with the optimised embedding, inversion.py:221-224)
+    c->tkv.use = false;
+    int r = unet_fwd(c, lat, 1, t, unc, false, 0, b.eps2);
+    if (r) return r;
+    if (num_inner_steps == 0) { r = unet_fwd(c, lat, 1, t, ctx_cond, false, 0, b.eps2 + E); if (r) return r; }
+    CK(launch_cfg_ddim_prev(cfg_step(L, b.eps2, lat, 1, 1, guidance_scale, a_t, a_p, lat), c->st));
+  }
+  return 0;
+}
+
+// DirectInversion.null_latent_calculate (models/p2p/inversion.py:419-460, "ablation_null-latent-inversion+p2p") for one (source, target)
+// prompt pair.  context4 rows = [unc_src, unc_tgt, cond_src, cond_tgt].  Per step: the unconditional embeddings are optimised as in
+// null-text inversion -- the reference's loss reads the SOURCE row only (:441), so the target row's embedding has a zero gradient, Adam
+// leaves it where it is, and only the source row needs the recording forward / reverse walk; its conditional prediction is constant over
+// the iterations -- then the step's effect becomes a latent offset for both rows:
+//   noise_loss[i] = prev_step(CFG with the optimised embeddings) - prev_step(CFG with the ORIGINAL ones),  latent_cur = plain + noise_loss[i]
+// (:449-459).  The two 4-row forwards run with rows ordered [unc_src, cond_src, unc_tgt, cond_tgt] (row results do not depend on the
+// order) so that the step kernel sees them as two one-row images.  noise_loss_out [nsteps][2][E].
+int pnpi_null_latent_calculate(pnpi_ctx* c, const float* ddim_latents, const float* context4, int nsteps, const int* ts, float guidance_scale,
+                               int num_inner_steps, float epsilon, float* noise_loss_out, int* iters_out, float* losses_out) {
+  if (!c || !ddim_latents || !context4 || !ts || !noise_loss_out || nsteps <= 0 || num_inner_steps < 0) return PNPI_EINVAL;
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 4, "null-latent inversion needs max_unet_rows >= 4"));
+  CKP(tape_ensure(c));
+  const size_t E = L.E, CE = L.CE;
+  const NullOptBufs b = null_bufs(L);
+  float* cur = misc_f(c, 2 * E);          // latent_cur [src, tgt]
+  float* in4 = misc_f(c, 4 * E);          // [src, src, tgt, tgt]
+  float* eps4 = misc_f(c, 4 * E);
+  float* opt = misc_f(c, 2 * E);
+  float* unc = misc_f(c, 2 * CE);         // the embeddings being optimised [src, tgt] (warm-started from step to step)
+  float* ctx4 = misc_f(c, 4 * CE);        // [unc_src, cond_src, unc_tgt, cond_tgt] of the forward at hand
+  CKP(loop_commit(L, false));
+  if (losses_out) for (int k = 0; k < nsteps * num_inner_steps; ++k) losses_out[k] = -1.f;
+  const float* cond = context4 + 2 * CE;
+  auto d2d = [&](float* d, const float* s, size_t n) { return hipMemcpyAsync(d, s, n * sizeof(float), hipMemcpyDeviceToDevice, c->st); };
+  CKH(d2d(unc, context4, 2 * CE));
+  CKH(d2d(cur, ddim_latents + (size_t)nsteps * E, E));
+  CKH(d2d(cur + E, ddim_latents + (size_t)nsteps * E, E));
+  CKH(d2d(ctx4 + CE, cond, CE));
+  CKH(d2d(ctx4 + 3 * CE, cond + CE, CE));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i];
+    float a_t, a_p; CKP(alphas_for(c, t, L.ratio, false, &a_t, &a_p));
+    const float* target = ddim_latents + (size_t)(nsteps - i - 1) * E;
+    int its = 0;
+    if (num_inner_steps > 0)
+      CKP(null_inner_loop(c, b, cur, t, i, unc, cond, target, guidance_scale, a_t, a_p, num_inner_steps, epsilon, &its,
+                          losses_out ? losses_out + (size_t)i * num_inner_steps : nullptr));
+    if (iters_out) iters_out[i] = its;
+    CKH(d2d(in4, cur, E)); CKH(d2d(in4 + E, cur, E)); CKH(d2d(in4 + 2 * E, cur + E, E)); CKH(d2d(in4 + 3 * E, cur + E, E));
+    c->tkv.use = false;
+    // with the optimised embeddings -> opt
+    CKH(d2d(ctx4, unc, CE)); CKH(d2d(ctx4 + 2 * CE, unc + CE, CE));
+    int r = unet_fwd(c, in4, 4, t, ctx4, false, 0, eps4);
+    if (r) return r;
+    CK(launch_cfg_ddim_prev(cfg_step(L, eps4, cur, 2, 1, guidance_scale, a_t, a_p, opt), c->st));
+    // with the original ones -> plain; loss = opt - plain; latent_cur = plain + loss
+    CKH(d2d(ctx4, context4, CE)); CKH(d2d(ctx4 + 2 * CE, context4 + CE, CE));
+    r = unet_fwd(c, in4, 4, t, ctx4, false, 0, eps4);
+    if (r) return r;
+    CfgStepP s = cfg_step(L, eps4, cur, 2, 1, guidance_scale, a_t, a_p, cur);
+    s.target = opt; s.offset_out = noise_loss_out + (size_t)i * 2 * E;
+    CK(launch_cfg_ddim_prev(s, c->st));
+  }
+  return 0;
+}

@@ -171,12 +171,18 @@ int launch_ddim_move(const float* x, const float* eps, float a_from, float a_to,
 // Classifier-free guidance + DDIM denoise step (+ direct-inversion offset). See include/pnpi.h pnpi_cfg_ddim_prev.
 int launch_ddim_prev_recon(const float* x, const float* eps, float a_from, float a_to, const float* ref, float lr, const float* mask, size_t n,
                            float* out, float* x0_out, hipStream_t st);
-int launch_cfg_ddim_prev(const float* eps, const float* x, int nimg, int rows_per_img, size_t row_elems, float gscale,
-                         float a_t, float a_prev, const float* noise_loss, int offset_rows, const float* target,
-                         float offset_scale, float* offset_out, float* x_out, hipStream_t st, const float* prox_thr = nullptr,
-                         int prox_mode = 0, const float* recon_ref = nullptr, float recon_lr = 0.f, int dilate = 0, int lat_h = 0,
-                         int lat_w = 0, const float* inv_ref = nullptr);   // recon_ref [nimg][row_elems]: reconstruction guidance; inv_ref
-                                                                          // [nimg][row_elems]: inversion guidance (both need prox_mode)
+struct CfgStepP {
+  const float* eps = nullptr;                                 // [nimg][2 * rows_per_img][row_elems]: per image the unconditional rows, then the conditional
+  const float* x = nullptr; float* x_out = nullptr;           // [nimg][rows_per_img][row_elems] (x_out may be x)
+  int nimg = 0, rows_per_img = 1; size_t row_elems = 0;
+  float gscale = 1.f, a_t = 1.f, a_prev = 1.f;                // the step goes from alpha_cumprod a_t to a_prev
+  const float* noise_loss = nullptr; int offset_rows = 0;     // like x: added to the first offset_rows rows of every image (ignored with a target)
+  const float* target = nullptr; float offset_scale = 1.f; float* offset_out = nullptr;   // target [nimg][row_elems], offset_out like x (offset_calculate)
+  const float* prox_thr = nullptr; int prox_mode = 0;         // [nimg] thresholds of the proximal step; mode 0 none, 1 l0, 2 l1
+  const float *recon_ref = nullptr, *inv_ref = nullptr;       // [nimg][row_elems] reconstruction / inversion guidance: both need prox_mode and the
+  float recon_lr = 0.f; int dilate = 0, lat_h = 0, lat_w = 0; // lat_h x lat_w planes of a row (dilation of the edit mask)
+};
+int launch_cfg_ddim_prev(const CfgStepP& p, hipStream_t st);
 // threshold of the proximal-guidance step: quantile q of |eps_c - eps_u| over the rows of each image (torch.quantile, linear)
 int launch_quantile_abs_diff(const float* eps, int nimg, int rows_per_img, size_t row_elems, float q, float* thr_out, hipStream_t st);
 int launch_fill_f32(float* p, int n, float v, hipStream_t st);

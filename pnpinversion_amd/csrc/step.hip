@@ -147,19 +147,16 @@ __global__ void cfg_ddim_prev_kernel(const float* __restrict__ eps, const float*
   }
 }
 
-int launch_cfg_ddim_prev(const float* eps, const float* x, int nimg, int rows_per_img, size_t row_elems, float gscale, float a_t,
-                         float a_prev, const float* noise_loss, int offset_rows, const float* target, float offset_scale,
-                         float* offset_out, float* x_out, hipStream_t st, const float* prox_thr, int prox_mode, const float* recon_ref,
-                         float recon_lr, int dilate, int lat_h, int lat_w, const float* inv_ref) {
-  float sa_f = sqrtf(a_t), sb_f = sqrtf(1.0f - a_t), sa_t = sqrtf(a_prev), sb_t = sqrtf(1.0f - a_prev);
-  size_t total = (size_t)nimg * rows_per_img * row_elems;
+int launch_cfg_ddim_prev(const CfgStepP& p, hipStream_t st) {
+  float sa_f = sqrtf(p.a_t), sb_f = sqrtf(1.0f - p.a_t), sa_t = sqrtf(p.a_prev), sb_t = sqrtf(1.0f - p.a_prev);
+  size_t total = (size_t)p.nimg * p.rows_per_img * p.row_elems;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 1024) blocks = 1024;
   if (blocks < 1) blocks = 1;
-  if ((recon_ref || inv_ref) && (lat_h <= 0 || lat_w <= 0 || row_elems % ((size_t)lat_h * lat_w))) return -3;
-  cfg_ddim_prev_kernel<<<blocks, 256, 0, st>>>(eps, x, nimg, rows_per_img, row_elems, gscale, sa_f, sb_f, sa_t, sb_t, noise_loss,
-                                               offset_rows, target, offset_scale, offset_out, x_out, prox_thr, prox_mode, recon_ref,
-                                               recon_lr, dilate, lat_h, lat_w, inv_ref);
+  if ((p.recon_ref || p.inv_ref) && (p.lat_h <= 0 || p.lat_w <= 0 || p.row_elems % ((size_t)p.lat_h * p.lat_w))) return -3;
+  cfg_ddim_prev_kernel<<<blocks, 256, 0, st>>>(p.eps, p.x, p.nimg, p.rows_per_img, p.row_elems, p.gscale, sa_f, sb_f, sa_t, sb_t, p.noise_loss,
+                                               p.offset_rows, p.target, p.offset_scale, p.offset_out, p.x_out, p.prox_thr, p.prox_mode,
+                                               p.recon_ref, p.recon_lr, p.dilate, p.lat_h, p.lat_w, p.inv_ref);
   return (int)hipGetLastError();
 }
 
