@@ -324,6 +324,27 @@ int pnpi_ef_edit(pnpi_ctx* ctx, const float* xT, const float* zs, int nimg, int 
                  const float* cfg_scales_host, const pnpi_ctrl_desc* ctrl_host, const float* etas_host, int nsteps_run, int nsteps_total,
                  const int* timesteps_host, float* latents_out);
 
+/* ---- Blended Latent Diffusion (run_editing_blended_latent_diffusion.py: BlendedLatnetDiffusion) -------------------------------
+ * Mask-guided editing with one prompt: after every CFG + DDIM step the latent outside the user's mask is replaced by the source latent
+ * noised to the step's own level t (edit_image :127-139).  Latents fp32 (the reference keeps fp16); random draws are inputs.
+ * pnpi_bld_mask: _read_mask (:164-173) for n full-resolution uint8 masks [n][H][W] -> fp32 0/1 [n][h][w], h = w = the context's latent size:
+ * PIL NEAREST (source pixel floor((i + 0.5) * H / h)), then `< 0.5 -> 0, else 1` (non-zero -> 1). */
+int pnpi_bld_mask(pnpi_ctx* ctx, const uint8_t* mask_u8, int n, int H, int W, float* mask_out);
+/* one step (:127-139) for nimg images in one launch: eps [nimg][2][row_elems] (uncond, cond), x / src / noise / x_out [nimg][row_elems] (x_out
+ * may be x), mask [nimg][map_elems] fp32 0/1 indexed by e % map_elems (row_elems % map_elems == 0).
+ *   e = eu + g (ec - eu);  prev = DDIMScheduler.step(e, t, x) with prev_t = t - step_ratio (final_alpha_cumprod below 0);
+ *   noised = sqrt(ab[t]) src + sqrt(1 - ab[t]) noise  (add_noise at t, not prev_t);  x_out = prev * mask + noised * (1 - mask). */
+int pnpi_bld_step(pnpi_ctx* ctx, const float* eps, const float* x, const float* src, const float* noise, const float* mask, int nimg,
+                  size_t row_elems, size_t map_elems, float guidance_scale, int t, int step_ratio, float* x_out);
+/* the loop of edit_image (:110-139), device-resident, over the last nsteps_run of the nsteps_total timesteps (timesteps[int(n * blending_
+ * percentage):]): x_start [nimg][E] the N(0,1) start latents (:102-106), src [nimg][E] = 0.18215 * posterior mean of the source images,
+ * noise [nsteps_run][nimg][E] the blending draws in step order (:137), mask [nimg][h*w] (pnpi_bld_mask), ctx_uncond / ctx_cond
+ * [nimg][77][768], latents_out [nimg][E].  One UNet launch of 2 * nimg rows per step, text K / V cached for the loop.  2 * nimg >
+ * max_unet_rows, nsteps_run outside 1 .. nsteps_total (PNPI_EINVAL) and arena overflow are refused before anything is launched. */
+int pnpi_bld_edit(pnpi_ctx* ctx, const float* x_start, int nimg, const float* src, const float* noise, const float* mask,
+                  const float* ctx_uncond, const float* ctx_cond, float guidance_scale, int nsteps_total, int nsteps_run,
+                  const int* timesteps_host, float* latents_out);
+
 /* ---- kernel-level entry points (used by tests/ and bench.py to exercise single kernels) ------------------------- */
 int pnpi_op_conv(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nhwc_f16, int C1, int C2, int B, int H, int W,
                  int ksize, int stride, int pad, int upsample, int Ho, int Wo, const void* w_f16 /*[N][k*k*(C1+C2)]*/,

@@ -143,6 +143,10 @@ SYMBOLS = {
     "pnpi_ef_reverse_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _sz, _fp, _i, _i, _f, _vp]),     # :254-258 + reverse_step :179-208
     "pnpi_ef_invert": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _f, _fp, _i, _ip, _vp, _vp]),         # inversion_forward_process :100-176
     "pnpi_ef_edit": (_i, [_vp, _vp, _vp, _i, _i, _vp, _fp, C.POINTER(CtrlDesc), _fp, _i, _i, _ip, _vp]),  # inversion_reverse_process :210-262
+    # Blended Latent Diffusion (run_editing_blended_latent_diffusion.py)
+    "pnpi_bld_mask": (_i, [_vp, _vp, _i, _i, _i, _vp]),                                        # _read_mask :164-173
+    "pnpi_bld_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _sz, _f, _i, _i, _vp]),      # edit_image :127-139
+    "pnpi_bld_edit": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _ip, _vp]),      # edit_image :110-139
 }
 
 _lib = None

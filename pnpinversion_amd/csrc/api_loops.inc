@@ -1,6 +1,6 @@
 // api_loops.inc -- part of api.hip (one translation unit: included there, last, inside its extern "C" block; not compiled on its own).
 // the level-2 entry points: whole inversion / editing loops in one C call (DDIM, direct inversion, Prompt-to-Prompt edit loops,
-// edit-friendly DDPM, null-text optimisation)
+// edit-friendly DDPM, Blended Latent Diffusion, null-text optimisation)
 // ---------------------------------------------------------------------------------------------------- loop scaffold
 // The loops' text context is constant over their steps: project K / V once, then every forward of the loop reads the cache.
 struct LoopKV {
@@ -454,6 +454,56 @@ int pnpi_ef_edit(pnpi_ctx* c, const float* xT, const float* zs, int nimg, int np
                               eta > 0.f ? 1 : 0, lat, c->st));
   }
   CKH(hipMemcpyAsync(latents_out, lat, (size_t)nimg * P * E * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- Blended Latent Diffusion
+// run_editing_blended_latent_diffusion.py, BlendedLatnetDiffusion (one prompt, one user mask; the background is re-anchored to the noised
+// source after every step).  _read_mask (:164-173) at the context's latent size.
+int pnpi_bld_mask(pnpi_ctx* c, const uint8_t* mask_u8, int n, int H, int W, float* mask_out) {
+  if (!c || !mask_u8 || !mask_out || n <= 0 || H <= 0 || W <= 0) return PNPI_EINVAL;
+  const int S = c->cfg.sample_size;
+  CK(launch_bld_mask(mask_u8, n, H, W, S, S, mask_out, c->st));
+  return 0;
+}
+// one step of the loop of edit_image (:127-139): scheduler.step at t (prev_t = t - step_ratio, final_alpha_cumprod below 0), add_noise at t
+int pnpi_bld_step(pnpi_ctx* c, const float* eps, const float* x, const float* src, const float* noise, const float* mask, int nimg,
+                  size_t row_elems, size_t map_elems, float guidance_scale, int t, int step_ratio, float* x_out) {
+  if (!c || !eps || !x || !src || !noise || !mask || !x_out || nimg <= 0 || row_elems == 0 || map_elems == 0) return PNPI_EINVAL;
+  if (row_elems % map_elems) return fail(c, PNPI_EINVAL, "row_elems must be a multiple of map_elems (the mask is broadcast over the channels)");
+  if (step_ratio <= 0) return fail(c, PNPI_EINVAL, "step_ratio must be positive");
+  float af, at; CKP(alphas_for(c, t, step_ratio, false, &af, &at));
+  CK(launch_bld_step(eps, x, src, noise, mask, nimg, row_elems, map_elems, guidance_scale, af, at, x_out, c->st));
+  return 0;
+}
+/* BlendedLatnetDiffusion.edit_image's loop (:110-139) for nimg images, device-resident: the last nsteps_run of the nsteps_total timesteps
+ * (`timesteps[int(n * blending_percentage):]`, :110-112).  The start latent is the caller's N(0,1) draw (:102-106), NOT the noised source.
+ * One UNet launch of the rows [img][uncond, cond] per step (the reference's torch.cat([latents] * 2), :114), then one bld_step launch;
+ * step k blends with the caller's draw noise[k] (the torch.randn_like of :137). */
+int pnpi_bld_edit(pnpi_ctx* c, const float* x_start, int nimg, const float* src, const float* noise, const float* mask, const float* ctx_uncond,
+                  const float* ctx_cond, float guidance_scale, int nsteps_total, int nsteps_run, const int* ts, float* latents_out) {
+  if (!c || !x_start || !src || !noise || !mask || !ctx_uncond || !ctx_cond || !ts || !latents_out || nimg <= 0 || nsteps_total <= 0) return PNPI_EINVAL;
+  if (nsteps_run < 1 || nsteps_run > nsteps_total) return fail(c, PNPI_EINVAL, "need 1 <= nsteps_run <= nsteps_total");
+  Loop L(c);
+  CKP(loop_begin(L, nsteps_total, 2 * nimg, "2 * nimg exceeds max_unet_rows (blended latent diffusion runs [uncond, cond] per image)"));
+  const size_t E = L.E, N = (size_t)nimg * E, HW = (size_t)c->cfg.sample_size * c->cfg.sample_size;
+  float* lat = misc_f(c, N);
+  float* ctx2 = misc_f(c, (size_t)L.rows * L.CE);
+  std::vector<int> inmap(L.rows);
+  for (int r = 0; r < L.rows; ++r) inmap[r] = r / 2;
+  int* d_inmap;
+  loop_map(L, inmap, &d_inmap);
+  CKP(loop_commit(L));
+  CKP(interleave_ctx(c, ctx2, ctx_uncond, ctx_cond, nimg, L.CE));
+  CKH(hipMemcpyAsync(lat, x_start, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  CKP(L.kv.begin(ctx2, L.rows));
+  for (int k = 0; k < nsteps_run; ++k) {
+    const int t = ts[nsteps_total - nsteps_run + k];
+    CKP(loop_unet(L, lat, d_inmap, t, ctx2, false, 0));
+    float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
+    CK(launch_bld_step(L.eps, lat, src, noise + (size_t)k * N, mask, nimg, E, HW, guidance_scale, af, at, lat, c->st));
+  }
+  CKH(hipMemcpyAsync(latents_out, lat, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
   return 0;
 }
 

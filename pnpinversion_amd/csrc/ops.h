@@ -195,6 +195,11 @@ int launch_ef_noise_map(const float* eps, int cfg, float g, const float* xt, flo
                         hipStream_t st);
 int launch_ef_reverse_step(const float* eps, const float* x, const float* z, int nimg, int P, size_t E, float g0, float g1, const float* sc,
                            int add_noise, float* out, hipStream_t st);
+// Blended Latent Diffusion: CFG + DDIM step + noised source + mask blend in one launch (x_out may be x); mask [nimg][HW] 0/1, E % HW == 0.
+int launch_bld_step(const float* eps, const float* x, const float* src, const float* noise, const float* mask, int nimg, size_t E, size_t HW,
+                    float g, float a_t, float a_prev, float* x_out, hipStream_t st);
+// uint8 [n][H][W] -> fp32 0/1 [n][h][w]: PIL-nearest resize, non-zero -> 1
+int launch_bld_mask(const uint8_t* in, int n, int H, int W, int h, int w, float* out, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
 // Activation-gradient kernels of the null-text path (bwd.hip)

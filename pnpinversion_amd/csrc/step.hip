@@ -403,3 +403,61 @@ int launch_ef_reverse_step(const float* eps, const float* x, const float* z, int
   ef_reverse_step_kernel<<<blocks, 256, 0, st>>>(eps, x, z, nimg, P, E, g0, g1, sc[0], sc[1], sc[2], sc[3], sc[4], add_noise, out);
   return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------- Blended Latent Diffusion
+// Reference: run_editing_blended_latent_diffusion.py, BlendedLatnetDiffusion.edit_image :110-139 with diffusers' DDIMScheduler.step
+// (eta = 0, no clipping) and add_noise.  One step for nimg images in one launch:
+//   e      = eu + g * (ec - eu)                                        (:127-130)   eps: [nimg][2][E] (uncond, cond)
+//   prev   = sa_p * ((x - sb_t * e) / sa_t) + sb_p * e                 (:133)       scheduler.step, t -> t - ratio
+//   noised = sa_t * src + sb_t * noise                                 (:136-138)   add_noise at the step's OWN t (not t - ratio)
+//   out    = prev * m + noised * (1 - m)                               (:139)       m = mask[img][e % HW]: broadcast over the channels
+// The blend is evaluated as written (two multiplies and an add, 1 - m computed), every operation rounded on its own.  x / x_out may
+// alias: a thread reads element i of x before it writes element i of x_out, and no other thread touches it.
+__global__ void bld_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ src,
+                                const float* __restrict__ noise, const float* __restrict__ mask, int nimg, size_t E, size_t HW, float g,
+                                float sa_t, float sb_t, float sa_p, float sb_p, float* x_out) {
+  const size_t total = (size_t)nimg * E;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / E, e_idx = i - img * E;
+    const float eu = eps[(img * 2) * E + e_idx], ec = eps[(img * 2 + 1) * E + e_idx];
+    const float e = __fadd_rn(eu, __fmul_rn(g, __fsub_rn(ec, eu)));
+    const float prev = ddim_update(x[i], e, sa_t, sb_t, sa_p, sb_p);
+    const float noised = __fadd_rn(__fmul_rn(sa_t, src[i]), __fmul_rn(sb_t, noise[i]));
+    const float m = mask[img * HW + e_idx % HW];
+    x_out[i] = __fadd_rn(__fmul_rn(prev, m), __fmul_rn(noised, __fsub_rn(1.0f, m)));
+  }
+}
+int launch_bld_step(const float* eps, const float* x, const float* src, const float* noise, const float* mask, int nimg, size_t E, size_t HW,
+                    float g, float a_t, float a_prev, float* x_out, hipStream_t st) {
+  if (nimg <= 0 || E == 0 || HW == 0 || E % HW) return -3;
+  // alphas_cumprod[t] ** 0.5 / (1 - alphas_cumprod[t]) ** 0.5 on 0-dim fp32 tensors: correctly rounded fp32 sqrt of fp32 operands
+  const float sa_t = sqrtf(a_t), sb_t = sqrtf(1.0f - a_t), sa_p = sqrtf(a_prev), sb_p = sqrtf(1.0f - a_prev);
+  size_t total = (size_t)nimg * E;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  bld_step_kernel<<<blocks, 256, 0, st>>>(eps, x, src, noise, mask, nimg, E, HW, g, sa_t, sb_t, sa_p, sb_p, x_out);
+  return (int)hipGetLastError();
+}
+
+// BlendedLatnetDiffusion._read_mask (:164-173): PIL NEAREST resize of the [H][W] mask to [h][w], then `mask < 0.5 -> 0, else 1` (for
+// uint8 values: non-zero -> 1).  PIL's nearest filter reads source pixel floor((i + 0.5) * H / h) (the centre of the destination pixel,
+// scaled): in integers floor((2 i + 1) H / (2 h)), clamped to the image.
+__global__ void bld_mask_kernel(const uint8_t* __restrict__ in, int n, int H, int W, int h, int w, float* __restrict__ out) {
+  const size_t total = (size_t)n * h * w;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % w), yo = (int)(i / w % h);
+    const size_t img = i / ((size_t)h * w);
+    int ys = (int)(((long long)(2 * yo + 1) * H) / (2 * h)), xs = (int)(((long long)(2 * xo + 1) * W) / (2 * w));
+    if (ys > H - 1) ys = H - 1;
+    if (xs > W - 1) xs = W - 1;
+    out[i] = in[(img * H + ys) * W + xs] != 0 ? 1.0f : 0.0f;
+  }
+}
+int launch_bld_mask(const uint8_t* in, int n, int H, int W, int h, int w, float* out, hipStream_t st) {
+  if (n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0) return -3;
+  size_t total = (size_t)n * h * w;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  bld_mask_kernel<<<blocks, 256, 0, st>>>(in, n, H, W, h, w, out);
+  return (int)hipGetLastError();
+}

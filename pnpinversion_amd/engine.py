@@ -654,6 +654,67 @@ class NativeEngine:
         self._keep = (x, z, ctx, sc, e, ts, arr, ctrls)
         return out
 
+    # ---- Blended Latent Diffusion (run_editing_blended_latent_diffusion.py)
+    def bld_mask(self, mask_u8):
+        """_read_mask (:164-173) on the device: uint8 [n, H, W] (or [H, W]) full-resolution masks -> fp32 0/1 [n, h, w] at the latent size
+        (PIL-nearest source pixel floor((i + 0.5) * H / h), non-zero -> 1)."""
+        m = torch.as_tensor(mask_u8)
+        if m.dim() == 2:
+            m = m[None]
+        if m.dim() != 3 or m.dtype != torch.uint8:
+            raise ValueError("mask must be uint8 [n, H, W], got %s %s" % (m.dtype, tuple(m.shape)))
+        m = m.to(self.device).contiguous()
+        n, H, W = m.shape
+        out = torch.empty(n, self.lat_hw, self.lat_hw, device=self.device)
+        self._call("pnpi_bld_mask", _p(m), n, H, W, _p(out))
+        self._keep = m
+        return out
+
+    def bld_step(self, eps, x, src, noise, mask, t, ratio, guidance_scale, inplace=False):
+        """One step of edit_image's loop (:127-139): eps [nimg, 2, C, h, w] (uncond, cond), x / src / noise [nimg, C, h, w], mask [nimg, h, w]
+        fp32 0/1 -> CFG, DDIM step t -> t - ratio, source noised to level t, blend by the mask.  inplace: the result overwrites (the
+        device copy of) x and that tensor is returned."""
+        e, xs, s, nz, m = self._f32(eps), self._f32(x), self._f32(src), self._f32(noise), self._f32(mask)
+        if xs.dim() != 4:
+            raise ValueError("x must be [nimg, C, h, w], got %s" % (tuple(xs.shape),))
+        nimg, _, h, w = xs.shape
+        if e.shape != (nimg, 2, *xs.shape[1:]):
+            raise ValueError("eps must be [nimg, 2, C, h, w] = %s, got %s" % ((nimg, 2, *xs.shape[1:]), tuple(e.shape)))
+        if s.shape != xs.shape or nz.shape != xs.shape:
+            raise ValueError("src and noise must be [nimg, C, h, w] = %s, got %s and %s" % (tuple(xs.shape), tuple(s.shape), tuple(nz.shape)))
+        if m.shape != (nimg, h, w):
+            raise ValueError("mask must be [nimg, h, w] = %s, got %s" % ((nimg, h, w), tuple(m.shape)))
+        out = xs if inplace else torch.empty_like(xs)
+        self._call("pnpi_bld_step", _p(e), _p(xs), _p(s), _p(nz), _p(m), nimg, xs[0].numel(), h * w, float(guidance_scale), int(t), int(ratio),
+                   _p(out))
+        self._keep = (e, xs, s, nz, m)
+        return out
+
+    def bld_edit(self, x_start, src, noise, mask, ctx_uncond, ctx_cond, guidance_scale, timesteps):
+        """BlendedLatnetDiffusion.edit_image's loop (:110-139) for nimg images, device-resident (pnpi_bld_edit).  x_start [nimg, 4, h, w] the
+        N(0,1) start latents, src [nimg, 4, h, w] the encoded sources, noise [nsteps_run, nimg, 4, h, w] the blending draws in step order,
+        mask [nimg, h, w] fp32 0/1, ctx_* [nimg, 77, D], timesteps: the full schedule (its last nsteps_run entries are executed).
+        -> latents [nimg, 4, h, w]"""
+        x, s, nz, m = self._f32(x_start), self._f32(src), self._f32(noise), self._f32(mask)
+        cu, cc = self._f32(ctx_uncond), self._f32(ctx_cond)
+        if x.dim() != 4 or x.shape[1:] != (self.cfg.in_channels, self.lat_hw, self.lat_hw):
+            raise ValueError("x_start must be [nimg, %d, %d, %d], got %s" % (self.cfg.in_channels, self.lat_hw, self.lat_hw, tuple(x.shape)))
+        nimg = x.shape[0]
+        if s.shape != x.shape:
+            raise ValueError("src must be [nimg, 4, h, w] = %s, got %s" % (tuple(x.shape), tuple(s.shape)))
+        if nz.dim() != 5 or nz.shape[1:] != x.shape:
+            raise ValueError("noise must be [nsteps_run, nimg, 4, h, w] = (nsteps_run, %s), got %s" % (", ".join(map(str, x.shape)), tuple(nz.shape)))
+        if m.shape != (nimg, self.lat_hw, self.lat_hw):
+            raise ValueError("mask must be [nimg, h, w] = %s, got %s" % ((nimg, self.lat_hw, self.lat_hw), tuple(m.shape)))
+        want = (nimg, self.cfg.ctx_len, self.cfg.cross_dim)
+        if cu.shape != want or cc.shape != want:
+            raise ValueError("ctx_uncond and ctx_cond must be [nimg, 77, D] = %s, got %s and %s" % (want, tuple(cu.shape), tuple(cc.shape)))
+        ts, tsp = self._ts(timesteps)
+        out = torch.empty_like(x)
+        self._call("pnpi_bld_edit", _p(x), nimg, _p(s), _p(nz), _p(m), _p(cu), _p(cc), float(guidance_scale), len(ts), nz.shape[0], tsp, _p(out))
+        self._keep = (x, s, nz, m, cu, cc, ts)
+        return out
+
 
 def ef_step_scalars(lib, alphas_cumprod, final_alpha, t, ratio, eta):
     """pnpi_ef_step_scalars without a context (host only, no GPU): the six fp32 scalars of one edit-friendly step."""
