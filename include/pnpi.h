@@ -364,6 +364,8 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
  * loaded with PNPI_LIBRARY=<path>); the product library REJECTS those values here with PNPI_EINVAL -- and "attn_pipe" = 1 / 2 (round 6: the
  * half-tile software-pipelined forms of the 64-wide flash kernel, measured slower) likewise.  "gn_slab" (0): 1 = a split-K launch whose
  * output goes to a small-map GroupNorm leaves its combine to that kernel (bit-identical, measured slower: profiles/round5_gn_slab_ab.txt).
+ * "ff_fold" (1): each transformer block's ff2 GEMM and 1x1 proj_out run as one launch over folded weights [Wp W2 | Wp] derived at load
+ * (same FLOPs, no hs3 round trip; fp16-rounding-level difference); 0 = the two launches.  May be switched on a live context.
  * Keys (default): "text_kv" (1) / "temb_cache" (1) per-loop caches; "gn_inline_rows" (0)
  * one-launch GroupNorm below this many rows; "igemm_dma" (1) LDS-DMA kernel family; "igemm_table" (1) measured tile table before the
  * cost model; "igemm_wide" (1) 128x320 / 128x256 tiles; "igemm_deep_rings" (1) deeper LDS rings on sparse launches; "igemm_vt_lds" (1)

@@ -276,6 +276,7 @@ int pnpi_load_weights(pnpi_ctx* c, const pnpi_named_tensor* ts, int n) {
   if (!c || !ts) return PNPI_EINVAL;
   if (c->warena_borrowed) return fail(c, PNPI_ESTATE, "this context borrows its weights (pnpi_create_shared): load them into the owning context");
   invalidate_derived(c);
+  bool fold_src = false;
   for (int i = 0; i < n; ++i) {
     const pnpi_named_tensor& t = ts[i];
     std::string name = t.name;
@@ -297,7 +298,9 @@ int pnpi_load_weights(pnpi_ctx* c, const pnpi_named_tensor* ts, int n) {
       CK(launch_repack_vec(t.data, t.dtype, s.n, (float*)s.dst, c->st, s.ilv_half));
     }
     s.loaded = true;
+    if (!fold_src && ff_fold_source(c, name)) { fold_src = true; c->warena_ref->ff_fold_ready = false; }
   }
+  if (fold_src) CK(build_ff_fold(c));     // the folded ff2 + proj_out weights follow their sources (same stream: ordered behind the repacks)
   return 0;
 }
 
@@ -328,6 +331,7 @@ int pnpi_weight_arena(pnpi_ctx* c, void** ptr, size_t* bytes) {
 int pnpi_mark_all_loaded(pnpi_ctx* c) {
   invalidate_derived(c);            // the arena was just overwritten by the broadcast
   for (auto& kv : c->slots) kv.second.loaded = true;
+  CK(build_ff_fold(c));             // derived after the broadcast, from the weights it delivered (a borrowing context leaves it to the owner)
   return 0;
 }
 
@@ -715,6 +719,7 @@ int pnpi_set_tuning(const char* key, int value) {
   if (!strcmp(key, "attn_aug")) { g_attn_aug = value; return 0; }
   if (!strcmp(key, "attn_pipe")) return attn_set_tuning_pipe(value) == 0 ? 0 : PNPI_EINVAL;
   if (!strcmp(key, "gn_slab")) { g_gn_slab = value; return 0; }
+  if (!strcmp(key, "ff_fold")) { g_ff_fold = value; return 0; }
   if (!strcmp(key, "op_attention_aug")) { g_op_attention_aug = value; return 0; }
   if (!strcmp(key, "op_attention_vt_perm")) { g_op_attention_vt_perm = value; return 0; }
   if (!strcmp(key, "attn_bwd_flash")) { g_attn_bwd_flash = value; return 0; }

@@ -17,6 +17,11 @@ static void prof_close(pnpi_ctx* c, ProfRec& r, int cls, double flops, double by
 // forward 4.53 -> 5.05 ms, twelve-row 14.89 -> 15.40) -- the slabs are the traffic either way (47 - 63 MB per launch at the 16 x 16 /
 // 8 x 8 levels) and the combine kernel streams them with every CU, the GroupNorm kernel with one block per (row, group)
 static int g_gn_slab = 0;
+// tuning "ff_fold" = 1: the transformer block's last two GEMMs (ff2, then the 1 x 1 proj_out) run as ONE launch over the folded weights
+// [Wp W2 | Wp] (TransformerW::fo) -- nothing non-linear sits between them and hs3 has no other reader.  Same FLOPs, one launch, no
+// hs3 round trip.  0: the two launches.  Results differ at fp16-rounding level only (hs3 is no longer rounded between the GEMMs;
+// Wp W2 is rounded once at load).
+static int g_ff_fold = 1;
 static int flush_pending(pnpi_ctx* c) {
   if (!c->pend_on) return 0;
   c->pend_on = false;
@@ -366,10 +371,18 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
     CK(op_gemm(c, n3, C, M, C, t.ff1.w, C, 8 * C, t.ff1.b, nullptr, 0, f1, 8 * C));
     if (!c->dry) PROF(PNPI_KC_GEGLU, 0.0, 12.0 * M * (double)C * 2.0, launch_geglu(f1, M, 4 * C, f2, c->st));
   }
-  half_t* hs3 = talloc(c, (size_t)M * C);
-  CK(op_gemm(c, f2, 4 * C, M, 4 * C, t.ff2.w, 4 * C, C, t.ff2.b, hs2, C, hs3, C));
   StatsReq qo;
-  CK(op_conv(c, hs3, C, nullptr, 0, B, H, W, t.proj_out, 1, 0, 0, t.proj_out.b, x, out, H, W, -1, nullptr, &qo));
+  // ff2 + proj_out as one two-source 1 x 1 convolution over f2 | hs2 (K = 4C + C: both parts are whole 64-wide k-chunks).  Only with
+  // folded weights that match the loaded ones (ff_fold_ready); the sizing dry run takes the two-launch path, which needs more memory
+  // (hs3), so the knob can be flipped on a live context
+  const bool fold = g_ff_fold && !c->dry && C % 64 == 0 && t.fo.w && c->warena_ref && c->warena_ref->ff_fold_ready && !keep_acts(c);
+  if (fold) {
+    CK(op_conv(c, f2, 4 * C, hs2, C, B, H, W, t.fo, 1, 0, 0, t.fo.b, x, out, H, W, -1, nullptr, &qo));
+  } else {
+    half_t* hs3 = talloc(c, (size_t)M * C);
+    CK(op_gemm(c, f2, 4 * C, M, 4 * C, t.ff2.w, 4 * C, C, t.ff2.b, hs2, C, hs3, C));
+    CK(op_conv(c, hs3, C, nullptr, 0, B, H, W, t.proj_out, 1, 0, 0, t.proj_out.b, x, out, H, W, -1, nullptr, &qo));
+  }
   if (so) { so->p = qo.buf; so->rows = qo.rows; }
   c->temp.release(mk);
   return 0;

@@ -90,6 +90,15 @@ static TransformerW make_transformer(pnpi_ctx* c, const std::string& pre, int C,
   c->slots[tb + ".ff.net.0.proj.bias"].ilv_half = 4 * C;
   t.ff2 = make_lin(c, tb + ".ff.net.2", 4 * C, C);
   t.proj_out = make_conv(c, pre + ".proj_out", C, C, 1);
+  // ff2 folded into proj_out (transformer_fwd): derived from the four tensors above by build_ff_fold, inside the arena so that every
+  // context sharing it sees the same pointers.  Narrow widths keep the two launches and spend no memory on it.
+  t.fo = ConvW{nullptr, nullptr, 5 * C, 5 * C, C, 1};
+  if (C % 64 == 0) {
+    t.fo.w = walloc_h(c, (size_t)C * 5 * C);
+    t.fo.b = walloc_f(c, C);
+    c->ff_folds.push_back({t.proj_out.w, t.proj_out.cin_pad, t.proj_out.b, t.ff2.w, t.ff2.b, C, t.fo.w, t.fo.b,
+                           {pre + ".proj_out.weight", pre + ".proj_out.bias", tb + ".ff.net.2.weight", tb + ".ff.net.2.bias"}});
+  }
   return t;
 }
 static VaeAttnW make_vae_attn(pnpi_ctx* c, const std::string& pre, int C) {
@@ -107,6 +116,30 @@ static VaeAttnW make_vae_attn(pnpi_ctx* c, const std::string& pre, int C) {
   return a;
 }
 
+// The folded ff2 + proj_out weights of every transformer block, from the packed weights next to them -- derived state of the arena,
+// like the caches invalidate_derived() drops: the owner of the arena rebuilds them after every load that touched a source
+// (pnpi_load_weights) and after the arena was overwritten wholesale (pnpi_mark_all_loaded).  Until all four sources of every block
+// are loaded the arena is marked not ready and every forward on it takes the two-launch path.
+static bool ff_fold_source(const pnpi_ctx* c, const std::string& name) {
+  for (const pnpi_ctx::FfFold& f : c->ff_folds)
+    for (const std::string& s : f.src) if (s == name) return true;
+  return false;
+}
+static int build_ff_fold(pnpi_ctx* c) {
+  if (c->warena_borrowed || !c->warena_ref) return 0;
+  c->warena_ref->ff_fold_ready = false;
+  if (c->ff_folds.empty()) return 0;
+  for (const pnpi_ctx::FfFold& f : c->ff_folds)
+    for (const std::string& s : f.src) {
+      auto it = c->slots.find(s);
+      if (it == c->slots.end() || !it->second.loaded) return 0;
+    }
+  for (const pnpi_ctx::FfFold& f : c->ff_folds)
+    if (int r = launch_ff_fold_weights(f.wp, f.ldp, f.bp, f.w2, f.b2, f.C, f.w_fo, f.b_fo, c->st)) return r;
+  c->warena_ref->ff_fold_ready = true;
+  return 0;
+}
+
 static int temb_total_channels(const pnpi_model_config& g) {
   int n = g.n_blocks, total = 0;
   for (int i = 0; i < n; ++i) total += g.layers_per_block * g.block_out_channels[i];
@@ -119,6 +152,7 @@ static void build_model(pnpi_ctx* c) {
   const pnpi_model_config& g = c->cfg;
   c->slots.clear();
   c->aug_biases.clear();
+  c->ff_folds.clear();
   UNetW& u = c->unet;
   u = UNetW();
   const int n = g.n_blocks, C0 = g.block_out_channels[0], TE = 4 * C0;

@@ -63,6 +63,8 @@ struct TransformerW {
   LinW o2;
   LinW ff1;           // [8C][C]
   LinW ff2;           // [C][4C]
+  ConvW fo;           // ff2 folded into proj_out (derived, C % 64 == 0 only; fo.w == nullptr otherwise): w [C][4C | C] = [Wp W2 | Wp] as a
+                      // two-source 1 x 1 convolution over f2 | hs2, b [C] = Wp b2 + bp -- rebuilt whenever ff2 / proj_out are (re)loaded
   int place;          // 0 down, 1 mid, 2 up
   int lb_slot0;       // first LocalBlend slot of this layer's cross-attention, or -1
 };
@@ -181,8 +183,13 @@ struct pnpi_ctx {
   Bump warena, persist, temp, ctrl_arena;
   struct AugBias { float* p; int heads, Dp, dh; };
   std::vector<AugBias> aug_biases;                  // the b_qkv_aug vectors of this build (filled after the arena exists)
+  // derived weights of the arena (tuning "ff_fold"): one entry per transformer block whose ff2 + proj_out pair has a folded form
+  struct FfFold { const half_t* wp; int ldp; const float* bp; const half_t* w2; const float* b2; int C; half_t* w_fo; float* b_fo; std::string src[4]; };
+  std::vector<FfFold> ff_folds;
   bool warena_borrowed = false;                     // pnpi_create_shared: warena.base is the parent's (never written here)
-  struct ArenaRef { void* base; std::atomic<int> refs; };
+  // ff_fold_ready: the folded weights in the arena match the ff2 / proj_out weights next to them (set by the owner after a load,
+  // read by every context on the arena before a forward takes the folded path)
+  struct ArenaRef { void* base; std::atomic<int> refs; bool ff_fold_ready = false; };
   ArenaRef* warena_ref = nullptr;                   // shared by the owner and every context that borrows the arena: the last pnpi_destroy frees it
   float* splitk_ws; size_t splitk_bytes;
   float* gn_partial;

@@ -869,6 +869,70 @@ int launch_repack_vec(const void* src, int src_f16, int n, float* dst, hipStream
   return (int)hipGetLastError();
 }
 
+// ff2 folded into proj_out (transformer_fwd, tuning "ff_fold"): out = [f2 | hs2] [Wp W2 | Wp]^T + (Wp b2 + bp) + x, so per block
+//   w_fo[n][0:4C] = sum_j Wp[n][j] W2[j][:],  w_fo[n][4C:5C] = Wp[n][:],  b_fo[n] = sum_j Wp[n][j] b2[j] + bp[n]
+// from the stored fp16 weights: products of two fp16 values are exact in fp32, the sum runs in fp32 in a fixed order (j ascending)
+// and is rounded to fp16 once.  C % 64 == 0 (the fold's own condition): whole 64 x 64 tiles, no tails.  grid (5C / 64, C / 64): the
+// first 4C / 64 tile columns hold the product, the last C / 64 the copy of Wp.
+__global__ void __launch_bounds__(256) ff_fold_weight_kernel(const half_t* __restrict__ wp, int ldp, const half_t* __restrict__ w2, int C,
+                                                             half_t* __restrict__ w_fo) {
+  const int tid = threadIdx.x, n0 = blockIdx.y * 64, k0 = blockIdx.x * 64, K4 = 4 * C, ldo = 5 * C;
+  if (k0 >= K4) {
+    for (int idx = tid; idx < 64 * 16; idx += 256) {
+      const int r = idx >> 4, v = (idx & 15) * 4;
+      *reinterpret_cast<half4*>(w_fo + (size_t)(n0 + r) * ldo + k0 + v) = *reinterpret_cast<const half4*>(wp + (size_t)(n0 + r) * ldp + (k0 - K4) + v);
+    }
+    return;
+  }
+  __shared__ float sA[16][64 + 4];   // Wp^T tile: [j][n]
+  __shared__ float sB[16][64 + 4];   // W2 tile:   [j][k]
+  const int tx = tid & 15, ty = tid >> 4;
+  float acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+  for (int j0 = 0; j0 < C; j0 += 16) {
+    const half4 av = *reinterpret_cast<const half4*>(wp + (size_t)(n0 + (tid >> 2)) * ldp + j0 + (tid & 3) * 4);
+    const half4 bv = *reinterpret_cast<const half4*>(w2 + (size_t)(j0 + ty) * K4 + k0 + tx * 4);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { sA[(tid & 3) * 4 + q][tid >> 2] = (float)av[q]; sB[ty][tx * 4 + q] = (float)bv[q]; }
+    __syncthreads();
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+      float a4[4], b4[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { a4[q] = sA[jj][ty * 4 + q]; b4[q] = sB[jj][tx * 4 + q]; }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_fmaf(a4[a], b4[b], acc[a][b]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const half4 h = {(half_t)acc[a][0], (half_t)acc[a][1], (half_t)acc[a][2], (half_t)acc[a][3]};
+    *reinterpret_cast<half4*>(w_fo + (size_t)(n0 + ty * 4 + a) * ldo + k0 + tx * 4) = h;
+  }
+}
+__global__ void __launch_bounds__(256) ff_fold_bias_kernel(const half_t* __restrict__ wp, int ldp, const float* __restrict__ b2,
+                                                           const float* __restrict__ bp, int C, float* __restrict__ b_fo) {
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;     // one wave per output channel
+  if (n >= C) return;
+  float s = 0.f;
+  for (int j = lane; j < C; j += 64) s = __builtin_fmaf((float)wp[(size_t)n * ldp + j], b2[j], s);
+  s = wave_sum(s);
+  if (lane == 0) b_fo[n] = s + bp[n];
+}
+int launch_ff_fold_weights(const half_t* wp, int ldp, const float* bp, const half_t* w2, const float* b2, int C, half_t* w_fo, float* b_fo,
+                           hipStream_t st) {
+  if (C <= 0 || C % 64 || ldp < C || ldp % 4) return -2;
+  ff_fold_weight_kernel<<<dim3(5 * C / 64, C / 64), 256, 0, st>>>(wp, ldp, w2, C, w_fo);
+  ff_fold_bias_kernel<<<(C + 3) / 4, 256, 0, st>>>(wp, ldp, b2, bp, C, b_fo);
+  return (int)hipGetLastError();
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // CLIP text encoder helpers (transformers CLIPTextEmbeddings; quick_gelu = x * sigmoid(1.702 x))

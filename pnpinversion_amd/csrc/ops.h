@@ -85,6 +85,10 @@ int launch_gemv(const float* x, int K, const half_t* W, int N, const float* bias
 int launch_repack_matrix(const void* src, int src_f16, int rows, int cols, int taps, half_t* dst, int dst_ld, int cin_pad,
                          int row0, int dh, int Dp, hipStream_t st, int ilv_half = 0);
 int launch_repack_vec(const void* src, int src_f16, int n, float* dst, hipStream_t st, int ilv_half = 0);
+// ff2 folded into proj_out: w_fo [C][5C] = [Wp W2 | Wp] (fp32 sums of the stored fp16 weights, rounded once), b_fo [C] = Wp b2 + bp.
+// wp [C][ldp], w2 [C][4C]; C % 64 == 0
+int launch_ff_fold_weights(const half_t* wp, int ldp, const float* bp, const half_t* w2, const float* b2, int C, half_t* w_fo, float* b_fo,
+                           hipStream_t st);
 int launch_nchw_f32_to_nhwc_f16(const float* in, int B, int C, int HW, int Cp, half_t* out, hipStream_t st);
 int launch_f32_to_f16(const float* in, size_t n, half_t* out, hipStream_t st);
 int launch_img_u8_to_nhwc(const uint8_t* img, int n, int HW, int Cp, half_t* out, hipStream_t st);
