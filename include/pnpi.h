@@ -362,8 +362,7 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
  * only READ them).  A non-zero "igemm_vpp" / "igemm_sched" and "igemm_v128" / "igemm_v320" = 11, 12, 15 select ablation instances
  * that exist only in a library built with `python -m pnpinversion_amd.build --ablations` (-DPNPI_ABLATIONS=1 -> csrc/libpnpi_ablations.so,
  * loaded with PNPI_LIBRARY=<path>); the product library REJECTS those values here with PNPI_EINVAL -- and "attn_pipe" = 1 / 2 (round 6: the
- * half-tile software-pipelined forms of the 64-wide flash kernel, measured slower) likewise.  "gn_slab" (0): 1 = a split-K launch whose
- * output goes to a small-map GroupNorm leaves its combine to that kernel (bit-identical, measured slower: profiles/round5_gn_slab_ab.txt).
+ * half-tile software-pipelined forms of the 64-wide flash kernel, measured slower) likewise.
  * "ff_fold" (1): each transformer block's ff2 GEMM and 1x1 proj_out run as one launch over folded weights [Wp W2 | Wp] derived at load
  * (same FLOPs, no hs3 round trip; fp16-rounding-level difference); 0 = the two launches.  May be switched on a live context.
  * Keys (default): "text_kv" (1) / "temb_cache" (1) per-loop caches; "gn_inline_rows" (0)

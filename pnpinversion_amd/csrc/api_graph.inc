@@ -10,27 +10,14 @@ static void prof_close(pnpi_ctx* c, ProfRec& r, int cls, double flops, double by
   r.cls = cls; r.flops = flops; r.bytes = bytes; r.M = M; r.N = N; r.K = K; r.ksize = ks;
   c->prof.push_back(r);
 }
-// the deferred split-K combine of the previous GEMM launch (pnpi_ctx::pend): every op wrapper runs it before its own launch unless it
-// is the GroupNorm that consumes the slabs
-// tuning "gn_slab" = 1: a split-K launch whose output goes to a small-map GroupNorm leaves its combine to that kernel (bit-identical
-// results, tests/test_gpu_sd1_extras.py).  OFF by default: measured slower at every row count (profiles/round5_gn_slab_ab.txt: one-row
-// forward 4.53 -> 5.05 ms, twelve-row 14.89 -> 15.40) -- the slabs are the traffic either way (47 - 63 MB per launch at the 16 x 16 /
-// 8 x 8 levels) and the combine kernel streams them with every CU, the GroupNorm kernel with one block per (row, group)
-static int g_gn_slab = 0;
 // tuning "ff_fold" = 1: the transformer block's last two GEMMs (ff2, then the 1 x 1 proj_out) run as ONE launch over the folded weights
 // [Wp W2 | Wp] (TransformerW::fo) -- nothing non-linear sits between them and hs3 has no other reader.  Same FLOPs, one launch, no
 // hs3 round trip.  0: the two launches.  Results differ at fp16-rounding level only (hs3 is no longer rounded between the GEMMs;
 // Wp W2 is rounded once at load).
 static int g_ff_fold = 1;
-static int flush_pending(pnpi_ctx* c) {
-  if (!c->pend_on) return 0;
-  c->pend_on = false;
-  return launch_splitk_reduce(c->pend, c->st);
-}
 #define PROF(cls, flops, bytes, expr) PROFD(cls, flops, bytes, 0, 0, 0, expr)
 #define PROFD(cls, flops, bytes, d0, d1, d2, expr)            \
   do {                                                        \
-    if (c->pend_on) { int _f = flush_pending(c); if (_f) return fail_launch(c, _f, "deferred split-K combine"); } \
     if (c->prof_on && !c->dry) {                              \
       ProfRec _pr; prof_open(c, _pr);                         \
       int _r = (expr);                                        \
@@ -88,8 +75,8 @@ static inline bool keep_acts(pnpi_ctx* c) { return c->tape && c->tape->rec; }
 
 // ---------------------------------------------------------------------------------------------------- op wrappers
 // Per-channel GroupNorm partial sums attached to an activation by the GEMM that produced it ([tiles][C][2], `rows` per tile).
+// op_conv fills one for its caller on request: rows = rows per tile actually produced (0 = none).
 struct Stats { const float* p = nullptr; int rows = 0; };
-struct StatsReq { float* buf = nullptr; int rows = 0; bool transient = false; };   // in: buffer; out: rows per tile actually produced (0 = none); transient: only the GroupNorm that follows reads the output
 
 static half_t* talloc(pnpi_ctx* c, size_t n) { return (half_t*)c->temp.alloc(n * sizeof(half_t)); }
 static half_t* palloc(pnpi_ctx* c, size_t n) { return (half_t*)c->persist.alloc(n * sizeof(half_t)); }
@@ -100,19 +87,6 @@ static int op_gn(pnpi_ctx* c, const half_t* x1, const half_t* x2, int C1, int C2
   if (taping(c)) {
     TapeOp o; o.kind = TK_GN; o.x1 = x1; o.x2 = x2; o.C1 = C1; o.C2 = C2; o.B = B; o.HW = HW; o.nw = &nw; o.G = G; o.eps = eps; o.silu = silu; o.out = out;
     c->tape->ops.push_back(o);
-  }
-  if (c->pend_on) {
-    // x1 is still the split-K slabs of the GEMM that produces it: small maps are summed by the GroupNorm kernel itself (same bits as
-    // the separate combine launch), anything else gets the combine first
-    const GemmP& q = c->pend;
-    if (q.out == x1 && q.N == C1 && q.ldo == C1 && q.M == B * HW && !taping(c) && groupnorm_slab_ok(C1, C2, HW, G) && (C2 == 0 || x2)) {
-      c->pend_on = false;
-      GnSlab sl; sl.slab = q.slab; sl.splitk = q.splitk; sl.stride = (size_t)q.M * q.N; sl.bias = q.bias; sl.res = q.res; sl.ldres = q.ldres;
-      sl.sum_out = c->pend_keep ? q.out : nullptr;
-      PROFD(PNPI_KC_GROUPNORM, 0.0, B * HW * ((double)C1 * (4.0 * q.splitk + (q.res ? 2.0 : 0.0) + (c->pend_keep ? 2.0 : 0.0) + 2.0) + 4.0 * C2), B * HW, C1 + C2, 2,
-            launch_groupnorm_slab(sl, x2, C1, C2, B, HW, G, eps, nw.g, nw.b, silu, out, c->st));
-      return 0;
-    }
   }
   const bool ok1 = s1.p && s1.rows > 0 && HW % s1.rows == 0 && HW / s1.rows <= 256;
   const bool ok2 = !x2 || (s2.p && s2.rows > 0 && HW % s2.rows == 0 && HW / s2.rows <= 256);
@@ -131,26 +105,21 @@ static int op_gn(pnpi_ctx* c, const half_t* x1, const half_t* x2, int C1, int C2
 struct VtOut { void* outT = nullptr; int col0 = 1 << 30; int ld = 0; int f32 = 0; int rpb = 1; int perm16 = 0; };
 
 
-static int igemm_prof(pnpi_ctx* c, const GemmP& p, double alg_flops, StatsReq* sr = nullptr) {
+static int igemm_prof(pnpi_ctx* c, const GemmP& p, double alg_flops, Stats* so = nullptr) {
   int srows = 0, r;
-  if (c->pend_on) { int f = flush_pending(c); if (f) return f; }    // the slab workspace is about to be reused
-  // a launch whose output goes to a GroupNorm (the caller asked for statistics) may leave its split-K combine to that GroupNorm
-  GemmP dfr; dfr.splitk = 1;
-  GemmP* dp = (sr && c->defer_ok && g_gn_slab && !keep_acts(c)) ? &dfr : nullptr;
   if (c->prof_on) {
     ProfRec pr; prof_open(c, pr);
     int used = 0;
-    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, &used, &srows, dp);
+    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, &used, &srows);
     // algorithmic HBM bytes: the input tensor(s) once, the weight once, the output once (+ the residual it adds)
     const double in_rows = (double)p.B * p.H * p.W;
     const double alg_bytes = 2.0 * (in_rows * (p.C1 + p.C2) + (double)p.N * p.K + (double)p.M * (p.geglu ? p.N / 2 : p.N) * (p.res ? 2.0 : 1.0));
     igemm_last_launch(&pr.cfg, &pr.split, pr.geom);
     prof_close(c, pr, used, alg_flops, alg_bytes, p.M, p.N, p.K, p.ksize);
   } else {
-    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, nullptr, &srows, dp);
+    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, nullptr, &srows);
   }
-  if (dp && dfr.splitk > 1 && !r) { c->pend = dfr; c->pend_on = true; c->pend_keep = !sr->transient; }
-  if (sr) sr->rows = srows;
+  if (so) so->rows = srows;
   return r;
 }
 static float* stats_alloc(pnpi_ctx* c, int M, int N) {   // worst case: 64-row tiles
@@ -159,7 +128,7 @@ static float* stats_alloc(pnpi_ctx* c, int M, int N) {   // worst case: 64-row t
 
 static int op_conv(pnpi_ctx* c, const half_t* x1, int C1, const half_t* x2, int C2, int B, int H, int W, const ConvW& w, int stride,
                    int pad, int ups, const float* bias, const half_t* res, half_t* out, int Ho, int Wo, int N = -1,
-                   const VtOut* vt = nullptr, StatsReq* sr = nullptr) {
+                   const VtOut* vt = nullptr, Stats* so = nullptr) {
   GemmP p; gemm_defaults(p);
   int C1p = C2 ? C1 : w.cin_pad;  // single-source inputs are stored with the padded channel count
   p.x1 = x1; p.x2 = x2; p.C1 = C1p; p.C2 = C2; p.ldx1 = C1p; p.ldx2 = C2;
@@ -169,14 +138,14 @@ static int op_conv(pnpi_ctx* c, const half_t* x1, int C1, const half_t* x2, int 
   p.bias = bias; p.res = res; p.ldres = p.N; p.out = out; p.ldo = p.N;
   if (vt) { p.outT = vt->outT; p.vt_col0 = vt->col0; p.vt_ld = vt->ld; p.vt_f32 = vt->f32; p.rows_per_batch = vt->rpb; }
   c->ctr.executed_gemm_flops += 2.0 * p.M * p.N * p.K;
-  if (sr) { sr->buf = stats_alloc(c, p.M, p.N); sr->rows = 0; p.stats = sr->buf; }
+  if (so) { p.stats = stats_alloc(c, p.M, p.N); so->p = p.stats; so->rows = 0; }
   if (c->dry) return 0;
   if (taping(c)) {
     TapeOp o; o.kind = TK_CONV; o.x1 = x1; o.x2 = x2; o.C1 = C1p; o.C2 = C2; o.B = B; o.H = H; o.W = W; o.Ho = Ho; o.Wo = Wo; o.stride = stride; o.pad = pad;
     o.ups = ups; o.N = p.N; o.cw = &w; o.res = res; o.out = out;
     c->tape->ops.push_back(o);
   }
-  return igemm_prof(c, p, 2.0 * p.M * (double)w.cout * w.k * w.k * w.cin, sr);
+  return igemm_prof(c, p, 2.0 * p.M * (double)w.cout * w.k * w.k * w.cin, so);
 }
 
 struct GemmBatch { int n = 1; long sa = 0, sw = 0, sout = 0, soutT = 0; };   // n problems: strides of a / w / out in elements, of vt->outT in bytes
@@ -208,26 +177,18 @@ static int resnet_fwd(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, c
   CK(op_gn(c, x1, x2, C1, C2, B, HW, r.n1, G, eps, 1, t1, s1, s2));
   half_t* t2 = talloc(c, M * r.cout);
   const float* b1 = r.temb_off >= 0 ? c->bias_eff + r.temb_off : r.c1.b;
-  StatsReq q1, q2;
-  q1.transient = true;          // t2 is read by norm2 only
-  CK(op_conv(c, t1, r.cin, nullptr, 0, B, H, W, r.c1, 1, 1, 0, b1, nullptr, t2, H, W, -1, nullptr, &q1));
+  Stats st2, sto;
+  CK(op_conv(c, t1, r.cin, nullptr, 0, B, H, W, r.c1, 1, 1, 0, b1, nullptr, t2, H, W, -1, nullptr, &st2));
   half_t* t3 = talloc(c, M * r.cout);
-  Stats st2; st2.p = q1.buf; st2.rows = q1.rows;
   CK(op_gn(c, t2, nullptr, r.cout, 0, B, HW, r.n2, G, eps, 1, t3, st2));
   const half_t* sc = x1;
-  if (r.has_sc) {
-    // conv2 below adds it as its residual; when conv2's split-K combine is left to the next block's GroupNorm, that kernel reads it
-    // after this function has released its temporaries -- so it lives in the per-forward arena then
-    // (only with tuning gn_slab: otherwise the shortcut is a block temporary, recycled with the others.  The sizing dry runs reserve
-    // it in BOTH arenas, so the knob can be flipped on a live context.)
-    half_t* s;
-    if (c->dry) { (void)palloc(c, M * r.cout); s = talloc(c, M * r.cout); }
-    else s = (c->defer_ok && g_gn_slab) ? palloc(c, M * r.cout) : talloc(c, M * r.cout);
+  if (r.has_sc) {      // conv2 below adds it as its residual
+    half_t* s = talloc(c, M * r.cout);
     CK(op_conv(c, x1, C1, x2, C2, B, H, W, r.sc, 1, 0, 0, r.sc.b, nullptr, s, H, W));
     sc = s;
   }
-  CK(op_conv(c, t3, r.cout, nullptr, 0, B, H, W, r.c2, 1, 1, 0, r.c2.b, sc, out, H, W, -1, nullptr, &q2));
-  if (so) { so->p = q2.buf; so->rows = q2.rows; }
+  CK(op_conv(c, t3, r.cout, nullptr, 0, B, H, W, r.c2, 1, 1, 0, r.c2.b, sc, out, H, W, -1, nullptr, &sto));
+  if (so) *so = sto;
   if (!keep_acts(c)) c->temp.release(mk);      // a recording forward keeps every activation for the backward pass
   return 0;
 }
@@ -371,7 +332,7 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
     CK(op_gemm(c, n3, C, M, C, t.ff1.w, C, 8 * C, t.ff1.b, nullptr, 0, f1, 8 * C));
     if (!c->dry) PROF(PNPI_KC_GEGLU, 0.0, 12.0 * M * (double)C * 2.0, launch_geglu(f1, M, 4 * C, f2, c->st));
   }
-  StatsReq qo;
+  Stats qo;
   // ff2 + proj_out as one two-source 1 x 1 convolution over f2 | hs2 (K = 4C + C: both parts are whole 64-wide k-chunks).  Only with
   // folded weights that match the loaded ones (ff_fold_ready); the sizing dry run takes the two-launch path, which needs more memory
   // (hs3), so the knob can be flipped on a live context
@@ -383,7 +344,7 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
     CK(op_gemm(c, f2, 4 * C, M, 4 * C, t.ff2.w, 4 * C, C, t.ff2.b, hs2, C, hs3, C));
     CK(op_conv(c, hs3, C, nullptr, 0, B, H, W, t.proj_out, 1, 0, 0, t.proj_out.b, x, out, H, W, -1, nullptr, &qo));
   }
-  if (so) { so->p = qo.buf; so->rows = qo.rows; }
+  if (so) *so = qo;
   c->temp.release(mk);
   return 0;
 }
@@ -481,9 +442,6 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   if (t < 0 || t >= g.n_train_timesteps) return fail(c, PNPI_EINVAL, "timestep out of range");
   c->persist.reset(); c->temp.reset();
   c->tf_index = 0;
-  c->pend_on = false;
-  struct DeferScope { pnpi_ctx* c; ~DeferScope() { c->defer_ok = false; c->pend_on = false; } } defer_scope{c};   // combines are deferred inside this forward only
-  c->defer_ok = true;
   const int S = g.sample_size, n = g.n_blocks, C0 = g.block_out_channels[0], TE = 4 * C0, G = g.norm_groups;
   const int B = rows;
   const float eps = 1e-5f;
@@ -524,11 +482,7 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   int H = S;
   half_t* h = palloc(c, (size_t)B * H * H * C0);
   Stats hs_;   // GroupNorm partial sums travelling with h
-  {
-    StatsReq q;
-    CK(op_conv(c, x0, 8, nullptr, 0, B, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, h, H, H, -1, nullptr, &q));
-    hs_.p = q.buf; hs_.rows = q.rows;
-  }
+  CK(op_conv(c, x0, 8, nullptr, 0, B, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, h, H, H, -1, nullptr, &hs_));
   int ch = C0;
   skips.push_back({h, ch, H, hs_});
   for (int i = 0; i < n; ++i) {
@@ -549,9 +503,8 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
     if (i != n - 1) {
       const int Ho = H / 2;
       half_t* o = palloc(c, (size_t)B * Ho * Ho * oc);
-      StatsReq q;
-      CK(op_conv(c, h, ch, nullptr, 0, B, H, H, u.down_samp[i], 2, 1, 0, u.down_samp[i].b, nullptr, o, Ho, Ho, -1, nullptr, &q));
-      h = o; H = Ho; hs_.p = q.buf; hs_.rows = q.rows;
+      CK(op_conv(c, h, ch, nullptr, 0, B, H, H, u.down_samp[i], 2, 1, 0, u.down_samp[i].b, nullptr, o, Ho, Ho, -1, nullptr, &hs_));
+      h = o; H = Ho;
       skips.push_back({h, ch, H, hs_});
     }
   }
@@ -584,9 +537,8 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
     if (i != n - 1) {
       const int Ho = H * 2;
       half_t* o = palloc(c, (size_t)B * Ho * Ho * oc);
-      StatsReq q;
-      CK(op_conv(c, h, ch, nullptr, 0, B, H, H, u.up_samp[i], 1, 1, 1, u.up_samp[i].b, nullptr, o, Ho, Ho, -1, nullptr, &q));
-      h = o; H = Ho; hs_.p = q.buf; hs_.rows = q.rows;
+      CK(op_conv(c, h, ch, nullptr, 0, B, H, H, u.up_samp[i], 1, 1, 1, u.up_samp[i].b, nullptr, o, Ho, Ho, -1, nullptr, &hs_));
+      h = o; H = Ho;
     }
   }
   half_t* gno = palloc(c, (size_t)B * H * H * ch);
@@ -595,7 +547,6 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
     VtOut v; v.outT = eps_out; v.col0 = 0; v.ld = H * H; v.f32 = 1; v.rpb = H * H;
     CK(op_conv(c, gno, ch, nullptr, 0, B, H, H, u.conv_out, 1, 1, 0, u.conv_out.b, nullptr, nullptr, H, H, -1, &v));
   }
-  CK(flush_pending(c));
   c->ctr.unet_calls += c->dry ? 0 : 1;
   c->ctr.unet_sample_forwards += c->dry ? 0 : rows;
   c->ctr.unet_sample_forwards_cached_kv += (c->dry || !c->tkv.use) ? 0 : rows;

@@ -513,8 +513,7 @@ static bool pp_eligible(const GemmP& p, int cfg, int split, bool dma_ok) {
 }
 
 int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_cfg, int force_split, int* cfg_used,
-                 int* stats_tile_rows, GemmP* deferred) {
-  if (deferred) deferred->splitk = 1;
+                 int* stats_tile_rows) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return -2;
   const int Cin = p.C1 + p.C2;
   if ((Cin & 7) || (p.K & 7) || (p.C1 & 7) || (p.ldw & 7) || (p.ldx1 & 7) || (p.C2 && (p.ldx2 & 7))) return -3;
@@ -728,21 +727,8 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
     if (blocks > 2048) blocks = 2048;
     const bool vec = p.N % 4 == 0 && p.vt_col0 >= p.N && p.ldo % 4 == 0 && (!p.res || p.ldres % 4 == 0) && (!p.bias || ((uintptr_t)p.bias & 15) == 0) &&
                      ((uintptr_t)p.out & 7) == 0 && (!p.res || ((uintptr_t)p.res & 7) == 0) && ((uintptr_t)ws & 15) == 0;
-    // a caller that asked for it gets the slabs instead of the combine launch (alpha == 1: `v * 1 + bias` has the same bits fused or
-    // not): it either runs launch_splitk_reduce itself or hands the slabs to a consumer that sums them in the same order (GroupNorm)
-    if (vec && deferred && p.alpha == 1.f) { *deferred = p; return (int)hipGetLastError(); }
     if (vec) splitk_reduce_vec_kernel<<<blocks, 256, 0, st>>>(p);
     else splitk_reduce_kernel<<<blocks, 256, 0, st>>>(p);
   }
-  return (int)hipGetLastError();
-}
-
-// the combine of a launch_igemm call that deferred it (`p` as returned through `deferred`: splitk > 1, the vectorised layout)
-int launch_splitk_reduce(const GemmP& p, hipStream_t st) {
-  if (p.splitk <= 1 || !p.slab) return -2;
-  const size_t total = (size_t)p.M * (p.N / 4);
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  splitk_reduce_vec_kernel<<<blocks, 256, 0, st>>>(p);
   return (int)hipGetLastError();
 }

@@ -221,8 +221,4 @@ struct pnpi_ctx {
   bool prof_on = false;
   std::vector<ProfRec> prof;
   Tape* tape = nullptr;          // non-null while a forward is being recorded for a backward pass
-  // A split-K launch of the UNet forward whose combine has not run yet (api_graph.inc: op_conv defers it, the next op either is the
-  // GroupNorm that reads the tensor -- it then sums the slabs itself -- or runs the combine first).  pend_keep: somebody besides that
-  // GroupNorm reads the fp16 tensor (residual / skip connection), so the fused kernel must also store it.
-  GemmP pend; bool pend_on = false, pend_keep = true, defer_ok = false;
 };

@@ -4,8 +4,7 @@ to the headline -- 8 images per set of launches (96-row launches: the b96 rows o
 overlapped on a second context -- each against the reference's own P2PEditor("directinversion+p2p") run on the same image, prompts and
 weights (tests/golden/e2e_sd1.npz, 2 + 2 steps, oracle/make_golden.py e2e_sd1) at the bars of tests/test_gpu_headline_parity.py.
 A tile-table row that goes wrong at 3 / 24 / 96 rows turns these red; the TINY16 / SMALL64 tests of test_gpu_loops.py never reach
-those rows.  Also one ping-pong convolution at B = 96, H = 64 (M = 393 216) against F.conv2d, and the split-K combine folded into
-GroupNorm (tuning gn_slab) against the separate-launch path: bit-identical forwards at 1 / 12 rows.
+those rows.  Also one ping-pong convolution at B = 96, H = 64 (M = 393 216) against F.conv2d.
 Reference: /root/reference/run_editing_p2p.py:102-146 (the sweep visits images one by one; every mode here is that loop's throughput form)."""
 import math
 import os
@@ -192,30 +191,6 @@ def test_sd1_in_flight_and_overlapped_streams_against_reference_golden(sd1):
     for i, p in enumerate(got):
         assert np.array_equal(p, one), "overlapped inversion: image %d differs from the one-by-one panel" % i
     ed.close_peers()
-
-
-@pytest.mark.parametrize("rows", [1, 12])
-def test_sd1_groupnorm_sums_splitk_slabs_bit_identically(sd1, rows):
-    """Round 5: with tuning gn_slab = 1 a split-K convolution whose output goes to a small-map GroupNorm leaves its slabs to that
-    GroupNorm kernel (gn_small_kernel<..., SLAB>, norm.hip): same summation order, same fp16 rounding as splitk_reduce_vec_kernel -> the
-    UNet output is bit-identical with the fusion on and off, at the row counts of the inversion and of the lock-step loop.  (Off by
-    default: it measured slower, profiles/round5_gn_slab_ab.txt; the option and this test keep the negative result reproducible.)"""
-    pipe, g = sd1
-    eng = pipe.engine
-    gen = torch.Generator().manual_seed(3)
-    lat = torch.randn(rows, 4, 64, 64, generator=gen)
-    ctx = weights.synth_context(SD1, rows, seed=4)
-    from pnpinversion_amd import _capi
-    lib = _capi.load_library()
-    try:
-        assert lib.pnpi_set_tuning(b"gn_slab", 0) == 0
-        ref = eng.unet(lat, 481, ctx).cpu()
-        assert lib.pnpi_set_tuning(b"gn_slab", 1) == 0
-        got = eng.unet(lat, 481, ctx).cpu()
-    finally:
-        lib.pnpi_set_tuning(b"gn_slab", 0)          # the default (the fused path measured slower: profiles/round5_gn_slab_ab.txt)
-    assert torch.isfinite(got).all()
-    assert torch.equal(got, ref), (got - ref).abs().max().item()
 
 
 def test_pingpong_conv_at_96_rows_of_64x64():
