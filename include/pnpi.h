@@ -459,6 +459,27 @@ int pnpi_null_latent_calculate(pnpi_ctx* ctx, const float* ddim_latents, const f
 int pnpi_op_attention(pnpi_ctx* ctx, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt,
                       int ldv, void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale,
                       const int* rows_dev /*[nrows][4]*/, int nrows);
+/* ---- mask-guided MasaCtrl (models/masactrl/masactrl.py:114-193, MutualSelfAttentionControlMask) --------------------------------
+ * Attach nimg pairs of BINARY uint8 masks [nimg][h][w] (host pointers, values 0 / 1) to the context: from then on, at the steps and
+ * blocks a kind-2 controller controls, each target row attends to its source row's K / V restricted by class -- query i sees the keys j
+ * with mask_s[j] == mask_t[i], both masks resized to the block's map by F.interpolate nearest (source = floor(dst * in / out)).  That is
+ * the reference's two masked passes + blend in one softmax (exact for 0 / 1 masks); a query whose class no key carries gets the mean
+ * of V, as the reference's all-finfo.min softmax does.  Source rows are untouched.  The resized masks live in context-owned memory at
+ * fixed addresses, rewritten by every call.  (NULL, NULL) clears the masks: plain MasaCtrl again.  Applies to pnpi_edit_loop,
+ * pnpi_direct_edit (every pass) and pnpi_unet_forward.  Refused with PNPI_EINVAL and a pnpi_last_error message, before anything is
+ * launched: a value other than 0 / 1, one mask without the other, nimg outside 1 .. max_unet_rows / 4 -- and, by the loop that finds
+ * kind-2 controllers, masks held for another nimg than the loop's. */
+int pnpi_masa_set_masks(pnpi_ctx* ctx, const uint8_t* mask_s_u8_host, const uint8_t* mask_t_u8_host, int nimg, int h, int w);
+/* read back level `level`'s resized masks (side = sample_size >> level), [nimg][side][side] bytes each, to host memory (tests) */
+int pnpi_masa_get_level_masks(pnpi_ctx* ctx, int level, uint8_t* mask_s_out_host, uint8_t* mask_t_out_host, int* side_out);
+/* kernel-level: the nearest resize of n device masks [n][H][W] -> [n][h][w] class bytes */
+int pnpi_op_masa_mask_level(pnpi_ctx* ctx, const uint8_t* in_dev, int n, int H, int W, int h, int w, uint8_t* out_dev);
+/* kernel-level: pnpi_op_attention with class-restricted keys.  kcls_dev [nmask][Nk] / qcls_dev [nmask][Nq] class bytes (non-zero = 1),
+ * mrow_dev [nrows]: the class row used by entry r of rows_dev.  Nk <= 16384. */
+int pnpi_op_attention_masked(pnpi_ctx* ctx, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt,
+                             int ldv, void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale,
+                             const int* rows_dev /*[nrows][4]*/, int nrows, const uint8_t* kcls_dev, const uint8_t* qcls_dev,
+                             const int* mrow_dev);
 int pnpi_op_cross_edit(pnpi_ctx* ctx, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt,
                        int ldv, void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale,
                        const int* pairs_dev, int npairs, const void* mmatT_f16, const float* c1, const float* c2,

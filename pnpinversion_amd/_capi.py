@@ -132,6 +132,11 @@ SYMBOLS = {
     "pnpi_null_text_optimize": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int), _f, _i, _f, _vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "pnpi_null_latent_calculate": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int), _f, _i, _f, _vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "pnpi_op_attention": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i]),
+    # mask-guided MasaCtrl (models/masactrl/masactrl.py:114-193)
+    "pnpi_masa_set_masks": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "pnpi_masa_get_level_masks": (_i, [_vp, _i, _vp, _vp, _ip]),
+    "pnpi_op_masa_mask_level": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "pnpi_op_attention_masked": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp]),
     "pnpi_op_cross_edit": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp,
                                 _vp, _vp, _vp, _i, _i]),
     "pnpi_op_local_blend": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _i]),

@@ -256,7 +256,7 @@ void pnpi_destroy(pnpi_ctx* c) {
   void* arena = nullptr;
   if (c->warena_ref && c->warena_ref->refs.fetch_sub(1) == 1) { arena = c->warena_ref->base; delete c->warena_ref; }
   void* bufs[] = {arena, c->persist.base, c->temp.base, c->ctrl_arena.base, c->splitk_ws, c->gn_partial, c->gn_bwd_ws,
-                  c->temb_table, c->temb_h, c->temb_emb, c->bias_scratch, c->bias_tab, c->tkv.base, c->rows_ident};
+                  c->temb_table, c->temb_h, c->temb_emb, c->bias_scratch, c->bias_tab, c->tkv.base, c->rows_ident, c->mm.base, c->mm.stage};
   for (void* b : bufs) (void)hipFree(b);
   if (c->tape) {
     (void)hipFree(c->tape->garena.base); (void)hipFree(c->tape->d_ctx); (void)hipFree(c->tape->attn_scratch);
@@ -828,6 +828,80 @@ int pnpi_op_attention(pnpi_ctx* c, const void* q, int ldq, int q_off, const void
   a.vt_perm = (g_op_attention_vt_perm && attn_flash_uses_dma64(Dp, Nk, 0)) ? 1 : 0;
   a.aug = g_op_attention_aug;
   CK(launch_attn_flash(a, c->st));
+  return 0;
+}
+/* pnpi_op_attention over class-restricted keys (attn.hip attn_flash_masked_kernel): kcls_dev [nmask][Nk], qcls_dev [nmask][Nq] class bytes,
+ * mrow_dev [nrows] the class row of each entry of rows_dev.  The tuning key "op_attention_vt_perm" applies as in pnpi_op_attention. */
+int pnpi_op_attention_masked(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt, int ldv,
+                             void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, const int* rows_dev, int nrows,
+                             const uint8_t* kcls_dev, const uint8_t* qcls_dev, const int* mrow_dev) {
+  if (!c || !q || !k || !vt || !o || !rows_dev || !kcls_dev || !qcls_dev || !mrow_dev) return PNPI_EINVAL;
+  AttnP a; a.q = (const half_t*)q; a.ldq = ldq; a.q_off = q_off; a.k = (const half_t*)k; a.ldk = ldk; a.k_off = k_off;
+  a.vt = (const half_t*)vt; a.ldv = ldv; a.o = (half_t*)o; a.ldo = ldo; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.Dp = Dp; a.dh = dh;
+  a.scale = scale; a.rows = rows_dev; a.nrows = nrows;
+  a.vt_perm = (g_op_attention_vt_perm && attn_flash_uses_dma64(Dp, Nk, 0)) ? 1 : 0;
+  AttnMaskP mk; mk.kcls = kcls_dev; mk.qcls = qcls_dev; mk.mrow = mrow_dev;
+  CK(launch_attn_flash_masked(a, mk, c->st));
+  return 0;
+}
+/* F.interpolate(mode="nearest") of n uint8 masks [n][H][W] to [n][h][w] class bytes (device pointers): the per-level resize of pnpi_masa_set_masks */
+int pnpi_op_masa_mask_level(pnpi_ctx* c, const uint8_t* in_dev, int n, int H, int W, int h, int w, uint8_t* out_dev) {
+  if (!c || !in_dev || !out_dev) return PNPI_EINVAL;
+  CK(launch_masa_mask_level(in_dev, n, H, W, h, w, out_dev, c->st));
+  return 0;
+}
+int pnpi_masa_set_masks(pnpi_ctx* c, const uint8_t* mask_s_host, const uint8_t* mask_t_host, int nimg, int h, int w) {
+  if (!c) return PNPI_EINVAL;
+  MasaMasks& mm = c->mm;
+  if (!mask_s_host && !mask_t_host) { mm.nimg = 0; return 0; }      // cleared: kind-2 controllers run plain MasaCtrl again
+  if (!mask_s_host || !mask_t_host) return fail(c, PNPI_EINVAL, "pnpi_masa_set_masks: mask_s and mask_t come together (NULL, NULL clears them)");
+  const pnpi_model_config& g = c->cfg;
+  const int cap = c->max_rows / 4;
+  if (nimg <= 0 || nimg > cap) return fail(c, PNPI_EINVAL, "pnpi_masa_set_masks: nimg must be 1 .. max_unet_rows / 4");
+  if (h <= 0 || w <= 0 || h > 4096 || w > 4096) return fail(c, PNPI_EINVAL, "pnpi_masa_set_masks: mask sides must be 1 .. 4096");
+  const size_t n = (size_t)nimg * h * w;
+  for (size_t i = 0; i < n; ++i)
+    if (mask_s_host[i] > 1 || mask_t_host[i] > 1)
+      return fail(c, PNPI_EINVAL, "pnpi_masa_set_masks: masks must be binary (0 / 1); the two-pass blend of fractional masks is not built");
+  if (!mm.base) {      // once per context: the level buffers keep their addresses
+    mm.cap_img = cap; mm.side.clear(); mm.off.clear();
+    size_t total = 0;
+    for (int i = 0; i < g.n_blocks; ++i) {
+      const int sd = g.sample_size >> i;
+      mm.side.push_back(sd); mm.off.push_back(total);
+      total += align_up((size_t)2 * cap * sd * sd, 256);
+    }
+    CKH(hipMalloc((void**)&mm.base, total));
+  }
+  if (mm.stage_bytes < 2 * n) {
+    CKH(hipStreamSynchronize(c->st));
+    if (mm.stage) CKH(hipFree(mm.stage));
+    mm.stage = nullptr; mm.stage_bytes = 0;
+    CKH(hipMalloc((void**)&mm.stage, 2 * n));
+    mm.stage_bytes = 2 * n;
+  }
+  mm.nimg = 0;
+  CKP(upload(c, mm.stage, mask_s_host, n));
+  CKP(upload(c, mm.stage + n, mask_t_host, n));
+  for (size_t l = 0; l < mm.side.size(); ++l) {
+    const int sd = mm.side[l];
+    CK(launch_masa_mask_level(mm.stage, nimg, h, w, sd, sd, mm.base + mm.off[l], c->st));
+    CK(launch_masa_mask_level(mm.stage + n, nimg, h, w, sd, sd, mm.base + mm.off[l] + (size_t)mm.cap_img * sd * sd, c->st));
+  }
+  mm.nimg = nimg;
+  return 0;
+}
+/* the resized masks of level `level` (side = sample_size >> level) as pnpi_masa_set_masks left them: [nimg][side][side] class bytes each */
+int pnpi_masa_get_level_masks(pnpi_ctx* c, int level, uint8_t* mask_s_out_host, uint8_t* mask_t_out_host, int* side_out) {
+  if (!c || !mask_s_out_host || !mask_t_out_host) return PNPI_EINVAL;
+  const MasaMasks& mm = c->mm;
+  if (mm.nimg <= 0) return fail(c, PNPI_ESTATE, "pnpi_masa_get_level_masks: no masks are set");
+  if (level < 0 || level >= (int)mm.side.size()) return fail(c, PNPI_EINVAL, "pnpi_masa_get_level_masks: level out of range");
+  const size_t n = (size_t)mm.nimg * mm.side[level] * mm.side[level];
+  CKH(hipStreamSynchronize(c->st));
+  CKH(hipMemcpy(mask_s_out_host, mm.s_at(level), n, hipMemcpyDeviceToHost));
+  CKH(hipMemcpy(mask_t_out_host, mm.t_at(level), n, hipMemcpyDeviceToHost));
+  if (side_out) *side_out = mm.side[level];
   return 0;
 }
 int pnpi_op_cross_edit(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt, int ldv,

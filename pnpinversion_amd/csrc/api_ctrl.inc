@@ -61,8 +61,16 @@ static int upload(pnpi_ctx* c, void* dst, const void* src, size_t bytes) {
 }
 
 // Build the device-side tables for `rows` UNet rows (rows_per_image = 4 when controllers are active).
-static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows, int rpi = 4, int src_off = 2, int tgt_off = 3) {
+// mask_nimg: the images of the caller's loop when the launch holds several pseudo-images per image (pnpi_direct_edit's passes: pseudo-image
+// q is image q % mask_nimg); 0 = nimg.  Only the masks of pnpi_masa_set_masks are indexed by it.
+static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows, int rpi = 4, int src_off = 2, int tgt_off = 3, int mask_nimg = 0) {
   CtrlDev& cd = c->cd;
+  if (cds && c->mm.nimg > 0) {      // refused before anything is uploaded or launched
+    bool any2 = false;
+    for (int i = 0; i < nimg; ++i) any2 = any2 || cds[i].kind == 2;
+    if (any2 && c->mm.nimg != (mask_nimg > 0 ? mask_nimg : nimg))
+      return fail(c, PNPI_EINVAL, "pnpi_masa_set_masks holds masks for another number of images than this call's nimg");
+  }
   c->ctrl_arena.reset();
   cd = CtrlDev();
   cd.nimg = nimg;
@@ -97,6 +105,24 @@ static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows
     if (cd.masa_any) {
       cd.rows_masa = (int*)c->ctrl_arena.alloc(masa.size() * sizeof(int));
       CKP(upload(c, cd.rows_masa, masa.data(), masa.size() * sizeof(int)));
+    }
+    if (cd.masa_any && c->mm.nimg > 0) {
+      std::vector<int> mplain, mtgt, mimg;
+      for (int r = 0; r < rows; ++r) {
+        const int i = r / 4;
+        if (cds[i].kind == 2 && (r & 1)) {
+          mtgt.insert(mtgt.end(), masa.begin() + r * 4, masa.begin() + r * 4 + 4);
+          mimg.push_back(i % c->mm.nimg);
+        } else mplain.insert(mplain.end(), masa.begin() + r * 4, masa.begin() + r * 4 + 4);
+      }
+      cd.masa_masked = true;
+      cd.n_masa_plain = (int)mplain.size() / 4; cd.n_masa_tgt = (int)mtgt.size() / 4;
+      cd.rows_masa_plain = (int*)c->ctrl_arena.alloc(mplain.size() * sizeof(int));
+      cd.rows_masa_tgt = (int*)c->ctrl_arena.alloc(mtgt.size() * sizeof(int));
+      cd.masa_tgt_img = (int*)c->ctrl_arena.alloc(mimg.size() * sizeof(int));
+      CKP(upload(c, cd.rows_masa_plain, mplain.data(), mplain.size() * sizeof(int)));
+      CKP(upload(c, cd.rows_masa_tgt, mtgt.data(), mtgt.size() * sizeof(int)));
+      CKP(upload(c, cd.masa_tgt_img, mimg.data(), mimg.size() * sizeof(int)));
     }
   }
   cd.any_edit = !edit_img.empty();

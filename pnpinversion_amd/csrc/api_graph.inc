@@ -271,6 +271,17 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
     c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * N * t.Dp;
     if (c->attn_cb && !c->dry) {
       CKP(attn_materialized(c, qk, 2 * hd, 0, qk, 2 * hd, hd, vt, ldv, ao, C, t.heads, N, N, t.Dp, t.dh, scale, B, 0, t.place, 2 * block_index));
+    } else if (!c->dry && masa && !rep && cd.masa_masked) {
+      // mask-guided MasaCtrl: source rows (and rows of other images) take the plain launch unchanged; every target row runs the
+      // class-restricted kernel over its source row's K / V with this level's resized masks (pnpi_masa_set_masks)
+      int lev = -1;
+      for (size_t l = 0; l < c->mm.side.size(); ++l) if (c->mm.side[l] == H && H == W) lev = (int)l;
+      if (lev < 0) return fail(c, PNPI_ESTATE, "mask-guided MasaCtrl: no resized mask for this self-attention level");
+      AttnP ap = a; ap.rows = cd.rows_masa_plain; ap.nrows = cd.n_masa_plain;
+      PROFD(PNPI_KC_ATTN_FLASH, 4.0 * ap.nrows * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash(ap, c->st));
+      AttnP am = a; am.rows = cd.rows_masa_tgt; am.nrows = cd.n_masa_tgt;
+      AttnMaskP mk; mk.kcls = c->mm.s_at(lev); mk.qcls = c->mm.t_at(lev); mk.mrow = cd.masa_tgt_img;
+      PROFD(PNPI_KC_ATTN_FLASH, 4.0 * am.nrows * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash_masked(am, mk, c->st));
     } else if (!c->dry) PROFD(PNPI_KC_ATTN_FLASH, 4.0 * B * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash(a, c->st));
   }
   half_t* hs1 = talloc(c, (size_t)M * C);

@@ -36,14 +36,14 @@ struct Loop {
 };
 // cds (nullable): controller descriptors of the nq (pseudo-)images of the launch, rows = rpi * nq
 static int loop_begin(Loop& L, int nsteps, int rows, const char* too_many_rows, const pnpi_ctrl_desc* cds = nullptr, int nq = 0, int rpi = 4,
-                      int src_off = 2, int tgt_off = 3) {
+                      int src_off = 2, int tgt_off = 3, int mask_nimg = 0) {
   pnpi_ctx* c = L.c;
   CKP(check_loop_ready(c));
   const pnpi_model_config& g = c->cfg;
   L.E = (size_t)g.in_channels * g.sample_size * g.sample_size; L.CE = (size_t)g.ctx_len * g.cross_dim;
   L.ratio = g.n_train_timesteps / nsteps; L.rows = rows;
   if (rows > c->max_rows) return fail(c, PNPI_EINVAL, too_many_rows);
-  return cds ? setup_ctrl(c, cds, nq, rows, rpi, src_off, tgt_off) : setup_ctrl(c, nullptr, 0, c->max_rows);
+  return cds ? setup_ctrl(c, cds, nq, rows, rpi, src_off, tgt_off, mask_nimg) : setup_ctrl(c, nullptr, 0, c->max_rows);
 }
 static void loop_map(Loop& L, const std::vector<int>& m, int** dev) {      // *dev is valid after loop_commit
   L.map_dst.push_back({dev, L.maps.size()});
@@ -246,7 +246,7 @@ int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* c
   memset(cds.data(), 0, cds.size() * sizeof(pnpi_ctrl_desc));      // the offset pass (pseudo-images 0..nimg-1) runs no controller
   if (ctrl_host) for (int i = 0; i < npass * nimg; ++i) cds[nimg + i] = ctrl_host[i];
   Loop L(c);
-  CKP(loop_begin(L, nsteps, 4 * NI, "(1 + npass) * nimg * 4 exceeds max_unet_rows", cds.data(), NI));
+  CKP(loop_begin(L, nsteps, 4 * NI, "(1 + npass) * nimg * 4 exceeds max_unet_rows", cds.data(), NI, 4, 2, 3, nimg));
   const size_t E = L.E, CE = L.CE; const int rows = L.rows;
   float* lat = misc_f(c, (size_t)NI * 2 * E);
   float* ctxrep = misc_f(c, (size_t)rows * CE);

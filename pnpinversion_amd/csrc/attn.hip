@@ -655,6 +655,283 @@ int launch_attn_flash(const AttnP& p, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Class-restricted self-attention: mask-guided MasaCtrl (models/masactrl/masactrl.py:138-193) for binary masks, in ONE softmax per query.
+// The reference runs the target row twice over the source row's keys -- logits + mask_s with the background (resp. foreground) keys
+// filled with finfo.min -- and blends the two outputs by mask_t.  For 0 / 1 masks a filled key contributes exp(finfo.min - max) = 0, the
+// +1 on the kept keys is a constant shift, and x * 1 + y * 0 = x: query i attends exactly to the keys j with kcls[j] == qcls[i].  If no key
+// carries the query's class every logit of that pass is finfo.min (sim + finfo.min rounds to finfo.min in fp32) and the reference's softmax
+// is uniform over ALL keys: such a query runs with a zero Q fragment and no restriction -- all scores 0, the mean of V.
+//
+// attn_flash_kernel<DP, true> (register prefetch of the next tile) with three additions:
+//   * prologue: the row's key classes as one bit per key in LDS (64-bit word t = key tile t), which classes exist at all, and the list of
+//     key tiles that hold a key of a class some query of this workgroup attends to -- only those are loaded;
+//   * per tile: a wave whose 32 queries attend to no key of the tile skips its MFMAs and exponentials (wave-uniform branch);
+//   * per score: one bit test against the query's 64-bit allow word.  Excluded keys score -inf; the running maximum starts at a finite
+//     -1e30 instead of -inf so that a tile without any allowed key leaves (mloc - mrun) = -inf, not NaN, and exp2(-inf) = 0.
+// VPERM: V^T in the permuted key order of the 4096-token sites (ops.h vt_perm16_pos) -- a lane's 8 keys of a 16-key step are contiguous.
+// ------------------------------------------------------------------------------------------------------------------
+static constexpr int MASK_MAX_TILES = ATTN_MASK_MAX_KEYS / KV_TILE;
+
+template <int DP, bool VPERM>
+__global__ void __launch_bounds__(256) attn_flash_masked_kernel(AttnP p, AttnMaskP mk) {
+  constexpr int KS = DP / 16, OT = DP / 32, SK_LD = DP + 8;
+  __shared__ __attribute__((aligned(16))) half_t sK[KV_TILE * SK_LD];
+  __shared__ __attribute__((aligned(16))) half_t sV[DP * SV_LD];
+  __shared__ unsigned long long sM[MASK_MAX_TILES];      // bit j of word t: class of key 64 t + j (keys past Nk: 0)
+  __shared__ unsigned short sList[MASK_MAX_TILES];       // the key tiles this workgroup visits, ascending
+  __shared__ int sCnt;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = lane >> 5, ql = lane & 31;
+  const int nqt = (p.Nq + 127) >> 7, T = nqt * p.heads * p.nrows, per = (T + 7) >> 3;
+  const int tix = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);      // XCD-aware order, see attn_flash_kernel
+  if (tix >= T) return;
+  const int qt = tix % nqt, head = (tix / nqt) % p.heads, ri = tix / (nqt * p.heads);
+  const int* rw = p.rows + ri * 4;
+  const int orow = rw[0], qrow = rw[1], krow = rw[2], vrow = rw[3];
+  const int mi = mk.mrow[ri];
+  const int qtok = qt * 128 + wave * 32 + ql;
+  const bool qok = qtok < p.Nq;
+  const int qc = mk.qcls[(size_t)mi * p.Nq + (qok ? qtok : 0)] != 0 ? 1 : 0;
+
+  half8 qf[KS];
+  {
+    const half_t* qp = p.q + ((size_t)qrow * p.Nq + (qok ? qtok : 0)) * p.ldq + p.q_off + head * DP + h * 8;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = qok ? ldg_half8(qp + ks * 16) : zero_half8();
+  }
+
+  // ---- key classes -> bits; 16 keys per thread and pass
+  const int ntiles = (p.Nk + KV_TILE - 1) / KV_TILE;
+  const uint8_t* kc = mk.kcls + (size_t)mi * p.Nk;
+  const bool vec = (p.Nk & 15) == 0 && ((uintptr_t)kc & 15) == 0;
+  int any1 = 0, any0 = 0;
+  for (int g = tid; g < ntiles * 4; g += 256) {
+    const int k0 = g * 16;
+    unsigned bits = 0;
+    if (vec && k0 < p.Nk) {
+      const uint4 w4 = *reinterpret_cast<const uint4*>(kc + k0);
+      const unsigned ww[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if ((ww[i] >> (8 * j)) & 0xffu) bits |= 1u << (4 * i + j);
+      any0 |= bits != 0xffffu;
+    } else {
+      for (int j = 0; j < 16; ++j)
+        if (k0 + j < p.Nk) {
+          if (kc[k0 + j]) bits |= 1u << j; else any0 = 1;
+        }
+    }
+    any1 |= bits != 0;
+    reinterpret_cast<unsigned short*>(sM)[g] = (unsigned short)bits;
+  }
+  const bool has1 = __syncthreads_or(any1) != 0;       // (the barriers also publish sM)
+  const bool has0 = __syncthreads_or(any0) != 0;
+  const bool uni = qc ? !has1 : !has0;                 // no key of this query's class: uniform over all keys
+  if (uni) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = zero_half8();
+  }
+  const int need = uni ? 3 : (1 << qc);                // bit 0: attends to class-0 keys, bit 1: to class-1 keys
+  const int wneed = (__ballot(need & 1) != 0 ? 1 : 0) | (__ballot(need & 2) != 0 ? 2 : 0);
+  const int bneed = (__syncthreads_or(need & 1) != 0 ? 1 : 0) | (__syncthreads_or(need & 2) != 0 ? 2 : 0);
+  auto tile_classes = [&](int t, unsigned long long m) {      // which classes the in-range keys of tile t carry
+    const int left = p.Nk - t * KV_TILE;
+    const unsigned long long valid = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
+    return ((m & valid) != 0 ? 2 : 0) | ((~m & valid) != 0 ? 1 : 0);
+  };
+  if (wave == 0) {
+    int cnt = 0;
+    for (int base = 0; base < ntiles; base += 64) {
+      const int t = base + lane;
+      const bool f = t < ntiles && (tile_classes(t, sM[t < ntiles ? t : 0]) & bneed) != 0;
+      const unsigned long long bal = __ballot(f);
+      if (f) sList[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)t;
+      cnt += __popcll(bal);
+    }
+    if (lane == 0) sCnt = cnt;
+  }
+  __syncthreads();
+  const int cnt = sCnt;      // >= 1: a restricted query's class has a key somewhere, an unrestricted one visits every tile
+
+  floatx16 O[OT];
+#pragma unroll
+  for (int ot = 0; ot < OT; ++ot)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) O[ot][r] = 0.f;
+  float mrun = -1e30f, lrun = 0.f;
+  const float c = p.scale * 1.44269504088896340736f;
+
+  const half_t* kbase = p.k + (size_t)krow * p.Nk * p.ldk + p.k_off + head * DP;
+  const half_t* vbase = p.vt + ((size_t)vrow * p.heads + head) * DP * (size_t)p.ldv;
+  constexpr int NKR = KV_TILE * (DP / 8) / 256, NVR = DP * (KV_TILE / 8) / 256;
+  static_assert(KV_TILE * (DP / 8) % 256 == 0 && DP * (KV_TILE / 8) % 256 == 0, "a tile is a whole number of 16-byte vectors per thread");
+  half8 rk[NKR], rv[NVR];
+  auto gload = [&](int kv0) {
+#pragma unroll
+    for (int i = 0; i < NKR; ++i) {
+      const int idx = tid + i * 256, r = idx / (DP / 8), v = idx - r * (DP / 8);
+      const int tok = kv0 + r;
+      rk[i] = tok < p.Nk ? ldg_half8(kbase + (size_t)tok * p.ldk + v * 8) : zero_half8();
+    }
+#pragma unroll
+    for (int i = 0; i < NVR; ++i) {
+      const int idx = tid + i * 256, d = idx >> 3, v = idx & 7;
+      const int tok0 = kv0 + v * 8;
+      const half_t* src = vbase + (size_t)d * p.ldv + tok0;
+      if (tok0 + 8 <= p.Nk) {
+        rv[i] = ldg_half8(src);
+      } else {
+        half8 val;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) val[j] = (tok0 + j < p.Nk) ? src[j] : (half_t)0.f;
+        rv[i] = val;
+      }
+    }
+  };
+  gload((int)sList[0] * KV_TILE);
+  for (int li = 0; li < cnt; ++li) {
+    const int t = sList[li], kv0 = t * KV_TILE;
+    __syncthreads();                    // every wave is done reading the previous tile
+#pragma unroll
+    for (int i = 0; i < NKR; ++i) {
+      const int idx = tid + i * 256, r = idx / (DP / 8), v = idx - r * (DP / 8);
+      *reinterpret_cast<half8*>(sK + r * SK_LD + v * 8) = rk[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NVR; ++i) {
+      const int idx = tid + i * 256, d = idx >> 3, v = idx & 7;
+      const half8 val = rv[i];
+      half4 lo = {val[0], val[1], val[2], val[3]}, hi = {val[4], val[5], val[6], val[7]};
+      *reinterpret_cast<half4*>(sV + d * SV_LD + v * 8) = lo;
+      *reinterpret_cast<half4*>(sV + d * SV_LD + v * 8 + 4) = hi;
+    }
+    __syncthreads();
+    if (li + 1 < cnt) gload((int)sList[li + 1] * KV_TILE);
+
+    const unsigned long long m = sM[t];
+    if ((tile_classes(t, m) & wneed) == 0) continue;      // wave-uniform: none of this wave's queries attends to a key of the tile
+
+    floatx16 s[2];
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[st][r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        half8 kf = *reinterpret_cast<const half8*>(sK + (st * 32 + ql) * SK_LD + ks * 16 + h * 8);
+        s[st] = mfma32(kf, qf[ks], s[st]);
+      }
+    }
+    {
+      // accumulator r of score tile st is key st * 32 + (r & 3) + 8 * (r >> 2) + 4 h: shift the allow word by 4 h once, test constant bits
+      const unsigned long long allow = uni ? ~0ull : (qc ? m : ~m);
+      const unsigned a2[2] = {(unsigned)(allow >> (4 * h)), (unsigned)(allow >> (32 + 4 * h))};
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (!((a2[st] >> ((r & 3) + 8 * (r >> 2))) & 1u)) s[st][r] = -INFINITY;
+    }
+    if (kv0 + KV_TILE > p.Nk) {         // only the last key tile can hold out-of-range keys
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kv0 + st * 32 + acc_row(r, lane) >= p.Nk) s[st][r] = -INFINITY;
+    }
+    float mloc = s[0][0];
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[st][r]);
+    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+    // deferred rescale as in attn_flash_kernel.  mrun is finite from the start: a query without an allowed key in this tile has
+    // mloc = -inf -> no move, and every exponential below is exp2(-inf) = 0; its first allowed key moves mrun up from -1e30 (alpha = 0 on O = 0)
+    const bool grow = (mloc - mrun) * c > 8.0f;
+    if (__any(grow)) {
+      const float mnew = fmaxf(mrun, mloc);
+      const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);
+      lrun *= alpha;
+#pragma unroll
+      for (int ot = 0; ot < OT; ++ot)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) O[ot][r] *= alpha;
+      mrun = mnew;
+    }
+    const float mc = mrun * c;
+    float psum = 0.f;
+    half8 pf[2][2];
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[st][r], c, -mc));
+        psum += pv;
+        pf[st][r >> 3][r & 7] = (half_t)pv;
+      }
+    lrun += psum;
+#pragma unroll
+    for (int ot = 0; ot < OT; ++ot) {
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+          // plain order: keys 4 h + {0..3, 8..11} of the 16-key step; permuted order: the same keys are positions 8 h + [0, 8)
+          const half_t* vb = sV + (ot * 32 + ql) * SV_LD + st * 32 + t2 * 16 + (VPERM ? 8 : 4) * h;
+          half4 lo = *reinterpret_cast<const half4*>(vb);
+          half4 hi = *reinterpret_cast<const half4*>(vb + (VPERM ? 4 : 8));
+          half8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          O[ot] = mfma32(vf, pf[st][t2], O[ot]);
+        }
+    }
+  }
+  const float ltot = lrun + __shfl_xor(lrun, 32, 64);
+  const float inv = 1.f / ltot;
+  if (qok) {
+    half_t* op = p.o + ((size_t)orow * p.Nq + qtok) * p.ldo + head * p.dh;
+#pragma unroll
+    for (int ot = 0; ot < OT; ++ot)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        int d = ot * 32 + 8 * g + 4 * h;
+        if (d + 3 < p.dh) {
+          half4 o4 = {(half_t)(O[ot][4 * g] * inv), (half_t)(O[ot][4 * g + 1] * inv), (half_t)(O[ot][4 * g + 2] * inv),
+                      (half_t)(O[ot][4 * g + 3] * inv)};
+          *reinterpret_cast<half4*>(op + d) = o4;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (d + j < p.dh) op[d + j] = (half_t)(O[ot][4 * g + j] * inv);
+        }
+      }
+  }
+}
+
+int launch_attn_flash_masked(const AttnP& p, const AttnMaskP& m, hipStream_t st) {
+  if (p.nrows <= 0) return 0;
+  if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.q_off & 7) || (p.k_off & 7) || (p.dh & 3) || (p.ldo & 3)) return -3;
+  if (!m.kcls || !m.qcls || !m.mrow || p.causal || p.lse) return -3;
+  if (p.Nk <= 0 || p.Nk > ATTN_MASK_MAX_KEYS) return -7;
+  if (p.vt_perm && (p.Nk & 15)) return -6;      // the permutation lives inside whole 16-token groups
+  const int total = ((p.Nq + 127) / 128) * p.heads * p.nrows;
+  dim3 grid((unsigned)(((total + 7) / 8) * 8), 1, 1);
+#define LAUNCH_MASKED(D) (p.vt_perm ? attn_flash_masked_kernel<D, true><<<grid, 256, 0, st>>>(p, m) : attn_flash_masked_kernel<D, false><<<grid, 256, 0, st>>>(p, m))
+  switch (p.Dp) {
+    case 32: LAUNCH_MASKED(32); break;
+    case 64: LAUNCH_MASKED(64); break;
+    case 96: LAUNCH_MASKED(96); break;
+    case 128: LAUNCH_MASKED(128); break;
+    case 160: LAUNCH_MASKED(160); break;
+    default: return -5;
+  }
+#undef LAUNCH_MASKED
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Cross-attention (<= 96 text tokens) for one (source, target) conditional row pair with the P2P edit fused in:
 //   P_src = softmax(Q_src K_src^T), P_tgt = softmax(Q_tgt K_tgt^T)
 //   P_tgt' = c1[j] * (P_src . Mmat)[j] + c2[j] * P_tgt[j]          (no renormalisation, as in the reference)

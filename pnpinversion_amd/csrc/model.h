@@ -151,6 +151,12 @@ struct CtrlDev {
   unsigned masa_layer_mask = 0;                     // bit 31: a layer_idx list was given (bits 0..15 = its blocks); 0 = the start_layer window
   std::vector<unsigned char> masa_step_on;          // step_idx list as a per-step flag array; empty + !masa_step_list = the start_step window
   bool masa_step_list = false;
+  // mask-guided MasaCtrl (pnpi_masa_set_masks): at the controlled sites the plain launch takes every row but the kind-2 target rows,
+  // which run the class-restricted kernel on {tgt, tgt, src, src} with the class rows of their image
+  bool masa_masked = false;
+  int* rows_masa_plain = nullptr; int n_masa_plain = 0;
+  int* rows_masa_tgt = nullptr; int n_masa_tgt = 0;     // [n_masa_tgt][4]
+  int* masa_tgt_img = nullptr;                          // [n_masa_tgt] mask image of each target row
   int n_plain = 0;
   int* pairs = nullptr;           // [npairs][2]
   half_t* mmatT = nullptr;        // [npairs][96][96]
@@ -166,6 +172,18 @@ struct TextKV {
   char* base = nullptr; size_t cap = 0;
   int rows = 0;                   // rows the cache holds (0 = invalid)
   bool use = false;               // the forward in flight reads the cache instead of projecting the context
+};
+
+// Mask-guided MasaCtrl: the source / target masks of pnpi_masa_set_masks resized to every self-attention level, one class byte per
+// token.  The buffer is allocated once per context (fixed addresses) and rewritten by every pnpi_masa_set_masks.
+struct MasaMasks {
+  uint8_t* base = nullptr;        // per level l: mask_s [cap_img][side_l^2], then mask_t [cap_img][side_l^2]
+  uint8_t* stage = nullptr; size_t stage_bytes = 0;    // the caller's full-size masks on the device
+  int cap_img = 0, nimg = 0;      // nimg == 0: no masks set
+  std::vector<int> side;          // level sides: sample_size >> i
+  std::vector<size_t> off;        // byte offset of level l's mask_s block
+  const uint8_t* s_at(int l) const { return base + off[l]; }
+  const uint8_t* t_at(int l) const { return base + off[l] + (size_t)cap_img * side[l] * side[l]; }
 };
 
 struct ProfRec { int cls; double flops, bytes; hipEvent_t a, b; int M, N, K, ksize; int cfg = -1, split = 0; int geom[7] = {0, 0, 0, 0, 0, 0, 0}; };
@@ -217,6 +235,7 @@ struct pnpi_ctx {
   bool sched_set;
   pnpi_counters ctr;
   CtrlDev cd;
+  MasaMasks mm;
   std::vector<char> host_stage;
   bool prof_on = false;
   std::vector<ProfRec> prof;

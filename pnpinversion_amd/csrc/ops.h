@@ -116,6 +116,17 @@ struct AttnP {
 int launch_attn_flash(const AttnP& p, hipStream_t st);
 int attn_set_tuning_pipe(int v);        // tuning "attn_pipe" (ablation builds only): the half-tile software-pipelined forms of the 64-wide LDS-DMA kernel
 bool attn_flash_uses_dma64(int Dp, int Nk, int causal);
+// Class-restricted self-attention (mask-guided MasaCtrl, models/masactrl/masactrl.py:138-193 for binary masks): query i attends only to the
+// keys j with kcls[j] == qcls[i]; a query whose class no key carries attends to all keys uniformly (the reference's softmax over logits
+// that all equal finfo.min).  One softmax per query; key tiles without a key of the workgroup's classes are neither loaded nor computed.
+struct AttnMaskP {
+  const uint8_t* kcls;            // device [nmask][Nk] 0 / 1 (non-zero reads as 1)
+  const uint8_t* qcls;            // device [nmask][Nq]
+  const int* mrow;                // device [nrows]: which of the nmask class rows entry r of AttnP::rows uses
+};
+static constexpr int ATTN_MASK_MAX_KEYS = 16384;   // the per-key class bits of one row sit in LDS
+// p.vt_perm: the permuted key order is read too (the 4096-token sites' projection writes it); p.aug is harmless (column dh of Q is zero padding)
+int launch_attn_flash_masked(const AttnP& p, const AttnMaskP& m, hipStream_t st);
 
 // Flash-style attention backward (null-text path): dQ / dK / dV of softmax(scale Q K^T) V without the [N][N] matrices in memory.
 struct BwdMat { const half_t* p; long hs; int ld; int w; };   // (head, row, col) -> p[head * hs + row * ld + col]; columns >= w read as zero (w % 8 == 0)
@@ -193,6 +204,8 @@ int launch_bld_step(const float* eps, const float* x, const float* src, const fl
                     float g, float a_t, float a_prev, float* x_out, hipStream_t st);
 // uint8 [n][H][W] -> fp32 0/1 [n][h][w]: PIL-nearest resize, non-zero -> 1
 int launch_bld_mask(const uint8_t* in, int n, int H, int W, int h, int w, float* out, hipStream_t st);
+// uint8 [n][H][W] -> uint8 0/1 [n][h][w]: F.interpolate(mode="nearest") indexing, source = min(floor(dst * (float)H / h), H - 1)
+int launch_masa_mask_level(const uint8_t* in, int n, int H, int W, int h, int w, uint8_t* out, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
 // Activation-gradient kernels of the null-text path (bwd.hip)

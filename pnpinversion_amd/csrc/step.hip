@@ -461,3 +461,27 @@ int launch_bld_mask(const uint8_t* in, int n, int H, int W, int h, int w, float*
   bld_mask_kernel<<<blocks, 256, 0, st>>>(in, n, H, W, h, w, out);
   return (int)hipGetLastError();
 }
+
+// Mask-guided MasaCtrl: the (h, w) source / target masks at one self-attention level, as the reference resizes them in every hooked
+// forward (masactrl.py:149, :187: F.interpolate(mask, (H, W)), mode "nearest").  torch's nearest index is
+// min(floor(dst * scale), in - 1) with scale = (float)in / out evaluated in fp32 (aten UpSampleNearest): the same expression here.
+__global__ void masa_mask_level_kernel(const uint8_t* __restrict__ in, int n, int H, int W, int h, int w, uint8_t* __restrict__ out) {
+  const size_t total = (size_t)n * h * w;
+  const float sy = (float)H / (float)h, sx = (float)W / (float)w;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % w), yo = (int)(i / w % h);
+    const size_t img = i / ((size_t)h * w);
+    int ys = (int)floorf((float)yo * sy), xs = (int)floorf((float)xo * sx);
+    if (ys > H - 1) ys = H - 1;
+    if (xs > W - 1) xs = W - 1;
+    out[i] = in[(img * H + ys) * W + xs] != 0 ? 1 : 0;
+  }
+}
+int launch_masa_mask_level(const uint8_t* in, int n, int H, int W, int h, int w, uint8_t* out, hipStream_t st) {
+  if (n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0) return -3;
+  size_t total = (size_t)n * h * w;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  masa_mask_level_kernel<<<blocks, 256, 0, st>>>(in, n, H, W, h, w, out);
+  return (int)hipGetLastError();
+}

@@ -84,6 +84,37 @@ class MasaCtrlTables:
         return d
 
 
+def masa_masks_u8(mask_s, mask_t):
+    """MutualSelfAttentionControlMask's mask_s / mask_t (models/masactrl/masactrl.py:124-131: (h, w) tensors, same shape) -> two contiguous
+    uint8 arrays [nimg, h, w] for pnpi_masa_set_masks ((h, w) is one image).  Only 0 / 1 values pass: the library runs the reference's two
+    masked passes + blend as one class-restricted softmax, which equals them for binary masks only."""
+    if mask_s is None or mask_t is None:
+        raise ValueError("mask-guided MasaCtrl needs both mask_s and mask_t; without masks use MutualSelfAttentionControl")
+    out = []
+    for name, m in (("mask_s", mask_s), ("mask_t", mask_t)):
+        a = m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.size == 0:
+            raise ValueError("%s must have shape (h, w) or (nimg, h, w), got %s" % (name, tuple(a.shape)))
+        if not np.isin(a, (0.0, 1.0)).all():
+            raise ValueError("%s must be binary (0 / 1): the blend of two masked passes for fractional masks is not built" % name)
+        out.append(np.ascontiguousarray(a.astype(np.uint8)))
+    if out[0].shape != out[1].shape:
+        raise ValueError("mask_s %s and mask_t %s must have the same shape" % (out[0].shape, out[1].shape))
+    return out[0], out[1]
+
+
+class MasaCtrlMaskTables(MasaCtrlTables):
+    """MutualSelfAttentionControlMask (models/masactrl/masactrl.py:114-193): the kind-2 descriptor plus the two masks, which travel
+    through pnpi_masa_set_masks (NativeEngine.masa_set_masks) when the editor is registered -- pnpi_ctrl_desc keeps its layout."""
+
+    def __init__(self, start_step=4, start_layer=10, layer_idx=None, step_idx=None, mask_s=None, mask_t=None):
+        super().__init__(start_step, start_layer, layer_idx, step_idx)
+        self.mask_s, self.mask_t = masa_masks_u8(mask_s, mask_t)
+
+
 def _desc_array(ctrls):
     """list[ControllerTables | None] -> (ctypes array of pnpi_ctrl_desc, keep-alive)"""
     if ctrls is None:
@@ -213,6 +244,27 @@ class NativeEngine:
 
     def reset_counters(self):
         self._call("pnpi_reset_counters")
+
+    def masa_set_masks(self, mask_s=None, mask_t=None):
+        """pnpi_masa_set_masks: attach binary masks [nimg, h, w] (or (h, w)) to the kind-2 controllers of this context; no arguments clears them."""
+        if mask_s is None and mask_t is None:
+            self._call("pnpi_masa_set_masks", None, None, 0, 0, 0)
+            self._masa_nimg = 0
+            return
+        s, t = masa_masks_u8(mask_s, mask_t)
+        self._masa_nimg = 0
+        self._call("pnpi_masa_set_masks", s.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), s.shape[0], s.shape[1], s.shape[2])
+        self._masa_nimg = s.shape[0]
+
+    def masa_level_masks(self, level):
+        """the resized masks of self-attention level `level` (side = sample_size >> level) -> (mask_s, mask_t) uint8 [nimg, side, side]"""
+        side = self.cfg.sample_size >> level
+        n = max(getattr(self, "_masa_nimg", 0), 1)
+        s, t = np.zeros((n, side, side), np.uint8), np.zeros((n, side, side), np.uint8)
+        got = C.c_int()
+        self._call("pnpi_masa_get_level_masks", int(level), s.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), C.byref(got))
+        assert got.value == side
+        return s, t
 
     def clock_probe(self, iters=100000):
         """effective matrix-pipe clock (GHz) under back-to-back MFMAs on every SIMD, and the probe's duration (ms)"""

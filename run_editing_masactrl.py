@@ -13,7 +13,7 @@ import torch.nn.functional as F
 from PIL import Image
 
 from pnpinversion_amd.masactrl.diffuser_utils import MasaCtrlPipeline
-from pnpinversion_amd.masactrl.masactrl import MutualSelfAttentionControl
+from pnpinversion_amd.masactrl.masactrl import MutualSelfAttentionControl, MutualSelfAttentionControlMask
 from pnpinversion_amd.masactrl.masactrl_utils import AttentionBase, regiter_attention_editor_diffusers
 from pnpinversion_amd.p2p.inversion import DirectInversion
 from pnpinversion_amd.utils.utils import load_512, txt_draw
@@ -40,22 +40,30 @@ class MasaCtrlEditor:
         self.scheduler = pipeline.scheduler
         self.model.scheduler.set_timesteps(self.num_ddim_steps)
 
-    def __call__(self, edit_method, image_path, prompt_src, prompt_tar, guidance_scale, step=4, layper=10):
+    def __call__(self, edit_method, image_path, prompt_src, prompt_tar, guidance_scale, step=4, layper=10, mask=None):
+        """mask (beyond the reference's signature): a binary (h, w) array -> mask-guided MasaCtrl with it as source AND target mask"""
+        kw = dict(mask=mask) if mask is not None else {}
         if edit_method == "ddim+masactrl":
-            return self.edit_image_ddim_MasaCtrl(image_path, prompt_src, prompt_tar, guidance_scale, step=step, layper=layper)
+            return self.edit_image_ddim_MasaCtrl(image_path, prompt_src, prompt_tar, guidance_scale, step=step, layper=layper, **kw)
         elif edit_method == "directinversion+masactrl":
-            return self.edit_image_directinversion_MasaCtrl(image_path, prompt_src, prompt_tar, guidance_scale, step=step, layper=layper)
+            return self.edit_image_directinversion_MasaCtrl(image_path, prompt_src, prompt_tar, guidance_scale, step=step, layper=layper, **kw)
         raise NotImplementedError(f"No edit method named {edit_method}")
 
     def _side(self):
         return self.model.engine.cfg.sample_size * self.model.engine.cfg.vae_scale
 
-    def _sample(self, prompt_tar, start, guidance_scale, step, layper, noise_loss_list):
+    def _sample(self, prompt_tar, start, guidance_scale, step, layper, noise_loss_list, mask=None):
         prompts = ["", prompt_tar]
         regiter_attention_editor_diffusers(self.model, AttentionBase())
         image_fixed = self.model([prompt_tar], latents=start[-1:], num_inference_steps=self.num_ddim_steps,
                                  guidance_scale=guidance_scale)                                   # "direct synthesis" (:104-110)
-        regiter_attention_editor_diffusers(self.model, MutualSelfAttentionControl(step, layper, total_steps=max(50, self.num_ddim_steps)))
+        total = max(50, self.num_ddim_steps)
+        if mask is None:
+            editor = MutualSelfAttentionControl(step, layper, total_steps=total)
+        else:
+            m = torch.as_tensor(np.asarray(mask), dtype=torch.float32)
+            editor = MutualSelfAttentionControlMask(step, layper, total_steps=total, mask_s=m, mask_t=m)
+        regiter_attention_editor_diffusers(self.model, editor)
         image_masactrl = self.model(prompts, latents=start, num_inference_steps=self.num_ddim_steps, guidance_scale=guidance_scale,
                                     noise_loss_list=noise_loss_list)
         return image_fixed, image_masactrl
@@ -77,27 +85,40 @@ class MasaCtrlEditor:
         return source_image, image_gt
 
     def edit_image_directinversion_MasaCtrl(self, image_path, prompt_src, prompt_tar, guidance_scale, step=4, layper=10,
-                                            return_stages=False):
+                                            return_stages=False, mask=None):
         """run_editing_masactrl.py:87-133"""
         source_image, image_gt = self._images(image_path)
         inv = DirectInversion(model=self.model, num_ddim_steps=self.num_ddim_steps)
         _, _, x_stars, noise_loss_list = inv.invert(image_gt=image_gt, prompt=["", prompt_tar], guidance_scale=guidance_scale)
         x_t = x_stars[-1]
-        _, image_masactrl = self._sample(prompt_tar, x_t.expand(2, -1, -1, -1), guidance_scale, step, layper, noise_loss_list)
+        _, image_masactrl = self._sample(prompt_tar, x_t.expand(2, -1, -1, -1), guidance_scale, step, layper, noise_loss_list, mask)
         panel = self._panel(source_image, image_masactrl, prompt_src, prompt_tar)
         return (panel, dict(x_stars=x_stars, noise_loss_list=noise_loss_list, images=image_masactrl)) if return_stages else panel
 
-    def edit_image_ddim_MasaCtrl(self, image_path, prompt_src, prompt_tar, guidance_scale, step=4, layper=10, return_stages=False):
+    def edit_image_ddim_MasaCtrl(self, image_path, prompt_src, prompt_tar, guidance_scale, step=4, layper=10, return_stages=False,
+                                 mask=None):
         """run_editing_masactrl.py:135-175"""
         source_image, _ = self._images(image_path)
         start_code, latents_list = self.model.invert(source_image, "", guidance_scale=guidance_scale,
                                                      num_inference_steps=self.num_ddim_steps, return_intermediates=True)
-        _, image_masactrl = self._sample(prompt_tar, start_code.expand(2, -1, -1, -1), guidance_scale, step, layper, None)
+        _, image_masactrl = self._sample(prompt_tar, start_code.expand(2, -1, -1, -1), guidance_scale, step, layper, None, mask)
         panel = self._panel(source_image, image_masactrl, prompt_src, prompt_tar)
         return (panel, dict(x_stars=latents_list, images=image_masactrl)) if return_stages else panel
 
 
-def main(argv=None):
+def latent_mask(rle, side=64):
+    """The PIE-Bench mask of an item (run-length list over the 512 x 512 image) as a binary (side, side) array: mask_decode, then PIL
+    NEAREST to the latent grid, as run_editing_blended_latent_diffusion.py reads its mask."""
+    m = Image.fromarray(np.uint8(mask_decode(rle)) * 255).resize((side, side), Image.NEAREST)
+    return (np.array(m) > 127).astype(np.uint8)
+
+
+def output_dir(output_path, method, mask_guided):
+    """output/<method> as in the reference; --mask_guided runs go to output/<method>-mask"""
+    return os.path.join(output_path, method + ("-mask" if mask_guided else ""))
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rerun_exist_images", action="store_true")
     ap.add_argument("--data_path", type=str, default="data")
@@ -106,9 +127,17 @@ def main(argv=None):
     ap.add_argument("--edit_method_list", nargs="+", type=str, default=["ddim+masactrl", "directinversion+masactrl"])
     ap.add_argument("--model_config", choices=("sd1", "small64"), default="sd1", help="small64: reduced-width test configuration")
     ap.add_argument("--num_ddim_steps", type=int, default=50)
-    from pnpinversion_amd.checkpoint import add_weight_args, resolve_weights
+    ap.add_argument("--mask_guided", action="store_true",
+                    help="mask-guided MasaCtrl (MutualSelfAttentionControlMask): the item's PIE-Bench mask at 64 x 64 is source and target "
+                         "mask; outputs go to <method>-mask.  Not an option of the reference's script.")
+    from pnpinversion_amd.checkpoint import add_weight_args
     add_weight_args(ap)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    from pnpinversion_amd.checkpoint import resolve_weights
+    args = build_parser().parse_args(argv)
     from pnpinversion_amd.distributed import broadcast_weights, shard_items
     from pnpinversion_amd.config import SD1, SMALL64
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -133,14 +162,15 @@ def main(argv=None):
         tgt = item["editing_prompt"].replace("[", "").replace("]", "")
         image_path = os.path.join(args.data_path, "annotation_images", item["image_path"])
         for method in args.edit_method_list:
-            out_path = image_path.replace(args.data_path, os.path.join(args.output_path, method))
+            out_path = image_path.replace(args.data_path, output_dir(args.output_path, method, args.mask_guided))
             if os.path.exists(out_path) and not args.rerun_exist_images:
                 print(f"skip image [{image_path}] with [{method}]")
                 continue
             print(f"editing image [{image_path}] with [{method}]")
             setup_seed()
             torch.cuda.empty_cache()
-            edited = editor(method, image_path=image_path, prompt_src=src, prompt_tar=tgt, guidance_scale=7.5, step=4, layper=10)
+            kw = dict(mask=latent_mask(item["mask"], cfg.sample_size)) if args.mask_guided else {}
+            edited = editor(method, image_path=image_path, prompt_src=src, prompt_tar=tgt, guidance_scale=7.5, step=4, layper=10, **kw)
             os.makedirs(os.path.dirname(out_path), exist_ok=True)
             edited.save(out_path)
             print("finish")
