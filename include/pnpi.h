@@ -141,6 +141,8 @@ typedef struct {
   uint64_t unet_sample_forwards_cached_kv;   /* of unet_sample_forwards, the rows that read the text K / V cache */
   uint64_t unet_backward_rows;     /* reverse walks (d loss / d context through one UNet row: null-text / null-latent inversion); the
                                       recording forward of each is counted in unet_sample_forwards */
+  uint64_t unet_dedup_prefix_rows; /* rows the text-independent UNet prefix ran on in forwards that deduplicated it (tuning "cfg_dedup":
+                                      one per distinct latent of the launch); forwards without deduplication add nothing */
 } pnpi_counters;
 
 /* ---- lifetime ------------------------------------------------------------------------------------------------ */
@@ -365,6 +367,12 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
  * half-tile software-pipelined forms of the 64-wide flash kernel, measured slower) likewise.
  * "ff_fold" (1): each transformer block's ff2 GEMM and 1x1 proj_out run as one launch over folded weights [Wp W2 | Wp] derived at load
  * (same FLOPs, no hs3 round trip; fp16-rounding-level difference); 0 = the two launches.  May be switched on a live context.
+ * "cfg_dedup" (2): in the loops that feed one latent to several UNet rows (classifier-free guidance: its unconditional and its
+ * conditional row), everything before the first cross-attention -- conv_in, the first ResNet, the first transformer block up to its
+ * cross-attention query -- runs once per distinct latent and is expanded to the rows of the launch there (behind the ResNet at steps
+ * where that block's self-attention redirects rows).  1 = the compact launches choose their own tiles (fp16-rounding-level difference
+ * where the choice differs), 2 = they are pinned to the tile / split-K of the full-row launch (bit-identical to 0), 0 = off.  Other
+ * values are rejected.  pnpi_unet_forward and one-row loops are not affected.  May be switched on a live context.
  * Keys (default): "text_kv" (1) / "temb_cache" (1) per-loop caches; "gn_inline_rows" (0)
  * one-launch GroupNorm below this many rows; "igemm_dma" (1) LDS-DMA kernel family; "igemm_table" (1) measured tile table before the
  * cost model; "igemm_wide" (1) 128x320 / 128x256 tiles; "igemm_deep_rings" (1) deeper LDS rings on sparse launches; "igemm_vt_lds" (1)

@@ -54,7 +54,8 @@ ATTN_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C
 class Counters(C.Structure):
     _fields_ = [("unet_sample_forwards", C.c_uint64), ("unet_calls", C.c_uint64), ("vae_encodes", C.c_uint64),
                 ("vae_decodes", C.c_uint64), ("executed_gemm_flops", C.c_double), ("executed_attn_flops", C.c_double),
-                ("text_kv_rows", C.c_uint64), ("unet_sample_forwards_cached_kv", C.c_uint64), ("unet_backward_rows", C.c_uint64)]
+                ("text_kv_rows", C.c_uint64), ("unet_sample_forwards_cached_kv", C.c_uint64), ("unet_backward_rows", C.c_uint64),
+                ("unet_dedup_prefix_rows", C.c_uint64)]
 
 
 KC_NAMES = ["igemm128", "igemm64", "igemm64_splitk", "attn_flash", "attn_cross_edit", "groupnorm", "layernorm", "geglu", "softmax", "igemm_wide"]

@@ -15,6 +15,15 @@ static void prof_close(pnpi_ctx* c, ProfRec& r, int cls, double flops, double by
 // hs3 round trip.  0: the two launches.  Results differ at fp16-rounding level only (hs3 is no longer rounded between the GEMMs;
 // Wp W2 is rounded once at load).
 static int g_ff_fold = 1;
+// tuning "cfg_dedup": the rows of a classifier-free-guidance launch that share a latent (its unconditional and its conditional row) share
+// everything the UNet computes before its first cross-attention.  1 / 2: that prefix runs once per distinct latent (unet_fwd, UNetDedup)
+// and is expanded to the rows of the launch where the text comes in; 2 pins every prefix GEMM to the tile / split-K of its full-row
+// form, which makes the forward bit-identical to 0 (per-element accumulation order does not depend on the tile's position).  0: off.
+// Default 2: at SD-1.x width 1 picks the same tiles (nearest table entry) with deeper rings, is no faster and moves panel pixels by up to 2 / 255.
+static int g_cfg_dedup = [] { const char* e = getenv("PNPI_CFG_DEDUP"); const int v = e ? atoi(e) : 2; return v >= 0 && v <= 2 ? v : 2; }();   // the variable: whole-benchmark A/B runs
+// the distinct latents of a launch: lat_u fp32 [U][C][S][S]; row r of the launch is latent hmap[r] (host) = dmap[r] (device)
+struct UNetDedup { const float* lat_u; int U; const int* hmap; const int* dmap; };
+struct TfDedup { int U; const int* dmap; };     // transformer_fwd: x holds U rows, the block's first half runs on them
 #define PROF(cls, flops, bytes, expr) PROFD(cls, flops, bytes, 0, 0, 0, expr)
 #define PROFD(cls, flops, bytes, d0, d1, d2, expr)            \
   do {                                                        \
@@ -107,17 +116,19 @@ struct VtOut { void* outT = nullptr; int col0 = 1 << 30; int ld = 0; int f32 = 0
 
 static int igemm_prof(pnpi_ctx* c, const GemmP& p, double alg_flops, Stats* so = nullptr) {
   int srows = 0, r;
+  // inside the pinned deduplicated prefix: configured as the same layer over all rows of the launch
+  const int sel_M = c->pin_to > 0 ? (int)((long)p.M / c->pin_from * c->pin_to) : 0;
   if (c->prof_on) {
     ProfRec pr; prof_open(c, pr);
     int used = 0;
-    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, &used, &srows);
+    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, &used, &srows, sel_M);
     // algorithmic HBM bytes: the input tensor(s) once, the weight once, the output once (+ the residual it adds)
     const double in_rows = (double)p.B * p.H * p.W;
     const double alg_bytes = 2.0 * (in_rows * (p.C1 + p.C2) + (double)p.N * p.K + (double)p.M * (p.geglu ? p.N / 2 : p.N) * (p.res ? 2.0 : 1.0));
     igemm_last_launch(&pr.cfg, &pr.split, pr.geom);
     prof_close(c, pr, used, alg_flops, alg_bytes, p.M, p.N, p.K, p.ksize);
   } else {
-    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, nullptr, &srows);
+    r = launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, -1, 0, nullptr, &srows, sel_M);
   }
   if (so) so->rows = srows;
   return r;
@@ -227,15 +238,33 @@ static int attn_materialized(pnpi_ctx* c, const half_t* q, int ldq, int q_off, c
 
 // SpatialTransformer + BasicTransformerBlock (my_diffusers/models/attention.py:140-200) with the hooked attention of
 // models/p2p/attention_control.py:20-47 and the controller semantics of :178-190, :269-282 fused into the kernels.
+// which row table a transformer block's self-attention takes at this step: 0 identity, 1 self-replace, 2 MasaCtrl
+static int self_attn_mode(pnpi_ctx* c, bool use_ctrl, int cur_step, int block_index, int N) {
+  const CtrlDev& cd = c->cd;
+  const bool edit = use_ctrl && cd.any_edit;
+  if (edit && cur_step >= cd.self_lo && cur_step < cd.self_hi && N <= cd.self_max_tokens) return 1;
+  const bool masa_step = cd.masa_step_list ? (cur_step >= 0 && cur_step < (int)cd.masa_step_on.size() && cd.masa_step_on[cur_step]) : cur_step >= cd.masa_start_step;
+  const bool masa_layer = cd.masa_layer_mask ? ((cd.masa_layer_mask >> block_index) & 1u) != 0 && block_index < 31 : block_index >= cd.masa_start_layer;
+  return (use_ctrl && cd.masa_any && masa_step && masa_layer) ? 2 : 0;
+}
+// dd (tuning "cfg_dedup"): x and sx hold dd->U rows, one per distinct latent of the B-row launch.  Everything up to the cross-attention
+// query reads no text, so it runs on those rows; hs1, q2 and x are then expanded to the B rows (row r = compact row dmap[r]) for the
+// second half.  Only for a block whose self-attention takes the identity row table at this step.
 static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, int B, int H, int W, const half_t* ctx16,
-                           bool use_ctrl, int cur_step, half_t* out, Stats sx = Stats(), Stats* so = nullptr) {
+                           bool use_ctrl, int cur_step, half_t* out, Stats sx = Stats(), Stats* so = nullptr, const TfDedup* dd = nullptr) {
   const pnpi_model_config& g = c->cfg;
   const size_t mk = c->temp.mark();
   const int block_index = c->tf_index++;    // transformer blocks in execution order (down 0.., mid, up ..15)
-  const int C = t.C, N = H * W, M = B * N, hd = t.heads * t.Dp, X = g.cross_dim, T = g.ctx_len;
+  const int C = t.C, N = H * W, hd = t.heads * t.Dp, X = g.cross_dim, T = g.ctx_len;
   const float scale = 1.0f / sqrtf((float)t.dh);
   CtrlDev& cd = c->cd;
   const bool edit = use_ctrl && cd.any_edit;
+  const int Bf = B, Mf = B * N;              // rows of the launch; B, M: the rows in hand (dd: of the text-independent first half)
+  if (dd) B = dd->U;
+  int M = B * N;
+  if (dd && ((N * C) % 8 || (N * hd) % 8)) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
+  // the sizing dry run takes the plain path and adds the three expanded tensors of the deduplicated one on top of it
+  if (c->dry && block_index == 0) { (void)talloc(c, (size_t)M * C); (void)talloc(c, (size_t)M * C); (void)talloc(c, (size_t)M * hd); }
 
   half_t* g0 = talloc(c, (size_t)M * C);
   CK(op_gn(c, x, nullptr, C, 0, B, N, t.gn, g.norm_groups, 1e-6f, 0, g0, sx));
@@ -263,10 +292,9 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
     AttnP a; a.q = qk; a.ldq = 2 * hd; a.q_off = 0; a.k = qk; a.ldk = 2 * hd; a.k_off = hd; a.vt = vt; a.ldv = ldv; a.vt_perm = vperm;
     a.aug = (t.b_qkv_aug && g_attn_aug) ? 1 : 0;      // K / V column dh hold 1.0 (the projection above added b_qkv_aug)
     a.o = ao; a.ldo = C; a.heads = t.heads; a.Nq = N; a.Nk = N; a.Dp = t.Dp; a.dh = t.dh; a.scale = scale;
-    const bool rep = edit && cur_step >= cd.self_lo && cur_step < cd.self_hi && N <= cd.self_max_tokens;
-    const bool masa_step = cd.masa_step_list ? (cur_step >= 0 && cur_step < (int)cd.masa_step_on.size() && cd.masa_step_on[cur_step]) : cur_step >= cd.masa_start_step;
-    const bool masa_layer = cd.masa_layer_mask ? ((cd.masa_layer_mask >> block_index) & 1u) != 0 && block_index < 31 : block_index >= cd.masa_start_layer;
-    const bool masa = use_ctrl && cd.masa_any && masa_step && masa_layer;
+    const int mode = self_attn_mode(c, use_ctrl, cur_step, block_index, N);
+    const bool rep = mode == 1, masa = mode == 2;
+    if (dd && (mode != 0 || c->attn_cb)) return fail(c, PNPI_ESTATE, "cfg_dedup: this block's self-attention redirects rows");
     a.rows = rep ? cd.rows_rep : (masa ? cd.rows_masa : cd.rows_id); a.nrows = B;
     c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * N * t.Dp;
     if (c->attn_cb && !c->dry) {
@@ -292,6 +320,15 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
   if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)C * 2.0, launch_layernorm(hs1, M, C, 1e-5f, t.ln2.g, t.ln2.b, n2, c->st));
   half_t* q2 = talloc(c, (size_t)M * hd);
   CK(op_gemm(c, n2, C, M, C, t.w_q2, C, hd, nullptr, nullptr, 0, q2, hd, 1.f, nullptr, 2.0 * M * (double)C * C));
+  if (dd) {            // from here on every row has its own text: the three tensors the second half reads, at the rows of the launch
+    c->pin_from = c->pin_to = 0;
+    B = Bf; M = Mf;
+    half_t *hs1f = talloc(c, (size_t)M * C), *q2f = talloc(c, (size_t)M * hd), *xf = talloc(c, (size_t)M * C);
+    CK(launch_gather_rows_f16(hs1, dd->dmap, B, (size_t)N * C, hs1f, c->st));
+    CK(launch_gather_rows_f16(q2, dd->dmap, B, (size_t)N * hd, q2f, c->st));
+    CK(launch_gather_rows_f16(x, dd->dmap, B, (size_t)N * C, xf, c->st));
+    hs1 = hs1f; q2 = q2f; x = xf;
+  }
   const int ldv2 = round_up_i(T, 8);
   half_t *k2, *vt2;
   if (c->tkv.use) {     // projected once per loop by text_kv_precompute
@@ -445,10 +482,12 @@ static int transformer_fwd_tape(pnpi_ctx* c, const TransformerW& t, const half_t
 }
 
 // UNet2DConditionModel.forward (my_diffusers/models/unet_2d_condition.py:189-273)
+// ud (nullable): the distinct latents behind the rows and the row -> latent map (the CFG loops); NULL = every row on its own
 static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const float* context, bool use_ctrl, int cur_step,
-                    float* eps_out) {
+                    float* eps_out, const UNetDedup* ud = nullptr) {
   const pnpi_model_config& g = c->cfg;
   const UNetW& u = c->unet;
+  c->pin_from = c->pin_to = 0;
   if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "unet rows out of range (max_unet_rows)");
   if (t < 0 || t >= g.n_train_timesteps) return fail(c, PNPI_EINVAL, "timestep out of range");
   c->persist.reset(); c->temp.reset();
@@ -488,6 +527,12 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
       c->bias_eff = c->bias_scratch;
     }
   }
+  // The text-independent prefix once per distinct latent (tuning "cfg_dedup"): conv_in, down_res[0][0] and, while block 0's
+  // self-attention takes the identity row table, the first half of down_attn[0][0].  Not for a recording forward (the tape walks
+  // full-row records), under a host attention callback, or in the sizing dry run (which sizes for both paths instead).
+  bool dedup = ud && g_cfg_dedup && !c->dry && ud->U > 0 && ud->U < rows && g.block_has_attn[0] && !keep_acts(c) && !c->attn_cb &&
+               ud->lat_u && ud->hmap && ud->dmap;
+  for (int r = 0; dedup && r < rows; ++r) dedup = ud->hmap[r] >= 0 && ud->hmap[r] < ud->U;
   struct Act { half_t* p; int C, H; Stats s; };
   std::vector<Act> skips;
   int H = S;
@@ -495,10 +540,50 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   Stats hs_;   // GroupNorm partial sums travelling with h
   CK(op_conv(c, x0, 8, nullptr, 0, B, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, h, H, H, -1, nullptr, &hs_));
   int ch = C0;
-  skips.push_back({h, ch, H, hs_});
+  skips.push_back({h, ch, H, hs_});      // the first skip tensor holds every row: conv_in (K = 72) runs on both row sets
+  if (c->dry && g.block_has_attn[0]) {   // what the deduplicated prefix keeps next to the plain path's tensors, at its upper bound U = B
+    const size_t px = (size_t)B * S * S;
+    (void)palloc(c, px * 8); (void)palloc(c, px * C0); (void)palloc(c, px * g.block_out_channels[0]); (void)palloc(c, px * g.block_out_channels[0]);
+    for (int k = 0; k < 5; ++k) (void)stats_alloc(c, (int)px, g.block_out_channels[0] > C0 ? g.block_out_channels[0] : C0);
+  }
   for (int i = 0; i < n; ++i) {
     const int oc = g.block_out_channels[i];
     for (int j = 0; j < g.layers_per_block; ++j) {
+      if (dedup && i == 0 && j == 0) {
+        const int U = ud->U;
+        half_t* x0c = palloc(c, (size_t)U * S * S * 8);
+        CK(launch_nchw_f32_to_nhwc_f16(ud->lat_u, U, g.in_channels, S * S, 8, x0c, c->st));
+        if (g_cfg_dedup == 2) { c->pin_from = U; c->pin_to = B; }
+        half_t* hc = palloc(c, (size_t)U * H * H * C0);
+        Stats hcs, rcs, ns;
+        CK(op_conv(c, x0c, 8, nullptr, 0, U, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, hc, H, H, -1, nullptr, &hcs));
+        half_t* rc = palloc(c, (size_t)U * H * H * oc);
+        CKP(resnet_fwd(c, u.down_res[0][0], hc, ch, nullptr, 0, U, H, H, G, eps, rc, hcs, Stats(), &rcs));
+        half_t* o2 = palloc(c, (size_t)B * H * H * oc);
+        if (self_attn_mode(c, use_ctrl, cur_step, c->tf_index, H * H) == 0) {
+          const TfDedup td{U, ud->dmap};
+          CKP(transformer_fwd(c, u.down_attn[0][0], rc, B, H, H, ctx16, use_ctrl, cur_step, o2, rcs, &ns, &td));   // unpins after its first half
+        } else {
+          // the self-attention redirects rows at this step: the prefix ends behind the ResNet, whose output and per-image GroupNorm
+          // partial sums are expanded to the rows of the launch
+          c->pin_from = c->pin_to = 0;
+          if (((size_t)H * H * oc) % 8) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
+          half_t* o = palloc(c, (size_t)B * H * H * oc);
+          CK(launch_gather_rows_f16(rc, ud->dmap, B, (size_t)H * H * oc, o, c->st));
+          Stats os;
+          if (rcs.p && rcs.rows > 0 && (H * H) % rcs.rows == 0) {
+            float* sp = stats_alloc(c, B * H * H, oc);
+            CK(launch_gather_rows_f32(rcs.p, ud->dmap, B, (size_t)(H * H / rcs.rows) * oc * 2, sp, c->st));
+            os.p = sp; os.rows = rcs.rows;
+          }
+          CKP(transformer_fwd(c, u.down_attn[0][0], o, B, H, H, ctx16, use_ctrl, cur_step, o2, os, &ns));
+        }
+        c->pin_from = c->pin_to = 0;
+        c->ctr.unet_dedup_prefix_rows += U;
+        h = o2; ch = oc; hs_ = ns;
+        skips.push_back({h, ch, H, hs_});
+        continue;
+      }
       half_t* o = palloc(c, (size_t)B * H * H * oc);
       Stats ns;
       CKP(resnet_fwd(c, u.down_res[i][j], h, ch, nullptr, 0, B, H, H, G, eps, o, hs_, Stats(), &ns));

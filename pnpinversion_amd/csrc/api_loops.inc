@@ -70,11 +70,17 @@ static int loop_commit(Loop& L, bool step_bufs = true) {
   for (auto& m : L.map_dst) *m.first = d + m.second;
   return L.maps.empty() ? 0 : upload(c, d, L.maps.data(), L.maps.size() * sizeof(int));
 }
-// inmap == NULL: lat already holds the rows of the launch
+// inmap == NULL: lat already holds the rows of the launch.  Otherwise lat holds the distinct latents of the step and inmap (one of the
+// loop's committed maps) sends every row to its latent: unet_fwd gets both, and runs what depends on the latent alone once per latent
 static int loop_unet(Loop& L, const float* lat, const int* inmap, int t, const float* ctx, bool use_ctrl, int step) {
   pnpi_ctx* c = L.c;
-  if (inmap) { CK(launch_gather_rows_f32(lat, inmap, L.rows, L.E, L.in, c->st)); lat = L.in; }
-  return unet_fwd(c, lat, L.rows, t, ctx, use_ctrl, step, L.eps);
+  if (!inmap) return unet_fwd(c, lat, L.rows, t, ctx, use_ctrl, step, L.eps);
+  CK(launch_gather_rows_f32(lat, inmap, L.rows, L.E, L.in, c->st));
+  UNetDedup ud{lat, 0, nullptr, inmap};
+  for (auto& m : L.map_dst)
+    if (*m.first == inmap && m.second + (size_t)L.rows <= L.maps.size()) ud.hmap = L.maps.data() + m.second;
+  for (int r = 0; ud.hmap && r < L.rows; ++r) ud.U = ud.hmap[r] + 1 > ud.U ? ud.hmap[r] + 1 : ud.U;
+  return unet_fwd(c, L.in, L.rows, t, ctx, use_ctrl, step, L.eps, ud.hmap ? &ud : nullptr);
 }
 // dst rows [img][uncond, cond] (ctx_cond == NULL: [img][uncond])
 static int interleave_ctx(pnpi_ctx* c, float* dst, const float* ctx_uncond, const float* ctx_cond, int nimg, size_t CE) {

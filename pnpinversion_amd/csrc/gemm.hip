@@ -513,7 +513,7 @@ static bool pp_eligible(const GemmP& p, int cfg, int split, bool dma_ok) {
 }
 
 int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_cfg, int force_split, int* cfg_used,
-                 int* stats_tile_rows) {
+                 int* stats_tile_rows, int sel_M) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return -2;
   const int Cin = p.C1 + p.C2;
   if ((Cin & 7) || (p.K & 7) || (p.C1 & 7) || (p.ldw & 7) || (p.ldx1 & 7) || (p.C2 && (p.ldx2 & 7))) return -3;
@@ -522,18 +522,21 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
   const bool fast = (Cin % BK == 0) && (p.C1 % BK == 0);
   const int nchunks = (p.K + BK - 1) / BK;
   const bool dma_ok = fast && g_use_dma && (p.K % BK == 0) && (p.ldw % 8 == 0) && ((size_t)p.K * 2 + 1024 <= ZERO_PAGE_BYTES);
-  auto tiles_of = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
+  // sel_M > 0: tile, split-K and ring depth are chosen as for a launch of sel_M rows (the same layer at another row count: the
+  // deduplicated UNet prefix pinned to its full-row configuration); the launch itself covers p.M rows
+  const int selM = sel_M > 0 ? sel_M : p.M;
+  auto tiles_of = [&](int bm, int bn) { return (long)((selM + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
   const long t64 = tiles_of(64, 64);
   int cfg = force_cfg;
   int split = 1;
   if (cfg < 0 && g_force_cfg >= 0) { cfg = g_force_cfg == 2 ? 1 : g_force_cfg; if (force_split <= 0) force_split = g_force_split; }
   if (cfg < 0 && g_use_table && dma_ok) {
-    if (const TileEntry* pe = tile_table_lookup(p.M, p.N, p.K, p.ksize, nullptr)) {
+    if (const TileEntry* pe = tile_table_lookup(selM, p.N, p.K, p.ksize, nullptr)) {
         const TileEntry& e = *pe;
         const int ebn = (e.cfg == 4 || e.cfg == 6 || e.cfg == 12 || e.cfg == 17) ? 320 : ((e.cfg == 5 || e.cfg == 7 || e.cfg == 15 || e.cfg == 16) ? 256 : ((e.cfg == 1 || e.cfg == 8 || e.cfg == 11) ? 64 : 128));
-        const bool split_ok = e.split == 1 || (!p.geglu && ws && (size_t)e.split * p.M * p.N * sizeof(float) <= ws_bytes);
+        const bool split_ok = e.split == 1 || (!p.geglu && ws && (size_t)e.split * selM * p.N * sizeof(float) <= ws_bytes);
         const bool vt_ok = p.vt_col0 >= p.N || p.vt_col0 % ebn == 0;
-        const bool pp_masked = (e.cfg == 16 || e.cfg == 17) && ((g_pp_only_n > 0 && p.N != g_pp_only_n) || (g_pp_only_k > 0 && p.K != g_pp_only_k) || (g_pp_only_m > 0 && p.M != g_pp_only_m) ||
+        const bool pp_masked = (e.cfg == 16 || e.cfg == 17) && ((g_pp_only_n > 0 && p.N != g_pp_only_n) || (g_pp_only_k > 0 && p.K != g_pp_only_k) || (g_pp_only_m > 0 && selM != g_pp_only_m) ||
                                                                  g_pp_only_n < 0);
         // a ping-pong entry (tile and split tuned together) applies only to a launch that kernel can take: otherwise the cost model
         // picks tile AND split for the 4-wave kernels (not the entry's split on a 128 x 128 tile)
@@ -553,7 +556,7 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
       if (tc.id >= 4 && !(dma_ok && g_wide)) continue;     // the wide tiles exist only as LDS-DMA kernels
       const long tiles = tiles_of(tc.bm, tc.bn);
       for (int s : splits) {
-        if (s > 1 && (nchunks / s < 4 || (size_t)s * p.M * p.N * sizeof(float) > ws_bytes || ws == nullptr)) continue;
+        if (s > 1 && (nchunks / s < 4 || (size_t)s * selM * p.N * sizeof(float) > ws_bytes || ws == nullptr)) continue;
         if (s > 1 && p.geglu) continue;
         // constants: tools/fit_cost_model2.py on tools/autotune2.py timings of every configuration per layer shape (rms log error
         // 0.10; the picks cost 1 % more than the per-shape best over a 12-row forward)
@@ -565,7 +568,7 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
         const double fill = per_cu >= tc.bpc ? 1.0 : (per_cu <= 1.0 ? 0.0 : (per_cu - 1.0) / (tc.bpc - 1.0));
         const double resid = 0.82 + 0.18 * fill;
         double t = (double)on_busiest * unit / resid;
-        if (s > 1) t += (double)(2 * s + 1) * p.M * p.N * 4.0 / 8.14e12 + 4.97e-6;   // slabs written, re-read, output + the reduce launch
+        if (s > 1) t += (double)(2 * s + 1) * selM * p.N * 4.0 / 8.14e12 + 4.97e-6;   // slabs written, re-read, output + the reduce launch
         if (p.vt_col0 < p.N && p.vt_col0 % tc.bn != 0) t *= 1.3;   // transposed columns not tile-aligned: scalar epilogue
         if (t < best) { best = t; cfg = tc.id; split = s; }
       }
@@ -585,7 +588,7 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
   // whatever chose the split (cost model or a caller-forced value): the slabs must fit the workspace and each split needs work
   if (split > 1) {
     if (split > nchunks) split = nchunks;
-    if (ws == nullptr || (size_t)split * p.M * p.N * sizeof(float) > ws_bytes || p.geglu || cfg == 3) split = 1;
+    if (ws == nullptr || (size_t)split * selM * p.N * sizeof(float) > ws_bytes || p.geglu || cfg == 3) split = 1;
   }
   if ((cfg == 16 || cfg == 17) && !pp_eligible(p, cfg, split, dma_ok)) cfg = 0;     // forced configurations (tests, sweeps): the 128 x 128 kernel instead
   const bool c64 = cfg == 1 || cfg == 8 || cfg == 11 || cfg == 12, c256m = cfg == 3 || cfg == 6 || cfg == 7 || cfg == 16;
@@ -620,7 +623,7 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
   // Ring depth by occupancy: with at most one block per CU nothing else covers the HBM latency of the weight stream (cold in a
   // forward: 1.7 GB of weights pass through per UNet call), and the whole 160 KB of LDS is free -- so sparse launches take an
   // 8-deep ring (7 chunks in flight per block); two blocks per CU a 4-deep one; fuller launches the shallow rings that fit 3 blocks.
-  const long units = (long)grid.x * grid.y * grid.z;
+  const long units = (long)((selM + bm - 1) / bm) * grid.y * grid.z;
   const int sparse = !g_deep_rings ? 0 : (units <= 256 ? 2 : (units <= 512 ? 1 : 0));
   if (!dma_ok) {
     if (cfg == 1) {
@@ -692,7 +695,7 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
     int var = g_var128;
     // 128-byte rows with 2 stages (64 KB, 2 blocks / CU) beat 64-byte rows with 3 stages (48 KB, 3 blocks / CU) once every CU
     // holds two blocks that cover for each other's exposed loads; below that the deeper ring wins
-    if (g_v128_bk64_tiles > 0 && var == 2 && (long)grid.x * grid.y * grid.z >= g_v128_bk64_tiles) var = 0;
+    if (g_v128_bk64_tiles > 0 && var == 2 && units >= g_v128_bk64_tiles) var = 0;
     if (var == 2 && sparse == 2) var = 8;
     else if (var == 2 && sparse == 1) var = 3;
     switch (var) {

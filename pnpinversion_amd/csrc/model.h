@@ -198,6 +198,8 @@ struct pnpi_ctx {
   int max_rows, max_vae;
   bool dry;
   int tf_index = 0;   // transformer block counter of the forward in flight (MasaCtrl start_layer)
+  // tuning "cfg_dedup" = 2, inside the deduplicated UNet prefix: a GEMM over pin_from rows takes the tile / split-K its pin_to-row form gets
+  int pin_from = 0, pin_to = 0;
   Bump warena, persist, temp, ctrl_arena;
   struct AugBias { float* p; int heads, Dp, dh; };
   std::vector<AugBias> aug_biases;                  // the b_qkv_aug vectors of this build (filled after the arena exists)

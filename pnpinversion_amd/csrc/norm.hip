@@ -767,6 +767,24 @@ int launch_gather_rows_f32(const float* in, const int* rows, int nrows, size_t r
   return (int)hipGetLastError();
 }
 
+// fp16 rows in 16-byte vectors (the CFG-deduplicated UNet prefix: per-latent activations expanded to the rows of the launch)
+__global__ void __launch_bounds__(256) gather_rows_f16_kernel(const uint4* __restrict__ in, const int* __restrict__ rows, int nrows, size_t row_vecs,
+                                                              uint4* __restrict__ out) {
+  const size_t total = (size_t)nrows * row_vecs;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    size_t r = idx / row_vecs, e = idx - r * row_vecs;
+    out[idx] = in[(size_t)rows[r] * row_vecs + e];
+  }
+}
+int launch_gather_rows_f16(const half_t* in, const int* rows, int nrows, size_t row_elems, half_t* out, hipStream_t st) {
+  if (nrows <= 0 || row_elems == 0 || row_elems % 8 != 0 || ((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return -2;
+  const size_t n = (size_t)nrows * (row_elems / 8);
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  gather_rows_f16_kernel<<<blocks, 256, 0, st>>>(reinterpret_cast<const uint4*>(in), rows, nrows, row_elems / 8, reinterpret_cast<uint4*>(out));
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ weight repack
 // src: PyTorch [rows][cols][taps] (conv [out][in][kh*kw] or linear [out][in], taps = 1)
 // dst: fp16 [row'][tap * cin_pad + c], row' = row0 + (dh ? (r / dh) * Dp + r % dh : r)   (attention heads padded to Dp)

@@ -39,8 +39,9 @@ struct GemmP {
 void gemm_defaults(GemmP& p);
 // ws: fp32 scratch for split-K slabs (ws_bytes available). force_cfg: -1 auto, 0 = 128x128, 1 = 64x64, 2 = 64x64 split-K.
 // stats_tile_rows (out): rows per m-tile of the p.stats partials actually produced, 0 if this launch produced none
+// sel_M > 0: the configuration is chosen as for sel_M rows instead of p.M (bit-identical per element to the sel_M-row launch's rows)
 int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_cfg = -1, int force_split = 0,
-                 int* cfg_used = nullptr, int* stats_tile_rows = nullptr);
+                 int* cfg_used = nullptr, int* stats_tile_rows = nullptr, int sel_M = 0);
 int igemm_init();  // sets dynamic-LDS attributes once
 // tile configuration id / split-K of the most recent launch_igemm and the <BM, BN, BKT, NST, WGM, ABL, WK> of its igemm_dma_kernel (profiling)
 void igemm_last_launch(int* cfg, int* split, int* geom7);
@@ -84,6 +85,8 @@ int launch_img_u8_to_nhwc(const uint8_t* img, int n, int HW, int Cp, half_t* out
 int launch_dec_to_u8(const float* nchw, int n, int HW, uint8_t* out_hwc, hipStream_t st);
 int launch_scale_f32(const float* in, size_t n, float s, float* out, hipStream_t st);
 int launch_gather_rows_f32(const float* in, const int* rows, int nrows, size_t row_elems, float* out, hipStream_t st);
+// out row r = in row rows[r], fp16, 16-byte vectors: row_elems % 8 == 0, both pointers 16-byte aligned
+int launch_gather_rows_f16(const half_t* in, const int* rows, int nrows, size_t row_elems, half_t* out, hipStream_t st);
 // CLIP text embeddings: out[m][:] = fp16(tok_emb[ids[m]] + pos_emb[m % T]); quick_gelu in place; fp16 -> fp32
 int launch_embed_tokens(const int* ids, int M, int T, int H, int vocab, const half_t* tok_emb, const half_t* pos_emb, half_t* out,
                         hipStream_t st);
