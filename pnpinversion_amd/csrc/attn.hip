@@ -21,54 +21,67 @@
 static constexpr int KV_TILE = 64;
 static constexpr int SV_LD = KV_TILE + 4;  // halfs; 136-byte rows: conflict-free ds_read_b64 over 32 rows
 
-// PF: prefetch the next K / V^T tile into registers under the current tile's work (self-attention: many key tiles, few workgroups);
-// without it the tile is loaded and stored in one go (cross-attention: two tiles, thousands of workgroups -- the extra registers of the
-// prefetch would only cost occupancy there).
-template <int DP, bool PF>
-__global__ void __launch_bounds__(256) attn_flash_kernel(AttnP p) {
-  constexpr int KS = DP / 16;  // k-steps over the head dim for S
-  constexpr int OT = DP / 32;  // 32-wide output tiles over the head dim
-  constexpr int SK_LD = DP + 8;
-  __shared__ __attribute__((aligned(16))) half_t sK[KV_TILE * SK_LD];
-  __shared__ __attribute__((aligned(16))) half_t sV[DP * SV_LD];
+// ------------------------------------------------------------------------------------------------------------------
+// The pieces of one flash tile step that the forward kernels below share.  All of them are inlined: the kernels stay separate
+// __global__ functions and differ only in how the K / V^T tile reaches LDS and in what they mask.
+// ------------------------------------------------------------------------------------------------------------------
+struct FlashItem {     // the work item of one lane: its (row group, head) and its query
+  int head, ri, orow, qrow, krow, vrow, qtok;
+  bool qok;
+};
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = lane >> 5, ql = lane & 31;
-  // XCD-aware order: workgroup ids are dealt round-robin to the 8 XCDs; give each XCD a contiguous run of (row, head)
-  // groups so that one group's K / V^T stay in one L2 instead of being fetched by all eight.
+// blockIdx -> work item; false: this workgroup only pads the grid to a multiple of 8.
+// XCD-aware order: workgroup ids are dealt round-robin to the 8 XCDs; give each XCD a contiguous run of (row, head)
+// groups so that one group's K / V^T stay in one L2 instead of being fetched by all eight.
+__device__ __forceinline__ bool flash_decode(const AttnP& p, int wave, int ql, FlashItem& w) {
   const int nqt = (p.Nq + 127) >> 7, T = nqt * p.heads * p.nrows, per = (T + 7) >> 3;
   const int tix = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-  if (tix >= T) return;
-  const int qt = tix % nqt, head = (tix / nqt) % p.heads;
-  const int* rw = p.rows + (tix / (nqt * p.heads)) * 4;
-  const int orow = rw[0], qrow = rw[1], krow = rw[2], vrow = rw[3];
-  const int qtok = qt * 128 + wave * 32 + ql;
-  const bool qok = qtok < p.Nq;
+  if (tix >= T) return false;
+  const int qt = tix % nqt;
+  w.head = (tix / nqt) % p.heads;
+  w.ri = tix / (nqt * p.heads);
+  const int* rw = p.rows + w.ri * 4;
+  w.orow = rw[0], w.qrow = rw[1], w.krow = rw[2], w.vrow = rw[3];
+  w.qtok = qt * 128 + wave * 32 + ql;
+  w.qok = w.qtok < p.Nq;
+  return true;
+}
 
-  half8 qf[KS];
-  {
-    const half_t* qp = p.q + ((size_t)qrow * p.Nq + (qok ? qtok : 0)) * p.ldq + p.q_off + head * DP + h * 8;
+// the query's MFMA B-operand fragments: KS 16-wide k-steps over the head dim (zeros for a query past Nq).  The address spells w.qok out
+// as its comparison: through the flag the compiler widens to 64 bits before it selects -- an extra shift and select per lane, and 1 - 8
+// more VGPRs in five of the six DMA instances.
+template <int DP, int KS>
+__device__ __forceinline__ void flash_load_q(const AttnP& p, const FlashItem& w, int h, half8 (&qf)[KS]) {
+  const half_t* qp = p.q + ((size_t)w.qrow * p.Nq + (w.qtok < p.Nq ? w.qtok : 0)) * p.ldq + p.q_off + w.head * DP + h * 8;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = qok ? ldg_half8(qp + ks * 16) : zero_half8();
-  }
-  floatx16 O[OT];
+  for (int ks = 0; ks < KS; ++ks) qf[ks] = w.qok ? ldg_half8(qp + ks * 16) : zero_half8();
+}
+
+template <int OT>
+__device__ __forceinline__ void flash_zero(floatx16 (&O)[OT]) {
 #pragma unroll
   for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
     for (int r = 0; r < 16; ++r) O[ot][r] = 0.f;
-  float mrun = -INFINITY, lrun = 0.f;
-  const float c = p.scale * 1.44269504088896340736f;
+}
 
-  const half_t* kbase = p.k + (size_t)krow * p.Nk * p.ldk + p.k_off + head * DP;
-  const half_t* vbase = p.vt + ((size_t)vrow * p.heads + head) * DP * (size_t)p.ldv;
-
-  // One K / V^T tile per thread in registers: the NEXT tile's global loads are issued right after this tile was published in LDS and
-  // fly under its MFMAs and softmax (the loop used to load, store, synchronise and only then compute: every 64-key tile paid a full
-  // global round trip -- 16 of them in a row at the 32 x 32 level, with at most a few blocks per CU to cover for each other).
-  constexpr int NKR = KV_TILE * (DP / 8) / 256, NVR = DP * (KV_TILE / 8) / 256;
+// One K / V^T tile per thread in registers, between global memory and the padded LDS layout (sK[KV_TILE][DP + 8], sV[DP][SV_LD]).
+// Prefetching kernels issue the NEXT tile's load() right after this tile was published in LDS, so that it flies under the tile's MFMAs
+// and softmax (the loop used to load, store, synchronise and only then compute: every 64-key tile paid a full global round trip -- 16 of
+// them in a row at the 32 x 32 level, with at most a few blocks per CU to cover for each other).
+template <int DP>
+struct KvStage {
+  static constexpr int SK_LD = DP + 8;
+  static constexpr int NKR = KV_TILE * (DP / 8) / 256, NVR = DP * (KV_TILE / 8) / 256;
   static_assert(KV_TILE * (DP / 8) % 256 == 0 && DP * (KV_TILE / 8) % 256 == 0, "a tile is a whole number of 16-byte vectors per thread");
+  const half_t* kbase;
+  const half_t* vbase;
   half8 rk[NKR], rv[NVR];
-  auto gload = [&](int kv0) {
+
+  __device__ __forceinline__ KvStage(const AttnP& p, const FlashItem& w)
+      : kbase(p.k + (size_t)w.krow * p.Nk * p.ldk + p.k_off + w.head * DP), vbase(p.vt + ((size_t)w.vrow * p.heads + w.head) * DP * (size_t)p.ldv) {}
+
+  __device__ __forceinline__ void load(const AttnP& p, int tid, int kv0) {
 #pragma unroll
     for (int i = 0; i < NKR; ++i) {
       const int idx = tid + i * 256, r = idx / (DP / 8), v = idx - r * (DP / 8);
@@ -89,11 +102,8 @@ __global__ void __launch_bounds__(256) attn_flash_kernel(AttnP p) {
         rv[i] = val;
       }
     }
-  };
-  if (PF) gload(0);
-  for (int kv0 = 0; kv0 < p.Nk; kv0 += KV_TILE) {
-    __syncthreads();                    // every wave is done reading the previous tile
-    if (!PF) gload(kv0);
+  }
+  __device__ __forceinline__ void publish(half_t* sK, half_t* sV, int tid) const {
 #pragma unroll
     for (int i = 0; i < NKR; ++i) {
       const int idx = tid + i * 256, r = idx / (DP / 8), v = idx - r * (DP / 8);
@@ -107,87 +117,86 @@ __global__ void __launch_bounds__(256) attn_flash_kernel(AttnP p) {
       *reinterpret_cast<half4*>(sV + d * SV_LD + v * 8) = lo;
       *reinterpret_cast<half4*>(sV + d * SV_LD + v * 8 + 4) = hi;
     }
-    __syncthreads();
-    if (PF && kv0 + KV_TILE < p.Nk) gload(kv0 + KV_TILE);
+  }
+};
 
-    floatx16 s[2];
+// S^T = K Q^T of one 64-key tile in the padded sK layout: two 32-key score tiles
+template <int DP>
+__device__ __forceinline__ void flash_scores(const half_t* sK, const half8 (&qf)[DP / 16], int ql, int h, floatx16 (&s)[2]) {
 #pragma unroll
-    for (int st = 0; st < 2; ++st) {
+  for (int st = 0; st < 2; ++st) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) s[st][r] = 0.f;
+    for (int r = 0; r < 16; ++r) s[st][r] = 0.f;
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        half8 kf = *reinterpret_cast<const half8*>(sK + (st * 32 + ql) * SK_LD + ks * 16 + h * 8);
-        s[st] = mfma32(kf, qf[ks], s[st]);
-      }
-    }
-    // Only the last key tile can hold out-of-range keys: the mask is a wave-uniform branch, not per-tile VALU work.
-    if (kv0 + KV_TILE > p.Nk) {
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kv0 + st * 32 + acc_row(r, lane) >= p.Nk) s[st][r] = -INFINITY;
-    }
-    if (p.causal) {   // wave-uniform flag: key j > query i is masked (every query keeps key 0, so the running max stays finite)
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kv0 + st * 32 + acc_row(r, lane) > qtok) s[st][r] = -INFINITY;
-    }
-    float mloc = s[0][0];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[st][r]);
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    // Deferred rescale (flash-attention style): the running reference max only moves when some row's tile max exceeds it by
-    // more than 8 in the exp2 domain, so P <= 2^8 (fp16 has the range) and O / l are rescaled on few tiles only.  The
-    // decision precedes this tile's exponentials and every earlier P.V is already in O, so all terms share one scale.
-    const bool grow = (mloc - mrun) * c > 8.0f;
-    if (__any(grow)) {
-      const float mnew = fmaxf(mrun, mloc);
-      const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);   // mrun = -inf on the first tile -> 0
-      lrun *= alpha;
-#pragma unroll
-      for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) O[ot][r] *= alpha;
-      mrun = mnew;
-    }
-    const float mc = mrun * c;
-    float psum = 0.f;
-    half8 pf[2][2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[st][r], c, -mc));
-        psum += pv;
-        pf[st][r >> 3][r & 7] = (half_t)pv;
-      }
-    lrun += psum;
-#pragma unroll
-    for (int ot = 0; ot < OT; ++ot) {
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const half_t* vb = sV + (ot * 32 + ql) * SV_LD + st * 32 + t * 16 + 4 * h;
-          half4 lo = *reinterpret_cast<const half4*>(vb);
-          half4 hi = *reinterpret_cast<const half4*>(vb + 8);
-          half8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          O[ot] = mfma32(vf, pf[st][t], O[ot]);
-        }
+    for (int ks = 0; ks < DP / 16; ++ks) {
+      half8 kf = *reinterpret_cast<const half8*>(sK + (st * 32 + ql) * (DP + 8) + ks * 16 + h * 8);
+      s[st] = mfma32(kf, qf[ks], s[st]);
     }
   }
-  const float ltot = lrun + __shfl_xor(lrun, 32, 64);
-  const float inv = 1.f / ltot;
-  // recording forward of the null-text path: log2 sum_k 2^(c S) per query, for the backward kernel (mrun is the reference exponent of lrun)
-  if (p.lse && qok && h == 0) p.lse[((size_t)orow * p.heads + head) * p.Nq + qtok] = mrun * c + __log2f(ltot);
-  if (qok) {
-    half_t* op = p.o + ((size_t)orow * p.Nq + qtok) * p.ldo + head * p.dh;
+}
+
+// One online-softmax step: the tile's scores s -> its probabilities pf as fp16 MFMA B-operand fragments (k-slot order = accumulator
+// register order), with the running reference max mrun, this lane's half of the row sum lrun and the output accumulators O kept in step.
+// Deferred rescale (flash-attention style): the running reference max only moves when some row's tile max exceeds it by
+// more than 8 in the exp2 domain, so P <= 2^8 (fp16 has the range) and O / l are rescaled on few tiles only.  The
+// decision precedes this tile's exponentials and every earlier P.V is already in O, so all terms share one scale.
+// mrun starts at -inf (or any finite value far below every score): the first move has alpha = exp2(-inf or -huge) = 0 on O = 0, l = 0.
+template <int OT>
+__device__ __forceinline__ void flash_softmax_step(const floatx16 (&s)[2], float c, float& mrun, float& lrun, floatx16 (&O)[OT], half8 (&pf)[2][2]) {
+  float mloc = s[0][0];
+#pragma unroll
+  for (int st = 0; st < 2; ++st)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[st][r]);
+  mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+  const bool grow = (mloc - mrun) * c > 8.0f;
+  if (__any(grow)) {
+    const float mnew = fmaxf(mrun, mloc);
+    const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);
+    lrun *= alpha;
+#pragma unroll
+    for (int ot = 0; ot < OT; ++ot)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) O[ot][r] *= alpha;
+    mrun = mnew;
+  }
+  const float mc = mrun * c;
+  float psum = 0.f;
+#pragma unroll
+  for (int st = 0; st < 2; ++st)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[st][r], c, -mc));
+      psum += pv;
+      pf[st][r >> 3][r & 7] = (half_t)pv;
+    }
+  lrun += psum;
+}
+
+// O^T += V^T P^T of one 64-key tile in the padded sV layout.  Plain key order: a lane's 8 keys of a 16-key step are 4 h + {0..3, 8..11};
+// VPERM (ops.h vt_perm16_pos): the same keys are positions 8 h + [0, 8).
+template <int DP, bool VPERM>
+__device__ __forceinline__ void flash_pv(const half_t* sV, const half8 (&pf)[2][2], int ql, int h, floatx16 (&O)[DP / 32]) {
+#pragma unroll
+  for (int ot = 0; ot < DP / 32; ++ot) {
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const half_t* vb = sV + (ot * 32 + ql) * SV_LD + st * 32 + t * 16 + (VPERM ? 8 : 4) * h;
+        half4 lo = *reinterpret_cast<const half4*>(vb);
+        half4 hi = *reinterpret_cast<const half4*>(vb + (VPERM ? 4 : 8));
+        half8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        O[ot] = mfma32(vf, pf[st][t], O[ot]);
+      }
+  }
+}
+
+// O^T * inv -> this lane's 4 halfs of every 8 of the query's output row (the head's dh valid columns)
+template <int OT>
+__device__ __forceinline__ void flash_store_o(const AttnP& p, const FlashItem& w, int h, const floatx16 (&O)[OT], float inv) {
+  if (w.qok) {
+    half_t* op = p.o + ((size_t)w.orow * p.Nq + w.qtok) * p.ldo + w.head * p.dh;
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
@@ -204,6 +213,66 @@ __global__ void __launch_bounds__(256) attn_flash_kernel(AttnP p) {
         }
       }
   }
+}
+
+// PF: prefetch the next K / V^T tile into registers under the current tile's work (self-attention: many key tiles, few workgroups);
+// without it the tile is loaded and stored in one go (cross-attention: two tiles, thousands of workgroups -- the extra registers of the
+// prefetch would only cost occupancy there).
+template <int DP, bool PF>
+__global__ void __launch_bounds__(256) attn_flash_kernel(AttnP p) {
+  constexpr int KS = DP / 16;  // k-steps over the head dim for S
+  constexpr int OT = DP / 32;  // 32-wide output tiles over the head dim
+  __shared__ __attribute__((aligned(16))) half_t sK[KV_TILE * (DP + 8)];
+  __shared__ __attribute__((aligned(16))) half_t sV[DP * SV_LD];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = lane >> 5, ql = lane & 31;
+  FlashItem w;
+  if (!flash_decode(p, wave, ql, w)) return;
+  half8 qf[KS];
+  flash_load_q<DP>(p, w, h, qf);
+  floatx16 O[OT];
+  flash_zero(O);
+  float mrun = -INFINITY, lrun = 0.f;
+  const float c = p.scale * 1.44269504088896340736f;
+
+  KvStage<DP> kv(p, w);
+  if (PF) kv.load(p, tid, 0);
+  for (int kv0 = 0; kv0 < p.Nk; kv0 += KV_TILE) {
+    __syncthreads();                    // every wave is done reading the previous tile
+    if (!PF) kv.load(p, tid, kv0);
+    kv.publish(sK, sV, tid);
+    __syncthreads();
+    if (PF && kv0 + KV_TILE < p.Nk) kv.load(p, tid, kv0 + KV_TILE);
+
+    floatx16 s[2];
+    flash_scores<DP>(sK, qf, ql, h, s);
+    // Only the last key tile can hold out-of-range keys: the mask is a wave-uniform branch, not per-tile VALU work.  It stays in the
+    // kernel (and in the masked one): as a shared helper its 32 key indices are kept live across the tile loop next to the causal mask's,
+    // 14 - 32 more VGPRs and one wave per SIMD less at DP = 32 / 64 / 96.
+    if (kv0 + KV_TILE > p.Nk) {
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kv0 + st * 32 + acc_row(r, lane) >= p.Nk) s[st][r] = -INFINITY;
+    }
+    if (p.causal) {   // wave-uniform flag: key j > query i is masked (every query keeps key 0, so the running max stays finite)
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kv0 + st * 32 + acc_row(r, lane) > w.qtok) s[st][r] = -INFINITY;
+    }
+    half8 pf[2][2];
+    flash_softmax_step(s, c, mrun, lrun, O, pf);
+    flash_pv<DP, false>(sV, pf, ql, h, O);
+  }
+  const float ltot = lrun + __shfl_xor(lrun, 32, 64);
+  const float inv = 1.f / ltot;
+  // recording forward of the null-text path: log2 sum_k 2^(c S) per query, for the backward kernel (mrun is the reference exponent of lrun)
+  if (p.lse && w.qok && h == 0) p.lse[((size_t)w.orow * p.heads + w.head) * p.Nq + w.qtok] = mrun * c + __log2f(ltot);
+  flash_store_o(p, w, h, O, inv);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -229,30 +298,17 @@ typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 // Same results to rounding (Q is rounded once more after the fp32 scaling: independent half-ulp errors, no bias); ~30 % fewer VALU cycles per tile.
 template <bool VPERM, int KSQ = 4, bool AUG = false>
 __global__ void __launch_bounds__(256) attn_flash_dma64_kernel(AttnP p) {
-  constexpr int DP = 64, KS = 4, OT = 2;
+  constexpr int DP = 64, OT = 2;
   constexpr int STAGE = 2 * 64 * 128;   // K tile + V^T tile, bytes
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, ql = lane & 31;
-  // XCD-aware order: workgroup ids are dealt round-robin to the 8 XCDs; give each XCD a contiguous run of (row, head)
-  // groups so that one group's K / V^T stay in one L2 instead of being fetched by all eight.
-  const int nqt = (p.Nq + 127) >> 7, T = nqt * p.heads * p.nrows, per = (T + 7) >> 3;
-  const int tix = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-  if (tix >= T) return;
-  const int qt = tix % nqt, head = (tix / nqt) % p.heads;
-  const int* rw = p.rows + (tix / (nqt * p.heads)) * 4;
-  const int orow = rw[0], qrow = rw[1], krow = rw[2], vrow = rw[3];
-  const int qtok = qt * 128 + wave * 32 + ql;
-  const bool qok = qtok < p.Nq;
-
+  FlashItem w;
+  if (!flash_decode(p, wave, ql, w)) return;
   half8 qf[KSQ];
-  {
-    const half_t* qp = p.q + ((size_t)qrow * p.Nq + (qok ? qtok : 0)) * p.ldq + p.q_off + head * DP + h * 8;
-#pragma unroll
-    for (int ks = 0; ks < KSQ; ++ks) qf[ks] = qok ? ldg_half8(qp + ks * 16) : zero_half8();
-  }
+  flash_load_q<DP>(p, w, h, qf);
   const float c = p.scale * 1.44269504088896340736f;
   if (AUG) {
     // S in the log2 domain straight from the MFMA.  The factor is applied in fp32 and the product rounded once: an fp16 factor
@@ -263,10 +319,7 @@ __global__ void __launch_bounds__(256) attn_flash_dma64_kernel(AttnP p) {
       for (int j = 0; j < 8; ++j) qf[ks][j] = (half_t)((float)qf[ks][j] * c);
   }
   floatx16 O[OT];
-#pragma unroll
-  for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) O[ot][r] = 0.f;
+  flash_zero(O);
   float mrun = AUG ? 0.f : -INFINITY, lrun = 0.f;     // AUG: the reference point carried in Q's column 40 (log2 domain, fp16-representable)
 
   // DMA lane roles: instruction j (1 KiB = 8 rows) of a 64-row tile; this wave issues j = 2*wave, 2*wave+1 for K and for V^T
@@ -278,8 +331,8 @@ __global__ void __launch_bounds__(256) attn_flash_dma64_kernel(AttnP p) {
     const int line = 4 * (j & 1) + (lane >> 4);
     const int R = (j >> 1) * 16 + ((lane >> 3) & 1) * 8 + line;
     const int ch = (lane & 7) ^ line;
-    kptr[i] = p.k + ((size_t)krow * p.Nk + R) * p.ldk + p.k_off + head * DP + ch * 8;            // + kv0 * ldk per tile
-    vptr[i] = p.vt + (((size_t)vrow * p.heads + head) * DP + R) * (size_t)p.ldv + ch * 8;        // + kv0 per tile
+    kptr[i] = p.k + ((size_t)w.krow * p.Nk + R) * p.ldk + p.k_off + w.head * DP + ch * 8;            // + kv0 * ldk per tile
+    vptr[i] = p.vt + (((size_t)w.vrow * p.heads + w.head) * DP + R) * (size_t)p.ldv + ch * 8;        // + kv0 per tile
   }
   auto issue = [&](int buf, int kv0) {
     char* sK = smem + buf * STAGE;
@@ -314,15 +367,14 @@ __global__ void __launch_bounds__(256) attn_flash_dma64_kernel(AttnP p) {
         s[st] = mfma32(kf, qf[ks], s[st]);
       }
     }
-    float mloc = s[0][0];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[st][r]);
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
     half8 pf[2][2];
-    float psum = 0.f;
     if (AUG) {
+      float mloc = s[0][0];
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[st][r]);
+      mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
       // s is S' = c S - m_run already.  The first tile always moves the reference point (its scores were computed against 0), later tiles
       // when the tile's maximum is more than 8 above it; the new point is rounded to fp16 so that Q's column 40 holds it exactly.
       const bool grow = it == 0 || mloc > 8.0f;
@@ -349,28 +401,8 @@ __global__ void __launch_bounds__(256) attn_flash_dma64_kernel(AttnP p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) pf[st][r >> 3][r & 7] = (half_t)__builtin_amdgcn_exp2f(s[st][r]);
     } else {
-    const bool grow = (mloc - mrun) * c > 8.0f;     // deferred rescale, see attn_flash_kernel
-    if (__any(grow)) {
-      const float mnew = fmaxf(mrun, mloc);
-      const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);
-      lrun *= alpha;
-#pragma unroll
-      for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) O[ot][r] *= alpha;
-      mrun = mnew;
+      flash_softmax_step(s, c, mrun, lrun, O, pf);
     }
-    const float mc = mrun * c;
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[st][r], c, -mc));
-        psum += pv;
-        pf[st][r >> 3][r & 7] = (half_t)pv;
-      }
-    }
-    lrun += psum;
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot) {
 #pragma unroll
@@ -401,25 +433,8 @@ __global__ void __launch_bounds__(256) attn_flash_dma64_kernel(AttnP p) {
   }
   const float inv = 1.f / ltot;
   // recording forward of the null-text path: log2 sum_k 2^(c S) per query, for the backward kernel (mrun is the reference exponent of lrun)
-  if (p.lse && qok && h == 0) p.lse[((size_t)orow * p.heads + head) * p.Nq + qtok] = (AUG ? mrun : mrun * c) + __log2f(ltot);
-  if (qok) {
-    half_t* op = p.o + ((size_t)orow * p.Nq + qtok) * p.ldo + head * p.dh;
-#pragma unroll
-    for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        int d = ot * 32 + 8 * g + 4 * h;
-        if (d + 3 < p.dh) {
-          half4 o4 = {(half_t)(O[ot][4 * g] * inv), (half_t)(O[ot][4 * g + 1] * inv), (half_t)(O[ot][4 * g + 2] * inv),
-                      (half_t)(O[ot][4 * g + 3] * inv)};
-          *reinterpret_cast<half4*>(op + d) = o4;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (d + j < p.dh) op[d + j] = (half_t)(O[ot][4 * g + j] * inv);
-        }
-      }
-  }
+  if (p.lse && w.qok && h == 0) p.lse[((size_t)w.orow * p.heads + w.head) * p.Nq + w.qtok] = (AUG ? mrun : mrun * c) + __log2f(ltot);
+  flash_store_o(p, w, h, O, inv);
 }
 
 #ifdef PNPI_ABLATIONS      // `python -m pnpinversion_amd.build --ablations` only: a measured-and-not-kept arm, kept reproducible (profiles/README.md, round 6)
@@ -454,30 +469,19 @@ __global__ void __launch_bounds__(256) attn_flash_pipe64_kernel(AttnP p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, ql = lane & 31;
-  const int nqt = (p.Nq + 127) >> 7, T = nqt * p.heads * p.nrows, per = (T + 7) >> 3;
-  const int tix = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-  if (tix >= T) return;
-  const int qt = tix % nqt, head = (tix / nqt) % p.heads;
-  const int* rw = p.rows + (tix / (nqt * p.heads)) * 4;
-  const int orow = rw[0], qrow = rw[1], krow = rw[2], vrow = rw[3];
-  const int qtok = qt * 128 + wave * 32 + ql;
-  const bool qok = qtok < p.Nq;
+  FlashItem w;
+  if (!flash_decode(p, wave, ql, w)) return;
   half8 qf[3];
+  flash_load_q<DP>(p, w, h, qf);
   {
-    const half_t* qp = p.q + ((size_t)qrow * p.Nq + (qok ? qtok : 0)) * p.ldq + p.q_off + head * DP + h * 8;
     const float c = p.scale * 1.44269504088896340736f;
 #pragma unroll
-    for (int ks = 0; ks < 3; ++ks) {
-      qf[ks] = qok ? ldg_half8(qp + ks * 16) : zero_half8();
+    for (int ks = 0; ks < 3; ++ks)
 #pragma unroll
       for (int j = 0; j < 8; ++j) qf[ks][j] = (half_t)((float)qf[ks][j] * c);
-    }
   }
   floatx16 O[2];
-#pragma unroll
-  for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) O[ot][r] = 0.f;
+  flash_zero(O);
   float mrun = 0.f;
   const half_t* kptr[2];
   const half_t* vptr[2];
@@ -487,8 +491,8 @@ __global__ void __launch_bounds__(256) attn_flash_pipe64_kernel(AttnP p) {
     const int line = 4 * (j & 1) + (lane >> 4);
     const int R = (j >> 1) * 16 + ((lane >> 3) & 1) * 8 + line;
     const int ch = (lane & 7) ^ line;
-    kptr[i] = p.k + ((size_t)krow * p.Nk + R) * p.ldk + p.k_off + head * DP + ch * 8;
-    vptr[i] = p.vt + (((size_t)vrow * p.heads + head) * DP + R) * (size_t)p.ldv + ch * 8;
+    kptr[i] = p.k + ((size_t)w.krow * p.Nk + R) * p.ldk + p.k_off + w.head * DP + ch * 8;
+    vptr[i] = p.vt + (((size_t)w.vrow * p.heads + w.head) * DP + R) * (size_t)p.ldv + ch * 8;
   }
   auto issue_k = [&](int slot, int kv0) {
 #pragma unroll
@@ -581,24 +585,8 @@ __global__ void __launch_bounds__(256) attn_flash_pipe64_kernel(AttnP p) {
   const float lrow = O[1][4], lother = __shfl_xor(lrow, 32, 64);
   const float ltot = h == 0 ? lrow : lother;
   const float inv = 1.f / ltot;
-  if (p.lse && qok && h == 0) p.lse[((size_t)orow * p.heads + head) * p.Nq + qtok] = mrun + __log2f(ltot);
-  if (qok) {
-    half_t* op = p.o + ((size_t)orow * p.Nq + qtok) * p.ldo + head * p.dh;
-#pragma unroll
-    for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = ot * 32 + 8 * g + 4 * h;
-        if (d + 3 < p.dh) {
-          half4 o4 = {(half_t)(O[ot][4 * g] * inv), (half_t)(O[ot][4 * g + 1] * inv), (half_t)(O[ot][4 * g + 2] * inv), (half_t)(O[ot][4 * g + 3] * inv)};
-          *reinterpret_cast<half4*>(op + d) = o4;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (d + j < p.dh) op[d + j] = (half_t)(O[ot][4 * g + j] * inv);
-        }
-      }
-  }
+  if (p.lse && w.qok && h == 0) p.lse[((size_t)w.orow * p.heads + w.head) * p.Nq + w.qtok] = mrun + __log2f(ltot);
+  flash_store_o(p, w, h, O, inv);
 }
 static int g_attn_pipe = 0;
 int attn_set_tuning_pipe(int v) { g_attn_pipe = v; return 0; }
@@ -613,13 +601,17 @@ bool attn_flash_uses_dma64(int Dp, int Nk, int causal) {
   return Dp == 64 && Nk % 64 == 0 && Nk >= 128 && !no_dma && !causal;
 }
 
+// every 16-byte load of Q / K / V^T and every 8-byte store of O is aligned
+static bool attn_vectors_aligned(const AttnP& p) {
+  return !((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.q_off & 7) || (p.k_off & 7) || (p.dh & 3) || (p.ldo & 3));
+}
+
 int launch_attn_flash(const AttnP& p, hipStream_t st) {
   if (p.nrows <= 0) return 0;
-  if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.q_off & 7) || (p.k_off & 7) || (p.dh & 3) || (p.ldo & 3)) return -3;
+  if (!attn_vectors_aligned(p)) return -3;
   const int total = ((p.Nq + 127) / 128) * p.heads * p.nrows;
   dim3 grid((unsigned)(((total + 7) / 8) * 8), 1, 1);
-  static const bool no_dma = getenv("PNPI_ATTN_NODMA") != nullptr;
-  if (p.Dp == 64 && p.Nk % 64 == 0 && p.Nk >= 128 && !no_dma && !p.causal) {
+  if (attn_flash_uses_dma64(p.Dp, p.Nk, p.causal)) {
     static const bool ksq3 = !(getenv("PNPI_ATTN_KSQ4") != nullptr);      // PNPI_ATTN_KSQ4: always four k-steps (A/B)
     static const bool no_aug = getenv("PNPI_ATTN_NOAUG") != nullptr;         // A/B: ignore AttnP::aug
     if (p.aug && p.dh == 40 && ksq3 && !no_aug) {
@@ -662,7 +654,7 @@ int launch_attn_flash(const AttnP& p, hipStream_t st) {
 // carries the query's class every logit of that pass is finfo.min (sim + finfo.min rounds to finfo.min in fp32) and the reference's softmax
 // is uniform over ALL keys: such a query runs with a zero Q fragment and no restriction -- all scores 0, the mean of V.
 //
-// attn_flash_kernel<DP, true> (register prefetch of the next tile) with three additions:
+// attn_flash_kernel<DP, true> (register prefetch of the next tile; the same shared pieces) with three additions:
 //   * prologue: the row's key classes as one bit per key in LDS (64-bit word t = key tile t), which classes exist at all, and the list of
 //     key tiles that hold a key of a class some query of this workgroup attends to -- only those are loaded;
 //   * per tile: a wave whose 32 queries attend to no key of the tile skips its MFMAs and exponentials (wave-uniform branch);
@@ -674,8 +666,8 @@ static constexpr int MASK_MAX_TILES = ATTN_MASK_MAX_KEYS / KV_TILE;
 
 template <int DP, bool VPERM>
 __global__ void __launch_bounds__(256) attn_flash_masked_kernel(AttnP p, AttnMaskP mk) {
-  constexpr int KS = DP / 16, OT = DP / 32, SK_LD = DP + 8;
-  __shared__ __attribute__((aligned(16))) half_t sK[KV_TILE * SK_LD];
+  constexpr int KS = DP / 16, OT = DP / 32;
+  __shared__ __attribute__((aligned(16))) half_t sK[KV_TILE * (DP + 8)];
   __shared__ __attribute__((aligned(16))) half_t sV[DP * SV_LD];
   __shared__ unsigned long long sM[MASK_MAX_TILES];      // bit j of word t: class of key 64 t + j (keys past Nk: 0)
   __shared__ unsigned short sList[MASK_MAX_TILES];       // the key tiles this workgroup visits, ascending
@@ -683,23 +675,12 @@ __global__ void __launch_bounds__(256) attn_flash_masked_kernel(AttnP p, AttnMas
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, ql = lane & 31;
-  const int nqt = (p.Nq + 127) >> 7, T = nqt * p.heads * p.nrows, per = (T + 7) >> 3;
-  const int tix = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);      // XCD-aware order, see attn_flash_kernel
-  if (tix >= T) return;
-  const int qt = tix % nqt, head = (tix / nqt) % p.heads, ri = tix / (nqt * p.heads);
-  const int* rw = p.rows + ri * 4;
-  const int orow = rw[0], qrow = rw[1], krow = rw[2], vrow = rw[3];
-  const int mi = mk.mrow[ri];
-  const int qtok = qt * 128 + wave * 32 + ql;
-  const bool qok = qtok < p.Nq;
-  const int qc = mk.qcls[(size_t)mi * p.Nq + (qok ? qtok : 0)] != 0 ? 1 : 0;
-
+  FlashItem w;
+  if (!flash_decode(p, wave, ql, w)) return;
+  const int mi = mk.mrow[w.ri];
+  const int qc = mk.qcls[(size_t)mi * p.Nq + (w.qok ? w.qtok : 0)] != 0 ? 1 : 0;
   half8 qf[KS];
-  {
-    const half_t* qp = p.q + ((size_t)qrow * p.Nq + (qok ? qtok : 0)) * p.ldq + p.q_off + head * DP + h * 8;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = qok ? ldg_half8(qp + ks * 16) : zero_half8();
-  }
+  flash_load_q<DP>(p, w, h, qf);
 
   // ---- key classes -> bits; 16 keys per thread and pass
   const int ntiles = (p.Nk + KV_TILE - 1) / KV_TILE;
@@ -757,74 +738,26 @@ __global__ void __launch_bounds__(256) attn_flash_masked_kernel(AttnP p, AttnMas
   const int cnt = sCnt;      // >= 1: a restricted query's class has a key somewhere, an unrestricted one visits every tile
 
   floatx16 O[OT];
-#pragma unroll
-  for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) O[ot][r] = 0.f;
+  flash_zero(O);
+  // mrun is finite from the start: a query without an allowed key in a tile has mloc = -inf -> (mloc - mrun) = -inf, not NaN: no move, and
+  // every exponential of the tile is exp2(-inf) = 0; its first allowed key moves mrun up from -1e30 (alpha = 0 on O = 0)
   float mrun = -1e30f, lrun = 0.f;
   const float c = p.scale * 1.44269504088896340736f;
 
-  const half_t* kbase = p.k + (size_t)krow * p.Nk * p.ldk + p.k_off + head * DP;
-  const half_t* vbase = p.vt + ((size_t)vrow * p.heads + head) * DP * (size_t)p.ldv;
-  constexpr int NKR = KV_TILE * (DP / 8) / 256, NVR = DP * (KV_TILE / 8) / 256;
-  static_assert(KV_TILE * (DP / 8) % 256 == 0 && DP * (KV_TILE / 8) % 256 == 0, "a tile is a whole number of 16-byte vectors per thread");
-  half8 rk[NKR], rv[NVR];
-  auto gload = [&](int kv0) {
-#pragma unroll
-    for (int i = 0; i < NKR; ++i) {
-      const int idx = tid + i * 256, r = idx / (DP / 8), v = idx - r * (DP / 8);
-      const int tok = kv0 + r;
-      rk[i] = tok < p.Nk ? ldg_half8(kbase + (size_t)tok * p.ldk + v * 8) : zero_half8();
-    }
-#pragma unroll
-    for (int i = 0; i < NVR; ++i) {
-      const int idx = tid + i * 256, d = idx >> 3, v = idx & 7;
-      const int tok0 = kv0 + v * 8;
-      const half_t* src = vbase + (size_t)d * p.ldv + tok0;
-      if (tok0 + 8 <= p.Nk) {
-        rv[i] = ldg_half8(src);
-      } else {
-        half8 val;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) val[j] = (tok0 + j < p.Nk) ? src[j] : (half_t)0.f;
-        rv[i] = val;
-      }
-    }
-  };
-  gload((int)sList[0] * KV_TILE);
+  KvStage<DP> kv(p, w);
+  kv.load(p, tid, (int)sList[0] * KV_TILE);
   for (int li = 0; li < cnt; ++li) {
     const int t = sList[li], kv0 = t * KV_TILE;
     __syncthreads();                    // every wave is done reading the previous tile
-#pragma unroll
-    for (int i = 0; i < NKR; ++i) {
-      const int idx = tid + i * 256, r = idx / (DP / 8), v = idx - r * (DP / 8);
-      *reinterpret_cast<half8*>(sK + r * SK_LD + v * 8) = rk[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NVR; ++i) {
-      const int idx = tid + i * 256, d = idx >> 3, v = idx & 7;
-      const half8 val = rv[i];
-      half4 lo = {val[0], val[1], val[2], val[3]}, hi = {val[4], val[5], val[6], val[7]};
-      *reinterpret_cast<half4*>(sV + d * SV_LD + v * 8) = lo;
-      *reinterpret_cast<half4*>(sV + d * SV_LD + v * 8 + 4) = hi;
-    }
+    kv.publish(sK, sV, tid);
     __syncthreads();
-    if (li + 1 < cnt) gload((int)sList[li + 1] * KV_TILE);
+    if (li + 1 < cnt) kv.load(p, tid, (int)sList[li + 1] * KV_TILE);
 
     const unsigned long long m = sM[t];
     if ((tile_classes(t, m) & wneed) == 0) continue;      // wave-uniform: none of this wave's queries attends to a key of the tile
 
     floatx16 s[2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[st][r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        half8 kf = *reinterpret_cast<const half8*>(sK + (st * 32 + ql) * SK_LD + ks * 16 + h * 8);
-        s[st] = mfma32(kf, qf[ks], s[st]);
-      }
-    }
+    flash_scores<DP>(sK, qf, ql, h, s);
     {
       // accumulator r of score tile st is key st * 32 + (r & 3) + 8 * (r >> 2) + 4 h: shift the allow word by 4 h once, test constant bits
       const unsigned long long allow = uni ? ~0ull : (qc ? m : ~m);
@@ -842,77 +775,17 @@ __global__ void __launch_bounds__(256) attn_flash_masked_kernel(AttnP p, AttnMas
         for (int r = 0; r < 16; ++r)
           if (kv0 + st * 32 + acc_row(r, lane) >= p.Nk) s[st][r] = -INFINITY;
     }
-    float mloc = s[0][0];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[st][r]);
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    // deferred rescale as in attn_flash_kernel.  mrun is finite from the start: a query without an allowed key in this tile has
-    // mloc = -inf -> no move, and every exponential below is exp2(-inf) = 0; its first allowed key moves mrun up from -1e30 (alpha = 0 on O = 0)
-    const bool grow = (mloc - mrun) * c > 8.0f;
-    if (__any(grow)) {
-      const float mnew = fmaxf(mrun, mloc);
-      const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);
-      lrun *= alpha;
-#pragma unroll
-      for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) O[ot][r] *= alpha;
-      mrun = mnew;
-    }
-    const float mc = mrun * c;
-    float psum = 0.f;
     half8 pf[2][2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[st][r], c, -mc));
-        psum += pv;
-        pf[st][r >> 3][r & 7] = (half_t)pv;
-      }
-    lrun += psum;
-#pragma unroll
-    for (int ot = 0; ot < OT; ++ot) {
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) {
-          // plain order: keys 4 h + {0..3, 8..11} of the 16-key step; permuted order: the same keys are positions 8 h + [0, 8)
-          const half_t* vb = sV + (ot * 32 + ql) * SV_LD + st * 32 + t2 * 16 + (VPERM ? 8 : 4) * h;
-          half4 lo = *reinterpret_cast<const half4*>(vb);
-          half4 hi = *reinterpret_cast<const half4*>(vb + (VPERM ? 4 : 8));
-          half8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          O[ot] = mfma32(vf, pf[st][t2], O[ot]);
-        }
-    }
+    flash_softmax_step(s, c, mrun, lrun, O, pf);
+    flash_pv<DP, VPERM>(sV, pf, ql, h, O);
   }
   const float ltot = lrun + __shfl_xor(lrun, 32, 64);
-  const float inv = 1.f / ltot;
-  if (qok) {
-    half_t* op = p.o + ((size_t)orow * p.Nq + qtok) * p.ldo + head * p.dh;
-#pragma unroll
-    for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        int d = ot * 32 + 8 * g + 4 * h;
-        if (d + 3 < p.dh) {
-          half4 o4 = {(half_t)(O[ot][4 * g] * inv), (half_t)(O[ot][4 * g + 1] * inv), (half_t)(O[ot][4 * g + 2] * inv),
-                      (half_t)(O[ot][4 * g + 3] * inv)};
-          *reinterpret_cast<half4*>(op + d) = o4;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (d + j < p.dh) op[d + j] = (half_t)(O[ot][4 * g + j] * inv);
-        }
-      }
-  }
+  flash_store_o(p, w, h, O, 1.f / ltot);
 }
 
 int launch_attn_flash_masked(const AttnP& p, const AttnMaskP& m, hipStream_t st) {
   if (p.nrows <= 0) return 0;
-  if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.q_off & 7) || (p.k_off & 7) || (p.dh & 3) || (p.ldo & 3)) return -3;
+  if (!attn_vectors_aligned(p)) return -3;
   if (!m.kcls || !m.qcls || !m.mrow || p.causal || p.lse) return -3;
   if (p.Nk <= 0 || p.Nk > ATTN_MASK_MAX_KEYS) return -7;
   if (p.vt_perm && (p.Nk & 15)) return -6;      // the permutation lives inside whole 16-token groups

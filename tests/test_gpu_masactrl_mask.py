@@ -140,6 +140,24 @@ def test_masked_attention_ragged_sizes_heads_and_class_rows(ctx, Nq, Nk, dh, Dp)
         assert rel_err(o[orow], ref) < ATTN_BAR, (orow, rel_err(o[orow], ref))
 
 
+@pytest.mark.parametrize("Nq,Nk,dh,Dp", [(200, 200, 40, 64), (130, 192, 80, 96), (64, 77, 160, 160)])
+def test_unrestricted_masked_attention_equals_plain_attention_bit_for_bit(ctx, Nq, Nk, dh, Dp):
+    """kcls = qcls = 1 restricts nothing: the masked kernel and attn_flash_kernel run the same shared tile body (attn.hip) on the same
+    tiles, and the finite -1e30 start of the running maximum gives alpha = exp2(-huge) = 0 on O = 0, l = 0 exactly as -inf does.  Shapes:
+    the prefetch instance with a ragged last key tile, three whole key tiles, and (77 keys) the plain side's non-prefetch instance."""
+    g = torch.Generator().manual_seed(11)
+    heads = 2
+    q, k, v = (torch.randn(4, heads, n, dh, generator=g).half().to(DEV) for n in (Nq, Nk, Nk))
+    qb, kb, vt, ldv = pack(q, k, v, Dp)
+    kcls = torch.ones(1, Nk, dtype=torch.uint8, device=DEV)
+    qcls = torch.ones(1, Nq, dtype=torch.uint8, device=DEV)
+    rows = [[1, 1, 0, 0]]                                        # [tgt, tgt, src, src]
+    masked = run_masked(ctx, qb, kb, vt, ldv, heads, Nq, Nk, Dp, dh, rows, kcls, qcls, [0], 4)
+    plain = run_masked(ctx, qb, kb, vt, ldv, heads, Nq, Nk, Dp, dh, rows, None, None, None, 4, masked=False)
+    assert plain[1].any() and torch.isfinite(plain.float()).all()
+    assert torch.equal(masked, plain)
+
+
 def test_masked_attention_refuses_what_it_cannot_run(ctx):
     z = torch.zeros(64, dtype=torch.half, device=DEV)
     b = torch.zeros(64, dtype=torch.uint8, device=DEV)
