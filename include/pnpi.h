@@ -142,7 +142,12 @@ typedef struct {
   uint64_t unet_backward_rows;     /* reverse walks (d loss / d context through one UNet row: null-text / null-latent inversion); the
                                       recording forward of each is counted in unet_sample_forwards */
   uint64_t unet_dedup_prefix_rows; /* rows the text-independent UNet prefix ran on in forwards that deduplicated it (tuning "cfg_dedup":
-                                      one per distinct latent of the launch); forwards without deduplication add nothing */
+                                      one per distinct latent of the launch); forwards without deduplication add nothing.  Under
+                                      "src_share" the distinct latents of the logical rows (rows served, as unet_sample_forwards) */
+  uint64_t unet_shared_rows;       /* tuning "src_share": of unet_sample_forwards, the rows that were NOT launched because another row of
+                                      the same launch computes them bit for bit (pnpi_direct_edit: 4 * nimg per step at npass = 2).
+                                      unet_sample_forwards, unet_sample_forwards_cached_kv and unet_dedup_prefix_rows count rows served;
+                                      rows launched = unet_sample_forwards - unet_shared_rows */
 } pnpi_counters;
 
 /* ---- lifetime ------------------------------------------------------------------------------------------------ */
@@ -275,7 +280,9 @@ int pnpi_edit_loop(pnpi_ctx* ctx, const float* x_T /*[nimg][4][h][w]*/, int nimg
  * (inversion.py:375-391) and npass direct_inversion_p2p_guidance_forward passes (p2p_guidance_forward.py:135-173; the
  * reference runs an AttentionStore reconstruction pass and the edit pass) advance in lock step, one UNet launch of
  * (1 + npass) * 4 * nimg rows per timestep.  ctrl_host: nullable or [npass][nimg] (kind 0 = no attention edit).
- * noise_loss_out [nsteps][nimg][2][4][h][w]; latents_out [npass][nimg][2][4][h][w]. */
+ * noise_loss_out [nsteps][nimg][2][4][h][w]; latents_out [npass][nimg][2][4][h][w].
+ * Tuning "src_share" (pnpi_set_tuning): the source rows of the guidance passes repeat the offset pass's bit for bit and are launched
+ * once -- (4 + 2 npass) * nimg rows per step; outputs, layouts and unet_sample_forwards are unchanged (see unet_shared_rows). */
 int pnpi_direct_edit(pnpi_ctx* ctx, const float* ddim_latents /*[nsteps+1][nimg][...]*/, int nimg, const float* context4,
                      int npass, const pnpi_ctrl_desc* ctrl_host, int offset_rows, int nsteps, const int* timesteps_host,
                      float guidance_scale, const float* offset_scale_host /*[nsteps], nullable*/, float* noise_loss_out,
@@ -373,6 +380,14 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
  * where that block's self-attention redirects rows).  1 = the compact launches choose their own tiles (fp16-rounding-level difference
  * where the choice differs), 2 = they are pinned to the tile / split-K of the full-row launch (bit-identical to 0), 0 = off.  Other
  * values are rejected.  pnpi_unet_forward and one-row loops are not affected.  May be switched on a live context.
+ * "src_share" (2): pnpi_direct_edit launches each step's three bit-identical copies of the unconditional and of the conditional source
+ * row (offset, reconstruction and edit pass) once and expands the prediction to the logical rows behind the UNet.  1 = the compact
+ * launch chooses its own tiles (fp16-rounding-level difference where the choice differs), 2 = every GEMM is configured as at the logical
+ * row count (bit-identical to 0), 0 = off.  The call falls back to 0 by itself with offset_rows < 1, a controller kind other than
+ * 0 / 1 / 2, under a host attention callback, or on a recording context (one that holds the activation tape of
+ * pnpi_unet_context_grad / the null-text loops: such a context keeps the full launch for every later call) -- the counter
+ * unet_shared_rows then stays put.  Other values are rejected.
+ * May be switched on a live context.
  * Keys (default): "text_kv" (1) / "temb_cache" (1) per-loop caches; "gn_inline_rows" (0)
  * one-launch GroupNorm below this many rows; "igemm_dma" (1) LDS-DMA kernel family; "igemm_table" (1) measured tile table before the
  * cost model; "igemm_wide" (1) 128x320 / 128x256 tiles; "igemm_deep_rings" (1) deeper LDS rings on sparse launches; "igemm_vt_lds" (1)
@@ -392,6 +407,12 @@ int pnpi_set_tuning(const char* key, int value);
  * returns 1 for an exact {M, N, K, ksize} entry, 2 when the same layer (N, K, ksize) is listed at another row count and the entry
  * nearest in M (at most 4x away) is used, 0 for none; cfg / split / entry_m (each nullable) receive the entry. */
 int pnpi_tile_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split, int* entry_m);
+/* Host-only: the row maps of pnpi_direct_edit's shared-row launch ("src_share") for nimg images and npass guidance passes.  Logical row
+ * 4 (p nimg + im) + k is row k of [unc_src, unc_tgt, cond_src, cond_tgt] of pass p (0 = the offset pass) of image im, on the logical
+ * latent 2 (p nimg + im) + k % 2.  Outputs (each nullable): lsel [compact latent] -> logical latent, cmap [compact row] -> compact latent,
+ * cctx [compact row] -> context4 row, omap [logical row] -> compact row, and the two counts ((4 + 2 npass) nimg rows on (2 + npass) nimg
+ * latents, per image O0 O1 O2 O3 then the two target rows of every guidance pass). */
+int pnpi_src_share_maps(int nimg, int npass, int* lsel, int* cmap, int* cctx, int* omap, int* compact_rows, int* compact_latents);
 int pnpi_op_gemm(pnpi_ctx* ctx, const void* a_f16, int lda, const void* w_f16, int ldw, int M, int N, int K, float alpha,
                  const float* bias, const void* residual_f16, void* out_f16, int ldo, int vt_col0, void* outT,
                  int vt_ld, int vt_f32, int rows_per_batch, int force_cfg, int force_split);

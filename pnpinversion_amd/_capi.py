@@ -55,7 +55,7 @@ class Counters(C.Structure):
     _fields_ = [("unet_sample_forwards", C.c_uint64), ("unet_calls", C.c_uint64), ("vae_encodes", C.c_uint64),
                 ("vae_decodes", C.c_uint64), ("executed_gemm_flops", C.c_double), ("executed_attn_flops", C.c_double),
                 ("text_kv_rows", C.c_uint64), ("unet_sample_forwards_cached_kv", C.c_uint64), ("unet_backward_rows", C.c_uint64),
-                ("unet_dedup_prefix_rows", C.c_uint64)]
+                ("unet_dedup_prefix_rows", C.c_uint64), ("unet_shared_rows", C.c_uint64)]
 
 
 KC_NAMES = ["igemm128", "igemm64", "igemm64_splitk", "attn_flash", "attn_cross_edit", "groupnorm", "layernorm", "geglu", "softmax", "igemm_wide"]
@@ -109,6 +109,7 @@ SYMBOLS = {
     "pnpi_op_conv_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _ip]),
     "pnpi_set_tuning": (_i, [C.c_char_p, _i]),
     "pnpi_tile_table_lookup": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pnpi_src_share_maps": (_i, [_i, _i] + [C.POINTER(C.c_int)] * 6),
     "pnpi_op_gemm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "pnpi_op_gemm_geglu": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i]),
     "pnpi_op_groupnorm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),

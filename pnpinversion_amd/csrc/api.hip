@@ -720,6 +720,7 @@ int pnpi_set_tuning(const char* key, int value) {
   if (!strcmp(key, "attn_pipe")) return attn_set_tuning_pipe(value) == 0 ? 0 : PNPI_EINVAL;
   if (!strcmp(key, "ff_fold")) { g_ff_fold = value; return 0; }
   if (!strcmp(key, "cfg_dedup")) { if (value < 0 || value > 2) return PNPI_EINVAL; g_cfg_dedup = value; return 0; }
+  if (!strcmp(key, "src_share")) { if (value < 0 || value > 2) return PNPI_EINVAL; g_src_share = value; return 0; }
   if (!strcmp(key, "op_attention_aug")) { g_op_attention_aug = value; return 0; }
   if (!strcmp(key, "op_attention_vt_perm")) { g_op_attention_vt_perm = value; return 0; }
   if (!strcmp(key, "attn_bwd_flash")) { g_attn_bwd_flash = value; return 0; }

@@ -25,6 +25,7 @@ static int text_kv_precompute(pnpi_ctx* c, const float* context, int rows) {
   if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "text K/V precompute: rows out of range (max_unet_rows)");
   if (text_kv_bytes(c, rows) > kv.cap) return fail(c, PNPI_ENOMEM, "text K/V cache arena too small");
   const int T = g.ctx_len, X = g.cross_dim, ldv = round_up_i(T, 8);
+  pin_base(c);      // pinned row sharing: the projections of the compact context rows are configured as at the logical row count
   c->persist.reset(); c->temp.reset();
   half_t* ctx16 = palloc(c, (size_t)rows * T * X);
   CK(launch_f32_to_f16(context, (size_t)rows * T * X, ctx16, c->st));
@@ -60,16 +61,36 @@ static int upload(pnpi_ctx* c, void* dst, const void* src, size_t bytes) {
   return 0;
 }
 
-// Build the device-side tables for `rows` UNet rows (rows_per_image = 4 when controllers are active).
+// The launch rows of one (pseudo-)image: its unconditional / conditional source and target row.  unc_src < 0: the launch has none
+// (the pruned schedule).  Several pseudo-images may name the same source rows (pnpi_direct_edit with shared source rows).
+struct CtrlRows { int unc_src, unc_tgt, cond_src, cond_tgt; };
+// the classic layout: image i owns the rows [i * rpi, (i + 1) * rpi), cond_src / cond_tgt at src_off / tgt_off, and with four rows
+// per image [unc_src, unc_tgt, cond_src, cond_tgt]
+static std::vector<CtrlRows> ctrl_rows_layout(int nimg, int rpi, int src_off, int tgt_off) {
+  std::vector<CtrlRows> rt(nimg > 0 ? nimg : 0);
+  for (int i = 0; i < nimg; ++i)
+    rt[i] = rpi == 4 ? CtrlRows{4 * i, 4 * i + 1, 4 * i + src_off, 4 * i + tgt_off} : CtrlRows{-1, -1, i * rpi + src_off, i * rpi + tgt_off};
+  return rt;
+}
+// Build the device-side tables for `rows` UNet rows; rt [nimg] (with cds): the launch rows of every (pseudo-)image.
 // mask_nimg: the images of the caller's loop when the launch holds several pseudo-images per image (pnpi_direct_edit's passes: pseudo-image
 // q is image q % mask_nimg); 0 = nimg.  Only the masks of pnpi_masa_set_masks are indexed by it.
-static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows, int rpi = 4, int src_off = 2, int tgt_off = 3, int mask_nimg = 0) {
+static int setup_ctrl_rows(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows, const CtrlRows* rt, int mask_nimg = 0) {
   CtrlDev& cd = c->cd;
   if (cds && c->mm.nimg > 0) {      // refused before anything is uploaded or launched
     bool any2 = false;
     for (int i = 0; i < nimg; ++i) any2 = any2 || cds[i].kind == 2;
     if (any2 && c->mm.nimg != (mask_nimg > 0 ? mask_nimg : nimg))
       return fail(c, PNPI_EINVAL, "pnpi_masa_set_masks holds masks for another number of images than this call's nimg");
+  }
+  if (cds) {
+    if (!rt) return fail(c, PNPI_EINVAL, "controllers need the row table of their images");
+    for (int i = 0; i < nimg; ++i) {
+      const int r4[4] = {rt[i].unc_src, rt[i].unc_tgt, rt[i].cond_src, rt[i].cond_tgt};
+      for (int k = 0; k < 4; ++k)
+        if (r4[k] >= rows || (r4[k] < 0 && (k >= 2 || cds[i].kind == 2)))
+          return fail(c, PNPI_EINVAL, cds[i].kind == 2 && r4[k] < 0 ? "MasaCtrl controllers need the 4-row layout" : "controller row outside the launch");
+    }
   }
   c->ctrl_arena.reset();
   cd = CtrlDev();
@@ -80,15 +101,12 @@ static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows
   const int T = c->cfg.ctx_len;
   if (T > 96) return fail(c, PNPI_ESHAPE, "ctx_len > 96 unsupported by the cross-attention edit kernel");
   std::vector<int> edit_img;
-  if (cds) {
-    if (rows != nimg * rpi) return fail(c, PNPI_EINVAL, "controllers need rows == rows_per_image * nimg");
+  if (cds)
     for (int i = 0; i < nimg; ++i) if (cds[i].kind == 1) edit_img.push_back(i);
-  }
   if (cds) {   // MasaCtrl images (kind 2): rows [unc_src, unc_tgt, cond_src, cond_tgt]; each target row reads its half's source K, V
     std::vector<int> masa = id;
     for (int i = 0; i < nimg; ++i) {
       if (cds[i].kind != 2) continue;
-      if (rpi != 4) return fail(c, PNPI_EINVAL, "MasaCtrl controllers need the 4-row layout");
       std::vector<unsigned char> step_on;
       const bool step_list = cds[i].masa_n_steps > 0 && cds[i].masa_step_on_host;
       if (step_list) step_on.assign(cds[i].masa_step_on_host, cds[i].masa_step_on_host + cds[i].masa_n_steps);
@@ -97,8 +115,8 @@ static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows
         return fail(c, PNPI_EINVAL, "all MasaCtrl controllers of one batch must share their step / layer windows (or lists)");
       cd.masa_any = true; cd.masa_start_step = cds[i].masa_start_step; cd.masa_start_layer = cds[i].masa_start_layer;
       cd.masa_layer_mask = cds[i].masa_layer_mask; cd.masa_step_list = step_list; cd.masa_step_on = step_on;
-      for (int half = 0; half < 2; ++half) {
-        const int src = i * 4 + 2 * half, tgt = src + 1;
+      for (int half = 0; half < 2; ++half) {      // a shared source row serves every pseudo-image that names it
+        const int src = half ? rt[i].cond_src : rt[i].unc_src, tgt = half ? rt[i].cond_tgt : rt[i].unc_tgt;
         masa[tgt * 4 + 2] = src; masa[tgt * 4 + 3] = src;
       }
     }
@@ -107,12 +125,13 @@ static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows
       CKP(upload(c, cd.rows_masa, masa.data(), masa.size() * sizeof(int)));
     }
     if (cd.masa_any && c->mm.nimg > 0) {
-      std::vector<int> mplain, mtgt, mimg;
-      for (int r = 0; r < rows; ++r) {
-        const int i = r / 4;
-        if (cds[i].kind == 2 && (r & 1)) {
+      std::vector<int> mplain, mtgt, mimg, tgt_img(rows, -1);
+      for (int i = 0; i < nimg; ++i)
+        if (cds[i].kind == 2) tgt_img[rt[i].unc_tgt] = tgt_img[rt[i].cond_tgt] = i % c->mm.nimg;
+      for (int r = 0; r < rows; ++r) {      // every other row of the launch takes the plain kernel, once
+        if (tgt_img[r] >= 0) {
           mtgt.insert(mtgt.end(), masa.begin() + r * 4, masa.begin() + r * 4 + 4);
-          mimg.push_back(i % c->mm.nimg);
+          mimg.push_back(tgt_img[r]);
         } else mplain.insert(mplain.end(), masa.begin() + r * 4, masa.begin() + r * 4 + 4);
       }
       cd.masa_masked = true;
@@ -129,7 +148,7 @@ static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows
   cd.npairs = (int)edit_img.size();
   std::vector<bool> is_pair_row(rows, false);
   for (int i : edit_img) {
-    int src = i * rpi + src_off, tgt = i * rpi + tgt_off;
+    int src = rt[i].cond_src, tgt = rt[i].cond_tgt;
     rep[tgt * 4 + 1] = src; rep[tgt * 4 + 2] = src;  // q and k of the target row come from the source row
     pairs.push_back(src); pairs.push_back(tgt);
     is_pair_row[tgt] = true;   // only the target row leaves the plain path; the source row stays bit-identical to it
@@ -203,6 +222,14 @@ static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows
   }
   if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "controller arena overflow");
   return 0;
+}
+
+// the classic layout (every caller but pnpi_direct_edit's shared-row launch)
+static int setup_ctrl(pnpi_ctx* c, const pnpi_ctrl_desc* cds, int nimg, int rows, int rpi = 4, int src_off = 2, int tgt_off = 3, int mask_nimg = 0) {
+  if (!cds) return setup_ctrl_rows(c, nullptr, nimg, rows, nullptr, mask_nimg);
+  if (rows != nimg * rpi) return fail(c, PNPI_EINVAL, "controllers need rows == rows_per_image * nimg");
+  const std::vector<CtrlRows> rt = ctrl_rows_layout(nimg, rpi, src_off, tgt_off);
+  return setup_ctrl_rows(c, cds, nimg, rows, rt.data(), mask_nimg);
 }
 
 static int apply_local_blend(pnpi_ctx* c, float* latents /*[nimg][2][E]*/, int step_index) {

@@ -23,6 +23,15 @@ static int g_ff_fold = 1;
 static int g_cfg_dedup = [] { const char* e = getenv("PNPI_CFG_DEDUP"); const int v = e ? atoi(e) : 2; return v >= 0 && v <= 2 ? v : 2; }();   // the variable: whole-benchmark A/B runs
 // the distinct latents of a launch: lat_u fp32 [U][C][S][S]; row r of the launch is latent hmap[r] (host) = dmap[r] (device)
 struct UNetDedup { const float* lat_u; int U; const int* hmap; const int* dmap; };
+// tuning "src_share": pnpi_direct_edit runs the source rows that its offset, reconstruction and edit passes repeat bit for bit once
+// per step (a compact launch, expanded to the logical rows behind the UNet).  1: the compact launch chooses its own tiles; 2: every
+// GEMM is configured as at the logical row count (sel_M, as "cfg_dedup" = 2 does for the prefix) -- bit-identical to 0; 0: off.
+static int g_src_share = [] { const char* e = getenv("PNPI_SRC_SHARE"); const int v = e ? atoi(e) : 2; return v >= 0 && v <= 2 ? v : 2; }();   // the variable: whole-benchmark A/B runs
+// the GEMM pin outside the deduplicated prefix: none, or (pinned row sharing) compact rows -> logical rows
+static inline void pin_base(pnpi_ctx* c) {
+  const bool on = c->share_pin && c->share_U > 0;
+  c->pin_from = on ? c->share_from : 0; c->pin_to = on ? c->share_to : 0;
+}
 struct TfDedup { int U; const int* dmap; };     // transformer_fwd: x holds U rows, the block's first half runs on them
 #define PROF(cls, flops, bytes, expr) PROFD(cls, flops, bytes, 0, 0, 0, expr)
 #define PROFD(cls, flops, bytes, d0, d1, d2, expr)            \
@@ -117,7 +126,11 @@ struct VtOut { void* outT = nullptr; int col0 = 1 << 30; int ld = 0; int f32 = 0
 static int igemm_prof(pnpi_ctx* c, const GemmP& p, double alg_flops, Stats* so = nullptr) {
   int srows = 0, r;
   // inside the pinned deduplicated prefix: configured as the same layer over all rows of the launch
-  const int sel_M = c->pin_to > 0 ? (int)((long)p.M / c->pin_from * c->pin_to) : 0;
+  // Invariant behind the bit-identity claims of "cfg_dedup" = 2 and "src_share" = 2: a pinned GEMM's M is proportional to the row
+  // count (M = pin_from rows x tokens), so M / pin_from * pin_to is exactly the M of the same layer in the full-row launch.  A GEMM
+  // whose M is no multiple of pin_from is not row-proportional (the one-row time-embedding products): it has the same M in the
+  // full-row launch and stays unpinned (sel_M = 0), as there.
+  const int sel_M = (c->pin_to > 0 && p.M % c->pin_from == 0) ? (int)((long)p.M / c->pin_from * c->pin_to) : 0;
   if (c->prof_on) {
     ProfRec pr; prof_open(c, pr);
     int used = 0;
@@ -321,7 +334,7 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
   half_t* q2 = talloc(c, (size_t)M * hd);
   CK(op_gemm(c, n2, C, M, C, t.w_q2, C, hd, nullptr, nullptr, 0, q2, hd, 1.f, nullptr, 2.0 * M * (double)C * C));
   if (dd) {            // from here on every row has its own text: the three tensors the second half reads, at the rows of the launch
-    c->pin_from = c->pin_to = 0;
+    pin_base(c);
     B = Bf; M = Mf;
     half_t *hs1f = talloc(c, (size_t)M * C), *q2f = talloc(c, (size_t)M * hd), *xf = talloc(c, (size_t)M * C);
     CK(launch_gather_rows_f16(hs1, dd->dmap, B, (size_t)N * C, hs1f, c->st));
@@ -487,7 +500,7 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
                     float* eps_out, const UNetDedup* ud = nullptr) {
   const pnpi_model_config& g = c->cfg;
   const UNetW& u = c->unet;
-  c->pin_from = c->pin_to = 0;
+  pin_base(c);
   if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "unet rows out of range (max_unet_rows)");
   if (t < 0 || t >= g.n_train_timesteps) return fail(c, PNPI_EINVAL, "timestep out of range");
   c->persist.reset(); c->temp.reset();
@@ -553,7 +566,10 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
         const int U = ud->U;
         half_t* x0c = palloc(c, (size_t)U * S * S * 8);
         CK(launch_nchw_f32_to_nhwc_f16(ud->lat_u, U, g.in_channels, S * S, 8, x0c, c->st));
-        if (g_cfg_dedup == 2) { c->pin_from = U; c->pin_to = B; }
+        // pinned row sharing: the compact prefix makes the choices of the logical launch's prefix (all rows under cfg_dedup = 2, its
+        // distinct latents under 1)
+        if (c->share_pin && c->share_U > 0) { c->pin_from = U; c->pin_to = g_cfg_dedup == 2 ? c->share_to : c->share_U; }
+        else if (g_cfg_dedup == 2) { c->pin_from = U; c->pin_to = B; }
         half_t* hc = palloc(c, (size_t)U * H * H * C0);
         Stats hcs, rcs, ns;
         CK(op_conv(c, x0c, 8, nullptr, 0, U, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, hc, H, H, -1, nullptr, &hcs));
@@ -566,7 +582,7 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
         } else {
           // the self-attention redirects rows at this step: the prefix ends behind the ResNet, whose output and per-image GroupNorm
           // partial sums are expanded to the rows of the launch
-          c->pin_from = c->pin_to = 0;
+          pin_base(c);
           if (((size_t)H * H * oc) % 8) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
           half_t* o = palloc(c, (size_t)B * H * H * oc);
           CK(launch_gather_rows_f16(rc, ud->dmap, B, (size_t)H * H * oc, o, c->st));
@@ -578,8 +594,8 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
           }
           CKP(transformer_fwd(c, u.down_attn[0][0], o, B, H, H, ctx16, use_ctrl, cur_step, o2, os, &ns));
         }
-        c->pin_from = c->pin_to = 0;
-        c->ctr.unet_dedup_prefix_rows += U;
+        pin_base(c);
+        c->ctr.unet_dedup_prefix_rows += c->share_U > 0 ? c->share_U : U;      // under row sharing: the logical latents served
         h = o2; ch = oc; hs_ = ns;
         skips.push_back({h, ch, H, hs_});
         continue;

@@ -34,15 +34,21 @@ struct Loop {
   std::vector<std::pair<int**, size_t>> map_dst;
   explicit Loop(pnpi_ctx* c_) : c(c_), kv(c_) {}
 };
-// cds (nullable): controller descriptors of the nq (pseudo-)images of the launch, rows = rpi * nq
-static int loop_begin(Loop& L, int nsteps, int rows, const char* too_many_rows, const pnpi_ctrl_desc* cds = nullptr, int nq = 0, int rpi = 4,
-                      int src_off = 2, int tgt_off = 3, int mask_nimg = 0) {
+// the entry checks of loop_begin alone (a loop that builds its controller tables itself)
+static int loop_entry(Loop& L, int nsteps, int rows, const char* too_many_rows) {
   pnpi_ctx* c = L.c;
   CKP(check_loop_ready(c));
   const pnpi_model_config& g = c->cfg;
   L.E = (size_t)g.in_channels * g.sample_size * g.sample_size; L.CE = (size_t)g.ctx_len * g.cross_dim;
   L.ratio = g.n_train_timesteps / nsteps; L.rows = rows;
   if (rows > c->max_rows) return fail(c, PNPI_EINVAL, too_many_rows);
+  return 0;
+}
+// cds (nullable): controller descriptors of the nq (pseudo-)images of the launch, rows = rpi * nq
+static int loop_begin(Loop& L, int nsteps, int rows, const char* too_many_rows, const pnpi_ctrl_desc* cds = nullptr, int nq = 0, int rpi = 4,
+                      int src_off = 2, int tgt_off = 3, int mask_nimg = 0) {
+  pnpi_ctx* c = L.c;
+  CKP(loop_entry(L, nsteps, rows, too_many_rows));
   return cds ? setup_ctrl(c, cds, nq, rows, rpi, src_off, tgt_off, mask_nimg) : setup_ctrl(c, nullptr, 0, c->max_rows);
 }
 static void loop_map(Loop& L, const std::vector<int>& m, int** dev) {      // *dev is valid after loop_commit
@@ -240,42 +246,127 @@ int pnpi_edit_loop_uncond_steps_recon(pnpi_ctx* c, const float* x_T, int nimg, c
                         uncond_first_only);
 }
 
+/* The row maps of pnpi_direct_edit's shared-row launch (tuning "src_share"), host only.  Logical rows: pseudo-image q = p * nimg + im
+ * (pass p = 0 the offset pass O, then the npass guidance passes) owns the rows 4 q .. 4 q + 3 = [unc_src, unc_tgt, cond_src, cond_tgt] on
+ * the latents 2 q (source) and 2 q + 1 (target).  The source rows of every pass repeat those of the offset pass bit for bit, so the
+ * launch holds, per image, O0 O1 O2 O3 and the two target rows of each guidance pass (4 + 2 npass rows on 2 + npass latents):
+ *   lsel [compact latent] -> logical latent     cmap [compact row] -> compact latent     cctx [compact row] -> context4 row
+ *   omap [logical row] -> compact row */
+struct SrcShareMaps { std::vector<int> lsel, cmap, cctx, omap; int crows = 0, nlat = 0; };
+static void src_share_maps(int nimg, int npass, SrcShareMaps& m) {
+  const int rpi = 4 + 2 * npass, lpi = 2 + npass;
+  m.crows = rpi * nimg; m.nlat = lpi * nimg;
+  m.lsel.assign(m.nlat, 0); m.cmap.assign(m.crows, 0); m.cctx.assign(m.crows, 0); m.omap.assign((size_t)(1 + npass) * 4 * nimg, 0);
+  for (int im = 0; im < nimg; ++im) {
+    const int rb = im * rpi, lb = im * lpi;
+    m.lsel[lb] = 2 * im; m.lsel[lb + 1] = 2 * im + 1;
+    for (int k = 0; k < 4; ++k) { m.cmap[rb + k] = lb + k % 2; m.cctx[rb + k] = 4 * im + k; }
+    for (int p = 1; p <= npass; ++p) {
+      m.lsel[lb + 1 + p] = 2 * (p * nimg + im) + 1;
+      for (int h = 0; h < 2; ++h) { m.cmap[rb + 2 + 2 * p + h] = lb + 1 + p; m.cctx[rb + 2 + 2 * p + h] = 4 * im + 2 * h + 1; }
+    }
+    for (int p = 0; p <= npass; ++p)
+      for (int k = 0; k < 4; ++k) m.omap[4 * (p * nimg + im) + k] = (p == 0 || k % 2 == 0) ? rb + k : rb + 2 + 2 * p + k / 2;
+  }
+}
+int pnpi_src_share_maps(int nimg, int npass, int* lsel, int* cmap, int* cctx, int* omap, int* compact_rows, int* compact_latents) {
+  if (nimg <= 0 || npass <= 0 || (long)(1 + npass) * 4 * nimg > (1 << 20)) return PNPI_EINVAL;
+  SrcShareMaps m;
+  src_share_maps(nimg, npass, m);
+  if (lsel) std::copy(m.lsel.begin(), m.lsel.end(), lsel);
+  if (cmap) std::copy(m.cmap.begin(), m.cmap.end(), cmap);
+  if (cctx) std::copy(m.cctx.begin(), m.cctx.end(), cctx);
+  if (omap) std::copy(m.omap.begin(), m.omap.end(), omap);
+  if (compact_rows) *compact_rows = m.crows;
+  if (compact_latents) *compact_latents = m.nlat;
+  return 0;
+}
+// the context's row-sharing state lives for one pnpi_direct_edit call, whichever way that call returns
+struct ShareScope {
+  pnpi_ctx* c;
+  explicit ShareScope(pnpi_ctx* c_) : c(c_) {}
+  ~ShareScope() { c->share_from = c->share_to = c->share_U = 0; c->share_pin = false; pin_base(c); }
+};
+
 /* offset_calculate + npass guidance-forward passes of P2PEditor.edit_image_directinversion (p2p_editor.py:99-160) advanced in
  * lock step: every pass walks the same timesteps and pass p's step i needs only noise_loss[i], which the offset pass produces
- * at the same step -- so one UNet launch per step serves all (1 + npass) * 4 * nimg rows. */
+ * at the same step -- so one UNet launch per step serves all (1 + npass) * 4 * nimg rows.
+ * Tuning "src_share": the unconditional and conditional SOURCE rows of the guidance passes repeat the offset pass's (same x_T, same
+ * context rows, no controller writes a source row, and with offset_rows >= 1 every pass advances its source latent by the same
+ * __fadd_rn(prev, noise_loss[i])), so the launch holds them once (src_share_maps) and eps is expanded to the logical rows behind it;
+ * every latent, offset and output below keeps its layout.  Falls back to the full launch where that identity is not given. */
 int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* context4, int npass, const pnpi_ctrl_desc* ctrl_host,
                      int offset_rows, int nsteps, const int* ts, float gs, const float* offset_scale_host, float* noise_loss_out,
                      float* latents_out) {
   if (!c || !lat_all || !context4 || !ts || !noise_loss_out || !latents_out || nsteps <= 0 || npass <= 0 || nimg <= 0) return PNPI_EINVAL;
-  const int NI = (1 + npass) * nimg;
+  const int NI = (1 + npass) * nimg, rows = 4 * NI;
   std::vector<pnpi_ctrl_desc> cds(NI);
   memset(cds.data(), 0, cds.size() * sizeof(pnpi_ctrl_desc));      // the offset pass (pseudo-images 0..nimg-1) runs no controller
   if (ctrl_host) for (int i = 0; i < npass * nimg; ++i) cds[nimg + i] = ctrl_host[i];
+  // Not on a recording context, under a host attention callback or in a sizing run.  This loop never records itself, so "recording
+  // context" can only mean one that holds an activation tape (pnpi_unet_context_grad or a null-text loop ran on it); nothing in the
+  // compact launch depends on the tape -- the fallback is the specified behaviour, visible in unet_shared_rows, not a necessity.
+  int share = (offset_rows >= 1 && !c->tape && !c->attn_cb && !c->dry) ? g_src_share : 0;
+  for (const pnpi_ctrl_desc& d : cds) if (d.kind < 0 || d.kind > 2) share = 0;
   Loop L(c);
-  CKP(loop_begin(L, nsteps, 4 * NI, "(1 + npass) * nimg * 4 exceeds max_unet_rows", cds.data(), NI, 4, 2, 3, nimg));
-  const size_t E = L.E, CE = L.CE; const int rows = L.rows;
+  ShareScope scope(c);
+  SrcShareMaps sm;
+  const char* too_many = "(1 + npass) * nimg * 4 exceeds max_unet_rows";
+  if (share) {
+    src_share_maps(nimg, npass, sm);
+    std::vector<CtrlRows> rt(NI);
+    for (int q = 0; q < NI; ++q) rt[q] = CtrlRows{sm.omap[4 * q], sm.omap[4 * q + 1], sm.omap[4 * q + 2], sm.omap[4 * q + 3]};
+    CKP(loop_entry(L, nsteps, rows, too_many));      // the logical rows are what max_unet_rows admits, whatever the knob says
+    L.rows = sm.crows;
+    CKP(setup_ctrl_rows(c, cds.data(), NI, sm.crows, rt.data(), nimg));
+    c->share_from = sm.crows; c->share_to = rows; c->share_U = 2 * NI; c->share_pin = share == 2;
+  } else {
+    CKP(loop_begin(L, nsteps, rows, too_many, cds.data(), NI, 4, 2, 3, nimg));
+  }
+  const size_t E = L.E, CE = L.CE;
   float* lat = misc_f(c, (size_t)NI * 2 * E);
-  float* ctxrep = misc_f(c, (size_t)rows * CE);
-  std::vector<int> ctxmap(rows);
-  for (int r = 0; r < rows; ++r) ctxmap[r] = 4 * (r / 4 % nimg) + r % 4;
-  int *d_expand, *d_inmap, *d_ctxmap;
-  loop_maps_cfg(L, NI, nimg, 2, &d_expand, &d_inmap);
-  loop_map(L, ctxmap, &d_ctxmap);
+  float* ctxrep = misc_f(c, (size_t)L.rows * CE);
+  float* latc = share ? misc_f(c, (size_t)sm.nlat * E) : nullptr;      // the distinct latents of the step
+  float* eps_all = share ? misc_f(c, (size_t)rows * E) : nullptr;      // eps at the logical rows
+  int *d_expand, *d_inmap, *d_ctxmap, *d_lsel = nullptr, *d_omap = nullptr;
+  if (share) {
+    std::vector<int> expand(NI * 2);
+    for (int k = 0; k < NI * 2; ++k) expand[k] = k / 2 % nimg;
+    loop_map(L, expand, &d_expand);
+    loop_map(L, sm.cmap, &d_inmap); loop_map(L, sm.cctx, &d_ctxmap); loop_map(L, sm.lsel, &d_lsel); loop_map(L, sm.omap, &d_omap);
+  } else {
+    std::vector<int> ctxmap(rows);
+    for (int r = 0; r < rows; ++r) ctxmap[r] = 4 * (r / 4 % nimg) + r % 4;
+    loop_maps_cfg(L, NI, nimg, 2, &d_expand, &d_inmap);
+    loop_map(L, ctxmap, &d_ctxmap);
+  }
   CKP(loop_commit(L));
   CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, NI * 2, E, lat, c->st));
-  CK(launch_gather_rows_f32(context4, d_ctxmap, rows, CE, ctxrep, c->st));
-  CKP(L.kv.begin(ctxrep, rows));
+  CK(launch_gather_rows_f32(context4, d_ctxmap, L.rows, CE, ctxrep, c->st));
+  CKP(L.kv.begin(ctxrep, L.rows));
   for (int i = 0; i < nsteps; ++i) {
     const int t = ts[i];
-    CKP(loop_unet(L, lat, d_inmap, t, ctxrep, true, i));
+    const float* eps = L.eps;
+    if (share) {
+      CK(launch_gather_rows_f32(lat, d_lsel, sm.nlat, E, latc, c->st));
+      CKP(loop_unet(L, latc, d_inmap, t, ctxrep, true, i));
+      CK(launch_gather_rows_f32(L.eps, d_omap, rows, E, eps_all, c->st));
+      eps = eps_all;
+      // the counters keep counting the rows served; unet_shared_rows tells how many of them were not launched
+      const uint64_t saved = (uint64_t)(rows - sm.crows);
+      c->ctr.unet_sample_forwards += saved; c->ctr.unet_shared_rows += saved;
+      if (c->tkv.use) c->ctr.unet_sample_forwards_cached_kv += saved;
+    } else {
+      CKP(loop_unet(L, lat, d_inmap, t, ctxrep, true, i));
+    }
     float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
     float* nl = noise_loss_out + (size_t)i * nimg * 2 * E;
-    CfgStepP s = cfg_step(L, L.eps, lat, nimg, 2, gs, af, at, lat);
+    CfgStepP s = cfg_step(L, eps, lat, nimg, 2, gs, af, at, lat);
     s.target = lat_all + (size_t)(nsteps - i - 1) * nimg * E; s.offset_scale = offset_scale_host ? offset_scale_host[i] : 1.f; s.offset_out = nl;
     CK(launch_cfg_ddim_prev(s, c->st));
     for (int p = 1; p <= npass; ++p) {
       float* lp = lat + (size_t)p * nimg * 2 * E;
-      s = cfg_step(L, L.eps + (size_t)p * nimg * 4 * E, lp, nimg, 2, gs, af, at, lp);
+      s = cfg_step(L, eps + (size_t)p * nimg * 4 * E, lp, nimg, 2, gs, af, at, lp);
       s.noise_loss = nl; s.offset_rows = offset_rows;
       CK(launch_cfg_ddim_prev(s, c->st));
     }

@@ -200,6 +200,11 @@ struct pnpi_ctx {
   int tf_index = 0;   // transformer block counter of the forward in flight (MasaCtrl start_layer)
   // tuning "cfg_dedup" = 2, inside the deduplicated UNet prefix: a GEMM over pin_from rows takes the tile / split-K its pin_to-row form gets
   int pin_from = 0, pin_to = 0;
+  // tuning "src_share", while pnpi_direct_edit launches its compact rows: share_U > 0 = the launch of share_from rows serves share_to
+  // logical rows resting on share_U logical latents.  share_pin (= 2): every GEMM of the forward is configured as at share_to rows
+  // (the prefix of "cfg_dedup" as at share_to / share_U rows), so each launch makes the choices of the full-row loop
+  int share_from = 0, share_to = 0, share_U = 0;
+  bool share_pin = false;
   Bump warena, persist, temp, ctrl_arena;
   struct AugBias { float* p; int heads, Dp, dh; };
   std::vector<AugBias> aug_biases;                  // the b_qkv_aug vectors of this build (filled after the arena exists)
