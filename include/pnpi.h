@@ -399,14 +399,22 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
  * "igemm_v256n" variant of a tile id; "tile_order" (-1) XCD traversal order; "igemm_vpp" (0) ablations of the 8-wave ping-pong kernel
  * (1 no MFMAs, 2 no DMA, 3 DMA only, 4 MFMAs only -- all but 0 produce garbage, timing only); "igemm_tapin" (0) the ping-pong kernel
  * walks a 3 x 3 convolution's K channel-slab-major; "igemm_pp_only_m" / "_n" / "_k" (0) the table's ping-pong entries apply only to
- * launches with that M / N / K (n < 0: to none; tools/pp_bisect.py); "attn_aug" (1) the 40-wide flash self-attention carries the running
- * maximum and the row sum in the padding column of Q / K / V (0: explicit shift and sum on the VALU; the column is written either way and ignored);"op_attention_aug" (0) pnpi_op_attention is handed K and V whose column 40 holds 1.0
+ * launches with that M / N / K (n < 0: to none; tools/pp_bisect.py); "pp_rowtile" (1, or the PNPI_PP_ROWTILE variable) a ping-pong
+ * launch takes the row height that fills the CUs at its launched M (pnpi_pp_rowtile_query; bit-identical to 0); "attn_aug" (1) the 40-wide flash self-attention carries the running
+ * maximum and the row sum in the padding column of Q / K / V (0: explicit shift and sum on the VALU; the column is written either way and ignored);"op_gemm_vt_perm16" (0) pnpi_op_gemm stores its
+ * transposed columns in the permuted key order of the 4096-token self-attention sites (token t of every aligned 16-token group at
+ * t ^ 12 for the two middle quads; rpb % 16 == 0, fp16; kernel tests);"op_attention_aug" (0) pnpi_op_attention is handed K and V whose column 40 holds 1.0
  * and runs that kernel (kernel tests). */
 int pnpi_set_tuning(const char* key, int value);
 /* Host-only query of the measured tile table launch_igemm consults before its cost model (no device work; used by the CPU tests):
  * returns 1 for an exact {M, N, K, ksize} entry, 2 when the same layer (N, K, ksize) is listed at another row count and the entry
  * nearest in M (at most 4x away) is used, 0 for none; cfg / split / entry_m (each nullable) receive the entry. */
 int pnpi_tile_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split, int* entry_m);
+/* Host-only: the row height launch_igemm gives a ping-pong launch (tuning "pp_rowtile" = 1).  cfg names the tile the table chose
+ * (16 = 256 x 256, 17 = 192 x 320; 19 = 128 x 320 and 20 = 192 x 256 name the same two families), M the LAUNCHED row count, split the
+ * split-K factor.  Returns the rows of the tile that runs (256, 192 or 128): the family's shorter tile when it needs no more rounds
+ * of one workgroup per CU on 256 CUs than the taller one; 0 when cfg is no ping-pong tile. */
+int pnpi_pp_rowtile_query(int cfg, int M, int N, int split);
 /* Host-only: the row maps of pnpi_direct_edit's shared-row launch ("src_share") for nimg images and npass guidance passes.  Logical row
  * 4 (p nimg + im) + k is row k of [unc_src, unc_tgt, cond_src, cond_tgt] of pass p (0 = the offset pass) of image im, on the logical
  * latent 2 (p nimg + im) + k % 2.  Outputs (each nullable): lsel [compact latent] -> logical latent, cmap [compact row] -> compact latent,

@@ -109,6 +109,7 @@ SYMBOLS = {
     "pnpi_op_conv_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _ip]),
     "pnpi_set_tuning": (_i, [C.c_char_p, _i]),
     "pnpi_tile_table_lookup": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pnpi_pp_rowtile_query": (_i, [_i, _i, _i, _i]),
     "pnpi_src_share_maps": (_i, [_i, _i] + [C.POINTER(C.c_int)] * 6),
     "pnpi_op_gemm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "pnpi_op_gemm_geglu": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i]),

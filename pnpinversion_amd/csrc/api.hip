@@ -710,6 +710,7 @@ int pnpi_op_conv_stats(pnpi_ctx* c, const void* x1, const void* x2, int C1, int 
 int pnpi_tile_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split, int* entry_m) {
   return igemm_table_lookup(M, N, K, ksize, cfg, split, entry_m);
 }
+int pnpi_pp_rowtile_query(int cfg, int M, int N, int split) { return igemm_pp_rowtile_query(cfg, M, N, split); }
 int pnpi_set_tuning(const char* key, int value) {
   if (!key) return PNPI_EINVAL;
   if (!strcmp(key, "text_kv")) { g_text_kv = value; return 0; }
@@ -723,6 +724,7 @@ int pnpi_set_tuning(const char* key, int value) {
   if (!strcmp(key, "src_share")) { if (value < 0 || value > 2) return PNPI_EINVAL; g_src_share = value; return 0; }
   if (!strcmp(key, "op_attention_aug")) { g_op_attention_aug = value; return 0; }
   if (!strcmp(key, "op_attention_vt_perm")) { g_op_attention_vt_perm = value; return 0; }
+  if (!strcmp(key, "op_gemm_vt_perm16")) { g_op_gemm_vt_perm16 = value ? 1 : 0; return 0; }
   if (!strcmp(key, "attn_bwd_flash")) { g_attn_bwd_flash = value; return 0; }
   return igemm_set_tuning(key, value) == 0 ? 0 : PNPI_EINVAL;
 }
@@ -733,7 +735,7 @@ int pnpi_op_gemm(pnpi_ctx* c, const void* a, int lda, const void* w, int ldw, in
   p.x1 = (const half_t*)a; p.C1 = K; p.ldx1 = lda; p.B = 1; p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.ksize = 1;
   p.w = (const half_t*)w; p.ldw = ldw; p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.bias = bias; p.res = (const half_t*)res;
   p.ldres = N; p.out = (half_t*)out; p.ldo = ldo;
-  if (outT) { p.outT = outT; p.vt_col0 = vt_col0; p.vt_ld = vt_ld; p.vt_f32 = vt_f32; p.rows_per_batch = rpb; }
+  if (outT) { p.outT = outT; p.vt_col0 = vt_col0; p.vt_ld = vt_ld; p.vt_f32 = vt_f32; p.rows_per_batch = rpb; p.vt_perm16 = g_op_gemm_vt_perm16; }
   CK(launch_igemm(p, c->splitk_ws, c->splitk_bytes, c->st, force_cfg, force_split));
   return 0;
 }

@@ -86,6 +86,7 @@ static int g_attn_aug = 1;           // tuning "attn_aug" = 0: the 64-wide flash
 static int g_vt_perm = 1;            // tuning "attn_vt_perm": V^T of the 4096-token self-attention sites in the permuted key order (A/B)
 static int g_attn_bwd_flash = 1;     // tuning "attn_bwd_flash": self-attention backward without the [N][N] matrices in memory (0: the materialised form everywhere)
 static int g_op_attention_aug = 0;       // tuning "op_attention_aug": pnpi_op_attention is handed K / V^T with 1.0 in column / row dh (kernel tests)
+static int g_op_gemm_vt_perm16 = 0;      // tuning "op_gemm_vt_perm16": pnpi_op_gemm writes its transposed columns in the permuted key order (GemmP::vt_perm16; kernel tests)
 static int g_op_attention_vt_perm = 0;   // tuning "op_attention_vt_perm": pnpi_op_attention is handed a permuted V^T (kernel tests)
 static inline bool taping(pnpi_ctx* c) { return c->tape && c->tape->rec && !c->dry; }
 // a recording forward (or the dry run that sizes the arenas for one) keeps every activation and takes the plain-layout transformer block

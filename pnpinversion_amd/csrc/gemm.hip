@@ -403,6 +403,7 @@ static int g_pp_only_n = 0, g_pp_only_k = 0, g_pp_only_m = 0;   // tuning "igemm
 static int g_tapin = 0;         // tuning "igemm_tapin" = 1: the ping-pong kernel walks 3 x 3 convolutions channel-slab-major (GemmP::k_order)
 static int g_varpp = 0;         // tuning "igemm_vpp": ablations of the ping-pong kernel (1 = no MFMAs, 2 = no DMA; both produce garbage)
 static int g_sched = 0;         // tuning "igemm_sched" = 1: the hand-scheduled main loop (igemm_dma_kernel<..., ABL = 4>) for the one-k-group tile configurations
+static int g_pp_rowtile = [] { const char* e = getenv("PNPI_PP_ROWTILE"); const int v = e ? atoi(e) : 1; return v == 0 ? 0 : 1; }();   // tuning "pp_rowtile": the ping-pong tile's row height follows the launched M (pp_rowtile_pick); 0: the table's tile as it stands
 static int g_force_split = 0;   // > 0 with igemm_force_cfg: split-K of every auto-configured launch (in-forward tuning sweeps)
 static thread_local int g_last_cfg = -1, g_last_split = 1;   // per thread: two contexts may launch from two threads   // what the most recent launch_igemm used (profiling dumps)
 void igemm_last_launch(int* cfg, int* split, int* geom) { *cfg = g_last_cfg; *split = g_last_split; for (int i = 0; i < 7; ++i) geom[i] = g_last_geom[i]; }
@@ -413,7 +414,7 @@ void igemm_set_dma(int on) { g_use_dma = on; }
 // process-wide tuning knobs (A/B measurements inside one process, tests of the non-default variants); 0 on success
 int igemm_set_tuning(const char* key, int v) {
   struct { const char* k; int* p; } tab[] = {{"igemm_dma", &g_use_dma}, {"igemm_v128", &g_var128}, {"igemm_v64", &g_var64}, {"igemm_v256", &g_var256},
-                                             {"igemm_v320", &g_var320}, {"igemm_v256n", &g_var256n}, {"igemm_wide", &g_wide}, {"tile_order", &g_tile_order}, {"igemm_force_cfg", &g_force_cfg}, {"igemm_force_split", &g_force_split}, {"igemm_bias_init", &g_bias_init}, {"igemm_sched", &g_sched}, {"igemm_vpp", &g_varpp}, {"igemm_tapin", &g_tapin}, {"igemm_pp_only_n", &g_pp_only_n}, {"igemm_pp_only_k", &g_pp_only_k}, {"igemm_pp_only_m", &g_pp_only_m}, {"igemm_deep_rings", &g_deep_rings}, {"igemm_vt_lds", &g_vt_lds}, {"igemm_res_late", &g_res_late}, {"igemm_table", &g_use_table}, {"igemm_table_near", &g_table_near}};
+                                             {"igemm_v320", &g_var320}, {"igemm_v256n", &g_var256n}, {"igemm_wide", &g_wide}, {"tile_order", &g_tile_order}, {"igemm_force_cfg", &g_force_cfg}, {"igemm_force_split", &g_force_split}, {"igemm_bias_init", &g_bias_init}, {"igemm_sched", &g_sched}, {"igemm_vpp", &g_varpp}, {"igemm_tapin", &g_tapin}, {"igemm_pp_only_n", &g_pp_only_n}, {"igemm_pp_only_k", &g_pp_only_k}, {"igemm_pp_only_m", &g_pp_only_m}, {"igemm_deep_rings", &g_deep_rings}, {"igemm_vt_lds", &g_vt_lds}, {"igemm_res_late", &g_res_late}, {"igemm_table", &g_use_table}, {"igemm_table_near", &g_table_near}, {"pp_rowtile", &g_pp_rowtile}};
 #ifndef PNPI_ABLATIONS
   // the ablation instances (no MFMAs / no DMA / no fragment reads, the hand-scheduled 4-wave loop) exist only in a `build --ablations`
   // library: a product build rejects their selectors here instead of silently timing the default kernel
@@ -487,7 +488,30 @@ int igemm_table_lookup(int M, int N, int K, int ks, int* cfg, int* split, int* e
 }
 // cfg 6 = 256x320, 7 = 256x256 (8 waves, 128-byte rows, two stages, one block per CU); 8-11: K-parallel wave groups; 12 = 64x320;
 // 13 = 128x128 with a two-stage ring; 14 / 15 = 128x128 / 128x256 with 128-byte rows; 18 = 128x128, 128-byte rows, three stages:
-// reached through the table or force_cfg
+// reached through the table or force_cfg.  19 / 20 = the shorter ping-pong tiles 128x320 / 192x256: force_cfg or pp_rowtile_pick, never the table
+
+// Row height of a ping-pong launch (tuning "pp_rowtile").  Tile and split-K are chosen first, as ever (table entry at sel_M); this
+// only swaps the tile for the other row height of the same BN (17 <-> 19: 192 / 128 x 320; 16 <-> 20: 256 / 192 x 256), which changes no
+// output bit (igemm_pp.inc), using the LAUNCHED M.  W(bm) = ceil(M / bm) * ceil(N / BN) * split workgroups run in ceil(W / 256) rounds
+// of one workgroup per CU.  The shorter tile runs when it needs no more rounds than the taller one: each round is then shorter and
+// more CUs take part.  (49152, 320) stays 192 (256 tiles, one round, against two); (32768, 320) becomes 128 (171 tiles on two thirds
+// of the chip -> 256); (2048, 1280) x 4 becomes 192 x 256 (160 -> 220 workgroups).  Not "the smaller rounds x bm": a round of the
+// 128-row tile was measured at 0.91 of a 192-row round, not 0.67 (the weight panel's bytes and the prologue / epilogue do not shrink
+// with BM), so four rounds of 128 lose to three of 192 -- (8192, 5120): 688 workgroups 77.7 us against 1024 workgroups 83.6 us
+// (profiles/pp_rowtile_ab.json).  Returns the cfg id to launch.
+static int pp_rowtile_pick(int cfg, int M, int N, int split) {
+  const bool f320 = cfg == 17 || cfg == 19;
+  const int bn = f320 ? 320 : 256, bm_tall = f320 ? 192 : 256, bm_short = f320 ? 128 : 192;
+  auto rounds = [&](int bm) { const long w = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * (split > 1 ? split : 1); return (w + 255) / 256; };
+  const bool tall = rounds(bm_short) > rounds(bm_tall);
+  return f320 ? (tall ? 17 : 19) : (tall ? 16 : 20);
+}
+// host-only query (tests): rows of the tile pp_rowtile_pick launches for a ping-pong configuration; 0: cfg is no ping-pong tile
+int igemm_pp_rowtile_query(int cfg, int M, int N, int split) {
+  if (cfg < 16 || cfg == 18 || cfg > 20 || M <= 0 || N <= 0) return 0;
+  const int c = pp_rowtile_pick(cfg, M, N, split);
+  return c == 16 ? 256 : (c == 19 ? 128 : 192);
+}
 
 // product tile configurations with one k-group: compiler-scheduled main loop, or (tuning "igemm_sched") the hand-scheduled one
 #ifdef PNPI_ABLATIONS
@@ -496,12 +520,14 @@ int igemm_table_lookup(int M, int N, int K, int ks, int* cfg, int* split, int* e
 #define LDMA(...) launch_dma<__VA_ARGS__>(p, grid, st, g_zero_page)
 #endif
 #define LDMA0(...) launch_dma<__VA_ARGS__>(p, grid, st, g_zero_page)
-// Can the 8-wave ping-pong kernel (cfg 16 = 256 x 256, 17 = 192 x 320) take this launch?  It has no scalar epilogue: a launch either takes
+// Can the 8-wave ping-pong kernel (cfg 16 = 256 x 256, 17 = 192 x 320, 19 = 128 x 320, 20 = 192 x 256) take this launch?  It has no scalar epilogue: a launch either takes
 // the LDS epilogue (whole tiles plain or transposed, 16-byte rows, 16-byte aligned bias) or writes split-K slabs; its DMA addresses are
 // 32-bit byte offsets under a 2 GiB buffer descriptor (operands beyond that stay on the 64-bit-pointer kernels); batched launches stay
-// on the 4-wave kernels.
+// on the 4-wave kernels.  The 192 x 256 tile cannot reproduce the 256 x 256 tile's statistics tree (16 row groups over 3 sub-blocks):
+// it takes no launch that produces GroupNorm statistics.
 static bool pp_eligible(const GemmP& p, int cfg, int split, bool dma_ok) {
-  const int bn_pp = cfg == 17 ? 320 : 256;
+  const int bn_pp = (cfg == 17 || cfg == 19) ? 320 : 256;
+  if (cfg == 20 && p.stats && split == 1) return false;
   const bool vt_none_ = p.vt_col0 >= p.N;
   const bool vt_lds_ = !vt_none_ && p.outT && !p.vt_f32 && p.vt_col0 % bn_pp == 0 && p.rows_per_batch % 8 == 0 && p.vt_ld % 8 == 0 && p.M % 8 == 0 && !p.res &&
                        !p.geglu && g_vt_lds;
@@ -530,6 +556,7 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
   int cfg = force_cfg;
   int split = 1;
   if (cfg < 0 && g_force_cfg >= 0) { cfg = g_force_cfg == 2 ? 1 : g_force_cfg; if (force_split <= 0) force_split = g_force_split; }
+  const bool cfg_forced = cfg >= 0;      // a caller's force_cfg or tuning "igemm_force_cfg" names its tile and keeps it
   if (cfg < 0 && g_use_table && dma_ok) {
     if (const TileEntry* pe = tile_table_lookup(selM, p.N, p.K, p.ksize, nullptr)) {
         const TileEntry& e = *pe;
@@ -590,15 +617,20 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
     if (split > nchunks) split = nchunks;
     if (ws == nullptr || (size_t)split * selM * p.N * sizeof(float) > ws_bytes || p.geglu || cfg == 3) split = 1;
   }
-  if ((cfg == 16 || cfg == 17) && !pp_eligible(p, cfg, split, dma_ok)) cfg = 0;     // forced configurations (tests, sweeps): the 128 x 128 kernel instead
+  if ((cfg == 16 || cfg == 17 || cfg == 19 || cfg == 20) && !pp_eligible(p, cfg, split, dma_ok)) cfg = 0;     // forced configurations (tests, sweeps): the 128 x 128 kernel instead
+  // the row height follows the launched M
+  if ((cfg == 16 || cfg == 17) && g_pp_rowtile && !cfg_forced && !g_varpp) {      // the ablation instances (igemm_vpp) exist for 16 / 17 only
+    const int c2 = pp_rowtile_pick(cfg, p.M, p.N, split);
+    if (c2 != cfg && pp_eligible(p, c2, split, dma_ok)) cfg = c2;
+  }
   const bool c64 = cfg == 1 || cfg == 8 || cfg == 11 || cfg == 12, c256m = cfg == 3 || cfg == 6 || cfg == 7 || cfg == 16;
-  const bool cpp = cfg == 16 || cfg == 17;      // the 8-wave ping-pong kernel: 16 = 256 x 256, 17 = 192 x 320
-  if (cfg_used) *cfg_used = split > 1 ? 2 : (((cfg >= 4 && cfg <= 7) || cfg == 12 || (cfg >= 15 && cfg <= 17)) ? 9 : (c64 ? 1 : 0));
+  const bool cpp = cfg == 16 || cfg == 17 || cfg == 19 || cfg == 20;      // the 8-wave ping-pong kernel: 16 = 256 x 256, 17 = 192 x 320, 19 = 128 x 320, 20 = 192 x 256
+  if (cfg_used) *cfg_used = split > 1 ? 2 : (((cfg >= 4 && cfg <= 7) || cfg == 12 || (cfg >= 15 && cfg <= 17) || cfg == 19 || cfg == 20) ? 9 : (c64 ? 1 : 0));
   p.splitk = split;
   p.kchunks_per_split = (nchunks + split - 1) / split;
   g_last_cfg = cfg; g_last_split = split;
   for (int i = 0; i < 7; ++i) g_last_geom[i] = 0;
-  const int bn_sel = (cfg == 4 || cfg == 6 || cfg == 12 || cfg == 17) ? 320 : ((cfg == 5 || cfg == 7 || cfg == 15 || cfg == 16) ? 256 : (c64 ? 64 : 128));
+  const int bn_sel = (cfg == 4 || cfg == 6 || cfg == 12 || cfg == 17 || cfg == 19) ? 320 : ((cfg == 5 || cfg == 7 || cfg == 15 || cfg == 16 || cfg == 20) ? 256 : (c64 ? 64 : 128));
   const bool vt_none = p.vt_col0 >= p.N;
   // transposed (V^T) columns through the LDS epilogue too, when whole tiles are either plain or transposed and 8-token runs stay
   // inside one batch item
@@ -611,7 +643,7 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
   if (p.vt_perm16 && (p.rows_per_batch % 16 != 0 || p.vt_f32)) return -9;   // permuted V^T: whole 16-token groups, fp16
   if (p.geglu && !(p.epi_lds && dma_ok && p.N % 64 == 0)) return -7;   // GEGLU exists only in the LDS epilogue
   if (!(p.epi_lds && dma_ok && !p.geglu)) p.stats = nullptr;       // statistics come only from the DMA kernel's LDS epilogue
-  const int bm = cfg == 17 ? 192 : (c256m ? 256 : (c64 ? 64 : 128));
+  const int bm = (cfg == 17 || cfg == 20) ? 192 : (c256m ? 256 : (c64 ? 64 : 128));
   const int bn = bn_sel;
   if (stats_tile_rows) *stats_tile_rows = p.stats ? (cpp ? 64 : bm) : 0;     // the ping-pong kernel writes its partials per 64-row sub-block
   p.slab = ws;
@@ -664,6 +696,10 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
     r = launch_dma<128, 128, 32, 3, 2, 0, 2>(p, grid, st, g_zero_page);    // 8 waves: 2 k-groups, 96 KB
   } else if (cfg == 10) {
     r = launch_dma<128, 128, 64, 2, 2, 0, 2>(p, grid, st, g_zero_page);    // 8 waves: 2 k-groups, 128-byte rows, 128 KB
+  } else if (cfg == 19 || cfg == 20) {
+    if (g_varpp) return -10;         // the shorter ping-pong tiles have no ablation instances
+    p.k_order = (g_tapin && p.ksize == 3) ? 1 : 0;
+    r = cfg == 19 ? launch_pp<128, 320, 1, 4>(p, grid, st, g_zero_page) : launch_pp<192, 256, 1, 4>(p, grid, st, g_zero_page);
   } else if (cfg == 16 || cfg == 17) {
     p.k_order = (g_tapin && p.ksize == 3) ? 1 : 0;
 #define LPP(...) (cfg == 16 ? launch_pp<256, 256, 2, 4, __VA_ARGS__>(p, grid, st, g_zero_page) : launch_pp<192, 320, 1, 4, __VA_ARGS__>(p, grid, st, g_zero_page))

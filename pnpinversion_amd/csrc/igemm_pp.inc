@@ -6,6 +6,11 @@
 //   * tile BM x BN x 64 with BM x BN = 256 x 256 or 192 x 320 (128 / 120 FLOP per operand byte against 64 for 128 x 128: the LDS-DMA
 //     path, which paces the 4-wave kernels, carries half the bytes per FLOP), v_mfma_f32_16x16x32_f16 (tiles are multiples of 16, so
 //     192 x 320 exists: (49152, 320), (12288, 640) x split 2, (3072, 1280) x split 4 all give exactly 256 workgroups);
+//   * each BN also has a shorter tile, 128 x 320 and 192 x 256 (91 / 110 FLOP per operand byte), for the launches whose row count
+//     leaves the taller tile with a part-filled round of workgroups (the 8-row lock step: (32768, 320) is 171 tiles of 192 rows but
+//     exactly 256 of 128).  An output element's K walk (K-tiles in order, two k-steps each) and its split-K ranges do not depend on
+//     BM, and the GroupNorm partial sums keep one reduction tree per BN (PpGeom::GPS), so the tiles of one BN are interchangeable
+//     bit for bit; launch_igemm picks the row height on the launched M (pp_rowtile_pick in gemm.hip, tuning "pp_rowtile");
 //   * the two waves that share a SIMD (wave w and w + 4) run half a phase apart: while one issues its MFMAs (s_setprio 1) the
 //     other reads its fragments and issues its DMA instructions, then they swap -- the matrix pipe of every SIMD always has a wave in
 //     its MFMA section.  Two raw s_barriers per phase keep the two groups in that order (group 1 starts one barrier late);
@@ -22,6 +27,22 @@
 // [W0 | A0 | A1 | W1]):  batch issued in phase p  ->  `vmcnt` in phase p + 4 retires it (every wave waits for its own part, the
 // phase's first barrier publishes it)  ->  first fragment read in phase p + 5 or later (RAW: one phase after the wait, which also
 // covers the one-barrier stagger between the groups);  a region is re-staged two or more phases after its last read (WAR).
+//
+// Unequal batches.  The shorter tiles have 7 slots per K-tile ([W0 W0 | A0 | A1 | W1 W1 W1] and [W0 W0 | A0 | A1 A1 | W1 W1]), split
+// 1, 2, 2, 2 (CB = 1, 3, 5, 7; PpGeom's static_assert: W0 and A0 end inside batch 2, A1 inside batch 3, A1 starts in batch >= 2, W1 in
+// batch >= 3).  Every wave issues exactly one instruction per slot, in a fixed order, so with N1..N4 the batch sizes and
+// NALL = N1 + N2 + N3 + N4 each counted wait is "the instructions issued BEHIND the batch that must have landed" -- never more (more
+// would let that batch stay in flight: a race), and written in N1..N4, not in NALL / 4:
+//   prologue      issued T0 b1 b2 b3 b4 [T1 b1 b2]; needs T0 b1 b2; behind them: N3 + N4 [+ N1 + N2 = NALL].
+//   phase 1       (rem >= 1) issues T(t+1) b3; needs T(t) b3; behind it: T(t) b4, T(t+1) b1 b2 b3 = NALL -- T(t+1) b1 b2 were issued by
+//                 the prologue (t = 0) or by phases 3, 4 of K-tile t - 1, where rem was >= 2.  (rem = 0) nothing issued since T(t) b4: N4.
+//   phase 2       (rem >= 1) issues T(t+1) b4; needs T(t) b4; behind it: T(t+1) b1 b2 b3 b4 = NALL.  (rem = 0) the queue's tail: 0.
+//   phase 3       issues T(t+2) b1 when rem >= 2; no wait (phase 4 reads nothing new).
+//   phase 4       (rem >= 2) issues T(t+2) b2; needs T(t+1) b1 b2; behind them: T(t+1) b3 b4, T(t+2) b1 b2 = NALL.  (rem = 1) phases
+//                 3, 4 issued nothing: behind them T(t+1) b3 b4 = N3 + N4.  (rem = 0) nothing left.
+// nt = 1: prologue N3 + N4, then N4, 0.  nt = 2: prologue NALL; t = 0: NALL, NALL, -, N3 + N4; t = 1: N4, 0.  nt = 3: t = 0 runs the
+// steady state (rem = 2), t = 1 as nt = 2's t = 0, t = 2 as its t = 1; odd / even nt differ only in the buffer a K-tile lands in.
+// The counts hold for any batch sizes; what unequal batches change is only which slots share a batch (the RAW / WAR assert above).
 #pragma once
 #include "igemm_dma.inc"
 
@@ -34,6 +55,8 @@ __device__ __forceinline__ const half_t* uniform_ptr(const half_t* q) {
 
 __device__ __forceinline__ floatx4 mfma16(half8 a, half8 b, floatx4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
+constexpr int pp_pow2_floor(int v) { int r = 1; while (2 * r <= v) r *= 2; return r; }
+
 template <int BM, int BN, int MI0, int NI0>
 struct PpGeom {
   static constexpr int WGM = 4, WGN = 2, NWV = 8, NT = 512;
@@ -44,7 +67,8 @@ struct PpGeom {
   static constexpr int OW0 = 0, OA0 = RW0, OA1 = RW0 + RA0, OW1 = RW0 + RA0 + RA1;          // first row of each region
   static constexpr int NPW = (BM + BN) / 64, NAS = BM / 64, NWS = BN / 64;                  // slots per K-tile: all / activation / weight
   static constexpr int KT_BYTES = (BM + BN) * 128, RING = 2 * KT_BYTES;
-  // DMA batches: slots [CB[b-1], CB[b]) are issued together; equal batches (NPW = 8: two instructions per wave per phase)
+  // DMA batches: slots [CB[b-1], CB[b]) are issued together; NPW = 8: four batches of two instructions per wave; NPW = 7 (the 128 x 320
+  // and 192 x 256 tiles): CB = 1, 3, 5, 7, batches of 1, 2, 2, 2 ("Unequal batches" in the header comment)
   static constexpr int CB0 = 0, CB1 = NPW / 4, CB2 = NPW / 2, CB3 = (3 * NPW) / 4, CB4 = NPW;
   static_assert(RW0 % 64 == 0 && RA0 % 64 == 0 && RA1 % 64 == 0 && RW1 % 64 == 0, "regions are whole DMA slots");
   static_assert(MI0 > 0 && MI1 > 0 && NI0 > 0 && NI1 > 0 && WM % 16 == 0 && WN % 16 == 0, "quadrants");
@@ -56,13 +80,15 @@ struct PpGeom {
   static constexpr int OLD = BN + 8, VPR = BN / 8, G = NT / VPR;
   static constexpr int STATS_B = G * BN * 2 * 4;
   static constexpr int EPASS = (BM * OLD * 2 + STATS_B <= 160 * 1024) ? 1 : 2;
-  static constexpr int EROWS = BM / EPASS, SB = EROWS / 64, GPS = G / SB, RPT = 64 / GPS;   // sub-blocks per pass, groups per sub-block, rows per thread
+  // GPS = the largest power of two the row groups allow: GA = SB * GPS of the G groups store (8 of 12 in the 128 x 320 tile), so that
+  // the reduction tree of a sub-block's statistics (RPT rows per thread, then GPS groups) is the same for every BM of one BN
+  static constexpr int EROWS = BM / EPASS, SB = EROWS / 64, GPS = pp_pow2_floor(G / SB), RPT = 64 / GPS, GA = SB * GPS;   // sub-blocks per pass, groups per sub-block, rows per thread, storing groups
   static constexpr int TOLD = EROWS + 8;
   static constexpr int EPI_PLAIN = EROWS * OLD * 2 + STATS_B, EPI_TR = BN * TOLD * 2;
   static constexpr int EPI = EPI_PLAIN > EPI_TR ? EPI_PLAIN : EPI_TR;
   static constexpr int LDS = RING > EPI ? RING : EPI;
   static_assert(LDS <= 160 * 1024, "LDS");
-  static_assert(EROWS % 64 == 0 && G % SB == 0 && 64 % GPS == 0 && (WGM / EPASS) * WM == EROWS, "epilogue geometry");
+  static_assert(EROWS % 64 == 0 && GA <= G && GPS >= 1 && 64 % GPS == 0 && (WGM / EPASS) * WM == EROWS, "epilogue geometry");
 };
 
 template <int BM, int BN, int MI0, int NI0, int ABL = 0>
@@ -377,11 +403,11 @@ igemm_pp_kernel(GemmP p_in) {
   const float* ebias = p.bias;
   const int fl = lane & 15, fq = lane >> 4;
   if (p.epi_lds && p.splitk <= 1) {
-    constexpr int OLD = GEO::OLD, VPR = GEO::VPR, G = GEO::G, EPASS = GEO::EPASS, EROWS = GEO::EROWS, GPS = GEO::GPS, RPT = GEO::RPT, SB = GEO::SB;
+    constexpr int OLD = GEO::OLD, VPR = GEO::VPR, EPASS = GEO::EPASS, EROWS = GEO::EROWS, GPS = GEO::GPS, RPT = GEO::RPT, SB = GEO::SB;
     half_t* sOut = reinterpret_cast<half_t*>(smem_raw);
     const bool tr_tile = p.outT != nullptr && n0 >= p.vt_col0;      // block-uniform (the launcher aligns vt_col0 to the tile width)
     const int sv = tid % VPR, sg = tid / VPR;
-    const bool s_active = sg < G;
+    const bool s_active = sg < GEO::GA;                             // the 128 x 320 tile: 8 of its 12 row groups
     const int srow0 = (sg / GPS) * 64 + (sg % GPS);                 // store loop: rows srow0 + GPS * k of the pass, all inside one 64-row sub-block
     floatx4 bv[NI];
     if (ebias) {
