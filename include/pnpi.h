@@ -415,6 +415,35 @@ int pnpi_tile_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split,
  * split-K factor.  Returns the rows of the tile that runs (256, 192 or 128): the family's shorter tile when it needs no more rounds
  * of one workgroup per CU on 256 CUs than the taller one; 0 when cfg is no ping-pong tile. */
 int pnpi_pp_rowtile_query(int cfg, int M, int N, int split);
+/* Host-only: everything launch_igemm decides for one launch -- tile, split-K, ring / variant, epilogue, grid, statistics -- without
+ * launching: selection is a pure function of this description and the tuning knobs (no context, no device).  The description is
+ * of a GEMM of M rows (a convolution's B * Ho * Wo): ksize 1 or 3, K = ksize^2 (C1 + C2), leading dimensions in elements; bias /
+ * residual / stats are presence flags (bias_aligned16: the bias pointer is 16-byte aligned); vt_col0 >= N: no transposed columns;
+ * rows_per_batch >= 1, nbatch >= 1; ws_bytes: split-K workspace (0: none); force_cfg -1 / force_split 0 / sel_M 0: the launcher
+ * chooses, at the launched M.  The plan: err is 0 or launch_igemm's rejection (-2 ... -10; id -1: rejected before a tile was chosen,
+ * stats_tile_rows -1: before the statistics were decided); id / split: tile id and split-K; variant / sparse: the tile's tuning
+ * variant (ring depth folded in for ids 0 / 1) and 2 / 1 / 0 for at most one / two / more blocks per CU; bm x bn tiles on a
+ * gx x gy x gz grid; epi_lds / bias_init / res_late / k_order: the epilogue flags the kernel gets; stats: requested statistics are
+ * produced, stats_tile_rows rows per partial; cls: the kernel class pnpi_profile_end counts the launch in; dma 0: register-staged
+ * fallback kernel (fastk: its 64-channel fast path). */
+typedef struct {
+  int M, N, K, ksize, C1, C2, ldx1, ldx2, ldw, ldo, ldres;
+  int bias, bias_aligned16, residual, geglu, stats;
+  int vt_col0, vt_ld, vt_f32, rows_per_batch, vt_perm16;
+  int nbatch;
+  long long ws_bytes;
+  int force_cfg, force_split, sel_M;
+} pnpi_igemm_launch_desc;
+typedef struct {
+  int err, id, split, kchunks_per_split;
+  int variant, sparse;
+  int bm, bn, gx, gy, gz;
+  int vt_col0;
+  int epi_lds, bias_init, res_late, k_order;
+  int stats, stats_tile_rows, cls;
+  int dma, fastk;
+} pnpi_igemm_plan;
+int pnpi_igemm_plan_query(const pnpi_igemm_launch_desc* desc, pnpi_igemm_plan* plan);
 /* Host-only: the row maps of pnpi_direct_edit's shared-row launch ("src_share") for nimg images and npass guidance passes.  Logical row
  * 4 (p nimg + im) + k is row k of [unc_src, unc_tgt, cond_src, cond_tgt] of pass p (0 = the offset pass) of image im, on the logical
  * latent 2 (p nimg + im) + k % 2.  Outputs (each nullable): lsel [compact latent] -> logical latent, cmap [compact row] -> compact latent,

@@ -65,6 +65,17 @@ class KernelStats(C.Structure):
     _fields_ = [("launches", C.c_uint64), ("total_ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class IgemmLaunchDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("M", "N", "K", "ksize", "C1", "C2", "ldx1", "ldx2", "ldw", "ldo", "ldres", "bias", "bias_aligned16", "residual",
+                                       "geglu", "stats", "vt_col0", "vt_ld", "vt_f32", "rows_per_batch", "vt_perm16", "nbatch")] + \
+               [("ws_bytes", C.c_longlong)] + [(n, C.c_int) for n in ("force_cfg", "force_split", "sel_M")]
+
+
+class IgemmPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("err", "id", "split", "kchunks_per_split", "variant", "sparse", "bm", "bn", "gx", "gy", "gz", "vt_col0", "epi_lds",
+                                       "bias_init", "res_late", "k_order", "stats", "stats_tile_rows", "cls", "dma", "fastk")]
+
+
 # every symbol include/pnpi.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
@@ -110,6 +121,7 @@ SYMBOLS = {
     "pnpi_set_tuning": (_i, [C.c_char_p, _i]),
     "pnpi_tile_table_lookup": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pnpi_pp_rowtile_query": (_i, [_i, _i, _i, _i]),
+    "pnpi_igemm_plan_query": (_i, [C.POINTER(IgemmLaunchDesc), C.POINTER(IgemmPlan)]),
     "pnpi_src_share_maps": (_i, [_i, _i] + [C.POINTER(C.c_int)] * 6),
     "pnpi_op_gemm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "pnpi_op_gemm_geglu": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i]),

@@ -711,6 +711,27 @@ int pnpi_tile_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split,
   return igemm_table_lookup(M, N, K, ksize, cfg, split, entry_m);
 }
 int pnpi_pp_rowtile_query(int cfg, int M, int N, int split) { return igemm_pp_rowtile_query(cfg, M, N, split); }
+int pnpi_igemm_plan_query(const pnpi_igemm_launch_desc* d, pnpi_igemm_plan* plan) {
+  static_assert(sizeof(pnpi_igemm_plan) == sizeof(IgemmPlan), "pnpi_igemm_plan mirrors IgemmPlan field for field");
+  if (!d || !plan) return PNPI_EINVAL;
+  half_t* const some = (half_t*)(uintptr_t)4096;      // operands are never dereferenced: only null / alignment are looked at
+  GemmP p;
+  gemm_defaults(p);
+  p.x1 = some; p.w = some; p.out = some; p.x2 = d->C2 ? some : nullptr;
+  p.M = d->M; p.N = d->N; p.K = d->K; p.ksize = d->ksize; p.pad = d->ksize / 2; p.C1 = d->C1; p.C2 = d->C2;
+  p.B = 1; p.H = d->M; p.W = 1; p.Ho = d->M; p.Wo = 1;      // rows only: B * H * W = M
+  p.ldx1 = d->ldx1; p.ldx2 = d->ldx2; p.ldw = d->ldw; p.ldo = d->ldo; p.ldres = d->ldres;
+  if (d->bias) p.bias = (const float*)((uintptr_t)some + (d->bias_aligned16 ? 0 : 4));
+  if (d->residual) p.res = some;
+  if (d->stats) p.stats = (float*)some;
+  p.geglu = d->geglu;
+  p.vt_col0 = d->vt_col0; p.vt_ld = d->vt_ld; p.vt_f32 = d->vt_f32; p.rows_per_batch = d->rows_per_batch; p.vt_perm16 = d->vt_perm16;
+  if (d->vt_col0 < d->N) p.outT = some;
+  p.nbatch = d->nbatch;
+  const IgemmPlan pl = igemm_plan(p, d->ws_bytes > 0, d->ws_bytes > 0 ? (size_t)d->ws_bytes : 0, d->force_cfg, d->force_split, d->sel_M);
+  memcpy(plan, &pl, sizeof pl);
+  return 0;
+}
 int pnpi_set_tuning(const char* key, int value) {
   if (!key) return PNPI_EINVAL;
   if (!strcmp(key, "text_kv")) { g_text_kv = value; return 0; }

@@ -290,47 +290,40 @@ __global__ void __launch_bounds__(256) igemm_kernel(GemmP p_in) {
 // Requires (C1 + C2) % 64 == 0 and C1 % 64 == 0 (every SD-1.x layer but the 4/3-channel stems, which stay on v1).
 // ------------------------------------------------------------------------------------------------------------------
 static int g_tile_order = -1;   // PNPI_TILE_ORDER: force 0 / 1 (ablation)
+static half_t* g_zero_page = nullptr;   // out-of-range lanes of igemm_dma_kernel read it (igemm_init)
 
 static thread_local int g_last_geom[7] = {0, 0, 0, 0, 0, 0, 0};   // template arguments of the most recent igemm_dma_kernel launch (all 0: the v1 kernel)
-template <int BM, int BN, int BKT, int NST, int WGM = 2, int ABL = 0, int WK = 1>
-static int launch_dma(const GemmP& p_in, dim3 grid, hipStream_t st, const half_t* zero_page) {
-  using GEO = IgemmGeom<BM, BN, BKT, NST, WGM, ABL, WK>;
-  g_last_geom[0] = BM; g_last_geom[1] = BN; g_last_geom[2] = BKT; g_last_geom[3] = NST; g_last_geom[4] = WGM; g_last_geom[5] = ABL; g_last_geom[6] = WK;
-  GemmP p = p_in;
+// What launch_dma and launch_pp share: the logical grid and the XCD traversal order into p, the launch grid flattened and rounded up
+// to 8 workgroups, the kernel's dynamic-LDS attribute once per device.
+static int dma_launch_prep(GemmP& p, dim3& grid, DeviceOnce& attr_once, const void* kernel, int lds) {
   p.gx = grid.x; p.gy = grid.y; p.gz = grid.z;
-  {
-    const double bytes_a = 2.0 * p.B * p.H * p.W * (p.C1 + p.C2), bytes_w = 2.0 * (double)p.N * p.K;
-    p.tile_order = (bytes_a + 8 * bytes_w <= 8 * bytes_a + bytes_w) ? 0 : 1;
-    if (g_tile_order >= 0) p.tile_order = g_tile_order;
-  }
+  const double bytes_a = 2.0 * p.B * p.H * p.W * (p.C1 + p.C2), bytes_w = 2.0 * (double)p.N * p.K;
+  p.tile_order = (bytes_a + 8 * bytes_w <= 8 * bytes_a + bytes_w) ? 0 : 1;
+  if (g_tile_order >= 0) p.tile_order = g_tile_order;
   const int total = (int)(grid.x * grid.y * grid.z);
   grid = dim3((unsigned)(((total + 7) / 8) * 8), 1, 1);
-  constexpr int lds = GEO::LDS;
+  return once_per_device(attr_once, [&]() { return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+}
+
+template <int BM, int BN, int BKT, int NST, int WGM = 2, int ABL = 0, int WK = 1>
+static int launch_dma(GemmP p, dim3 grid, hipStream_t st) {
+  using GEO = IgemmGeom<BM, BN, BKT, NST, WGM, ABL, WK>;
+  g_last_geom[0] = BM; g_last_geom[1] = BN; g_last_geom[2] = BKT; g_last_geom[3] = NST; g_last_geom[4] = WGM; g_last_geom[5] = ABL; g_last_geom[6] = WK;
   static DeviceOnce attr_once;
-  if (int r = once_per_device(attr_once, [&]() { return (int)hipFuncSetAttribute((const void*)igemm_dma_kernel<BM, BN, BKT, NST, WGM, ABL, WK>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); })) return r;
-  igemm_dma_kernel<BM, BN, BKT, NST, WGM, ABL, WK><<<grid, GEO::NT_ALL, lds, st>>>(p, zero_page);
+  if (int r = dma_launch_prep(p, grid, attr_once, (const void*)igemm_dma_kernel<BM, BN, BKT, NST, WGM, ABL, WK>, GEO::LDS)) return r;
+  igemm_dma_kernel<BM, BN, BKT, NST, WGM, ABL, WK><<<grid, GEO::NT_ALL, GEO::LDS, st>>>(p, g_zero_page);
   return 0;
 }
 
-// The 8-wave ping-pong kernel (igemm_pp.inc): one workgroup per CU, same tile-order / grid conventions as launch_dma.
+// The 8-wave ping-pong kernel (igemm_pp.inc): one workgroup per CU, same tile-order / grid conventions as launch_dma.  Its out-of-range
+// lanes read zeros through the buffer descriptor's bounds check: no zero page.
 template <int BM, int BN, int MI0, int NI0, int ABL = 0>
-static int launch_pp(const GemmP& p_in, dim3 grid, hipStream_t st, const half_t* zero_page) {
+static int launch_pp(GemmP p, dim3 grid, hipStream_t st) {
   using GEO = PpGeom<BM, BN, MI0, NI0>;
   g_last_geom[0] = BM; g_last_geom[1] = BN; g_last_geom[2] = MI0; g_last_geom[3] = NI0; g_last_geom[4] = ABL; g_last_geom[5] = 0; g_last_geom[6] = -1;   // [6] = -1: igemm_pp_kernel
-  GemmP p = p_in;
-  p.gx = grid.x; p.gy = grid.y; p.gz = grid.z;
-  {
-    const double bytes_a = 2.0 * p.B * p.H * p.W * (p.C1 + p.C2), bytes_w = 2.0 * (double)p.N * p.K;
-    p.tile_order = (bytes_a + 8 * bytes_w <= 8 * bytes_a + bytes_w) ? 0 : 1;
-    if (g_tile_order >= 0) p.tile_order = g_tile_order;
-  }
-  const int total = (int)(grid.x * grid.y * grid.z);
-  grid = dim3((unsigned)(((total + 7) / 8) * 8), 1, 1);
-  constexpr int lds = GEO::LDS;
   static DeviceOnce attr_once;
-  if (int r = once_per_device(attr_once, [&]() { return (int)hipFuncSetAttribute((const void*)igemm_pp_kernel<BM, BN, MI0, NI0, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); })) return r;
-  (void)zero_page;      // the ping-pong kernel's out-of-range lanes read zeros through the buffer descriptor's bounds check (igemm_pp.inc)
-  igemm_pp_kernel<BM, BN, MI0, NI0, ABL><<<grid, GEO::NT, lds, st>>>(p);
+  if (int r = dma_launch_prep(p, grid, attr_once, (const void*)igemm_pp_kernel<BM, BN, MI0, NI0, ABL>, GEO::LDS)) return r;
+  igemm_pp_kernel<BM, BN, MI0, NI0, ABL><<<grid, GEO::NT, GEO::LDS, st>>>(p);
   return 0;
 }
 
@@ -389,7 +382,6 @@ void gemm_defaults(GemmP& p) {
 
 static constexpr size_t lds_bytes(int BM, int BN) { return (size_t)(2 * BM + 2 * BN) * LDS_LD * sizeof(half_t); }
 
-static half_t* g_zero_page = nullptr;
 static constexpr size_t ZERO_PAGE_BYTES = 128 << 10;   // >= 2 * (longest K + one chunk): out-of-range rows walk it like real rows
 static int g_wide = 1;      // PNPI_IGEMM_WIDE=0: never pick the 128x320 / 128x256 tiles (ablation)
 static int g_use_dma = 1;      // 0: register-staged v1 kernel everywhere
@@ -447,22 +439,92 @@ int igemm_init() {
   return 0;
 }
 
-// Tile configurations of the LDS-DMA kernel (cfg ids of launch_igemm's force_cfg / tools): 0 = 128x128, 1 = 64x64 (2 = the same
-// with split-K forced), 3 = 256x128 (ablation), 4 = 128x320, 5 = 128x256.
-struct TileCfg { int id, bm, bn; double rate, t_fix; int bpc; };   // rate: FLOP/s of the whole chip with every CU full; t_fix: per-tile
-static const TileCfg kTiles[] = {                                  // prologue + epilogue seconds; bpc: co-resident blocks per CU
-  {0, 128, 128, 868e12, 1.22e-6, 3},
-  {1, 64, 64, 572e12, 0.25e-6, 4},
-  {4, 128, 320, 1228e12, 5.15e-6, 2},
-  {5, 128, 256, 1178e12, 3.61e-6, 2},
+// product tile configurations with one k-group: compiler-scheduled main loop, or (tuning "igemm_sched", in a `build --ablations` library:
+// tools/pp_ablate.py, tools/profile_pp.sh) the hand-scheduled ones
+#ifdef PNPI_ABLATIONS
+static constexpr bool kAblations = true;
+#else
+static constexpr bool kAblations = false;
+#endif
+template <int BM, int BN, int BKT, int NST>
+static int launch_dma_s(GemmP p, dim3 grid, hipStream_t st) {
+#ifdef PNPI_ABLATIONS
+  if (g_sched == 1) return launch_dma<BM, BN, BKT, NST, 2, 4>(p, grid, st);
+  if (g_sched == 2) return launch_dma<BM, BN, BKT, NST, 2, 5>(p, grid, st);
+#endif
+  return launch_dma<BM, BN, BKT, NST>(p, grid, st);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Tile descriptors: one row per tile id (launch_igemm's force_cfg, the tools' CFG / NAME maps, csrc/tile_table.inc).  Everything the
+// launcher needs to know about a tile is a field here: a new tile is a row of this table (plus a case in igemm_dispatch if it has variants).
+// Id 2 is no tile: it is the caller's alias for "id 1 with split-K chosen by the launcher".
+//   fam       FAM_V1: 4-wave LDS-DMA kernel that also exists as the register-staged v1 kernel (shapes the DMA kernels cannot take);
+//             FAM_DMA: 4-wave LDS-DMA kernel only (WGM x 2 waves per k-group); FAM_PP: the 8-wave ping-pong kernel (igemm_pp.inc)
+//   kgroups   K-parallel wave groups (intra-block split-K for launches with at most one tile per CU)
+//   wide      left out by tuning "igemm_wide" = 0 (table entries and the cost model)
+//   cls       kernel class reported through cfg_used when the launch has no split-K (0 igemm128, 1 igemm64, 9 igemm_wide; split-K: 2)
+//   stat_rows rows per GroupNorm statistics partial: the ping-pong kernel writes them per 64-row sub-block, the others per tile
+//   alt       ping-pong tiles: the id of the other row height of the same BN (pp_rowtile_pick); -1 otherwise
+//   splits    takes split-K;  stats: takes a launch that produces statistics (the 192 x 256 tile cannot reproduce the 256 x 256 tile's
+//             statistics tree: 16 row groups over 3 sub-blocks)
+//   launch    the tile's kernel instance; nullptr: it has several, igemm_dispatch picks by the plan's variant
+// ------------------------------------------------------------------------------------------------------------------
+enum TileFam { FAM_V1, FAM_DMA, FAM_PP };
+struct TileDesc { int id, bm, bn; TileFam fam; int kgroups; bool wide; int cls, stat_rows, alt; bool splits, stats; int (*launch)(GemmP, dim3, hipStream_t); };
+static constexpr TileDesc kTileDesc[] = {
+  // id, bm, bn, fam, kgroups, wide, cls, stat_rows, alt, splits, stats, launch
+  {0, 128, 128, FAM_V1, 1, false, 0, 128, -1, true, true, nullptr},     // 64-byte rows x 3 stages; deeper rings on sparse launches (igemm_v128)
+  {1, 64, 64, FAM_V1, 1, false, 1, 64, -1, true, true, nullptr},        // (igemm_v64)
+  {3, 256, 128, FAM_DMA, 1, false, 0, 256, -1, false, true, nullptr},   // ablation: too few tiles at these sizes
+  {4, 128, 320, FAM_DMA, 1, true, 9, 128, -1, true, true, nullptr},     // (igemm_v320)
+  {5, 128, 256, FAM_DMA, 1, true, 9, 128, -1, true, true, nullptr},     // (igemm_v256n)
+  {6, 256, 320, FAM_DMA, 1, true, 9, 256, -1, true, true, launch_dma<256, 320, 64, 2, 4>},     // 6 / 7: 8 waves, 128-byte rows, two stages, one block per CU
+  {7, 256, 256, FAM_DMA, 1, true, 9, 256, -1, true, true, launch_dma<256, 256, 64, 2, 4>},
+  {8, 64, 64, FAM_DMA, 4, true, 1, 64, -1, true, true, launch_dma<64, 64, 64, 2, 2, 0, 4>},        // 16 waves: 4 k-groups
+  {9, 128, 128, FAM_DMA, 2, true, 0, 128, -1, true, true, launch_dma<128, 128, 32, 3, 2, 0, 2>},     // 8 waves: 2 k-groups, 96 KB
+  {10, 128, 128, FAM_DMA, 2, true, 0, 128, -1, true, true, launch_dma<128, 128, 64, 2, 2, 0, 2>},    // 8 waves: 2 k-groups, 128-byte rows, 128 KB
+  {11, 64, 64, FAM_DMA, 2, true, 1, 64, -1, true, true, launch_dma<64, 64, 64, 2, 2, 0, 2>},       // 8 waves: 2 k-groups, 64 KB (2 blocks / CU)
+  {12, 64, 320, FAM_DMA, 1, true, 9, 64, -1, true, true, launch_dma<64, 320, 32, 2>},      // 768 tiles on the 12-row 64 x 64 level = 3 per CU
+  {13, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, launch_dma_s<128, 128, 32, 2>},   // 32 KB two-stage ring (two-pass epilogue): 4 blocks / CU for the short-K layers
+  {14, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, launch_dma_s<128, 128, 64, 2>},   // 128-byte rows, half the barriers per k: 64 KB, 2 blocks / CU
+  {15, 128, 256, FAM_DMA, 1, true, 9, 128, -1, true, true, launch_dma<128, 256, 64, 2>},    // the same for the 128 x 256 tile: 96 KB, 1 block / CU
+  {16, 256, 256, FAM_PP, 1, true, 9, 64, 20, true, true, nullptr},
+  {17, 192, 320, FAM_PP, 1, true, 9, 64, 19, true, true, nullptr},
+  {18, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, launch_dma<128, 128, 64, 3>},   // 128-byte rows, three stages (96 KB, 1 block / CU): the one-wave launches of the 16 x 16 level
+  {19, 128, 320, FAM_PP, 1, true, 9, 64, 17, true, true, launch_pp<128, 320, 1, 4>},      // 19 / 20: the shorter ping-pong tiles: force_cfg or pp_rowtile_pick, never the table
+  {20, 192, 256, FAM_PP, 1, true, 9, 64, 16, true, false, launch_pp<192, 256, 1, 4>},
+};
+static constexpr const TileDesc* tile_desc(int id) {      // nullptr: no such tile (id 2 included)
+  return (id < 0 || id == 2 || id > 20) ? nullptr : &kTileDesc[id < 2 ? id : id - 1];
+}
+// the one-k-group tile of the same shape class that every launch can fall back to (it also exists as a v1 kernel)
+static const TileDesc* plain_twin(const TileDesc* d) { return tile_desc(d->bm == 64 && d->bn == 64 ? 1 : 0); }
+
+// Cost-model constants of the tiles the model chooses among.  rate: FLOP/s of the whole chip with every CU full; t_fix: per-tile
+// prologue + epilogue seconds; bpc: co-resident blocks per CU
+struct TileCost { int id; double rate, t_fix; int bpc; };
+static const TileCost kTiles[] = {
+  {0, 868e12, 1.22e-6, 3},
+  {1, 572e12, 0.25e-6, 4},
+  {4, 1228e12, 5.15e-6, 2},
+  {5, 1178e12, 3.61e-6, 2},
 };
 // Measured choices for the SD-1.x layer shapes at the row counts of the benchmarked schedule (1-row inversion, 12-row lock step):
 // per-shape best of every tile / split-K / k-group configuration (tools/autotune2.py -> tools/gen_tile_table.py).  The cost model
 // below covers every other shape (other row counts, other model widths).
 struct TileEntry { int M, N, K, ks, cfg, split; };
-static const TileEntry kTileTable[] = {
+static constexpr TileEntry kTileTable[] = {
 #include "tile_table.inc"
 };
+static constexpr bool tile_tables_consistent() {      // every id finds its own row; every table entry names a tile
+  for (const TileDesc& d : kTileDesc)
+    if (tile_desc(d.id) != &d) return false;
+  for (const TileEntry& e : kTileTable)
+    if (!tile_desc(e.cfg)) return false;
+  return sizeof(kTileDesc) / sizeof(kTileDesc[0]) == 20;
+}
+static_assert(tile_tables_consistent(), "kTileDesc rows out of place, or tile_table.inc names an id without a row");
 // Table lookup: the exact {M, N, K, ksize}; else -- the same layer (N, K, ksize) at another row count, e.g. --batch_size 2 ... 7 of the
 // sweep driver -- the entry whose M is nearest in ratio, up to 4x away.  Held out of the table one row count at a time, the nearest
 // entry's configuration costs 13.3 / 10.1 / 6.7 / 5.2 ms per 12- / 8- / 4- / 3-row forward against 15.3 / 10.4 / 6.9 / 6.1 ms for the
@@ -486,9 +548,6 @@ int igemm_table_lookup(int M, int N, int K, int ks, int* cfg, int* split, int* e
   if (e) { if (cfg) *cfg = e->cfg; if (split) *split = e->split; if (entry_m) *entry_m = e->M; }
   return how;
 }
-// cfg 6 = 256x320, 7 = 256x256 (8 waves, 128-byte rows, two stages, one block per CU); 8-11: K-parallel wave groups; 12 = 64x320;
-// 13 = 128x128 with a two-stage ring; 14 / 15 = 128x128 / 128x256 with 128-byte rows; 18 = 128x128, 128-byte rows, three stages:
-// reached through the table or force_cfg.  19 / 20 = the shorter ping-pong tiles 128x320 / 192x256: force_cfg or pp_rowtile_pick, never the table
 
 // Row height of a ping-pong launch (tuning "pp_rowtile").  Tile and split-K are chosen first, as ever (table entry at sel_M); this
 // only swaps the tile for the other row height of the same BN (17 <-> 19: 192 / 128 x 320; 16 <-> 20: 256 / 192 x 256), which changes no
@@ -498,77 +557,87 @@ int igemm_table_lookup(int M, int N, int K, int ks, int* cfg, int* split, int* e
 // of the chip -> 256); (2048, 1280) x 4 becomes 192 x 256 (160 -> 220 workgroups).  Not "the smaller rounds x bm": a round of the
 // 128-row tile was measured at 0.91 of a 192-row round, not 0.67 (the weight panel's bytes and the prologue / epilogue do not shrink
 // with BM), so four rounds of 128 lose to three of 192 -- (8192, 5120): 688 workgroups 77.7 us against 1024 workgroups 83.6 us
-// (profiles/pp_rowtile_ab.json).  Returns the cfg id to launch.
-static int pp_rowtile_pick(int cfg, int M, int N, int split) {
-  const bool f320 = cfg == 17 || cfg == 19;
-  const int bn = f320 ? 320 : 256, bm_tall = f320 ? 192 : 256, bm_short = f320 ? 128 : 192;
-  auto rounds = [&](int bm) { const long w = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * (split > 1 ? split : 1); return (w + 255) / 256; };
-  const bool tall = rounds(bm_short) > rounds(bm_tall);
-  return f320 ? (tall ? 17 : 19) : (tall ? 16 : 20);
+// (profiles/pp_rowtile_ab.json).  Returns the tile to launch.
+static bool pp_is_tall(const TileDesc* d) { return d->bm > tile_desc(d->alt)->bm; }
+static const TileDesc* pp_rowtile_pick(const TileDesc* d, int M, int N, int split) {
+  const TileDesc* tall = pp_is_tall(d) ? d : tile_desc(d->alt);
+  const TileDesc* shrt = tile_desc(tall->alt);
+  auto rounds = [&](int bm) { const long w = (long)((M + bm - 1) / bm) * ((N + tall->bn - 1) / tall->bn) * (split > 1 ? split : 1); return (w + 255) / 256; };
+  return rounds(shrt->bm) > rounds(tall->bm) ? tall : shrt;
 }
 // host-only query (tests): rows of the tile pp_rowtile_pick launches for a ping-pong configuration; 0: cfg is no ping-pong tile
 int igemm_pp_rowtile_query(int cfg, int M, int N, int split) {
-  if (cfg < 16 || cfg == 18 || cfg > 20 || M <= 0 || N <= 0) return 0;
-  const int c = pp_rowtile_pick(cfg, M, N, split);
-  return c == 16 ? 256 : (c == 19 ? 128 : 192);
+  const TileDesc* d = tile_desc(cfg);
+  if (!d || d->fam != FAM_PP || M <= 0 || N <= 0) return 0;
+  return pp_rowtile_pick(d, M, N, split)->bm;
 }
 
-// product tile configurations with one k-group: compiler-scheduled main loop, or (tuning "igemm_sched") the hand-scheduled one
-#ifdef PNPI_ABLATIONS
-#define LDMA(...) (g_sched == 1 ? launch_dma<__VA_ARGS__, 2, 4>(p, grid, st, g_zero_page) : g_sched == 2 ? launch_dma<__VA_ARGS__, 2, 5>(p, grid, st, g_zero_page) : launch_dma<__VA_ARGS__>(p, grid, st, g_zero_page))
-#else
-#define LDMA(...) launch_dma<__VA_ARGS__>(p, grid, st, g_zero_page)
-#endif
-#define LDMA0(...) launch_dma<__VA_ARGS__>(p, grid, st, g_zero_page)
-// Can the 8-wave ping-pong kernel (cfg 16 = 256 x 256, 17 = 192 x 320, 19 = 128 x 320, 20 = 192 x 256) take this launch?  It has no scalar epilogue: a launch either takes
-// the LDS epilogue (whole tiles plain or transposed, 16-byte rows, 16-byte aligned bias) or writes split-K slabs; its DMA addresses are
-// 32-bit byte offsets under a 2 GiB buffer descriptor (operands beyond that stay on the 64-bit-pointer kernels); batched launches stay
-// on the 4-wave kernels.  The 192 x 256 tile cannot reproduce the 256 x 256 tile's statistics tree (16 row groups over 3 sub-blocks):
-// it takes no launch that produces GroupNorm statistics.
-static bool pp_eligible(const GemmP& p, int cfg, int split, bool dma_ok) {
-  const int bn_pp = (cfg == 17 || cfg == 19) ? 320 : 256;
-  if (cfg == 20 && p.stats && split == 1) return false;
-  const bool vt_none_ = p.vt_col0 >= p.N;
-  const bool vt_lds_ = !vt_none_ && p.outT && !p.vt_f32 && p.vt_col0 % bn_pp == 0 && p.rows_per_batch % 8 == 0 && p.vt_ld % 8 == 0 && p.M % 8 == 0 && !p.res &&
-                       !p.geglu && g_vt_lds;
-  const bool epi_ok = (vt_none_ || vt_lds_) && (p.N % 8 == 0) && (p.vt_col0 == 0 || p.ldo % 8 == 0) && (!p.res || p.ldres % 8 == 0) &&
-                      (!p.bias || ((uintptr_t)p.bias & 15) == 0) && (!p.vt_perm16 || p.rows_per_batch % 16 == 0);
+// Which epilogue a launch on tiles BN wide takes.  vt_lds: the transposed (V^T) columns go through the LDS epilogue too -- whole tiles
+// are either plain or transposed and 8-token runs stay inside one batch item.  epi_lds: the coalesced LDS-staged epilogue with 16-byte
+// row stores applies (never under split-K: the kernel writes slabs).  pp_ok: the ping-pong kernel, which has no scalar epilogue, can
+// take the launch: slabs, or the LDS epilogue with a 16-byte aligned bias and whole 16-token groups under vt_perm16.
+struct EpiSel { bool vt_none, vt_lds, epi_lds, pp_ok; };
+static EpiSel epi_select(const GemmP& p, int bn, int split, bool dma_ok) {
+  EpiSel e;
+  e.vt_none = p.vt_col0 >= p.N;
+  e.vt_lds = !e.vt_none && dma_ok && p.outT && !p.vt_f32 && p.vt_col0 % bn == 0 && p.rows_per_batch % 8 == 0 && p.vt_ld % 8 == 0 &&
+             p.M % 8 == 0 && !p.res && !p.geglu && g_vt_lds;
+  const bool rows16 = (e.vt_none || e.vt_lds) && (p.N % 8 == 0) && (p.vt_col0 == 0 || p.ldo % 8 == 0) && (!p.res || p.ldres % 8 == 0);
+  e.epi_lds = rows16 && split == 1;
+  e.pp_ok = split > 1 || (rows16 && (!p.bias || ((uintptr_t)p.bias & 15) == 0) && (!p.vt_perm16 || p.rows_per_batch % 16 == 0));
+  return e;
+}
+// Can the ping-pong tile d take this launch?  Beyond its epilogue (epi_select): its DMA addresses are 32-bit byte offsets under a 2 GiB
+// buffer descriptor (operands beyond that stay on the 64-bit-pointer kernels); its split-K slabs are written four columns at a time;
+// batched launches stay on the 4-wave kernels; d->stats.
+static bool pp_eligible(const GemmP& p, const TileDesc* d, int split, bool dma_ok) {
+  if (!d->stats && p.stats && split == 1) return false;
   const double lim = 2147483648.0 - 1048576.0;
   const bool off32_ok = 2.0 * p.B * p.H * p.W * (double)(p.ldx1 > p.ldx2 ? p.ldx1 : p.ldx2) < lim && 2.0 * (double)p.N * p.ldw < lim;
-  return dma_ok && off32_ok && !(split == 1 && !epi_ok) && !(split > 1 && p.N % 4 != 0) && p.nbatch <= 1;
+  return dma_ok && off32_ok && epi_select(p, d->bn, split, dma_ok).pp_ok && !(split > 1 && p.N % 4 != 0) && p.nbatch <= 1;
 }
 
-int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_cfg, int force_split, int* cfg_used,
-                 int* stats_tile_rows, int sel_M) {
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return -2;
+// Selection as a pure function of the launch description and the tuning globals: no HIP call, no g_last_* state, no operand is
+// dereferenced (pointers are looked at for null / alignment only).  Order of decisions: forced tile (caller's force_cfg, else tuning
+// "igemm_force_cfg") | measured table at sel_M | cost model; then the fall-backs -- batched launches lose split-K and k-groups, shapes
+// the DMA kernels cannot take go to the v1 tiles, split-K is clamped to the workspace, a ping-pong tile the launch is not eligible for
+// becomes 128 x 128 -- then the ping-pong row height on the launched M, the epilogue, the grid and the ring depth.
+IgemmPlan igemm_plan(GemmP p, bool have_ws, size_t ws_bytes, int force_cfg, int force_split, int sel_M) {
+  IgemmPlan pl = {};
+  pl.id = -1; pl.split = 1; pl.stats_tile_rows = -1;
+  auto fail = [&](int err) { pl.err = err; return pl; };
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return fail(-2);
   const int Cin = p.C1 + p.C2;
-  if ((Cin & 7) || (p.K & 7) || (p.C1 & 7) || (p.ldw & 7) || (p.ldx1 & 7) || (p.C2 && (p.ldx2 & 7))) return -3;
-  if (p.K != p.ksize * p.ksize * Cin) return -4;
+  if ((Cin & 7) || (p.K & 7) || (p.C1 & 7) || (p.ldw & 7) || (p.ldx1 & 7) || (p.C2 && (p.ldx2 & 7))) return fail(-3);
+  if (p.K != p.ksize * p.ksize * Cin) return fail(-4);
   if (p.vt_col0 > p.N) p.vt_col0 = p.N;
+  pl.vt_col0 = p.vt_col0;
   const bool fast = (Cin % BK == 0) && (p.C1 % BK == 0);
   const int nchunks = (p.K + BK - 1) / BK;
   const bool dma_ok = fast && g_use_dma && (p.K % BK == 0) && (p.ldw % 8 == 0) && ((size_t)p.K * 2 + 1024 <= ZERO_PAGE_BYTES);
+  pl.fastk = fast; pl.dma = dma_ok;
   // sel_M > 0: tile, split-K and ring depth are chosen as for a launch of sel_M rows (the same layer at another row count: the
   // deduplicated UNet prefix pinned to its full-row configuration); the launch itself covers p.M rows
   const int selM = sel_M > 0 ? sel_M : p.M;
   auto tiles_of = [&](int bm, int bn) { return (long)((selM + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  const long t64 = tiles_of(64, 64);
+  auto slabs_fit = [&](int s) { return have_ws && (size_t)s * selM * p.N * sizeof(float) <= ws_bytes; };
   int cfg = force_cfg;
   int split = 1;
   if (cfg < 0 && g_force_cfg >= 0) { cfg = g_force_cfg == 2 ? 1 : g_force_cfg; if (force_split <= 0) force_split = g_force_split; }
   const bool cfg_forced = cfg >= 0;      // a caller's force_cfg or tuning "igemm_force_cfg" names its tile and keeps it
+  if (cfg_forced && cfg != 2 && !tile_desc(cfg)) return fail(-2);
   if (cfg < 0 && g_use_table && dma_ok) {
-    if (const TileEntry* pe = tile_table_lookup(selM, p.N, p.K, p.ksize, nullptr)) {
-        const TileEntry& e = *pe;
-        const int ebn = (e.cfg == 4 || e.cfg == 6 || e.cfg == 12 || e.cfg == 17) ? 320 : ((e.cfg == 5 || e.cfg == 7 || e.cfg == 15 || e.cfg == 16) ? 256 : ((e.cfg == 1 || e.cfg == 8 || e.cfg == 11) ? 64 : 128));
-        const bool split_ok = e.split == 1 || (!p.geglu && ws && (size_t)e.split * selM * p.N * sizeof(float) <= ws_bytes);
-        const bool vt_ok = p.vt_col0 >= p.N || p.vt_col0 % ebn == 0;
-        const bool pp_masked = (e.cfg == 16 || e.cfg == 17) && ((g_pp_only_n > 0 && p.N != g_pp_only_n) || (g_pp_only_k > 0 && p.K != g_pp_only_k) || (g_pp_only_m > 0 && selM != g_pp_only_m) ||
-                                                                 g_pp_only_n < 0);
-        // a ping-pong entry (tile and split tuned together) applies only to a launch that kernel can take: otherwise the cost model
-        // picks tile AND split for the 4-wave kernels (not the entry's split on a 128 x 128 tile)
-        const bool pp_ok = !(e.cfg == 16 || e.cfg == 17) || pp_eligible(p, e.cfg, e.split, dma_ok);
-        if (split_ok && vt_ok && !pp_masked && pp_ok && (g_wide || e.cfg < 4 || e.cfg == 13 || e.cfg == 14 || e.cfg == 18)) { cfg = e.cfg; split = e.split; }
+    if (const TileEntry* e = tile_table_lookup(selM, p.N, p.K, p.ksize, nullptr)) {
+      const TileDesc* ed = tile_desc(e->cfg);
+      const bool pp = ed->fam == FAM_PP;
+      const bool split_ok = e->split == 1 || (!p.geglu && slabs_fit(e->split));
+      const bool vt_ok = p.vt_col0 >= p.N || p.vt_col0 % ed->bn == 0;
+      const bool pp_masked = pp && ((g_pp_only_n > 0 && p.N != g_pp_only_n) || (g_pp_only_k > 0 && p.K != g_pp_only_k) ||
+                                    (g_pp_only_m > 0 && selM != g_pp_only_m) || g_pp_only_n < 0);
+      // a ping-pong entry (tile and split tuned together) applies only to a launch that kernel can take: otherwise the cost model
+      // picks tile AND split for the 4-wave kernels (not the entry's split on a 128 x 128 tile)
+      const bool pp_ok = !pp || pp_eligible(p, ed, e->split, dma_ok);
+      if (split_ok && vt_ok && !pp_masked && pp_ok && (g_wide || !ed->wide)) { cfg = e->cfg; split = e->split; }
     }
   }
   if (cfg < 0) {
@@ -579,15 +648,16 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
     // low-resolution layers to put work on all 256 CUs.
     double best = 1e30;
     static const int splits[] = {1, 2, 3, 4, 6, 8, 12, 16};
-    for (const TileCfg& tc : kTiles) {
-      if (tc.id >= 4 && !(dma_ok && g_wide)) continue;     // the wide tiles exist only as LDS-DMA kernels
-      const long tiles = tiles_of(tc.bm, tc.bn);
+    for (const TileCost& tc : kTiles) {
+      const TileDesc* td = tile_desc(tc.id);
+      if (td->wide && !(dma_ok && g_wide)) continue;     // the wide tiles exist only as LDS-DMA kernels
+      const long tiles = tiles_of(td->bm, td->bn);
       for (int s : splits) {
-        if (s > 1 && (nchunks / s < 4 || (size_t)s * selM * p.N * sizeof(float) > ws_bytes || ws == nullptr)) continue;
+        if (s > 1 && (nchunks / s < 4 || !slabs_fit(s))) continue;
         if (s > 1 && p.geglu) continue;
         // constants: tools/fit_cost_model2.py on tools/autotune2.py timings of every configuration per layer shape (rms log error
         // 0.10; the picks cost 1 % more than the per-shape best over a 12-row forward)
-        const double unit = tc.t_fix + (double)((nchunks + s - 1) / s) * (2.0 * tc.bm * tc.bn * BK) / (tc.rate / 256.0);   // padded tiles do real work
+        const double unit = tc.t_fix + (double)((nchunks + s - 1) / s) * (2.0 * td->bm * td->bn * BK) / (tc.rate / 256.0);   // padded tiles do real work
         const long units = tiles * s;
         const long on_busiest = (units + 255) / 256;
         const double per_cu = (double)units / 256.0;
@@ -596,11 +666,12 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
         const double resid = 0.82 + 0.18 * fill;
         double t = (double)on_busiest * unit / resid;
         if (s > 1) t += (double)(2 * s + 1) * selM * p.N * 4.0 / 8.14e12 + 4.97e-6;   // slabs written, re-read, output + the reduce launch
-        if (p.vt_col0 < p.N && p.vt_col0 % tc.bn != 0) t *= 1.3;   // transposed columns not tile-aligned: scalar epilogue
+        if (p.vt_col0 < p.N && p.vt_col0 % td->bn != 0) t *= 1.3;   // transposed columns not tile-aligned: scalar epilogue
         if (t < best) { best = t; cfg = tc.id; split = s; }
       }
     }
   } else if (cfg == 2) {
+    const long t64 = tiles_of(64, 64);
     cfg = 1;
     split = force_split > 0 ? force_split : (int)((512 + t64 - 1) / t64);
     if (split > 16) split = 16;
@@ -609,158 +680,145 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
   } else if (force_split > 1) {
     split = force_split;
   }
-  if (p.nbatch > 1) { split = 1; if (cfg >= 8 && cfg <= 11) cfg = (cfg == 8 || cfg == 11) ? 1 : 0; }   // no split-K / k-groups across problems
-  if (cfg >= 8 && !dma_ok) cfg = (cfg == 8 || cfg == 11) ? 1 : 0;
-  if (cfg >= 3 && !dma_ok) cfg = 0;                                 // 256x128 / 128x320 / 128x256 exist only as LDS-DMA kernels
+  const TileDesc* d = tile_desc(cfg);
+  if (p.nbatch > 1) { split = 1; if (d->kgroups > 1) d = plain_twin(d); }   // no split-K / k-groups across problems
+  if (!dma_ok && d->fam != FAM_V1) d = plain_twin(d);                      // every other tile exists only as an LDS-DMA kernel
   // whatever chose the split (cost model or a caller-forced value): the slabs must fit the workspace and each split needs work
   if (split > 1) {
     if (split > nchunks) split = nchunks;
-    if (ws == nullptr || (size_t)split * selM * p.N * sizeof(float) > ws_bytes || p.geglu || cfg == 3) split = 1;
+    if (!slabs_fit(split) || p.geglu || !d->splits) split = 1;
   }
-  if ((cfg == 16 || cfg == 17 || cfg == 19 || cfg == 20) && !pp_eligible(p, cfg, split, dma_ok)) cfg = 0;     // forced configurations (tests, sweeps): the 128 x 128 kernel instead
+  if (d->fam == FAM_PP && !pp_eligible(p, d, split, dma_ok)) d = tile_desc(0);     // forced configurations (tests, sweeps): the 128 x 128 kernel instead
   // the row height follows the launched M
-  if ((cfg == 16 || cfg == 17) && g_pp_rowtile && !cfg_forced && !g_varpp) {      // the ablation instances (igemm_vpp) exist for 16 / 17 only
-    const int c2 = pp_rowtile_pick(cfg, p.M, p.N, split);
-    if (c2 != cfg && pp_eligible(p, c2, split, dma_ok)) cfg = c2;
+  if (d->fam == FAM_PP && g_pp_rowtile && !cfg_forced && !g_varpp) {      // forced tiles keep theirs; the ablation instances (igemm_vpp) exist for the tall tiles only
+    const TileDesc* o = pp_rowtile_pick(d, p.M, p.N, split);
+    if (o != d && pp_eligible(p, o, split, dma_ok)) d = o;
   }
-  const bool c64 = cfg == 1 || cfg == 8 || cfg == 11 || cfg == 12, c256m = cfg == 3 || cfg == 6 || cfg == 7 || cfg == 16;
-  const bool cpp = cfg == 16 || cfg == 17 || cfg == 19 || cfg == 20;      // the 8-wave ping-pong kernel: 16 = 256 x 256, 17 = 192 x 320, 19 = 128 x 320, 20 = 192 x 256
-  if (cfg_used) *cfg_used = split > 1 ? 2 : (((cfg >= 4 && cfg <= 7) || cfg == 12 || (cfg >= 15 && cfg <= 17) || cfg == 19 || cfg == 20) ? 9 : (c64 ? 1 : 0));
-  p.splitk = split;
-  p.kchunks_per_split = (nchunks + split - 1) / split;
-  g_last_cfg = cfg; g_last_split = split;
-  for (int i = 0; i < 7; ++i) g_last_geom[i] = 0;
-  const int bn_sel = (cfg == 4 || cfg == 6 || cfg == 12 || cfg == 17 || cfg == 19) ? 320 : ((cfg == 5 || cfg == 7 || cfg == 15 || cfg == 16 || cfg == 20) ? 256 : (c64 ? 64 : 128));
-  const bool vt_none = p.vt_col0 >= p.N;
-  // transposed (V^T) columns through the LDS epilogue too, when whole tiles are either plain or transposed and 8-token runs stay
-  // inside one batch item
-  const bool vt_lds = !vt_none && dma_ok && p.outT && !p.vt_f32 && p.vt_col0 % bn_sel == 0 && p.rows_per_batch % 8 == 0 && p.vt_ld % 8 == 0 &&
-                      p.M % 8 == 0 && !p.res && !p.geglu && g_vt_lds;
-  p.epi_lds = (vt_none || vt_lds) && (p.N % 8 == 0) && (p.vt_col0 == 0 || p.ldo % 8 == 0) && (!p.res || p.ldres % 8 == 0) && split == 1;
-  if (vt_lds) p.stats = nullptr;
-  p.res_late = g_res_late;
-  p.bias_init = (dma_ok && split == 1 && p.bias && p.alpha == 1.f && p.N % 4 == 0 && ((uintptr_t)p.bias & 15) == 0 && g_bias_init && !cpp) ? 1 : 0;
-  if (p.vt_perm16 && (p.rows_per_batch % 16 != 0 || p.vt_f32)) return -9;   // permuted V^T: whole 16-token groups, fp16
-  if (p.geglu && !(p.epi_lds && dma_ok && p.N % 64 == 0)) return -7;   // GEGLU exists only in the LDS epilogue
-  if (!(p.epi_lds && dma_ok && !p.geglu)) p.stats = nullptr;       // statistics come only from the DMA kernel's LDS epilogue
-  const int bm = (cfg == 17 || cfg == 20) ? 192 : (c256m ? 256 : (c64 ? 64 : 128));
-  const int bn = bn_sel;
-  if (stats_tile_rows) *stats_tile_rows = p.stats ? (cpp ? 64 : bm) : 0;     // the ping-pong kernel writes its partials per 64-row sub-block
-  p.slab = ws;
-  if (p.nbatch > 1) {
-    if (split != 1 || p.bias || p.res || p.stats || p.geglu || p.x2) return -8;     // batched launches: plain products only
-  }
-  dim3 grid((p.M + bm - 1) / bm, (p.N + bn - 1) / bn, p.nbatch > 1 ? p.nbatch : split);
-  int r = 0;
+  const bool cpp = d->fam == FAM_PP;
+  pl.id = d->id; pl.split = split; pl.bm = d->bm; pl.bn = d->bn;
+  pl.cls = split > 1 ? 2 : d->cls;
+  pl.kchunks_per_split = (nchunks + split - 1) / split;
+  const EpiSel epi = epi_select(p, d->bn, split, dma_ok);
+  pl.epi_lds = epi.epi_lds;
+  pl.res_late = g_res_late;
+  pl.bias_init = (dma_ok && split == 1 && p.bias && p.alpha == 1.f && p.N % 4 == 0 && ((uintptr_t)p.bias & 15) == 0 && g_bias_init && !cpp) ? 1 : 0;
+  pl.k_order = cpp ? ((g_tapin && p.ksize == 3) ? 1 : 0) : p.k_order;
+  if (p.vt_perm16 && (p.rows_per_batch % 16 != 0 || p.vt_f32)) return fail(-9);   // permuted V^T: whole 16-token groups, fp16
+  if (p.geglu && !(pl.epi_lds && dma_ok && p.N % 64 == 0)) return fail(-7);   // GEGLU exists only in the LDS epilogue
+  // statistics come only from the DMA kernels' LDS epilogue, and not from a launch whose V^T columns take it
+  pl.stats = p.stats && !epi.vt_lds && pl.epi_lds && dma_ok && !p.geglu;
+  pl.stats_tile_rows = pl.stats ? d->stat_rows : 0;
+  if (p.nbatch > 1 && (split != 1 || p.bias || p.res || pl.stats || p.geglu || p.x2)) return fail(-8);     // batched launches: plain products only
+  pl.gx = (p.M + d->bm - 1) / d->bm; pl.gy = (p.N + d->bn - 1) / d->bn; pl.gz = p.nbatch > 1 ? p.nbatch : split;
   // Ring depth by occupancy: with at most one block per CU nothing else covers the HBM latency of the weight stream (cold in a
   // forward: 1.7 GB of weights pass through per UNet call), and the whole 160 KB of LDS is free -- so sparse launches take an
   // 8-deep ring (7 chunks in flight per block); two blocks per CU a 4-deep one; fuller launches the shallow rings that fit 3 blocks.
-  const long units = (long)((selM + bm - 1) / bm) * grid.y * grid.z;
-  const int sparse = !g_deep_rings ? 0 : (units <= 256 ? 2 : (units <= 512 ? 1 : 0));
-  if (!dma_ok) {
-    if (cfg == 1) {
-      if (fast) igemm_kernel<64, 64, true><<<grid, 256, lds_bytes(64, 64), st>>>(p);
-      else igemm_kernel<64, 64, false><<<grid, 256, lds_bytes(64, 64), st>>>(p);
-    } else {
-      if (fast) igemm_kernel<128, 128, true><<<grid, 256, lds_bytes(128, 128), st>>>(p);
-      else igemm_kernel<128, 128, false><<<grid, 256, lds_bytes(128, 128), st>>>(p);
-    }
-  } else if (cfg == 3) {
-    r = g_var256 == 1 ? launch_dma<256, 128, 32, 2, 2>(p, grid, st, g_zero_page) : launch_dma<256, 128, 32, 3, 2>(p, grid, st, g_zero_page);
-  } else if (cfg == 4) {
-    if (sparse == 2 && g_var320 == 1) r = LDMA0(128, 320, 32, 5);
-    else switch (g_var320) {
-      case 0: r = LDMA0(128, 320, 32, 3); break;       // 84 KB ring = whole-tile epilogue, 1 block / CU
-      case 2: r = LDMA0(128, 320, 64, 2); break;       // 128-byte rows, 112 KB, 1 block / CU
-#ifdef PNPI_ABLATIONS
-      case 11: r = launch_dma<128, 320, 32, 2, 2, 1>(p, grid, st, g_zero_page); break;   // ablation: DMA only
-      case 12: r = launch_dma<128, 320, 32, 2, 2, 2>(p, grid, st, g_zero_page); break;   // ablation: compute only
-#endif
-      default: r = LDMA(128, 320, 32, 2); break;      // 56 KB ring, two-pass epilogue, 2 blocks / CU
-    }
-  } else if (cfg == 12) {
-    r = LDMA0(64, 320, 32, 2);             // 64 x 320: 768 tiles on the 12-row 64 x 64 level = 3 per CU
-  } else if (cfg == 13) {
-    r = LDMA(128, 128, 32, 2);            // 32 KB ring (two-pass epilogue): 4 blocks / CU for the short-K layers
-  } else if (cfg == 18) {
-    r = LDMA0(128, 128, 64, 3);           // 128-byte rows, three stages (96 KB, 1 block / CU): the one-wave launches of the 16 x 16 level
-  } else if (cfg == 14) {
-    r = LDMA(128, 128, 64, 2);            // 128-byte rows, half the barriers per k: 64 KB, 2 blocks / CU
-  } else if (cfg == 15) {
-    r = LDMA0(128, 256, 64, 2);            // the same for the 128 x 256 tile: 96 KB, 1 block / CU
-  } else if (cfg == 8) {
-    r = launch_dma<64, 64, 64, 2, 2, 0, 4>(p, grid, st, g_zero_page);      // 16 waves: 4 k-groups
-  } else if (cfg == 11) {
-    r = launch_dma<64, 64, 64, 2, 2, 0, 2>(p, grid, st, g_zero_page);      // 8 waves: 2 k-groups, 64 KB (2 blocks / CU)
-  } else if (cfg == 9) {
-    r = launch_dma<128, 128, 32, 3, 2, 0, 2>(p, grid, st, g_zero_page);    // 8 waves: 2 k-groups, 96 KB
-  } else if (cfg == 10) {
-    r = launch_dma<128, 128, 64, 2, 2, 0, 2>(p, grid, st, g_zero_page);    // 8 waves: 2 k-groups, 128-byte rows, 128 KB
-  } else if (cfg == 19 || cfg == 20) {
-    if (g_varpp) return -10;         // the shorter ping-pong tiles have no ablation instances
-    p.k_order = (g_tapin && p.ksize == 3) ? 1 : 0;
-    r = cfg == 19 ? launch_pp<128, 320, 1, 4>(p, grid, st, g_zero_page) : launch_pp<192, 256, 1, 4>(p, grid, st, g_zero_page);
-  } else if (cfg == 16 || cfg == 17) {
-    p.k_order = (g_tapin && p.ksize == 3) ? 1 : 0;
-#define LPP(...) (cfg == 16 ? launch_pp<256, 256, 2, 4, __VA_ARGS__>(p, grid, st, g_zero_page) : launch_pp<192, 320, 1, 4, __VA_ARGS__>(p, grid, st, g_zero_page))
-#ifdef PNPI_ABLATIONS      // `python -m pnpinversion_amd.build --ablations`: tools/pp_ablate.py, tools/profile_pp.sh
-    switch (g_varpp) {
-      case 1: r = LPP(1); break;     // ablations: no MFMAs
-      case 2: r = LPP(2); break;     // no DMA
-      case 3: r = LPP(3); break;     // DMA only
-      case 4: r = LPP(4); break;     // MFMAs only
-      default: r = LPP(0); break;
-    }
-#else
-    if (g_varpp) return -10;         // the ablation instances are not in this build
-    r = LPP(0);
-#endif
-#undef LPP
-  } else if (cfg == 6) {
-    r = launch_dma<256, 320, 64, 2, 4>(p, grid, st, g_zero_page);
-  } else if (cfg == 7) {
-    r = launch_dma<256, 256, 64, 2, 4>(p, grid, st, g_zero_page);
-  } else if (cfg == 5) {
-    if (sparse == 2 && g_var256n == 1) r = LDMA0(128, 256, 32, 6);
-    else switch (g_var256n) {
-      case 0: r = LDMA0(128, 256, 32, 3); break;       // 72 KB, 2 blocks / CU
-      case 2: r = LDMA0(128, 256, 64, 2); break;
-      default: r = LDMA(128, 256, 32, 2); break;      // 48 KB: two-pass epilogue, 3 blocks / CU by LDS
-    }
-  } else if (cfg == 0) {
-    int var = g_var128;
-    // 128-byte rows with 2 stages (64 KB, 2 blocks / CU) beat 64-byte rows with 3 stages (48 KB, 3 blocks / CU) once every CU
-    // holds two blocks that cover for each other's exposed loads; below that the deeper ring wins
-    if (g_v128_bk64_tiles > 0 && var == 2 && units >= g_v128_bk64_tiles) var = 0;
-    if (var == 2 && sparse == 2) var = 8;
-    else if (var == 2 && sparse == 1) var = 3;
-    switch (var) {
-      case 1: r = LDMA0(128, 128, 64, 3); break;
-      case 2: r = LDMA(128, 128, 32, 3); break;
-      case 3: r = LDMA0(128, 128, 32, 4); break;
-      case 4: r = LDMA(128, 128, 32, 2); break;
-      case 8: r = LDMA0(128, 128, 32, 8); break;       // 128 KB ring: sparse launches
-#ifdef PNPI_ABLATIONS
-      case 11: r = launch_dma<128, 128, 32, 3, 2, 1>(p, grid, st, g_zero_page); break;   // ablation: DMA only
-      case 12: r = launch_dma<128, 128, 32, 3, 2, 2>(p, grid, st, g_zero_page); break;   // ablation: compute only
-      case 15: r = launch_dma<128, 128, 32, 3, 2, 3>(p, grid, st, g_zero_page); break;   // ablation: activation loads for tap 0 only
-#endif
-      default: r = LDMA(128, 128, 64, 2); break;
-    }
-  } else {
-    int v64 = g_var64;
-    if (v64 == 0 && sparse == 2) v64 = 8;
-    else if (v64 == 0 && sparse == 1) v64 = 2;
-    switch (v64) {
-      case 8: r = LDMA0(64, 64, 64, 8); break;         // 128 KB ring: sparse launches
-      case 1: r = LDMA0(64, 64, 64, 2); break;
-      case 2: r = LDMA0(64, 64, 64, 4); break;
-      case 3: r = LDMA0(64, 64, 32, 4); break;
-      default: r = LDMA(64, 64, 64, 3); break;
+  const long units = (long)((selM + d->bm - 1) / d->bm) * pl.gy * pl.gz;
+  pl.sparse = !g_deep_rings ? 0 : (units <= 256 ? 2 : (units <= 512 ? 1 : 0));
+  if (cpp) {
+    // igemm_vpp: the ablation instances exist in a `build --ablations` library only, and there for the tall tiles only
+    if (g_varpp && !(kAblations && pp_is_tall(d))) return fail(-10);
+    pl.variant = g_varpp;
+  } else if (dma_ok) {
+    switch (d->id) {     // the tiles with tuning variants; ids 0 and 1 fold the ring depth in
+    case 0:
+      pl.variant = g_var128;
+      // 128-byte rows with 2 stages (64 KB, 2 blocks / CU) beat 64-byte rows with 3 stages (48 KB, 3 blocks / CU) once every CU
+      // holds two blocks that cover for each other's exposed loads; below that the deeper ring wins
+      if (g_v128_bk64_tiles > 0 && pl.variant == 2 && units >= g_v128_bk64_tiles) pl.variant = 0;
+      if (pl.variant == 2 && pl.sparse) pl.variant = pl.sparse == 2 ? 8 : 3;
+      break;
+    case 1:
+      pl.variant = g_var64;
+      if (pl.variant == 0 && pl.sparse) pl.variant = pl.sparse == 2 ? 8 : 2;
+      break;
+    case 3: pl.variant = g_var256; break;
+    case 4: pl.variant = g_var320; break;
+    case 5: pl.variant = g_var256n; break;
     }
   }
-  if (r) return r;
-  if (split > 1) {
+  return pl;
+}
+
+// The kernel instance of a plan: tile id, then the plan's variant where a tile has several.
+static int igemm_dispatch(const IgemmPlan& pl, const GemmP& p, hipStream_t st) {
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+  if (!pl.dma) {      // register-staged v1 kernel: ids 0 and 1
+    void (*const k)(GemmP) = pl.bm == 64 ? (pl.fastk ? igemm_kernel<64, 64, true> : igemm_kernel<64, 64, false>)
+                                         : (pl.fastk ? igemm_kernel<128, 128, true> : igemm_kernel<128, 128, false>);
+    k<<<grid, 256, lds_bytes(pl.bm, pl.bn), st>>>(p);
+    return 0;
+  }
+  if (const auto launch = tile_desc(pl.id)->launch) return launch(p, grid, st);
+  switch (pl.id) {
+    case 0: switch (pl.variant) {
+      case 1: return launch_dma<128, 128, 64, 3>(p, grid, st);
+      case 2: return launch_dma_s<128, 128, 32, 3>(p, grid, st);
+      case 3: return launch_dma<128, 128, 32, 4>(p, grid, st);
+      case 4: return launch_dma_s<128, 128, 32, 2>(p, grid, st);
+      case 8: return launch_dma<128, 128, 32, 8>(p, grid, st);       // 128 KB ring: sparse launches
+#ifdef PNPI_ABLATIONS
+      case 11: return launch_dma<128, 128, 32, 3, 2, 1>(p, grid, st);   // ablation: DMA only
+      case 12: return launch_dma<128, 128, 32, 3, 2, 2>(p, grid, st);   // ablation: compute only
+      case 15: return launch_dma<128, 128, 32, 3, 2, 3>(p, grid, st);   // ablation: activation loads for tap 0 only
+#endif
+      default: return launch_dma_s<128, 128, 64, 2>(p, grid, st);
+    }
+    case 1: switch (pl.variant) {
+      case 8: return launch_dma<64, 64, 64, 8>(p, grid, st);         // 128 KB ring: sparse launches
+      case 1: return launch_dma<64, 64, 64, 2>(p, grid, st);
+      case 2: return launch_dma<64, 64, 64, 4>(p, grid, st);
+      case 3: return launch_dma<64, 64, 32, 4>(p, grid, st);
+      default: return launch_dma_s<64, 64, 64, 3>(p, grid, st);
+    }
+    case 3: return pl.variant == 1 ? launch_dma<256, 128, 32, 2, 2>(p, grid, st) : launch_dma<256, 128, 32, 3, 2>(p, grid, st);
+    case 4:
+      if (pl.sparse == 2 && pl.variant == 1) return launch_dma<128, 320, 32, 5>(p, grid, st);
+      switch (pl.variant) {
+        case 0: return launch_dma<128, 320, 32, 3>(p, grid, st);       // 84 KB ring = whole-tile epilogue, 1 block / CU
+        case 2: return launch_dma<128, 320, 64, 2>(p, grid, st);       // 128-byte rows, 112 KB, 1 block / CU
+#ifdef PNPI_ABLATIONS
+        case 11: return launch_dma<128, 320, 32, 2, 2, 1>(p, grid, st);   // ablation: DMA only
+        case 12: return launch_dma<128, 320, 32, 2, 2, 2>(p, grid, st);   // ablation: compute only
+#endif
+        default: return launch_dma_s<128, 320, 32, 2>(p, grid, st);      // 56 KB ring, two-pass epilogue, 2 blocks / CU
+      }
+    case 5:
+      if (pl.sparse == 2 && pl.variant == 1) return launch_dma<128, 256, 32, 6>(p, grid, st);
+      switch (pl.variant) {
+        case 0: return launch_dma<128, 256, 32, 3>(p, grid, st);       // 72 KB, 2 blocks / CU
+        case 2: return launch_dma<128, 256, 64, 2>(p, grid, st);
+        default: return launch_dma_s<128, 256, 32, 2>(p, grid, st);      // 48 KB: two-pass epilogue, 3 blocks / CU by LDS
+      }
+#define LPP(...) (pl.id == 16 ? launch_pp<256, 256, 2, 4, __VA_ARGS__>(p, grid, st) : launch_pp<192, 320, 1, 4, __VA_ARGS__>(p, grid, st))
+    case 16: case 17: switch (pl.variant) {
+#ifdef PNPI_ABLATIONS
+      case 1: return LPP(1);     // ablations: no MFMAs
+      case 2: return LPP(2);     // no DMA
+      case 3: return LPP(3);     // DMA only
+      case 4: return LPP(4);     // MFMAs only
+#endif
+      default: return LPP(0);
+    }
+#undef LPP
+  }
+  return -2;
+}
+
+int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_cfg, int force_split, int* cfg_used,
+                 int* stats_tile_rows, int sel_M) {
+  const IgemmPlan pl = igemm_plan(p, ws != nullptr, ws_bytes, force_cfg, force_split, sel_M);
+  if (pl.id < 0) return pl.err;      // rejected before a tile was chosen
+  if (cfg_used) *cfg_used = pl.cls;
+  g_last_cfg = pl.id; g_last_split = pl.split;
+  for (int i = 0; i < 7; ++i) g_last_geom[i] = 0;
+  if (stats_tile_rows && pl.stats_tile_rows >= 0) *stats_tile_rows = pl.stats_tile_rows;
+  if (pl.err) return pl.err;
+  p.vt_col0 = pl.vt_col0; p.splitk = pl.split; p.kchunks_per_split = pl.kchunks_per_split; p.slab = ws;
+  p.epi_lds = pl.epi_lds; p.bias_init = pl.bias_init; p.res_late = pl.res_late; p.k_order = pl.k_order;
+  if (!pl.stats) p.stats = nullptr;
+  if (int r = igemm_dispatch(pl, p, st)) return r;
+  if (pl.split > 1) {
     size_t total = (size_t)p.M * ((p.N + 3) / 4);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 2048) blocks = 2048;

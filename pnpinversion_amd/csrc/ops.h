@@ -42,6 +42,19 @@ void gemm_defaults(GemmP& p);
 // sel_M > 0: the configuration is chosen as for sel_M rows instead of p.M (bit-identical per element to the sel_M-row launch's rows)
 int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_cfg = -1, int force_split = 0,
                  int* cfg_used = nullptr, int* stats_tile_rows = nullptr, int sel_M = 0);
+// What launch_igemm decides before it launches, as plain integers (igemm_plan: a pure host function of the launch description and the
+// tuning knobs; pnpi_igemm_plan_query hands it to the CPU tests).  err: 0, or launch_igemm's -2 ... -10 (id -1: rejected before a tile
+// was chosen; stats_tile_rows -1: rejected before the statistics were decided).
+struct IgemmPlan {
+  int err, id, split, kchunks_per_split;
+  int variant, sparse;      // the tile's tuning variant (ids 0 / 1: ring depth folded in; ping-pong: igemm_vpp); 2 / 1 / 0: at most one / two / more blocks per CU
+  int bm, bn, gx, gy, gz;
+  int vt_col0;              // clamped to N
+  int epi_lds, bias_init, res_late, k_order;   // the GemmP fields of the same names
+  int stats, stats_tile_rows, cls;             // requested statistics survive; rows per partial (0: none); cfg_used class
+  int dma, fastk;           // LDS-DMA kernel families (0: the register-staged v1 kernel, with FASTK = fastk)
+};
+IgemmPlan igemm_plan(GemmP p, bool have_ws, size_t ws_bytes, int force_cfg, int force_split, int sel_M);
 int igemm_init();  // sets dynamic-LDS attributes once
 // tile configuration id / split-K of the most recent launch_igemm and the <BM, BN, BKT, NST, WGM, ABL, WK> of its igemm_dma_kernel (profiling)
 void igemm_last_launch(int* cfg, int* split, int* geom7);
