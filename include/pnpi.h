@@ -458,6 +458,15 @@ int pnpi_op_gemm_geglu(pnpi_ctx* ctx, const void* a_f16, int lda, const void* w_
                        const float* bias, void* out_f16, int ldo);
 int pnpi_op_groupnorm(pnpi_ctx* ctx, const void* x1, const void* x2, int C1, int C2, int B, int HW, int groups, float eps,
                       const float* gamma, const float* beta, int silu, void* out);
+/* The GroupNorm the UNet forward runs behind a convolution that handed over its statistics: no statistics pass, st1 / st2 are the
+ * per-(m-tile, channel) partials pnpi_op_conv_stats wrote for x1 / x2 ([B * HW / rows][C][2] fp32, batch item b's tiles from
+ * b * HW / rows on; rows1 / rows2 the producers' tile_rows_out; st2 / rows2 ignored without x2).  PNPI_ESHAPE, with `out`
+ * untouched, where the forward would recompute the statistics instead: rows <= 0, HW % rows != 0 or more than 256 tiles per item.
+ * Tensors small enough for the one-launch kernel of pnpi_op_groupnorm (groups of C / G % 4 == 0 channels and at most 24576 elements
+ * per item) take it and ignore the partials, as in the forward. */
+int pnpi_op_groupnorm_stats(pnpi_ctx* ctx, const void* x1, const void* x2, int C1, int C2, int B, int HW, int groups, float eps,
+                            const float* gamma, const float* beta, int silu, void* out, const float* st1, int rows1,
+                            const float* st2, int rows2);
 int pnpi_op_layernorm(pnpi_ctx* ctx, const void* x, int M, int C, float eps, const float* gamma, const float* beta, void* out);
 int pnpi_op_geglu(pnpi_ctx* ctx, const void* x, int M, int inner, void* out);
 int pnpi_op_softmax_rows(pnpi_ctx* ctx, void* x, int M, int N, int ld);

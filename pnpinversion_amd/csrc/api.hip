@@ -162,6 +162,7 @@ static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device,
   CKH(hipMalloc((void**)&c->splitk_ws, c->splitk_bytes));
   size_t gnp = (size_t)(max_unet_rows > max_vae_images ? max_unet_rows : max_vae_images) * (128 * 64 * 2 + 4096 * 2) * sizeof(float);
   CKH(hipMalloc((void**)&c->gn_partial, gnp));
+  c->gn_partial_floats = gnp / sizeof(float);
   CKH(hipMalloc((void**)&c->temb_h, TE * sizeof(float)));
   CKH(hipMalloc((void**)&c->temb_emb, TE * sizeof(float)));
   CKH(hipMalloc((void**)&c->bias_scratch, (size_t)c->unet.temb_total * sizeof(float)));
@@ -770,7 +771,23 @@ int pnpi_op_gemm_geglu(pnpi_ctx* c, const void* a, int lda, const void* w, int l
 }
 int pnpi_op_groupnorm(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int HW, int G, float eps, const float* gamma,
                       const float* beta, int silu, void* out) {
+  if (!c || !x1 || !gamma || !beta || !out || B <= 0 || HW <= 0 || G <= 0) return PNPI_EINVAL;
+  if (groupnorm_scratch_floats(C1, C2, B, HW, G, false) > c->gn_partial_floats)
+    return fail(c, PNPI_ESHAPE, "groupnorm: the context's statistics scratch is sized for max_unet_rows batch items");
   CK(launch_groupnorm((const half_t*)x1, (const half_t*)x2, C1, C2, B, HW, G, eps, gamma, beta, silu, (half_t*)out, c->gn_partial, c->st));
+  return 0;
+}
+/* the statistics-fed GroupNorm of op_gn: the producers' partials instead of a statistics pass, refused where op_gn would recompute */
+int pnpi_op_groupnorm_stats(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int HW, int G, float eps, const float* gamma,
+                            const float* beta, int silu, void* out, const float* st1, int rows1, const float* st2, int rows2) {
+  if (!c || !x1 || !gamma || !beta || !out || !st1 || B <= 0 || HW <= 0 || G <= 0 || C1 <= 0 || C2 < 0) return PNPI_EINVAL;
+  if ((x2 != nullptr) != (C2 > 0) || (x2 && !st2)) return PNPI_EINVAL;
+  if (!gn_stats_usable(HW, rows1) || (x2 && !gn_stats_usable(HW, rows2)))
+    return fail(c, PNPI_ESHAPE, "groupnorm_stats: partials need rows > 0, HW % rows == 0 and HW / rows <= 256 (op_gn recomputes the statistics here)");
+  if (groupnorm_scratch_floats(C1, C2, B, HW, G, true) > c->gn_partial_floats)
+    return fail(c, PNPI_ESHAPE, "groupnorm_stats: the context's statistics scratch is sized for max_unet_rows batch items");
+  CK(launch_groupnorm_fused((const half_t*)x1, (const half_t*)x2, C1, C2, B, HW, G, eps, gamma, beta, silu, (half_t*)out, st1, HW / rows1, st2,
+                            x2 ? HW / rows2 : 1, c->gn_partial, c->st));
   return 0;
 }
 int pnpi_op_layernorm(pnpi_ctx* c, const void* x, int M, int C, float eps, const float* gamma, const float* beta, void* out) {

@@ -96,6 +96,10 @@ static inline bool keep_acts(pnpi_ctx* c) { return c->tape && c->tape->rec; }
 // Per-channel GroupNorm partial sums attached to an activation by the GEMM that produced it ([tiles][C][2], `rows` per tile).
 // op_conv fills one for its caller on request: rows = rows per tile actually produced (0 = none).
 struct Stats { const float* p = nullptr; int rows = 0; };
+// Can launch_groupnorm_fused consume partials of `rows` rows per m-tile for maps of HW pixels?  The partials are indexed by global
+// m-tile, so a tile must not straddle two batch items (HW % rows); beyond 256 tiles per item the statistics are recomputed.
+// One rule for op_gn (which falls back to launch_groupnorm) and pnpi_op_groupnorm_stats (which refuses).
+static inline bool gn_stats_usable(int HW, int rows) { return rows > 0 && HW % rows == 0 && HW / rows <= 256; }
 
 static half_t* talloc(pnpi_ctx* c, size_t n) { return (half_t*)c->temp.alloc(n * sizeof(half_t)); }
 static half_t* palloc(pnpi_ctx* c, size_t n) { return (half_t*)c->persist.alloc(n * sizeof(half_t)); }
@@ -107,8 +111,8 @@ static int op_gn(pnpi_ctx* c, const half_t* x1, const half_t* x2, int C1, int C2
     TapeOp o; o.kind = TK_GN; o.x1 = x1; o.x2 = x2; o.C1 = C1; o.C2 = C2; o.B = B; o.HW = HW; o.nw = &nw; o.G = G; o.eps = eps; o.silu = silu; o.out = out;
     c->tape->ops.push_back(o);
   }
-  const bool ok1 = s1.p && s1.rows > 0 && HW % s1.rows == 0 && HW / s1.rows <= 256;
-  const bool ok2 = !x2 || (s2.p && s2.rows > 0 && HW % s2.rows == 0 && HW / s2.rows <= 256);
+  const bool ok1 = s1.p && gn_stats_usable(HW, s1.rows);
+  const bool ok2 = !x2 || (s2.p && gn_stats_usable(HW, s2.rows));
   static const bool gn_nofuse = getenv("PNPI_GN_NOFUSE") != nullptr;   // ablation: always recompute the statistics
   if (ok1 && ok2 && !gn_nofuse) {
     PROFD(PNPI_KC_GROUPNORM, 0.0, 2.0 * B * HW * (double)(C1 + C2) * 2.0, B * HW, C1 + C2, 1,

@@ -217,7 +217,7 @@ struct pnpi_ctx {
   struct ArenaRef { void* base; std::atomic<int> refs; bool ff_fold_ready = false; };
   ArenaRef* warena_ref = nullptr;                   // shared by the owner and every context that borrows the arena: the last pnpi_destroy frees it
   float* splitk_ws; size_t splitk_bytes;
-  float* gn_partial;
+  float* gn_partial; size_t gn_partial_floats = 0;
   float* temb_table;      // [n_train][C0] fp32 sinusoid table
   float* temb_h;          // [4*C0]
   float* temb_emb;        // [4*C0]

@@ -457,6 +457,14 @@ int launch_groupnorm_fused(const half_t* x1, const half_t* x2, int C1, int C2, i
   return (int)hipGetLastError();
 }
 
+size_t groupnorm_scratch_floats(int C1, int C2, int B, int HW, int G, bool fused) {
+  const int C = C1 + C2;
+  if ((C & 7) || (C1 & 7) || G <= 0 || C % G || G > 64) return 0;      // rejected by the launch itself
+  if (fused) return (size_t)B * C * 2;      // (an upper bound where the one-launch kernel takes the tensor)
+  if (gn_small_ok(C1, C2, HW, G, B)) return 0;
+  return (size_t)B * ((size_t)gn_nchunk(HW) * G * 2 + (size_t)C * 2);
+}
+
 // ------------------------------------------------------------------------------------------------ LayerNorm
 // A wavefront owns RPW token rows at once; the rows stay in registers (C <= 2048) so mean and variance are two exact passes.
 // VPL = 16-byte vectors per lane and row.  One row per wave (640 bytes at C = 320) left a single load in flight per lane and the

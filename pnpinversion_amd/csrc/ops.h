@@ -76,6 +76,8 @@ int launch_groupnorm_fused(const half_t* x1, const half_t* x2, int C1, int C2, i
                            const float* gamma, const float* beta, int silu, half_t* out, const float* st1, int tpb1,
                            const float* st2, int tpb2, float* scratch, hipStream_t st);
 void norm_set_tuning_gn_inline_rows(int v);   // tuning "gn_inline_rows"
+// fp32 elements of `partial` (fused = false) / `scratch` (fused = true) that launch writes at most
+size_t groupnorm_scratch_floats(int C1, int C2, int B, int HW, int G, bool fused);
 int launch_layernorm(const half_t* x, int M, int C, float eps, const float* gamma, const float* beta, half_t* out,
                      hipStream_t st);
 int launch_geglu(const half_t* x, int M, int I, half_t* out, hipStream_t st);       // x [M][2I] -> out [M][I]
