@@ -498,6 +498,13 @@ int pnpi_op_attention_bwd(pnpi_ctx* ctx, const void* q, int ldq, int q_off, cons
                           int v_off, const void* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, void* dq,
                           void* dk, void* dv, void* scratch, size_t scratch_bytes);
 size_t pnpi_op_attention_bwd_scratch_bytes(int Nq, int Nk, int dh);
+/* kernel-level: pnpi_op_attention_bwd handed what the recording forward left -- lse_fwd [B][heads][Nq] (fp32, log2 domain:
+ * log2 sum_k 2^(scale * log2(e) * q.k)) and its output o_fwd [B*Nq][ld_ofwd].  With both (and the flash form, see "attn_bwd_flash") dQ
+ * skips its first pass over the keys; either NULL: exactly pnpi_op_attention_bwd. */
+int pnpi_op_attention_bwd_fwd(pnpi_ctx* ctx, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* v, int ldv,
+                              int v_off, const void* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, void* dq,
+                              void* dk, void* dv, void* scratch, size_t scratch_bytes, const float* lse_fwd, const void* o_fwd,
+                              int ld_ofwd);
 
 /* ---- differentiable UNet forward (null-text path; groundwork) ---------------------------------------------------------------
  * pnpi_unet_context_grad: eps = unet(latents [1][4][h][w], t, context [1][77][768]) with every activation recorded, then the reverse
@@ -534,6 +541,12 @@ int pnpi_null_latent_calculate(pnpi_ctx* ctx, const float* ddim_latents, const f
 int pnpi_op_attention(pnpi_ctx* ctx, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt,
                       int ldv, void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale,
                       const int* rows_dev /*[nrows][4]*/, int nrows);
+/* kernel-level: pnpi_op_attention with causal (non-zero: key j > query i is masked, the CLIP text encoder's launch) and lse_dev
+ * (nullable; [rows][heads][Nq] fp32 indexed by the OUTPUT row of each rows_dev entry: the log2-domain log-sum-exp of the recording
+ * forward).  NULL q / k / vt / o / rows_dev: PNPI_EINVAL.  pnpi_op_attention is this call with (0, NULL). */
+int pnpi_op_attention_ex(pnpi_ctx* ctx, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt,
+                         int ldv, void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale,
+                         const int* rows_dev /*[nrows][4]*/, int nrows, int causal, float* lse_dev);
 /* ---- mask-guided MasaCtrl (models/masactrl/masactrl.py:114-193, MutualSelfAttentionControlMask) --------------------------------
  * Attach nimg pairs of BINARY uint8 masks [nimg][h][w] (host pointers, values 0 / 1) to the context: from then on, at the steps and
  * blocks a kind-2 controller controls, each target row attends to its source row's K / V restricted by class -- query i sees the keys j

@@ -802,13 +802,21 @@ int pnpi_op_softmax_rows(pnpi_ctx* c, void* x, int M, int N, int ld) {
   CK(launch_softmax_rows((half_t*)x, M, N, ld, c->st));
   return 0;
 }
+/* pnpi_op_attention_bwd with what the recording forward left (kernel tests of the hand-over): lse_fwd [B][heads][Nq] log2-domain
+ * log-sum-exp and o_fwd [B*Nq][ld_ofwd] the forward's output -- the flash dQ then skips its first pass over the keys.  Both nullable. */
+int pnpi_op_attention_bwd_fwd(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* v, int ldv, int v_off,
+                              const void* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, void* dq, void* dk, void* dv,
+                              void* scratch, size_t scratch_bytes, const float* lse_fwd, const void* o_fwd, int ld_ofwd) {
+  if (!c || !q || !k || !v || !d_o || !dq || !dk || !dv) return PNPI_EINVAL;
+  CKP(attn_bwd(c, (const half_t*)q, ldq, q_off, (const half_t*)k, ldk, k_off, (const half_t*)v, ldv, v_off, (const half_t*)d_o, ldo,
+               heads, Nq, Nk, Dp, dh, scale, B, (half_t*)dq, (half_t*)dk, (half_t*)dv, scratch, scratch_bytes, lse_fwd, (const half_t*)o_fwd, ld_ofwd));
+  return 0;
+}
 int pnpi_op_attention_bwd(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* v, int ldv, int v_off,
                           const void* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, void* dq, void* dk, void* dv,
                           void* scratch, size_t scratch_bytes) {
-  if (!c || !q || !k || !v || !d_o || !dq || !dk || !dv) return PNPI_EINVAL;
-  CKP(attn_bwd(c, (const half_t*)q, ldq, q_off, (const half_t*)k, ldk, k_off, (const half_t*)v, ldv, v_off, (const half_t*)d_o, ldo,
-               heads, Nq, Nk, Dp, dh, scale, B, (half_t*)dq, (half_t*)dk, (half_t*)dv, scratch, scratch_bytes));
-  return 0;
+  return pnpi_op_attention_bwd_fwd(c, q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch,
+                                   scratch_bytes, nullptr, nullptr, 0);
 }
 size_t pnpi_op_attention_bwd_scratch_bytes(int Nq, int Nk, int dh) { return attn_bwd_scratch_bytes(Nq, Nk, dh); }
 // ---- activation-gradient kernels (null-text path groundwork; tests/test_gpu_backward.py)
@@ -862,15 +870,24 @@ int pnpi_op_adam_step(pnpi_ctx* c, float* p, float* m, float* v, const float* g,
   CK(launch_adam_step(p, m, v, g, n, k, lr, inv_scale, c->st));
   return 0;
 }
-int pnpi_op_attention(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt, int ldv,
-                      void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, const int* rows_dev, int nrows) {
+/* pnpi_op_attention with the two AttnP fields only the model sets: causal (CLIP text encoder) and lse_dev [nrows_out][heads][Nq], the
+ * log2-domain log-sum-exp the recording forward leaves for the backward (nullable).  The tuning keys apply as in pnpi_op_attention. */
+int pnpi_op_attention_ex(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt, int ldv,
+                         void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, const int* rows_dev, int nrows, int causal,
+                         float* lse_dev) {
+  if (!c || !q || !k || !vt || !o || !rows_dev) return PNPI_EINVAL;
   AttnP a; a.q = (const half_t*)q; a.ldq = ldq; a.q_off = q_off; a.k = (const half_t*)k; a.ldk = ldk; a.k_off = k_off;
   a.vt = (const half_t*)vt; a.ldv = ldv; a.o = (half_t*)o; a.ldo = ldo; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.Dp = Dp; a.dh = dh;
   a.scale = scale; a.rows = rows_dev; a.nrows = nrows;
-  a.vt_perm = (g_op_attention_vt_perm && attn_flash_uses_dma64(Dp, Nk, 0)) ? 1 : 0;
+  a.causal = causal ? 1 : 0; a.lse = lse_dev;
+  a.vt_perm = (g_op_attention_vt_perm && attn_flash_uses_dma64(Dp, Nk, a.causal)) ? 1 : 0;
   a.aug = g_op_attention_aug;
   CK(launch_attn_flash(a, c->st));
   return 0;
+}
+int pnpi_op_attention(pnpi_ctx* c, const void* q, int ldq, int q_off, const void* k, int ldk, int k_off, const void* vt, int ldv,
+                      void* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, const int* rows_dev, int nrows) {
+  return pnpi_op_attention_ex(c, q, ldq, q_off, k, ldk, k_off, vt, ldv, o, ldo, heads, Nq, Nk, Dp, dh, scale, rows_dev, nrows, 0, nullptr);
 }
 /* pnpi_op_attention over class-restricted keys (attn.hip attn_flash_masked_kernel): kcls_dev [nmask][Nk], qcls_dev [nmask][Nq] class bytes,
  * mrow_dev [nrows] the class row of each entry of rows_dev.  The tuning key "op_attention_vt_perm" applies as in pnpi_op_attention. */
