@@ -354,6 +354,49 @@ int pnpi_bld_edit(pnpi_ctx* ctx, const float* x_start, int nimg, const float* sr
                   const float* ctx_uncond, const float* ctx_cond, float guidance_scale, int nsteps_total, int nsteps_run,
                   const int* timesteps_host, float* latents_out);
 
+/* ---- Plug-and-Play (run_editing_pnp.py: PNP, register_conv_control_efficient, register_attention_control_efficient) -----------
+ * Feature and self-attention injection from a source row.  Every UNet launch holds three rows per image, [source latent of this level, x,
+ * x] on the contexts ["", negative prompt, target prompt]; classifier-free guidance runs over rows 1 and 2 and the source row is never
+ * stepped.  Latents and the step arithmetic are fp32 (the reference runs an fp16 pipeline).
+ * pnpi_pnp_desc: which steps and which sites inject.  conv_site: decoder ResNet in execution order (up block i, layer j ->
+ * i * (layers_per_block + 1) + j), -1 = none: after conv2 and before the shortcut add, rows 1 and 2 take row 0's hidden states
+ * (:276-281).  qk_block_mask: bit b = transformer block b in execution order (down 0 .., mid, up ..): rows 1 and 2 take row 0's q and k
+ * in its self-attention and keep their own v (:190-201), at every token count.  conv_steps / qk_steps: the number of LEADING steps that
+ * inject (init_pnp :371-375: scheduler.timesteps[:n]). */
+typedef struct pnpi_pnp_desc {
+  uint32_t struct_size;            /* = sizeof(pnpi_pnp_desc), set by the caller (as pnpi_recon_desc); a mismatch is PNPI_EINVAL */
+  int conv_steps;
+  int qk_steps;
+  int conv_site;
+  uint32_t qk_block_mask;
+} pnpi_pnp_desc;
+size_t pnpi_pnp_desc_sizeof(void);
+/* The reference's sites and schedule, derived from the model's structure (host only, no context): conv_site = the second ResNet of the
+ * first decoder level that has attention (up_blocks[1].resnets[1] at SD-1.x), qk_block_mask = every decoder transformer block but the
+ * first of that level (res_dict :231; blocks 8 .. 15 at SD-1.x), conv_steps = int(nsteps * 0.8), qk_steps = int(nsteps * 0.5)
+ * (run_pnp :386-387).  PNPI_ESHAPE when the decoder has no such level. */
+int pnpi_pnp_desc_default(const pnpi_model_config* cfg, int nsteps, pnpi_pnp_desc* out);
+/* level 1, denoise_step :363-368 for nimg images in one launch: eps [nimg][3][row_elems] (row 0 unread), x / x_out [nimg][row_elems] (x_out
+ * may be x):  e = e1 + g (e2 - e1);  x_out = DDIMScheduler.step(e, t, x) with prev_t = t - step_ratio (final_alpha_cumprod below 0), eta 0.
+ * Bit-exact against eager fp32 PyTorch. */
+int pnpi_pnp_step(pnpi_ctx* ctx, const float* eps, const float* x, int nimg, size_t row_elems, float guidance_scale, int t, int step_ratio,
+                  float* x_out);
+/* level 1: ONE forward of 3 * nimg rows [img][source, x, x] with a given injection state (the hooked UNet of denoise_step :361):
+ * latents / eps_out [nimg][3][E], context [nimg][3][77][768], conv_on / qk_on: does desc's conv site / do desc's blocks inject in this
+ * forward.  With conv_on the injected ResNet's norm1 -> conv1 -> norm2 -> conv2 run on the nimg source rows only (the other rows' results
+ * would be overwritten) and pnpi_counters.executed_gemm_flops is lower by exactly that work.  3 * nimg > max_unet_rows, a wrong
+ * struct_size and a site outside the model are refused before anything is launched. */
+int pnpi_unet_forward_pnp(pnpi_ctx* ctx, const float* latents, int nimg, int t, const float* context, const pnpi_pnp_desc* desc,
+                          int conv_on, int qk_on, float* eps_out);
+/* level 2, PNP.sample_loop :393-396, device-resident for nimg images: src_latents [nsteps][nimg][E] the source latent of every step IN
+ * STEP ORDER (step i is the reference's noisy_latent[-1 - i]), x_start [nimg][E] (noisy_latent[-1]), context [nimg][3][77][768],
+ * timesteps_host [nsteps] (with steps_offset: 981, 961, .., 1), latents_out [nimg][E].  Step i injects at the conv site while
+ * i < desc->conv_steps and in the q/k blocks while i < desc->qk_steps.  One UNet launch of 3 * nimg rows and one pnpi_pnp_step launch
+ * per step, no host round trip, text K / V projected once.  3 * nimg > max_unet_rows, nsteps <= 0, a wrong struct_size, a site outside the
+ * model and arena overflow are refused before anything is launched. */
+int pnpi_pnp_edit(pnpi_ctx* ctx, const float* src_latents, const float* x_start, int nimg, const float* context, const pnpi_pnp_desc* desc,
+                  int nsteps, const int* timesteps_host, float guidance_scale, float* latents_out);
+
 /* ---- kernel-level entry points (used by tests/ and bench.py to exercise single kernels) ------------------------- */
 int pnpi_op_conv(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nhwc_f16, int C1, int C2, int B, int H, int W,
                  int ksize, int stride, int pad, int upsample, int Ho, int Wo, const void* w_f16 /*[N][k*k*(C1+C2)]*/,

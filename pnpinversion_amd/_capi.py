@@ -48,6 +48,15 @@ class ReconDesc(C.Structure):
         return cls(C.sizeof(cls), ref_image, float(recon_lr), int(recon_t), int(dilate_mask), inv_x_stars)
 
 
+class PnpDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("conv_steps", C.c_int), ("qk_steps", C.c_int), ("conv_site", C.c_int),
+                ("qk_block_mask", C.c_uint32)]
+
+    @classmethod
+    def make(cls, conv_steps, qk_steps, conv_site, qk_block_mask):
+        return cls(C.sizeof(cls), int(conv_steps), int(qk_steps), int(conv_site), int(qk_block_mask))
+
+
 ATTN_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
 
 
@@ -171,6 +180,12 @@ SYMBOLS = {
     "pnpi_bld_mask": (_i, [_vp, _vp, _i, _i, _i, _vp]),                                        # _read_mask :164-173
     "pnpi_bld_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _sz, _f, _i, _i, _vp]),      # edit_image :127-139
     "pnpi_bld_edit": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _ip, _vp]),      # edit_image :110-139
+    # Plug-and-Play (run_editing_pnp.py)
+    "pnpi_pnp_desc_sizeof": (_sz, []),
+    "pnpi_pnp_desc_default": (_i, [C.POINTER(ModelConfig), _i, C.POINTER(PnpDesc)]),             # res_dict :231, run_pnp :386-387
+    "pnpi_pnp_step": (_i, [_vp, _vp, _vp, _i, _sz, _f, _i, _i, _vp]),                          # denoise_step :363-368
+    "pnpi_unet_forward_pnp": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(PnpDesc), _i, _i, _vp]),   # denoise_step :361 (hooked UNet)
+    "pnpi_pnp_edit": (_i, [_vp, _vp, _vp, _i, _vp, C.POINTER(PnpDesc), _i, _ip, _f, _vp]),     # sample_loop :393-396
 }
 
 _lib = None

@@ -222,6 +222,46 @@ static int resnet_fwd(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, c
   return 0;
 }
 
+// The same block at a Plug-and-Play conv-injection step (run_editing_pnp.py:276-281: after conv2, before the shortcut add, rows 1 and 2
+// of every image take row 0's hidden states).  Everything the main branch computes for rows 1 and 2 is overwritten unread, so
+// norm1 -> conv1 (+temb) -> norm2 -> conv2 run on the nimg source rows only and out[r] = shortcut(x[r]) + h[image of r]: the shortcut
+// convolution writes `out`, add_rows_bcast_f16 adds the broadcast main branch in place (two fp16 roundings where conv2's residual
+// epilogue has one).  The block's output carries no GroupNorm partial sums: its consumer recomputes the statistics.
+static int resnet_fwd_pnp(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, int B, int H, int W, int G,
+                          float eps, half_t* out, Stats s1, Stats s2) {
+  const PnpState& ps = c->pnp;
+  const int HW = H * W, n = ps.nimg;
+  if (B != 3 * n || !x2) return fail(c, PNPI_ESTATE, "Plug-and-Play conv injection: a decoder ResNet of a [img][3]-row launch expected");
+  if (((size_t)HW * C1) % 8 || ((size_t)HW * C2) % 8 || ((size_t)HW * r.cout) % 8)
+    return fail(c, PNPI_ESHAPE, "Plug-and-Play conv injection: row size is no multiple of 8 halfs");
+  const size_t mk = c->temp.mark();
+  const size_t M = (size_t)n * HW;
+  const half_t *xs1 = x1, *xs2 = x2;
+  if (n > 1) {      // the source rows 3 i, gathered; their statistics are recomputed (the partial sums are indexed by the launch's tiles)
+    half_t *g1 = talloc(c, M * C1), *g2 = talloc(c, M * C2);
+    if (!c->dry) {
+      CK(launch_gather_rows_f16(x1, ps.src_rows, n, (size_t)HW * C1, g1, c->st));
+      CK(launch_gather_rows_f16(x2, ps.src_rows, n, (size_t)HW * C2, g2, c->st));
+    }
+    xs1 = g1; xs2 = g2; s1 = s2 = Stats();
+  }
+  half_t* t1 = talloc(c, M * r.cin);
+  CK(op_gn(c, xs1, xs2, C1, C2, n, HW, r.n1, G, eps, 1, t1, s1, s2));
+  half_t* t2 = talloc(c, M * r.cout);
+  const float* b1 = r.temb_off >= 0 ? c->bias_eff + r.temb_off : r.c1.b;
+  Stats st2;
+  CK(op_conv(c, t1, r.cin, nullptr, 0, n, H, W, r.c1, 1, 1, 0, b1, nullptr, t2, H, W, -1, nullptr, &st2));
+  half_t* t3 = talloc(c, M * r.cout);
+  CK(op_gn(c, t2, nullptr, r.cout, 0, n, HW, r.n2, G, eps, 1, t3, st2));
+  half_t* hsrc = talloc(c, M * r.cout);
+  CK(op_conv(c, t3, r.cout, nullptr, 0, n, H, W, r.c2, 1, 1, 0, r.c2.b, nullptr, hsrc, H, W));
+  if (!r.has_sc) return fail(c, PNPI_ESHAPE, "Plug-and-Play conv injection: the site has no shortcut convolution");   // a decoder ResNet concatenates its skip: cin != cout
+  CK(op_conv(c, x1, C1, x2, C2, B, H, W, r.sc, 1, 0, 0, r.sc.b, nullptr, out, H, W));
+  if (!c->dry) CK(launch_add_rows_bcast_f16(out, hsrc, ps.hrow, B, (size_t)HW * r.cout, out, c->st));
+  c->temp.release(mk);
+  return 0;
+}
+
 // The hooked attention forward of models/p2p/attention_control.py:20-47, literally: sim = q k^T * scale -> softmax -> controller(attn,
 // is_cross, place) -> attn v, with the probabilities materialised in fp32 for a host callback (level-1 fallback for controllers
 // without a descriptor).  One GEMM pair per (row, head); rows are not redirected (the callback does the editing).
@@ -314,6 +354,12 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
     const bool rep = mode == 1, masa = mode == 2;
     if (dd && (mode != 0 || c->attn_cb)) return fail(c, PNPI_ESTATE, "cfg_dedup: this block's self-attention redirects rows");
     a.rows = rep ? cd.rows_rep : (masa ? cd.rows_masa : cd.rows_id); a.nrows = B;
+    // Plug-and-Play q/k injection (run_editing_pnp.py:190-201): {r, src, src, r} for the rows of every image, at every token count
+    if (c->pnp.on && c->pnp.qk && block_index < 32 && ((c->pnp.qk_mask >> block_index) & 1u)) {
+      if (dd || c->attn_cb || mode != 0 || B != 3 * c->pnp.nimg)
+        return fail(c, PNPI_ESTATE, "Plug-and-Play q/k injection does not combine with cfg_dedup, a host callback or a controller");
+      a.rows = c->pnp.rows;
+    }
     c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * N * t.Dp;
     if (c->attn_cb && !c->dry) {
       CKP(attn_materialized(c, qk, 2 * hd, 0, qk, 2 * hd, hd, vt, ldv, ao, C, t.heads, N, N, t.Dp, t.dh, scale, B, 0, t.place, 2 * block_index));
@@ -549,7 +595,10 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   // self-attention takes the identity row table, the first half of down_attn[0][0].  Not for a recording forward (the tape walks
   // full-row records), under a host attention callback, or in the sizing dry run (which sizes for both paths instead).
   bool dedup = ud && g_cfg_dedup && !c->dry && ud->U > 0 && ud->U < rows && g.block_has_attn[0] && !keep_acts(c) && !c->attn_cb &&
-               ud->lat_u && ud->hmap && ud->dmap;
+               ud->lat_u && ud->hmap && ud->dmap && !c->pnp.on;      // the Plug-and-Play layout [source, x, x] redirects rows: never deduplicated
+  if (c->pnp.on && (c->share_U > 0 || keep_acts(c) || c->attn_cb || use_ctrl || rows != 3 * c->pnp.nimg))
+    return fail(c, PNPI_ESTATE, "Plug-and-Play forward: three rows per image, no src_share, tape, host callback or controller");
+  c->pnp.up_res_index = 0;
   for (int r = 0; dedup && r < rows; ++r) dedup = ud->hmap[r] >= 0 && ud->hmap[r] < ud->U;
   struct Act { half_t* p; int C, H; Stats s; };
   std::vector<Act> skips;
@@ -642,7 +691,9 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
       Act s = skips.back(); skips.pop_back();
       half_t* o = palloc(c, (size_t)B * H * H * oc);
       Stats ns;
-      CKP(resnet_fwd(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s, &ns));
+      if (c->pnp.on && c->pnp.conv && c->pnp.up_res_index == c->pnp.conv_site) CKP(resnet_fwd_pnp(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s));
+      else CKP(resnet_fwd(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s, &ns));
+      c->pnp.up_res_index++;
       h = o; ch = oc; hs_ = ns;
       if (g.block_has_attn[n - 1 - i]) {
         half_t* o2 = palloc(c, (size_t)B * H * H * oc);

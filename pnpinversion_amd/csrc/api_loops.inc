@@ -604,6 +604,140 @@ int pnpi_bld_edit(pnpi_ctx* c, const float* x_start, int nimg, const float* src,
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------- Plug-and-Play
+// run_editing_pnp.py: PNP.denoise_step / sample_loop with register_conv_control_efficient and register_attention_control_efficient.
+// Rows [img][source latent of this level, x, x] on the contexts ["", negative prompt, target prompt]; the source row is read from the
+// caller's list every step and never stepped.
+size_t pnpi_pnp_desc_sizeof(void) { return sizeof(pnpi_pnp_desc); }
+static int pnp_transformer_count(const pnpi_model_config& g) {
+  int n = 1;
+  for (int i = 0; i < g.n_blocks; ++i) if (g.block_has_attn[i]) n += g.layers_per_block + (g.layers_per_block + 1);
+  return n;
+}
+int pnpi_pnp_desc_default(const pnpi_model_config* g, int nsteps, pnpi_pnp_desc* out) {
+  if (!g || !out || nsteps <= 0 || g->n_blocks <= 0 || g->n_blocks > 4 || g->layers_per_block < 1) return PNPI_EINVAL;
+  const int n = g->n_blocks, lpb = g->layers_per_block;
+  int first = -1;      // the first decoder level with attention (up_blocks[1] at SD-1.x)
+  for (int i = 0; i < n && first < 0; ++i) if (g->block_has_attn[n - 1 - i]) first = i;
+  if (first < 0) return PNPI_ESHAPE;
+  int tf = 1;          // transformer blocks in execution order: the encoder's, the middle one, then the decoder's
+  for (int i = 0; i < n; ++i) if (g->block_has_attn[i]) tf += lpb;
+  uint32_t mask = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!g->block_has_attn[n - 1 - i]) continue;
+    for (int j = 0; j <= lpb; ++j, ++tf)
+      if (!(i == first && j == 0) && tf < 32) mask |= 1u << tf;
+  }
+  out->struct_size = (uint32_t)sizeof(pnpi_pnp_desc);
+  out->conv_steps = (int)(nsteps * 0.8);      // int(n_timesteps * pnp_f_t), Python float arithmetic
+  out->qk_steps = (int)(nsteps * 0.5);
+  out->conv_site = first * (lpb + 1) + 1;
+  out->qk_block_mask = mask;
+  return 0;
+}
+static int pnp_check(pnpi_ctx* c, const pnpi_pnp_desc* d, int nimg) {
+  if (d->struct_size != (uint32_t)sizeof(pnpi_pnp_desc)) return fail(c, PNPI_EINVAL, "pnpi_pnp_desc.struct_size is not sizeof(pnpi_pnp_desc) of this library");
+  const pnpi_model_config& g = c->cfg;
+  if (nimg > c->max_rows / 3) return fail(c, PNPI_EINVAL, "3 * nimg exceeds max_unet_rows (Plug-and-Play runs [source, negative, target] per image)");
+  if (d->conv_site < -1 || d->conv_site >= g.n_blocks * (g.layers_per_block + 1)) return fail(c, PNPI_EINVAL, "pnpi_pnp_desc.conv_site is no decoder ResNet of this model");
+  const int ntf = pnp_transformer_count(g);
+  if (ntf < 32 && (d->qk_block_mask >> ntf)) return fail(c, PNPI_EINVAL, "pnpi_pnp_desc.qk_block_mask names a transformer block this model does not have");
+  if (d->conv_steps < 0 || d->qk_steps < 0) return fail(c, PNPI_EINVAL, "pnpi_pnp_desc: negative step count");
+  return 0;
+}
+// the injection state lives for one call, whichever way that call returns
+struct PnpScope {
+  pnpi_ctx* c;
+  explicit PnpScope(pnpi_ctx* c_) : c(c_) {}
+  ~PnpScope() { c->pnp = PnpState(); }
+};
+// rows [3 nimg][4] = {r, source row of r's image, the same, r};  src_rows [nimg];  hrow [3 nimg]
+static void pnp_maps(int nimg, std::vector<int>& rows, std::vector<int>& src_rows, std::vector<int>& hrow) {
+  rows.resize((size_t)nimg * 12); src_rows.resize(nimg); hrow.resize((size_t)nimg * 3);
+  for (int i = 0; i < nimg; ++i) {
+    src_rows[i] = 3 * i;
+    for (int k = 0; k < 3; ++k) {
+      const int r = 3 * i + k;
+      rows[4 * r] = r; rows[4 * r + 1] = 3 * i; rows[4 * r + 2] = 3 * i; rows[4 * r + 3] = r;
+      hrow[r] = i;
+    }
+  }
+}
+static void pnp_arm(pnpi_ctx* c, const pnpi_pnp_desc* d, int nimg, bool conv, bool qk) {
+  c->pnp.on = true; c->pnp.nimg = nimg; c->pnp.conv_site = d->conv_site; c->pnp.qk_mask = d->qk_block_mask;
+  c->pnp.conv = conv && d->conv_site >= 0; c->pnp.qk = qk && d->qk_block_mask != 0;
+}
+
+int pnpi_pnp_step(pnpi_ctx* c, const float* eps, const float* x, int nimg, size_t row_elems, float guidance_scale, int t, int step_ratio,
+                  float* x_out) {
+  if (!c || !eps || !x || !x_out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
+  if (step_ratio <= 0) return fail(c, PNPI_EINVAL, "step_ratio must be positive");
+  float af, at; CKP(alphas_for(c, t, step_ratio, false, &af, &at));
+  CK(launch_pnp_step(eps, x, nullptr, nimg, row_elems, guidance_scale, af, at, x_out, nullptr, c->st));
+  return 0;
+}
+
+int pnpi_unet_forward_pnp(pnpi_ctx* c, const float* latents, int nimg, int t, const float* context, const pnpi_pnp_desc* desc, int conv_on,
+                          int qk_on, float* eps_out) {
+  if (!c || !latents || !eps_out || !desc || nimg <= 0) return PNPI_EINVAL;
+  CKP(check_ready(c));
+  CKP(pnp_check(c, desc, nimg));
+  const int rows = 3 * nimg;
+  if (c->attn_cb) return fail(c, PNPI_ESTATE, "an attention callback is installed: the Plug-and-Play forward takes its descriptor only");
+  if (!context && c->tkv.rows != rows) return fail(c, PNPI_ESTATE, "context is NULL: call pnpi_text_kv_precompute for this row count first");
+  struct UseKV { pnpi_ctx* c; ~UseKV() { c->tkv.use = false; } } guard{c};
+  c->tkv.use = context == nullptr;
+  CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
+  std::vector<int> rt, sr, hr;
+  pnp_maps(nimg, rt, sr, hr);
+  int* d = (int*)c->ctrl_arena.alloc((rt.size() + sr.size() + hr.size()) * sizeof(int));
+  if (c->ctrl_arena.overflow) return fail(c, PNPI_ENOMEM, "controller arena overflow");
+  std::vector<int> all(rt);
+  all.insert(all.end(), sr.begin(), sr.end()); all.insert(all.end(), hr.begin(), hr.end());
+  CKP(upload(c, d, all.data(), all.size() * sizeof(int)));
+  PnpScope scope(c);
+  pnp_arm(c, desc, nimg, conv_on != 0, qk_on != 0);
+  c->pnp.rows = d; c->pnp.src_rows = d + rt.size(); c->pnp.hrow = d + rt.size() + sr.size();
+  return unet_fwd(c, latents, rows, t, context, false, 0, eps_out);
+}
+
+int pnpi_pnp_edit(pnpi_ctx* c, const float* src_latents, const float* x_start, int nimg, const float* context, const pnpi_pnp_desc* desc,
+                  int nsteps, const int* ts, float gs, float* latents_out) {
+  if (!c || !src_latents || !x_start || !context || !desc || !ts || !latents_out || nimg <= 0) return PNPI_EINVAL;
+  if (nsteps <= 0 || nsteps > c->cfg.n_train_timesteps) return fail(c, PNPI_EINVAL, "need 1 <= nsteps <= n_train_timesteps");
+  CKP(pnp_check(c, desc, nimg));
+  for (int i = 0; i < nsteps; ++i)
+    if (ts[i] < 0 || ts[i] >= c->cfg.n_train_timesteps) return fail(c, PNPI_EINVAL, "timestep out of range");
+  if (!c->sched_set) return fail(c, PNPI_ESTATE, "pnpi_set_scheduler not called");
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 3 * nimg, "3 * nimg exceeds max_unet_rows (Plug-and-Play runs [source, negative, target] per image)"));
+  const size_t E = L.E, N = (size_t)nimg * E;
+  float* x = misc_f(c, N);
+  float* rows3 = misc_f(c, 3 * N);
+  L.eps = misc_f(c, 3 * N);
+  std::vector<int> rt, sr, hr;
+  pnp_maps(nimg, rt, sr, hr);
+  PnpScope scope(c);
+  loop_map(L, rt, &c->pnp.rows); loop_map(L, sr, &c->pnp.src_rows); loop_map(L, hr, &c->pnp.hrow);
+  CKP(loop_commit(L, false));      // the rows of a launch are written in place by pnp_step: no gathered input buffer
+  const size_t w = E * sizeof(float);
+  CKH(hipMemcpyAsync(x, x_start, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  CKH(hipMemcpy2DAsync(rows3, 3 * w, src_latents, w, w, nimg, hipMemcpyDeviceToDevice, c->st));
+  CKH(hipMemcpy2DAsync(rows3 + E, 3 * w, x_start, w, w, nimg, hipMemcpyDeviceToDevice, c->st));
+  CKH(hipMemcpy2DAsync(rows3 + 2 * E, 3 * w, x_start, w, w, nimg, hipMemcpyDeviceToDevice, c->st));
+  CKP(L.kv.begin(context, L.rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const int t = ts[i];
+    pnp_arm(c, desc, nimg, i < desc->conv_steps, i < desc->qk_steps);
+    CKP(loop_unet(L, rows3, nullptr, t, context, false, i));
+    float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
+    // CFG over rows 1 and 2, the DDIM step, and the next launch's rows [source latent of the next level, x, x]
+    CK(launch_pnp_step(L.eps, x, i + 1 < nsteps ? src_latents + (size_t)(i + 1) * N : nullptr, nimg, E, gs, af, at, x, rows3, c->st));
+  }
+  CKH(hipMemcpyAsync(latents_out, x, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------- null-text optimisation
 // differentiable UNet forward: one recorded row, reverse walk in api_backward.inc
 static int tape_ensure(pnpi_ctx* c) {

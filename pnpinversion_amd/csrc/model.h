@@ -186,6 +186,19 @@ struct MasaMasks {
   const uint8_t* t_at(int l) const { return base + off[l] + (size_t)cap_img * side[l] * side[l]; }
 };
 
+// Plug-and-Play injection state of the forward in flight (pnpi_unet_forward_pnp, pnpi_pnp_edit): rows [img][source, negative, target].
+// conv: the decoder ResNet `conv_site` (execution order) runs its main branch on the source rows only and every row adds its image's
+// result to its own shortcut; qk: the transformer blocks of qk_mask take the row table `rows` ({r, src, src, r}) in their self-attention.
+struct PnpState {
+  bool on = false, conv = false, qk = false;
+  int nimg = 0, conv_site = -1;
+  unsigned qk_mask = 0;
+  int up_res_index = 0;           // decoder ResNet counter of the forward in flight
+  int* rows = nullptr;            // [3 nimg][4] device
+  int* src_rows = nullptr;        // [nimg] device: launch row of image i's source (3 i)
+  int* hrow = nullptr;            // [3 nimg] device: launch row -> its image (r / 3)
+};
+
 struct ProfRec { int cls; double flops, bytes; hipEvent_t a, b; int M, N, K, ksize; int cfg = -1, split = 0; int geom[7] = {0, 0, 0, 0, 0, 0, 0}; };
 
 struct Tape;   // activation tape of a differentiable forward (null-text path; api.hip)
@@ -242,6 +255,7 @@ struct pnpi_ctx {
   bool sched_set;
   pnpi_counters ctr;
   CtrlDev cd;
+  PnpState pnp;
   MasaMasks mm;
   std::vector<char> host_stage;
   bool prof_on = false;

@@ -793,6 +793,33 @@ int launch_gather_rows_f16(const half_t* in, const int* rows, int nrows, size_t 
   return (int)hipGetLastError();
 }
 
+// out[r] = a[r] + h[hrow[r]] over fp16 rows in 16-byte vectors, each sum formed in fp32 and rounded once (Plug-and-Play's injected ResNet
+// block: every row of the launch adds its image's source-row main branch to its own shortcut).  a and out may be the same buffer (a
+// thread reads vector idx of a before it writes vector idx of out); h must not overlap out.
+__global__ void __launch_bounds__(256) add_rows_bcast_f16_kernel(const uint4* a, const uint4* __restrict__ h, const int* __restrict__ hrow, int nrows,
+                                                                 size_t row_vecs, uint4* out) {
+  const size_t total = (size_t)nrows * row_vecs;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = idx / row_vecs, e = idx - r * row_vecs;
+    uint4 va = a[idx];
+    const uint4 vh = h[(size_t)hrow[r] * row_vecs + e];
+    half_t* pa = reinterpret_cast<half_t*>(&va);
+    const half_t* ph = reinterpret_cast<const half_t*>(&vh);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pa[j] = (half_t)((float)pa[j] + (float)ph[j]);
+    out[idx] = va;
+  }
+}
+int launch_add_rows_bcast_f16(const half_t* a, const half_t* h, const int* hrow, int nrows, size_t row_elems, half_t* out, hipStream_t st) {
+  if (nrows <= 0 || row_elems == 0 || row_elems % 8 != 0 || ((uintptr_t)a & 15) || ((uintptr_t)h & 15) || ((uintptr_t)out & 15)) return -2;
+  const size_t n = (size_t)nrows * (row_elems / 8);
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  add_rows_bcast_f16_kernel<<<blocks, 256, 0, st>>>(reinterpret_cast<const uint4*>(a), reinterpret_cast<const uint4*>(h), hrow, nrows, row_elems / 8,
+                                                    reinterpret_cast<uint4*>(out));
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ weight repack
 // src: PyTorch [rows][cols][taps] (conv [out][in][kh*kw] or linear [out][in], taps = 1)
 // dst: fp16 [row'][tap * cin_pad + c], row' = row0 + (dh ? (r / dh) * Dp + r % dh : r)   (attention heads padded to Dp)

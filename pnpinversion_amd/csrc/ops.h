@@ -103,6 +103,7 @@ int launch_scale_f32(const float* in, size_t n, float s, float* out, hipStream_t
 int launch_gather_rows_f32(const float* in, const int* rows, int nrows, size_t row_elems, float* out, hipStream_t st);
 // out row r = in row rows[r], fp16, 16-byte vectors: row_elems % 8 == 0, both pointers 16-byte aligned
 int launch_gather_rows_f16(const half_t* in, const int* rows, int nrows, size_t row_elems, half_t* out, hipStream_t st);
+int launch_add_rows_bcast_f16(const half_t* a, const half_t* h, const int* hrow, int nrows, size_t row_elems, half_t* out, hipStream_t st);
 // CLIP text embeddings: out[m][:] = fp16(tok_emb[ids[m]] + pos_emb[m % T]); quick_gelu in place; fp16 -> fp32
 int launch_embed_tokens(const int* ids, int M, int T, int H, int vocab, const half_t* tok_emb, const half_t* pos_emb, half_t* out,
                         hipStream_t st);
@@ -223,6 +224,8 @@ int launch_bld_step(const float* eps, const float* x, const float* src, const fl
                     float g, float a_t, float a_prev, float* x_out, hipStream_t st);
 // uint8 [n][H][W] -> fp32 0/1 [n][h][w]: PIL-nearest resize, non-zero -> 1
 int launch_bld_mask(const uint8_t* in, int n, int H, int W, int h, int w, float* out, hipStream_t st);
+int launch_pnp_step(const float* eps, const float* x, const float* src_next, int nimg, size_t E, float g, float a_t, float a_prev, float* x_out,
+                    float* rows_next, hipStream_t st);
 // uint8 [n][H][W] -> uint8 0/1 [n][h][w]: F.interpolate(mode="nearest") indexing, source = min(floor(dst * (float)H / h), H - 1)
 int launch_masa_mask_level(const uint8_t* in, int n, int H, int W, int h, int w, uint8_t* out, hipStream_t st);
 

@@ -439,6 +439,42 @@ int launch_bld_step(const float* eps, const float* x, const float* src, const fl
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------- Plug-and-Play
+// Reference: run_editing_pnp.py, PNP.denoise_step :351-369 with diffusers' DDIMScheduler.step (eta = 0, no clipping).  One step for nimg
+// images in one launch, eps [nimg][3][E] = (source row: unread, negative prompt, target prompt):
+//   e    = eu + g * (ec - eu)                              (:364-365)
+//   prev = sa_p * ((x - sb_t * e) / sa_t) + sb_p * e       (:368)        scheduler.step, t -> t - ratio
+// rows_next (nullable) [nimg][3][E]: the next launch's input rows [src_next, prev, prev] (:353; src_next [nimg][E] is the source latent
+// of the next level, NULL: row 0 is left alone).  x / x_out may alias (element i is read before it is written, by one thread).
+__global__ void pnp_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ src_next, int nimg, size_t E, float g,
+                                float sa_t, float sb_t, float sa_p, float sb_p, float* x_out, float* __restrict__ rows_next) {
+  const size_t total = (size_t)nimg * E;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / E, e_idx = i - img * E;
+    const float eu = eps[(img * 3 + 1) * E + e_idx], ec = eps[(img * 3 + 2) * E + e_idx];
+    const float e = __fadd_rn(eu, __fmul_rn(g, __fsub_rn(ec, eu)));
+    const float prev = ddim_update(x[i], e, sa_t, sb_t, sa_p, sb_p);
+    x_out[i] = prev;
+    if (rows_next) {
+      float* r = rows_next + img * 3 * E + e_idx;
+      if (src_next) r[0] = src_next[i];
+      r[E] = prev;
+      r[2 * E] = prev;
+    }
+  }
+}
+int launch_pnp_step(const float* eps, const float* x, const float* src_next, int nimg, size_t E, float g, float a_t, float a_prev, float* x_out,
+                    float* rows_next, hipStream_t st) {
+  if (nimg <= 0 || E == 0) return -3;
+  // alpha_prod_t ** 0.5 / beta_prod_t ** 0.5 on 0-dim fp32 tensors: correctly rounded fp32 sqrt of fp32 operands
+  const float sa_t = sqrtf(a_t), sb_t = sqrtf(1.0f - a_t), sa_p = sqrtf(a_prev), sb_p = sqrtf(1.0f - a_prev);
+  size_t total = (size_t)nimg * E;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  pnp_step_kernel<<<blocks, 256, 0, st>>>(eps, x, src_next, nimg, E, g, sa_t, sb_t, sa_p, sb_p, x_out, rows_next);
+  return (int)hipGetLastError();
+}
+
 // BlendedLatnetDiffusion._read_mask (:164-173): PIL NEAREST resize of the [H][W] mask to [h][w], then `mask < 0.5 -> 0, else 1` (for
 // uint8 values: non-zero -> 1).  PIL's nearest filter reads source pixel floor((i + 0.5) * H / h) (the centre of the destination pixel,
 // scaled): in integers floor((2 i + 1) H / (2 h)), clamped to the image.

@@ -767,6 +767,70 @@ class NativeEngine:
         self._keep = (x, s, nz, m, cu, cc, ts)
         return out
 
+    # ---- Plug-and-Play (run_editing_pnp.py)
+    def pnp_desc(self, nsteps, conv_steps=None, qk_steps=None):
+        """The reference's injection sites for this model (pnp_desc_default) with its schedule int(n * 0.8) / int(n * 0.5), or the given
+        numbers of leading steps that inject"""
+        d = pnp_desc_default(self.lib, self.cfg, nsteps)
+        if conv_steps is not None:
+            d.conv_steps = int(conv_steps)
+        if qk_steps is not None:
+            d.qk_steps = int(qk_steps)
+        return d
+
+    def pnp_step(self, eps, x, t, ratio, guidance_scale):
+        """denoise_step :363-368: eps [nimg, 3, C, h, w] (source row unread, negative, target), x [nimg, C, h, w] -> CFG over rows 1 and 2,
+        then DDIMScheduler.step t -> t - ratio"""
+        e, xs = self._f32(eps), self._f32(x)
+        if xs.dim() != 4 or e.shape != (xs.shape[0], 3, *xs.shape[1:]):
+            raise ValueError("eps must be [nimg, 3, C, h, w] and x [nimg, C, h, w], got %s and %s" % (tuple(e.shape), tuple(xs.shape)))
+        out = torch.empty_like(xs)
+        self._call("pnpi_pnp_step", _p(e), _p(xs), xs.shape[0], xs[0].numel(), float(guidance_scale), int(t), int(ratio), _p(out))
+        self._keep = (e, xs)
+        return out
+
+    def unet_pnp(self, latents, t, context, desc, conv_on, qk_on):
+        """One hooked forward of denoise_step (:361): latents [nimg, 3, C, h, w] = [source, x, x] per image, context [nimg, 3, 77, D]
+        (None: the rows of text_kv_precompute) -> eps [nimg, 3, C, h, w] with desc's conv site / q/k blocks injecting or not"""
+        lat = self._f32(latents)
+        if lat.dim() != 5 or lat.shape[1] != 3:
+            raise ValueError("latents must be [nimg, 3, C, h, w], got %s" % (tuple(lat.shape),))
+        ctx = self._f32(context) if context is not None else None
+        if ctx is not None and ctx.shape != (lat.shape[0], 3, self.cfg.ctx_len, self.cfg.cross_dim):
+            raise ValueError("context must be [nimg, 3, %d, %d], got %s" % (self.cfg.ctx_len, self.cfg.cross_dim, tuple(ctx.shape)))
+        out = torch.empty_like(lat)
+        self._call("pnpi_unet_forward_pnp", _p(lat), lat.shape[0], int(t), _p(ctx), C.byref(desc), int(bool(conv_on)), int(bool(qk_on)), _p(out))
+        self._keep = (lat, ctx, desc)
+        return out
+
+    def pnp_edit(self, src_latents, x_start, context, desc, timesteps, guidance_scale):
+        """PNP.sample_loop (:393-396) for nimg images, device-resident (pnpi_pnp_edit).  src_latents [nsteps, nimg, C, h, w]: the source
+        latent of every step in step order, x_start [nimg, C, h, w], context [nimg, 3, 77, D] -> latents [nimg, C, h, w]"""
+        src, x, ctx = self._f32(src_latents), self._f32(x_start), self._f32(context)
+        ts, tsp = self._ts(timesteps)
+        if x.dim() != 4 or x.shape[1:] != (self.cfg.in_channels, self.lat_hw, self.lat_hw):
+            raise ValueError("x_start must be [nimg, %d, %d, %d], got %s" % (self.cfg.in_channels, self.lat_hw, self.lat_hw, tuple(x.shape)))
+        nimg = x.shape[0]
+        if src.shape != (len(ts), *x.shape):
+            raise ValueError("src_latents must be [nsteps, nimg, C, h, w] = %s, got %s" % ((len(ts), *x.shape), tuple(src.shape)))
+        if ctx.shape != (nimg, 3, self.cfg.ctx_len, self.cfg.cross_dim):
+            raise ValueError("context must be [nimg, 3, %d, %d], got %s" % (self.cfg.ctx_len, self.cfg.cross_dim, tuple(ctx.shape)))
+        out = torch.empty_like(x)
+        self._call("pnpi_pnp_edit", _p(src), _p(x), nimg, _p(ctx), C.byref(desc), len(ts), tsp, float(guidance_scale), _p(out))
+        self._keep = (src, x, ctx, ts, desc)
+        return out
+
+
+def pnp_desc_default(lib, cfg, nsteps):
+    """pnpi_pnp_desc_default without a context (host only, no GPU): the reference's conv site, q/k blocks and schedule for this model"""
+    d = _capi.PnpDesc()
+    ccfg = cfg.to_c()
+    st = lib.pnpi_pnp_desc_default(C.byref(ccfg), int(nsteps), C.byref(d))
+    if st != 0:
+        raise _capi.PnpiError(st, "pnpi_pnp_desc_default: this model has no decoder level with attention, or nsteps <= 0")
+    return d
+
+
 
 def ef_step_scalars(lib, alphas_cumprod, final_alpha, t, ratio, eta):
     """pnpi_ef_step_scalars without a context (host only, no GPU): the six fp32 scalars of one edit-friendly step."""
