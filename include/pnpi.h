@@ -417,19 +417,20 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
  * half-tile software-pipelined forms of the 64-wide flash kernel, measured slower) likewise.
  * "ff_fold" (1): each transformer block's ff2 GEMM and 1x1 proj_out run as one launch over folded weights [Wp W2 | Wp] derived at load
  * (same FLOPs, no hs3 round trip; fp16-rounding-level difference); 0 = the two launches.  May be switched on a live context.
- * "cfg_dedup" (2): in the loops that feed one latent to several UNet rows (classifier-free guidance: its unconditional and its
+ * "cfg_dedup" (1): in the loops that feed one latent to several UNet rows (classifier-free guidance: its unconditional and its
  * conditional row), everything before the first cross-attention -- conv_in, the first ResNet, the first transformer block up to its
  * cross-attention query -- runs once per distinct latent and is expanded to the rows of the launch there (behind the ResNet at steps
  * where that block's self-attention redirects rows).  1 = the compact launches choose their own tiles (fp16-rounding-level difference
  * where the choice differs), 2 = they are pinned to the tile / split-K of the full-row launch (bit-identical to 0), 0 = off.  Other
  * values are rejected.  pnpi_unet_forward and one-row loops are not affected.  May be switched on a live context.
- * "src_share" (2): pnpi_direct_edit launches each step's three bit-identical copies of the unconditional and of the conditional source
+ * "src_share" (1): pnpi_direct_edit launches each step's three bit-identical copies of the unconditional and of the conditional source
  * row (offset, reconstruction and edit pass) once and expands the prediction to the logical rows behind the UNet.  1 = the compact
  * launch chooses its own tiles (fp16-rounding-level difference where the choice differs), 2 = every GEMM is configured as at the logical
  * row count (bit-identical to 0), 0 = off.  The call falls back to 0 by itself with offset_rows < 1, a controller kind other than
  * 0 / 1 / 2, under a host attention callback, or on a recording context (one that holds the activation tape of
  * pnpi_unet_context_grad / the null-text loops: such a context keeps the full launch for every later call) -- the counter
- * unet_shared_rows then stays put.  Other values are rejected.
+ * unet_shared_rows then stays put; under 1 the full launch of a recording context is configured as the compact launch would be, so the
+ * context gives the same bits as one without a tape.  Other values are rejected.
  * May be switched on a live context.
  * Keys (default): "text_kv" (1) / "temb_cache" (1) per-loop caches; "gn_inline_rows" (0)
  * one-launch GroupNorm below this many rows; "igemm_dma" (1) LDS-DMA kernel family; "igemm_table" (1) measured tile table before the

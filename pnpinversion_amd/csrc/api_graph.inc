@@ -19,14 +19,18 @@ static int g_ff_fold = 1;
 // everything the UNet computes before its first cross-attention.  1 / 2: that prefix runs once per distinct latent (unet_fwd, UNetDedup)
 // and is expanded to the rows of the launch where the text comes in; 2 pins every prefix GEMM to the tile / split-K of its full-row
 // form, which makes the forward bit-identical to 0 (per-element accumulation order does not depend on the tile's position).  0: off.
-// Default 2: at SD-1.x width 1 picks the same tiles (nearest table entry) with deeper rings, is no faster and moves panel pixels by up to 2 / 255.
-static int g_cfg_dedup = [] { const char* e = getenv("PNPI_CFG_DEDUP"); const int v = e ? atoi(e) : 2; return v >= 0 && v <= 2 ? v : 2; }();   // the variable: whole-benchmark A/B runs
+// Default 1: every prefix GEMM is planned on the rows it launches (igemm_plan at the launched M: the table's rows for the compact shapes,
+// tile_table.inc); against 2 that moves fp32 summation order only (panel pixels by up to 2 / 255, profiles/rowfit_ab.json).
+static int g_cfg_dedup = [] { const char* e = getenv("PNPI_CFG_DEDUP"); const int v = e ? atoi(e) : 1; return v >= 0 && v <= 2 ? v : 1; }();   // the variable: whole-benchmark A/B runs
 // the distinct latents of a launch: lat_u fp32 [U][C][S][S]; row r of the launch is latent hmap[r] (host) = dmap[r] (device)
 struct UNetDedup { const float* lat_u; int U; const int* hmap; const int* dmap; };
 // tuning "src_share": pnpi_direct_edit runs the source rows that its offset, reconstruction and edit passes repeat bit for bit once
 // per step (a compact launch, expanded to the logical rows behind the UNet).  1: the compact launch chooses its own tiles; 2: every
 // GEMM is configured as at the logical row count (sel_M, as "cfg_dedup" = 2 does for the prefix) -- bit-identical to 0; 0: off.
-static int g_src_share = [] { const char* e = getenv("PNPI_SRC_SHARE"); const int v = e ? atoi(e) : 2; return v >= 0 && v <= 2 ? v : 2; }();   // the variable: whole-benchmark A/B runs
+// Default 1: the source rows of the three passes are one launch row, so they see the same arithmetic whatever tile is chosen, and the
+// 8-row launch takes the table's 8-row entries (text K/V projections included: they are planned at their launched M like every GEMM).
+// A context that holds a tape keeps the full launch, configured as the compact one (pnpi_direct_edit), so it gives the same bits.
+static int g_src_share = [] { const char* e = getenv("PNPI_SRC_SHARE"); const int v = e ? atoi(e) : 1; return v >= 0 && v <= 2 ? v : 1; }();
 // the GEMM pin outside the deduplicated prefix: none, or (pinned row sharing) compact rows -> logical rows
 static inline void pin_base(pnpi_ctx* c) {
   const bool on = c->share_pin && c->share_U > 0;
@@ -649,7 +653,7 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
           CKP(transformer_fwd(c, u.down_attn[0][0], o, B, H, H, ctx16, use_ctrl, cur_step, o2, os, &ns));
         }
         pin_base(c);
-        c->ctr.unet_dedup_prefix_rows += c->share_U > 0 ? c->share_U : U;      // under row sharing: the logical latents served
+        c->ctr.unet_dedup_prefix_rows += c->share_U > U ? c->share_U : U;      // under row sharing: the logical latents served (a mirrored full launch runs them all)
         h = o2; ch = oc; hs_ = ns;
         skips.push_back({h, ch, H, hs_});
         continue;

@@ -306,8 +306,12 @@ int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* c
   // Not on a recording context, under a host attention callback or in a sizing run.  This loop never records itself, so "recording
   // context" can only mean one that holds an activation tape (pnpi_unet_context_grad or a null-text loop ran on it); nothing in the
   // compact launch depends on the tape -- the fallback is the specified behaviour, visible in unet_shared_rows, not a necessity.
-  int share = (offset_rows >= 1 && !c->tape && !c->attn_cb && !c->dry) ? g_src_share : 0;
-  for (const pnpi_ctrl_desc& d : cds) if (d.kind < 0 || d.kind > 2) share = 0;
+  bool can_share = offset_rows >= 1 && !c->attn_cb && !c->dry;
+  for (const pnpi_ctrl_desc& d : cds) if (d.kind < 0 || d.kind > 2) can_share = false;
+  const int share = (can_share && !c->tape) ? g_src_share : 0;
+  // Free tile choice (1) on a context that keeps the full launch for its tape only: the full launch is configured as the compact one
+  // would be (the pin of 2, turned round), so a context gives the same bits with and without a tape -- as it does under 0 and 2
+  const bool mirror = can_share && c->tape && g_src_share == 1;
   Loop L(c);
   ShareScope scope(c);
   SrcShareMaps sm;
@@ -322,6 +326,10 @@ int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* c
     c->share_from = sm.crows; c->share_to = rows; c->share_U = 2 * NI; c->share_pin = share == 2;
   } else {
     CKP(loop_begin(L, nsteps, rows, too_many, cds.data(), NI, 4, 2, 3, nimg));
+    if (mirror) {
+      src_share_maps(nimg, npass, sm);
+      c->share_from = rows; c->share_to = sm.crows; c->share_U = sm.nlat; c->share_pin = true;
+    }
   }
   const size_t E = L.E, CE = L.CE;
   float* lat = misc_f(c, (size_t)NI * 2 * E);

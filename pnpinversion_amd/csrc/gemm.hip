@@ -620,7 +620,9 @@ IgemmPlan igemm_plan(GemmP p, bool have_ws, size_t ws_bytes, int force_cfg, int 
   // deduplicated UNet prefix pinned to its full-row configuration); the launch itself covers p.M rows
   const int selM = sel_M > 0 ? sel_M : p.M;
   auto tiles_of = [&](int bm, int bn) { return (long)((selM + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  auto slabs_fit = [&](int s) { return have_ws && (size_t)s * selM * p.N * sizeof(float) <= ws_bytes; };
+  // the slabs are written for the launched rows: a launch configured as at FEWER rows than it has must still fit them
+  const int slabM = selM > p.M ? selM : p.M;
+  auto slabs_fit = [&](int s) { return have_ws && (size_t)s * slabM * p.N * sizeof(float) <= ws_bytes; };
   int cfg = force_cfg;
   int split = 1;
   if (cfg < 0 && g_force_cfg >= 0) { cfg = g_force_cfg == 2 ? 1 : g_force_cfg; if (force_split <= 0) force_split = g_force_split; }

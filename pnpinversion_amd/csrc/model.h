@@ -216,6 +216,7 @@ struct pnpi_ctx {
   // tuning "src_share", while pnpi_direct_edit launches its compact rows: share_U > 0 = the launch of share_from rows serves share_to
   // logical rows resting on share_U logical latents.  share_pin (= 2): every GEMM of the forward is configured as at share_to rows
   // (the prefix of "cfg_dedup" as at share_to / share_U rows), so each launch makes the choices of the full-row loop
+  // (share_from > share_to: the full launch of a tape-holding context under "src_share" = 1, configured as the compact launch it replaces)
   int share_from = 0, share_to = 0, share_U = 0;
   bool share_pin = false;
   Bump warena, persist, temp, ctrl_arena;
