@@ -525,6 +525,28 @@ int pnpi_op_softmax_rows(pnpi_ctx* ctx, void* x, int M, int N, int ld);
 int pnpi_op_layernorm_bwd(pnpi_ctx* ctx, const void* x, const void* dy, int M, int C, float eps, const float* gamma, void* dx);
 int pnpi_op_groupnorm_bwd(pnpi_ctx* ctx, const void* x1, const void* x2, int C1, int C2, int B, int HW, int groups, float eps,
                           const float* gamma, const float* beta, int silu, const void* dy, void* dx);
+/* kernel-level: the forms of these kernels that the reverse walk (tape_backward) launches.
+ *   groupnorm_bwd_split: the three-phase chip-wide GroupNorm backward with the walk's two destinations: columns 0 .. C1 of the gradient go
+ *   to dx1 (row stride ld1), columns C1 .. C1 + C2 to dx2 (row stride ld2); acc != 0 adds into what is there (fp32 sum, one rounding); a
+ *   NULL destination is not written (the source that needs no gradient).  scratch NULL: the context's workspace; otherwise a device buffer
+ *   of scratch_floats >= pnpi_op_groupnorm_bwd_scratch_floats(B, HW, groups) floats (smaller: PNPI_ESHAPE).  Needs C1 % 8 == 0,
+ *   (C1 + C2) % 8 == 0, ld % 8 == 0, 256 % groups == 0.
+ *   groupnorm_bwd_ref: pnpi_op_groupnorm_bwd's arguments, always the one-block-per-group kernel (the walk's fallback for C1 % 8 != 0).
+ *   strided_add: dst[r][0 .. C) (+)= src[r * ld + off + 0 .. C), r < R; C, ld, off multiples of 8.
+ *   pad_heads: [R][heads * dh] -> [R][heads * Dp], pad columns zero.   add_f16_to_f32: dst (fp32) += scale * src (fp16), n elements.
+ *   transpose: nbatch matrices s_src / s_dst elements apart, dst[c][r] = src[r][c] for r < R, c < Cc, dst columns R .. ld_dst zero.
+ *   repack_dgrad_pad: pnpi_op_repack_dgrad into wd[Cin][taps][Npad], columns N .. Npad zero (conv_out's gradient map has 8 channels). */
+int pnpi_op_groupnorm_bwd_split(pnpi_ctx* ctx, const void* x1, const void* x2, int C1, int C2, int B, int HW, int groups, float eps,
+                                const float* gamma, const float* beta, int silu, const void* dy, void* dx1, int ld1, int acc1, void* dx2,
+                                int ld2, int acc2, float* scratch, size_t scratch_floats);
+size_t pnpi_op_groupnorm_bwd_scratch_floats(int B, int HW, int groups);
+int pnpi_op_groupnorm_bwd_ref(pnpi_ctx* ctx, const void* x1, const void* x2, int C1, int C2, int B, int HW, int groups, float eps,
+                              const float* gamma, const float* beta, int silu, const void* dy, void* dx);
+int pnpi_op_strided_add(pnpi_ctx* ctx, void* dst, const void* src, int ld, int off, size_t R, int C, int accumulate);
+int pnpi_op_pad_heads(pnpi_ctx* ctx, const void* src, size_t R, int heads, int dh, int Dp, void* dst);
+int pnpi_op_add_f16_to_f32(pnpi_ctx* ctx, float* dst, const void* src, size_t n, float scale);
+int pnpi_op_transpose(pnpi_ctx* ctx, const void* src, int ld_src, int R, int Cc, void* dst, int ld_dst, int nbatch, long s_src, long s_dst);
+int pnpi_op_repack_dgrad_pad(pnpi_ctx* ctx, const void* w, int N, int Npad, int taps, int Cin, void* wd);
 int pnpi_op_geglu_bwd(pnpi_ctx* ctx, const void* h, const void* dy, int M, int inner, void* dh);
 int pnpi_op_softmax_bwd_rows(pnpi_ctx* ctx, const float* P, const float* dP, int R, int N, int ld, float scale, void* dS);
 int pnpi_op_accumulate(pnpi_ctx* ctx, void* dst, const void* src, size_t n);

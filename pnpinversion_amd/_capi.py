@@ -141,6 +141,14 @@ SYMBOLS = {
     "pnpi_op_softmax_rows": (_i, [_vp, _vp, _i, _i, _i]),
     "pnpi_op_layernorm_bwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "pnpi_op_groupnorm_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "pnpi_op_groupnorm_bwd_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.c_size_t]),
+    "pnpi_op_groupnorm_bwd_scratch_floats": (C.c_size_t, [_i, _i, _i]),
+    "pnpi_op_groupnorm_bwd_ref": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "pnpi_op_strided_add": (_i, [_vp, _vp, _vp, _i, _i, C.c_size_t, _i, _i]),
+    "pnpi_op_pad_heads": (_i, [_vp, _vp, C.c_size_t, _i, _i, _i, _vp]),
+    "pnpi_op_add_f16_to_f32": (_i, [_vp, _vp, _vp, C.c_size_t, _f]),
+    "pnpi_op_transpose": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_long, C.c_long]),
+    "pnpi_op_repack_dgrad_pad": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "pnpi_op_geglu_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "pnpi_op_softmax_bwd_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "pnpi_op_accumulate": (_i, [_vp, _vp, _vp, C.c_size_t]),

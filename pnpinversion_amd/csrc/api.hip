@@ -837,6 +837,60 @@ int pnpi_op_groupnorm_bwd(pnpi_ctx* c, const void* x1, const void* x2, int C1, i
   CK(launch_groupnorm_bwd((const half_t*)x1, (const half_t*)x2, C1, C2, B, HW, G, eps, gamma, beta, silu, (const half_t*)dy, (half_t*)dx, c->st));
   return 0;
 }
+/* kernel-level forms of what tape_backward launches (tests/test_gpu_bwd_walk_ops.py).  groupnorm_bwd_split: the three-phase kernel with
+ * the walk's two separate destinations (ld, accumulate, or none); scratch NULL = the context's workspace, else the caller's buffer of
+ * scratch_floats floats.  groupnorm_bwd_ref: always the one-block-per-group kernel the walk falls back to. */
+size_t pnpi_op_groupnorm_bwd_scratch_floats(int B, int HW, int G) {
+  if (B <= 0 || HW <= 0 || G <= 0) return 0;
+  return groupnorm_bwd2_scratch_floats(B, HW, G);
+}
+int pnpi_op_groupnorm_bwd_split(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int HW, int G, float eps, const float* gamma,
+                                const float* beta, int silu, const void* dy, void* dx1, int ld1, int acc1, void* dx2, int ld2, int acc2,
+                                float* scratch, size_t scratch_floats) {
+  if (!c || !x1 || !gamma || !beta || !dy || B <= 0 || HW <= 0 || G <= 0 || C1 <= 0 || C2 < 0) return PNPI_EINVAL;
+  if ((dx1 && ld1 < C1) || (dx2 && ld2 < C2))
+    return fail(c, PNPI_ESHAPE, "groupnorm_bwd_split: a destination's row stride is shorter than its channel count");
+  float* ws = scratch;
+  if (!ws) CKP(gn_bwd_workspace(c, B, HW, G, &ws));
+  else if (scratch_floats < groupnorm_bwd2_scratch_floats(B, HW, G))
+    return fail(c, PNPI_ESHAPE, "groupnorm_bwd_split: scratch is smaller than pnpi_op_groupnorm_bwd_scratch_floats(B, HW, G)");
+  CK(launch_groupnorm_bwd2((const half_t*)x1, (const half_t*)x2, C1, C2, B, HW, G, eps, gamma, beta, silu, (const half_t*)dy,
+                           GnbOut{(half_t*)dx1, ld1, acc1 ? 1 : 0}, GnbOut{C2 ? (half_t*)dx2 : nullptr, ld2, acc2 ? 1 : 0}, ws, c->st));
+  return 0;
+}
+int pnpi_op_groupnorm_bwd_ref(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int HW, int G, float eps, const float* gamma,
+                              const float* beta, int silu, const void* dy, void* dx) {
+  if (!c || !x1 || !gamma || !beta || !dy || !dx || G <= 0 || C1 <= 0 || C2 < 0) return PNPI_EINVAL;
+  CK(launch_groupnorm_bwd((const half_t*)x1, (const half_t*)x2, C1, C2, B, HW, G, eps, gamma, beta, silu, (const half_t*)dy, (half_t*)dx, c->st));
+  return 0;
+}
+int pnpi_op_strided_add(pnpi_ctx* c, void* dst, const void* src, int ld, int off, size_t R, int C, int accumulate) {
+  if (!c || !dst || !src || ld <= 0 || off < 0 || C <= 0) return PNPI_EINVAL;
+  if (off + C > ld) return fail(c, PNPI_ESHAPE, "strided_add: columns off .. off + C reach past the source row (ld)");
+  CK(launch_strided_add_f16((half_t*)dst, (const half_t*)src, ld, off, R, C, accumulate, c->st));
+  return 0;
+}
+int pnpi_op_pad_heads(pnpi_ctx* c, const void* src, size_t R, int heads, int dh, int Dp, void* dst) {
+  if (!c || !src || !dst || heads <= 0 || dh <= 0) return PNPI_EINVAL;
+  if (Dp < dh) return fail(c, PNPI_ESHAPE, "pad_heads: Dp < dh");
+  CK(launch_pad_heads_f16((const half_t*)src, R, heads, dh, Dp, (half_t*)dst, c->st));
+  return 0;
+}
+int pnpi_op_add_f16_to_f32(pnpi_ctx* c, float* dst, const void* src, size_t n, float scale) {
+  if (!c || !dst || !src) return PNPI_EINVAL;
+  CK(launch_add_f16_to_f32(dst, (const half_t*)src, n, scale, c->st));
+  return 0;
+}
+int pnpi_op_transpose(pnpi_ctx* c, const void* src, int ld_src, int R, int Cc, void* dst, int ld_dst, int nbatch, long s_src, long s_dst) {
+  if (!c || !src || !dst) return PNPI_EINVAL;
+  CK(launch_transpose_f16((const half_t*)src, ld_src, R, Cc, (half_t*)dst, ld_dst, c->st, nbatch, s_src, s_dst));
+  return 0;
+}
+int pnpi_op_repack_dgrad_pad(pnpi_ctx* c, const void* w, int N, int Npad, int taps, int Cin, void* wd) {
+  if (!c || !w || !wd || N <= 0 || taps <= 0 || Cin <= 0) return PNPI_EINVAL;
+  CK(launch_repack_dgrad((const half_t*)w, N, Npad, taps, Cin, (half_t*)wd, c->st));
+  return 0;
+}
 int pnpi_op_geglu_bwd(pnpi_ctx* c, const void* h, const void* dy, int M, int inner, void* dh) {
   CK(launch_geglu_bwd((const half_t*)h, (const half_t*)dy, M, inner, (half_t*)dh, c->st));
   return 0;
