@@ -397,6 +397,32 @@ int pnpi_unet_forward_pnp(pnpi_ctx* ctx, const float* latents, int nimg, int t, 
 int pnpi_pnp_edit(pnpi_ctx* ctx, const float* src_latents, const float* x_start, int nimg, const float* context, const pnpi_pnp_desc* desc,
                   int nsteps, const int* timesteps_host, float guidance_scale, float* latents_out);
 
+/* ---- InstructPix2Pix (run_editing_instructpix2pix.py: CFGDenoiser around k-diffusion's CompVisDenoiser, sample_euler_ancestral) ------
+ * The same UNet graph with an 8-channel conv_in (pnpi_model_config.in_channels = 8, out_channels = 4): input [z * c_in | image latent],
+ * rows [img][edit text + image, null text + image, null text + zero image], a FRACTIONAL timestep (k-diffusion's sigma_to_t).
+ * Step scalars: 6 host floats per step [sigma, sigma_down - sigma, sigma_up, c_in, t, sigma_next > 0 ? 1 : 0], evaluated by the caller in
+ * the reference's fp32 order (pnpinversion_amd/instructpix2pix.py: step_table).
+ *
+ * level 1: pnpi_unet_forward (no controller) at a float timestep 0 <= t <= n_train - 1.  The sinusoid row is evaluated as the context's
+ * table is (fp64 -> fp32, cos half first; the reference multiplies in fp32), so an integer t reproduces pnpi_unet_forward bit for bit; the
+ * per-timestep bias cache is neither read nor filled.  latents [rows][in_channels][h][w], eps_out [rows][out_channels][h][w]. */
+int pnpi_unet_forward_t(pnpi_ctx* ctx, const float* latents, int rows, float t, const float* context, float* eps_out);
+/* level 1, one launch for nimg images: eps [nimg][3][row_elems], z / noise / image / z_out [nimg][row_elems] (z_out may be z):
+ *   den_k = z + eps_k * (-sigma);  den = den_2 + cfg_text * (den_0 - den_1) + cfg_image * (den_1 - den_2);
+ *   d = (z - den) / sigma;  z_out = z + d * (sigma_down - sigma);  z_out += noise * sigma_up  (only when sc6_host[5] != 0: noise is not
+ *   read otherwise and may be NULL).  in_next (nullable) [nimg][2][2 * row_elems]: the next launch's two distinct inputs per image,
+ *   [z_out * c_in_next | image] and [z_out * c_in_next | 0].  Bit-exact against eager fp32 PyTorch. */
+int pnpi_ip2p_step(pnpi_ctx* ctx, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t row_elems,
+                   float cfg_text, float cfg_image, const float* sc6_host, float c_in_next, float* z_out, float* in_next);
+/* level 2, edit_instruct_pix2pix's sampler (:125-134), device-resident for nimg images: z0 [nimg][E] = randn * sigmas[0], image [nimg][E]
+ * the VAE encoder's posterior mean (NOT scaled by 0.18215), noise [nsteps][nimg][E] the draws in step order, context [nimg][3][77][768] =
+ * [edit, null, null], scalars_host [nsteps][6], z_out [nimg][E], trajectory_out (nullable) [nsteps][nimg][E] z after every step;
+ * E = 4 h w.  One UNet launch of 3 * nimg rows on 2 * nimg distinct inputs (tuning "cfg_dedup" runs the text-independent prefix once per
+ * input) and one pnpi_ip2p_step launch per step, no host round trip, text K / V projected once.  3 * nimg > max_unet_rows, a context whose
+ * in_channels != 8 or out_channels != 4, nsteps <= 0, a scalar out of range and arena overflow are refused before anything is launched. */
+int pnpi_ip2p_edit(pnpi_ctx* ctx, const float* z0, const float* image, const float* noise, int nimg, const float* context, float cfg_text,
+                   float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out);
+
 /* ---- kernel-level entry points (used by tests/ and bench.py to exercise single kernels) ------------------------- */
 int pnpi_op_conv(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nhwc_f16, int C1, int C2, int B, int H, int W,
                  int ksize, int stride, int pad, int upsample, int Ho, int Wo, const void* w_f16 /*[N][k*k*(C1+C2)]*/,

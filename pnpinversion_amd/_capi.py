@@ -194,6 +194,10 @@ SYMBOLS = {
     "pnpi_pnp_step": (_i, [_vp, _vp, _vp, _i, _sz, _f, _i, _i, _vp]),                          # denoise_step :363-368
     "pnpi_unet_forward_pnp": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(PnpDesc), _i, _i, _vp]),   # denoise_step :361 (hooked UNet)
     "pnpi_pnp_edit": (_i, [_vp, _vp, _vp, _i, _vp, C.POINTER(PnpDesc), _i, _ip, _f, _vp]),     # sample_loop :393-396
+    # InstructPix2Pix (run_editing_instructpix2pix.py)
+    "pnpi_unet_forward_t": (_i, [_vp, _vp, _i, _f, _vp, _vp]),                                  # UNet at k-diffusion's sigma_to_t(sigma)
+    "pnpi_ip2p_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _fp, _f, _vp, _vp]),     # CFGDenoiser :46 + sample_euler_ancestral
+    "pnpi_ip2p_edit": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _f, _i, _fp, _vp, _vp]),          # edit_instruct_pix2pix :125-134
 }
 
 _lib = None

@@ -39,6 +39,117 @@ def load_checkpoint_dir(path):
     return unet, vae, clip, tok
 
 
+# ---- CompVis-layout checkpoints (what run_editing_instructpix2pix.py loads: one .ckpt whose state_dict holds model.diffusion_model.*,
+# first_stage_model.* and cond_stage_model.transformer.*) -> the diffusers-layout names load_state_dict takes
+_LDM_RES = {"in_layers.0": "norm1", "in_layers.2": "conv1", "emb_layers.1": "time_emb_proj", "out_layers.0": "norm2", "out_layers.3": "conv2",
+            "skip_connection": "conv_shortcut"}
+_LDM_VAE_ATTN = {"norm": "group_norm", "q": "query", "k": "key", "v": "value", "proj_out": "proj_attn"}
+_LDM_VAE_RES = {"nin_shortcut": "conv_shortcut"}
+
+
+def _ldm_res(rest):
+    for a, b in _LDM_RES.items():
+        if rest.startswith(a + "."):
+            return b + rest[len(a):]
+    raise KeyError(rest)
+
+
+def _ldm_unet_key(k, lpb, ups):
+    """one openaimodel.UNetModel key -> UNet2DConditionModel key.  lpb: ResNets per level; ups: output blocks whose LAST member upsamples"""
+    p = k.split(".")
+    if p[0] == "time_embed":
+        return "time_embedding.linear_%d.%s" % ({"0": 1, "2": 2}[p[1]], p[2])
+    if p[0] == "out":
+        return {"0": "conv_norm_out", "2": "conv_out"}[p[1]] + "." + p[2]
+    if p[0] == "input_blocks":
+        i, j, rest = int(p[1]), int(p[2]), ".".join(p[3:])
+        if i == 0:
+            return "conv_in." + rest
+        b, l = (i - 1) // (lpb + 1), (i - 1) % (lpb + 1)
+        if l == lpb:
+            return "down_blocks.%d.downsamplers.0.conv.%s" % (b, rest[len("op."):])
+        return "down_blocks.%d.resnets.%d.%s" % (b, l, _ldm_res(rest)) if j == 0 else "down_blocks.%d.attentions.%d.%s" % (b, l, rest)
+    if p[0] == "middle_block":
+        j, rest = int(p[1]), ".".join(p[2:])
+        return "mid_block.attentions.0." + rest if j == 1 else "mid_block.resnets.%d.%s" % (j // 2, _ldm_res(rest))
+    if p[0] == "output_blocks":
+        i, j, rest = int(p[1]), int(p[2]), ".".join(p[3:])
+        b, l = i // (lpb + 1), i % (lpb + 1)
+        if j == 0:
+            return "up_blocks.%d.resnets.%d.%s" % (b, l, _ldm_res(rest))
+        if (i, j) in ups:
+            return "up_blocks.%d.upsamplers.0.%s" % (b, rest)
+        return "up_blocks.%d.attentions.%d.%s" % (b, l, rest)
+    raise KeyError(k)
+
+
+def _ldm_vae_key(k, v, n_up):
+    p = k.split(".")
+    if p[0] in ("quant_conv", "post_quant_conv"):
+        return k, v
+    side, p = p[0], p[1:]
+    if side not in ("encoder", "decoder"):
+        raise KeyError(k)
+    if p[0] in ("conv_in", "conv_out"):
+        return side + "." + ".".join(p), v
+    if p[0] == "norm_out":
+        return side + ".conv_norm_out." + p[1], v
+    if p[0] == "mid":
+        if p[1].startswith("block_"):
+            return "%s.mid_block.resnets.%d.%s" % (side, int(p[1][6:]) - 1, ".".join(p[2:])), v
+        if p[1] == "attn_1":
+            return "%s.mid_block.attentions.0.%s.%s" % (side, _LDM_VAE_ATTN[p[2]], p[3]), (v.reshape(v.shape[0], v.shape[1]) if v.dim() == 4 else v)
+    if p[0] in ("down", "up"):
+        b = int(p[1]) if p[0] == "down" else n_up - 1 - int(p[1])                 # ldm's decoder lists its levels from the output side
+        pre = "%s.%s_blocks.%d." % (side, p[0], b)
+        if p[2] == "block":
+            return pre + "resnets.%s.%s.%s" % (p[3], _LDM_VAE_RES.get(p[4], p[4]), p[5]), v
+        if p[2] in ("downsample", "upsample"):
+            return pre + "%ssamplers.0.conv.%s" % (p[0], p[4]), v
+    raise KeyError(k)
+
+
+def convert_ldm_state_dict(sd):
+    """CompVis-layout state dict -> (unet_sd, vae_sd, clip_sd) in the names load_state_dict takes.  Every key under the three model
+    prefixes is consumed (an unknown one raises KeyError); what a training checkpoint holds besides (EMA copies, schedule buffers) is
+    left alone.  The block structure is read from the keys themselves."""
+    U, V, T = "model.diffusion_model.", "first_stage_model.", "cond_stage_model.transformer."
+    uk = [k[len(U):] for k in sd if k.startswith(U)]
+    unet, vae, clip = {}, {}, {}
+    if uk:
+        downs = sorted(int(k.split(".")[1]) for k in uk if k.startswith("input_blocks.") and k.endswith(".0.op.weight"))
+        n_in = 1 + max(int(k.split(".")[1]) for k in uk if k.startswith("input_blocks."))
+        lpb = downs[0] - 1 if downs else n_in - 1
+        ups = {(int(k.split(".")[1]), int(k.split(".")[2])) for k in uk if k.startswith("output_blocks.") and k.endswith(".conv.weight")
+               and k.count(".") == 4}
+        for k in uk:
+            unet[_ldm_unet_key(k, lpb, ups)] = sd[U + k]
+    vk = [k[len(V):] for k in sd if k.startswith(V)]
+    if vk:
+        n_up = 1 + max(int(k.split(".")[2]) for k in vk if k.startswith("decoder.up."))
+        for k in vk:
+            if k.startswith("loss."):
+                continue                                                           # the training discriminator of an autoencoder checkpoint
+            nk, nv = _ldm_vae_key(k, sd[V + k], n_up)
+            vae[nk] = nv
+    for k in sd:
+        if k.startswith(T):
+            r = k[len(T):]
+            if "position_ids" in r:
+                continue
+            clip[r[len("text_model."):] if r.startswith("text_model.") else r] = sd[k]
+    for name, d, n in (("UNet", unet, len(uk)), ("VAE", vae, len([k for k in vk if not k.startswith("loss.")]))):
+        if len(d) != n:
+            raise KeyError("%s: two checkpoint keys map to one name" % name)
+    return unet, vae, clip
+
+
+def load_ldm_checkpoint(path):
+    """a CompVis .ckpt as the reference's load_model_from_config reads it (:49-70) -> (unet_sd, vae_sd, clip_sd)"""
+    pl_sd = torch.load(path, map_location="cpu", weights_only=False)
+    return convert_ldm_state_dict(pl_sd["state_dict"] if "state_dict" in pl_sd else pl_sd)
+
+
 SYNTHETIC_WARNING = ("WARNING: running on SEEDED SYNTHETIC (random) Stable-Diffusion weights and a word-level stand-in tokenizer -- the "
                      "saved panels are numerically meaningful (parity / timing) but are NOT edits of a trained model.  Pass "
                      "--checkpoint_dir <diffusers SD-1.x directory> for real weights.")

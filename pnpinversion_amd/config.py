@@ -3,6 +3,7 @@
 SD-1.x values: diffusers ctor args of UNet2DConditionModel / AutoencoderKL as used by the reference
 (models/edict/my_diffusers/models/unet_2d_condition.py:57-82, vae.py:508-519) and the in-tree v1-inference.yaml
 (models/instructpix2pix/stable_diffusion/configs/stable-diffusion/v1-inference.yaml:29-65)."""
+import dataclasses
 from dataclasses import dataclass
 from typing import Tuple
 
@@ -72,3 +73,9 @@ SMALL64 = ModelConfig(block_out_channels=(32, 64, 128, 128), cross_dim=64, sampl
 # used for the full 50 + 50-step schedule against the oracle (22 attention sites instead of 32)
 SMALL64_LB = ModelConfig(block_out_channels=(32, 64, 128, 128), block_has_attn=(0, 1, 1, 0), cross_dim=64, sample_size=64, layers_per_block=2,
                          vae_block_out_channels=(32, 32, 64, 64), vae_layers_per_block=2, clip_layers=2, clip_heads=2, clip_intermediate=256)
+
+# InstructPix2Pix (models/instructpix2pix/configs/generate.yaml: in_channels 8, out_channels 4): the same graph with an 8-channel conv_in
+# that reads [noisy latent | image latent]
+SD1_IP2P = dataclasses.replace(SD1, in_channels=8)
+TINY16_IP2P = dataclasses.replace(TINY16, in_channels=8)
+SMALL64_IP2P = dataclasses.replace(SMALL64, in_channels=8)

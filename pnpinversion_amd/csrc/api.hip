@@ -164,6 +164,7 @@ static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device,
   CKH(hipMalloc((void**)&c->gn_partial, gnp));
   c->gn_partial_floats = gnp / sizeof(float);
   CKH(hipMalloc((void**)&c->temb_h, TE * sizeof(float)));
+  CKH(hipMalloc((void**)&c->temb_row, C0 * sizeof(float)));
   CKH(hipMalloc((void**)&c->temb_emb, TE * sizeof(float)));
   CKH(hipMalloc((void**)&c->bias_scratch, (size_t)c->unet.temb_total * sizeof(float)));
   c->bias_eff = c->bias_scratch;
@@ -257,7 +258,7 @@ void pnpi_destroy(pnpi_ctx* c) {
   void* arena = nullptr;
   if (c->warena_ref && c->warena_ref->refs.fetch_sub(1) == 1) { arena = c->warena_ref->base; delete c->warena_ref; }
   void* bufs[] = {arena, c->persist.base, c->temp.base, c->ctrl_arena.base, c->splitk_ws, c->gn_partial, c->gn_bwd_ws,
-                  c->temb_table, c->temb_h, c->temb_emb, c->bias_scratch, c->bias_tab, c->tkv.base, c->rows_ident, c->mm.base, c->mm.stage};
+                  c->temb_table, c->temb_row, c->temb_h, c->temb_emb, c->bias_scratch, c->bias_tab, c->tkv.base, c->rows_ident, c->mm.base, c->mm.stage};
   for (void* b : bufs) (void)hipFree(b);
   if (c->tape) {
     (void)hipFree(c->tape->garena.base); (void)hipFree(c->tape->d_ctx); (void)hipFree(c->tape->attn_scratch);

@@ -551,13 +551,15 @@ static int transformer_fwd_tape(pnpi_ctx* c, const TransformerW& t, const half_t
 
 // UNet2DConditionModel.forward (my_diffusers/models/unet_2d_condition.py:189-273)
 // ud (nullable): the distinct latents behind the rows and the row -> latent map (the CFG loops); NULL = every row on its own
+// temb_row (nullable, device [C0]): the sinusoid row of this forward, given by the caller (a fractional timestep); t is then not read, the
+// three GEMVs run into bias_row (device [temb_total], NULL: the context's scratch row) and the per-timestep cache is neither read nor filled
 static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const float* context, bool use_ctrl, int cur_step,
-                    float* eps_out, const UNetDedup* ud = nullptr) {
+                    float* eps_out, const UNetDedup* ud = nullptr, const float* temb_row = nullptr, float* bias_row = nullptr) {
   const pnpi_model_config& g = c->cfg;
   const UNetW& u = c->unet;
   pin_base(c);
   if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "unet rows out of range (max_unet_rows)");
-  if (t < 0 || t >= g.n_train_timesteps) return fail(c, PNPI_EINVAL, "timestep out of range");
+  if (!temb_row && (t < 0 || t >= g.n_train_timesteps)) return fail(c, PNPI_EINVAL, "timestep out of range");
   c->persist.reset(); c->temp.reset();
   c->tf_index = 0;
   const int S = g.sample_size, n = g.n_blocks, C0 = g.block_out_channels[0], TE = 4 * C0, G = g.norm_groups;
@@ -579,7 +581,13 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
     }
     // conv1 bias + time embedding of every ResNet for this timestep (TimestepEmbedding + the 22 time_emb_proj linears as three
     // GEMVs): a function of t and the weights only -> computed on the first forward at t, then read from the table
-    if (c->bias_tab && g_temb_cache) {
+    if (temb_row) {
+      float* row = bias_row ? bias_row : c->bias_scratch;
+      CK(launch_gemv(temb_row, C0, u.t1.w, TE, u.t1.b, nullptr, 0, c->temb_h, c->st));
+      CK(launch_gemv(c->temb_h, TE, u.t2.w, TE, u.t2.b, nullptr, 1, c->temb_emb, c->st));
+      CK(launch_gemv(c->temb_emb, TE, u.temb_w, u.temb_total, u.temb_b, u.conv1_b, 1, row, c->st));
+      c->bias_eff = row;
+    } else if (c->bias_tab && g_temb_cache) {
       float* row = c->bias_tab + (size_t)t * u.temb_total;
       if (!c->bias_valid[t]) {
         CK(launch_gemv(c->temb_table + (size_t)t * C0, C0, u.t1.w, TE, u.t1.b, nullptr, 0, c->temb_h, c->st));

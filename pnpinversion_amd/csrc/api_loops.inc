@@ -26,29 +26,35 @@ struct LoopKV {
 //   loop_unet     a step's prologue: gather the rows of the launch, run the UNet on them
 struct Loop {
   pnpi_ctx* c;
-  size_t E = 0, CE = 0;                        // floats per latent row / per context row
+  size_t E = 0, CE = 0;                        // floats per latent (input) row / per context row
+  size_t E_out = 0;                            // floats per prediction row: E unless the model's in_channels != out_channels
   int ratio = 0, rows = 0;                     // scheduler stride; UNet rows per launch
-  float *in = nullptr, *eps = nullptr;         // [rows][E] gathered input (loops with row maps only) and prediction of a step
+  float *in = nullptr, *eps = nullptr;         // [rows][E] gathered input (loops with row maps only) and [rows][E_out] prediction of a step
+  const float* temb_rows = nullptr;            // [nsteps][C0] sinusoid rows of a loop at fractional timesteps (loop_unet: step's row) ...
+  float* bias_row = nullptr;                   // ... and the loop-owned [temb_total] bias row its GEMVs write
   LoopKV kv;
   std::vector<int> maps;                       // host copy of all row maps, back to back
   std::vector<std::pair<int**, size_t>> map_dst;
   explicit Loop(pnpi_ctx* c_) : c(c_), kv(c_) {}
 };
 // the entry checks of loop_begin alone (a loop that builds its controller tables itself)
-static int loop_entry(Loop& L, int nsteps, int rows, const char* too_many_rows) {
+// split_io: the loop keeps input rows (E) and prediction rows (E_out) apart; every other loop steps a latent by its own prediction
+static int loop_entry(Loop& L, int nsteps, int rows, const char* too_many_rows, bool split_io = false) {
   pnpi_ctx* c = L.c;
   CKP(check_loop_ready(c));
   const pnpi_model_config& g = c->cfg;
+  if (!split_io && g.in_channels != g.out_channels) return fail(c, PNPI_EINVAL, "this loop needs a model with in_channels == out_channels");
   L.E = (size_t)g.in_channels * g.sample_size * g.sample_size; L.CE = (size_t)g.ctx_len * g.cross_dim;
+  L.E_out = (size_t)g.out_channels * g.sample_size * g.sample_size;
   L.ratio = g.n_train_timesteps / nsteps; L.rows = rows;
   if (rows > c->max_rows) return fail(c, PNPI_EINVAL, too_many_rows);
   return 0;
 }
 // cds (nullable): controller descriptors of the nq (pseudo-)images of the launch, rows = rpi * nq
 static int loop_begin(Loop& L, int nsteps, int rows, const char* too_many_rows, const pnpi_ctrl_desc* cds = nullptr, int nq = 0, int rpi = 4,
-                      int src_off = 2, int tgt_off = 3, int mask_nimg = 0) {
+                      int src_off = 2, int tgt_off = 3, int mask_nimg = 0, bool split_io = false) {
   pnpi_ctx* c = L.c;
-  CKP(loop_entry(L, nsteps, rows, too_many_rows));
+  CKP(loop_entry(L, nsteps, rows, too_many_rows, split_io));
   return cds ? setup_ctrl(c, cds, nq, rows, rpi, src_off, tgt_off, mask_nimg) : setup_ctrl(c, nullptr, 0, c->max_rows);
 }
 static void loop_map(Loop& L, const std::vector<int>& m, int** dev) {      // *dev is valid after loop_commit
@@ -68,7 +74,7 @@ static void loop_maps_cfg(Loop& L, int nq, int nimg, int P, int** d_expand, int*
 }
 static int loop_commit(Loop& L, bool step_bufs = true) {
   pnpi_ctx* c = L.c;
-  if (step_bufs) L.eps = misc_f(c, (size_t)L.rows * L.E);
+  if (step_bufs) L.eps = misc_f(c, (size_t)L.rows * L.E_out);
   if (step_bufs && !L.maps.empty()) L.in = misc_f(c, (size_t)L.rows * L.E);
   int* d = (int*)c->ctrl_arena.alloc(L.maps.size() * sizeof(int));
   // Bump::alloc hands out the arena's base on overflow: nothing may be launched on (or uploaded to) such scratch
@@ -80,13 +86,14 @@ static int loop_commit(Loop& L, bool step_bufs = true) {
 // loop's committed maps) sends every row to its latent: unet_fwd gets both, and runs what depends on the latent alone once per latent
 static int loop_unet(Loop& L, const float* lat, const int* inmap, int t, const float* ctx, bool use_ctrl, int step) {
   pnpi_ctx* c = L.c;
-  if (!inmap) return unet_fwd(c, lat, L.rows, t, ctx, use_ctrl, step, L.eps);
+  const float* trow = L.temb_rows ? L.temb_rows + (size_t)step * c->cfg.block_out_channels[0] : nullptr;
+  if (!inmap) return unet_fwd(c, lat, L.rows, t, ctx, use_ctrl, step, L.eps, nullptr, trow, L.bias_row);
   CK(launch_gather_rows_f32(lat, inmap, L.rows, L.E, L.in, c->st));
   UNetDedup ud{lat, 0, nullptr, inmap};
   for (auto& m : L.map_dst)
     if (*m.first == inmap && m.second + (size_t)L.rows <= L.maps.size()) ud.hmap = L.maps.data() + m.second;
   for (int r = 0; ud.hmap && r < L.rows; ++r) ud.U = ud.hmap[r] + 1 > ud.U ? ud.hmap[r] + 1 : ud.U;
-  return unet_fwd(c, L.in, L.rows, t, ctx, use_ctrl, step, L.eps, ud.hmap ? &ud : nullptr);
+  return unet_fwd(c, L.in, L.rows, t, ctx, use_ctrl, step, L.eps, ud.hmap ? &ud : nullptr, trow, L.bias_row);
 }
 // dst rows [img][uncond, cond] (ctx_cond == NULL: [img][uncond])
 static int interleave_ctx(pnpi_ctx* c, float* dst, const float* ctx_uncond, const float* ctx_cond, int nimg, size_t CE) {
@@ -743,6 +750,116 @@ int pnpi_pnp_edit(pnpi_ctx* c, const float* src_latents, const float* x_start, i
     CK(launch_pnp_step(L.eps, x, i + 1 < nsteps ? src_latents + (size_t)(i + 1) * N : nullptr, nimg, E, gs, af, at, x, rows3, c->st));
   }
   CKH(hipMemcpyAsync(latents_out, x, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- InstructPix2Pix
+// run_editing_instructpix2pix.py: CFGDenoiser (:33-46) around k-diffusion's CompVisDenoiser, sampled by sample_euler_ancestral.  The UNet
+// takes 8 channels [z * c_in | image latent] and a FRACTIONAL timestep (sigma_to_t); rows [img][edit text + image, null text + image,
+// null text + zero image].  The per-step scalars are the caller's: 6 floats per step [sigma, sigma_down - sigma, sigma_up, c_in, t,
+// sigma_next > 0], evaluated on the host in the reference's fp32 order (pnpinversion_amd/instructpix2pix.py: step_table).
+// The sinusoid row at a float timestep, cos half first.  A fractional t as the reference evaluates it (ldm's timestep_embedding: fp32 freqs =
+// exp(-log(10000) * i / half), fp32 t * freqs, fp32 cos / sin); an integer t as the context's table is built (fp64, rounded once), so that it
+// reproduces pnpi_unet_forward bit for bit.
+static void temb_row_host(const pnpi_model_config& g, float t, float* row) {
+  const int C0 = g.block_out_channels[0], half = C0 / 2;
+  const bool whole = t == floorf(t);
+  const float nl = (float)(-log(10000.0));
+  for (int i = 0; i < half; ++i) {
+    if (whole) {
+      double e = exp(-log(10000.0) * (double)i / (double)half);
+      double a = (double)t * e;
+      row[i] = (float)cos(a);
+      row[half + i] = (float)sin(a);
+    } else {
+      const float f = expf(nl * (float)i / (float)half);
+      const float a = t * f;
+      row[i] = cosf(a);
+      row[half + i] = sinf(a);
+    }
+  }
+}
+static int ip2p_model_check(pnpi_ctx* c) {
+  if (c->cfg.in_channels != 8 || c->cfg.out_channels != 4)
+    return fail(c, PNPI_EINVAL, "InstructPix2Pix needs a model with in_channels == 8 and out_channels == 4 (4 latent + 4 image-latent channels in, 4 out)");
+  return 0;
+}
+static int ip2p_scalars_check(pnpi_ctx* c, const float* sc, int n) {
+  for (int i = 0; i < n; ++i) {
+    const float* s = sc + 6 * (size_t)i;
+    if (!(s[0] > 0.f) || !(s[3] > 0.f)) return fail(c, PNPI_EINVAL, "InstructPix2Pix step scalars: sigma and c_in must be positive");
+    if (!(s[4] >= 0.f) || !(s[4] <= (float)(c->cfg.n_train_timesteps - 1))) return fail(c, PNPI_EINVAL, "timestep out of range");
+  }
+  return 0;
+}
+// pnpi_unet_forward at a float timestep (no controller): the sinusoid row is evaluated here, the per-timestep bias cache is not touched
+int pnpi_unet_forward_t(pnpi_ctx* c, const float* latents, int rows, float t, const float* context, float* eps_out) {
+  if (!c || !latents || !eps_out) return PNPI_EINVAL;
+  CKP(check_ready(c));
+  if (c->attn_cb) return fail(c, PNPI_ESTATE, "an attention callback is installed: pnpi_unet_forward_t runs no controller");
+  if (!(t >= 0.f) || !(t <= (float)(c->cfg.n_train_timesteps - 1))) return fail(c, PNPI_EINVAL, "timestep out of range");
+  if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "unet rows out of range (max_unet_rows)");
+  if (!context && c->tkv.rows != rows) return fail(c, PNPI_ESTATE, "context is NULL: call pnpi_text_kv_precompute for this row count first");
+  struct UseKV { pnpi_ctx* c; ~UseKV() { c->tkv.use = false; } } guard{c};
+  c->tkv.use = context == nullptr;
+  if (c->cd.any_edit || c->cd.nimg != 0) CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
+  std::vector<float> row(c->cfg.block_out_channels[0]);
+  temb_row_host(c->cfg, t, row.data());
+  CKP(upload(c, c->temb_row, row.data(), row.size() * sizeof(float)));
+  return unet_fwd(c, latents, rows, 0, context, false, 0, eps_out, nullptr, c->temb_row, nullptr);
+}
+// one step (level 1): eps [nimg][3][row_elems], z / noise / image / z_out [nimg][row_elems], sc6_host the step's scalars (c_in and t unread),
+// in_next (nullable) [nimg][2][2 * row_elems] scaled by c_in_next.  noise is not read when sc6_host[5] == 0 (sigma_next == 0).
+int pnpi_ip2p_step(pnpi_ctx* c, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t row_elems,
+                   float cfg_text, float cfg_image, const float* sc6_host, float c_in_next, float* z_out, float* in_next) {
+  if (!c || !eps || !z || !sc6_host || !z_out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
+  if (!(sc6_host[0] > 0.f)) return fail(c, PNPI_EINVAL, "InstructPix2Pix step scalars: sigma and c_in must be positive");
+  const int add_noise = sc6_host[5] != 0.f;
+  if (add_noise && !noise) return fail(c, PNPI_EINVAL, "sigma_next > 0: the step needs its draw");
+  if (in_next && !image) return fail(c, PNPI_EINVAL, "in_next needs the image latent");
+  CK(launch_ip2p_step(eps, z, noise, image, nimg, row_elems, cfg_text, cfg_image, sc6_host, add_noise, c_in_next, z_out, in_next, c->st));
+  return 0;
+}
+/* edit_instruct_pix2pix's sampler (:125-134) for nimg images, device-resident.  z0 [nimg][4 S^2] = randn * sigmas[0], image [nimg][4 S^2] the
+ * encoder's posterior mean (not scaled), noise [nsteps][nimg][4 S^2] the draws in step order (the last is not read when its sigma_next is 0),
+ * context [nimg][3][77][D] = [edit, null, null].  Per step one UNet launch of 3 * nimg rows on 2 * nimg distinct inputs (rows 0 and 1 share
+ * theirs: the input map "cfg_dedup" compacts) and one ip2p_step launch.  trajectory_out (nullable) [nsteps][nimg][4 S^2]: z after every step. */
+int pnpi_ip2p_edit(pnpi_ctx* c, const float* z0, const float* image, const float* noise, int nimg, const float* context, float cfg_text,
+                   float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out) {
+  if (!c) return PNPI_EINVAL;
+  if (nsteps <= 0 || nsteps > c->cfg.n_train_timesteps) return fail(c, PNPI_EINVAL, "need 1 <= nsteps <= n_train_timesteps");
+  if (!z0 || !image || !noise || !context || !scalars_host || !z_out || nimg <= 0) return PNPI_EINVAL;
+  CKP(ip2p_model_check(c));
+  CKP(ip2p_scalars_check(c, scalars_host, nsteps));
+  Loop L(c);
+  CKP(loop_begin(L, nsteps, 3 * nimg, "3 * nimg exceeds max_unet_rows (InstructPix2Pix runs [edit + image, null + image, null + no image] per image)",
+                 nullptr, 0, 4, 2, 3, 0, true));
+  const size_t E4 = L.E_out, N = (size_t)nimg * E4;
+  const int C0 = c->cfg.block_out_channels[0];
+  float* z = misc_f(c, N);
+  float* in2 = misc_f(c, 2 * (size_t)nimg * L.E);      // [img][with image, without] 8-channel inputs
+  float* trows = misc_f(c, (size_t)nsteps * C0);
+  L.bias_row = misc_f(c, (size_t)c->unet.temb_total);
+  std::vector<int> inmap((size_t)L.rows);
+  for (int r = 0; r < L.rows; ++r) inmap[r] = 2 * (r / 3) + (r % 3 == 2);
+  int* d_inmap;
+  loop_map(L, inmap, &d_inmap);
+  CKP(loop_commit(L));
+  std::vector<float> rows_h((size_t)nsteps * C0);
+  for (int i = 0; i < nsteps; ++i) temb_row_host(c->cfg, scalars_host[6 * (size_t)i + 4], rows_h.data() + (size_t)i * C0);
+  CKP(upload(c, trows, rows_h.data(), rows_h.size() * sizeof(float)));
+  L.temb_rows = trows;
+  CK(launch_ip2p_step(nullptr, z0, nullptr, image, nimg, E4, cfg_text, cfg_image, nullptr, 0, scalars_host[3], z, in2, c->st));
+  CKP(L.kv.begin(context, L.rows));
+  for (int i = 0; i < nsteps; ++i) {
+    const float* sc = scalars_host + 6 * (size_t)i;
+    CKP(loop_unet(L, in2, d_inmap, 0, context, false, i));
+    const bool last = i + 1 == nsteps;
+    CK(launch_ip2p_step(L.eps, z, noise + (size_t)i * N, image, nimg, E4, cfg_text, cfg_image, sc, sc[5] != 0.f, last ? 0.f : sc[6 + 3], z,
+                        last ? nullptr : in2, c->st));
+    if (trajectory_out) CKH(hipMemcpyAsync(trajectory_out + (size_t)i * N, z, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
+  }
+  CKH(hipMemcpyAsync(z_out, z, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
   return 0;
 }
 

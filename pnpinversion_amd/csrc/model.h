@@ -233,6 +233,7 @@ struct pnpi_ctx {
   float* splitk_ws; size_t splitk_bytes;
   float* gn_partial; size_t gn_partial_floats = 0;
   float* temb_table;      // [n_train][C0] fp32 sinusoid table
+  float* temb_row = nullptr;   // [C0] the caller's sinusoid row of pnpi_unet_forward_t
   float* temb_h;          // [4*C0]
   float* temb_emb;        // [4*C0]
   float* bias_eff;        // [temb_total] of the forward in flight (points into bias_tab once cached)

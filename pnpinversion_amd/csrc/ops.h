@@ -226,6 +226,10 @@ int launch_bld_step(const float* eps, const float* x, const float* src, const fl
 int launch_bld_mask(const uint8_t* in, int n, int H, int W, int h, int w, float* out, hipStream_t st);
 int launch_pnp_step(const float* eps, const float* x, const float* src_next, int nimg, size_t E, float g, float a_t, float a_prev, float* x_out,
                     float* rows_next, hipStream_t st);
+// InstructPix2Pix: the three denoised rows, the two-scale CFG combine and the Euler-ancestral move in one launch (z_out may be z), and the next
+// launch's two distinct 8-channel inputs per image.  sc (host): [sigma, sigma_down - sigma, sigma_up]; eps == NULL: inputs only
+int launch_ip2p_step(const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t E, float g_text, float g_image,
+                     const float* sc, int add_noise, float c_in_next, float* z_out, float* in_next, hipStream_t st);
 // uint8 [n][H][W] -> uint8 0/1 [n][h][w]: F.interpolate(mode="nearest") indexing, source = min(floor(dst * (float)H / h), H - 1)
 int launch_masa_mask_level(const uint8_t* in, int n, int H, int W, int h, int w, uint8_t* out, hipStream_t st);
 

@@ -475,6 +475,87 @@ int launch_pnp_step(const float* eps, const float* x, const float* src_next, int
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------- InstructPix2Pix
+// Reference: run_editing_instructpix2pix.py, CFGDenoiser :33-46 around k-diffusion's CompVisDenoiser, and sample_euler_ancestral.  One step
+// for nimg images in one launch, eps [nimg][3][E] = (edit text + image, null text + image, null text + zero image), sc = the step's host
+// scalars [sigma, sigma_down - sigma, sigma_up]:
+//   den_k = z + eps_k * (-sigma)                                                  CompVisDenoiser.forward: input + eps * c_out
+//   den   = den_2 + g_text * (den_0 - den_1) + g_image * (den_1 - den_2)          (:46), summed left to right
+//   d     = (z - den) / sigma;   z' = z + d * (sigma_down - sigma);   z' = z' + noise * sigma_up   (only when sigma_next > 0)
+// eps == NULL: no step, z' = z (the loop's first launch, which only forms the inputs).  in_next (nullable) [nimg][2][2 E]: the two distinct
+// 8-channel inputs of the next launch, [z' * c_in_next | image] and [z' * c_in_next | 0] (only z is scaled, :43).  z / z_out may alias
+// (element i is read before it is written, by one thread).  V = 4: E % 4 == 0 and every pointer 16-byte aligned.
+struct Ip2pStepP {
+  const float *eps, *z, *noise, *image;
+  int nimg; size_t E;
+  float g_text, g_image, neg_sigma, sigma, dt, up, c_in_next;
+  int add_noise;
+  float *z_out, *in_next;
+};
+__device__ __forceinline__ float ip2p_move(const Ip2pStepP& p, float z, float e0, float e1, float e2, float nz) {
+  const float d0 = __fadd_rn(z, __fmul_rn(e0, p.neg_sigma)), d1 = __fadd_rn(z, __fmul_rn(e1, p.neg_sigma)), d2 = __fadd_rn(z, __fmul_rn(e2, p.neg_sigma));
+  const float den = __fadd_rn(__fadd_rn(d2, __fmul_rn(p.g_text, __fsub_rn(d0, d1))), __fmul_rn(p.g_image, __fsub_rn(d1, d2)));
+  const float d = __fdiv_rn(__fsub_rn(z, den), p.sigma);
+  float zn = __fadd_rn(z, __fmul_rn(d, p.dt));
+  if (p.add_noise) zn = __fadd_rn(zn, __fmul_rn(nz, p.up));
+  return zn;
+}
+template <int V>
+__global__ void ip2p_step_kernel(const Ip2pStepP p) {
+  const size_t EV = p.E / V, total = (size_t)p.nimg * EV;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / EV, e_idx = (i - img * EV) * V, at = img * p.E + e_idx;
+    alignas(16) float z[V], zn[V], sc[V], im[V], zero[V];
+    if (V == 4) *(float4*)z = *(const float4*)(p.z + at);
+    else z[0] = p.z[at];
+    if (p.eps) {
+      alignas(16) float e0[V], e1[V], e2[V], nz[V];
+      const float* e = p.eps + img * 3 * p.E + e_idx;
+      if (V == 4) {
+        *(float4*)e0 = *(const float4*)e; *(float4*)e1 = *(const float4*)(e + p.E); *(float4*)e2 = *(const float4*)(e + 2 * p.E);
+        if (p.add_noise) *(float4*)nz = *(const float4*)(p.noise + at);
+      } else {
+        e0[0] = e[0]; e1[0] = e[p.E]; e2[0] = e[2 * p.E];
+        if (p.add_noise) nz[0] = p.noise[at];
+      }
+      for (int k = 0; k < V; ++k) zn[k] = ip2p_move(p, z[k], e0[k], e1[k], e2[k], p.add_noise ? nz[k] : 0.f);
+    } else {
+      for (int k = 0; k < V; ++k) zn[k] = z[k];
+    }
+    if (V == 4) *(float4*)(p.z_out + at) = *(const float4*)zn;
+    else p.z_out[at] = zn[0];
+    if (p.in_next) {
+      for (int k = 0; k < V; ++k) { sc[k] = __fmul_rn(zn[k], p.c_in_next); zero[k] = 0.f; }
+      float* r = p.in_next + img * 4 * p.E + e_idx;      // [row 0: z part, image part][row 1: z part, zero part]
+      if (V == 4) {
+        *(float4*)im = *(const float4*)(p.image + at);
+        *(float4*)r = *(const float4*)sc; *(float4*)(r + p.E) = *(const float4*)im;
+        *(float4*)(r + 2 * p.E) = *(const float4*)sc; *(float4*)(r + 3 * p.E) = *(const float4*)zero;
+      } else {
+        r[0] = sc[0]; r[p.E] = p.image[at]; r[2 * p.E] = sc[0]; r[3 * p.E] = 0.f;
+      }
+    }
+  }
+}
+int launch_ip2p_step(const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t E, float g_text, float g_image,
+                     const float* sc, int add_noise, float c_in_next, float* z_out, float* in_next, hipStream_t st) {
+  if (nimg <= 0 || E == 0 || !z || !z_out || (in_next && !image) || (eps && !sc) || (eps && add_noise && !noise)) return -3;
+  if (eps && !(sc[0] > 0.f)) return -3;
+  Ip2pStepP p;
+  p.eps = eps; p.z = z; p.noise = noise; p.image = image; p.nimg = nimg; p.E = E; p.g_text = g_text; p.g_image = g_image;
+  p.sigma = eps ? sc[0] : 1.f; p.neg_sigma = -p.sigma; p.dt = eps ? sc[1] : 0.f; p.up = eps ? sc[2] : 0.f; p.c_in_next = c_in_next;
+  p.add_noise = eps && add_noise ? 1 : 0; p.z_out = z_out; p.in_next = in_next;
+  const uintptr_t al = (uintptr_t)eps | (uintptr_t)z | (uintptr_t)(p.add_noise ? noise : nullptr) | (uintptr_t)(in_next ? image : nullptr) |
+                       (uintptr_t)z_out | (uintptr_t)in_next;
+  const bool vec = E % 4 == 0 && al % 16 == 0;
+  const size_t total = (size_t)nimg * (vec ? E / 4 : E);
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  if (vec) ip2p_step_kernel<4><<<blocks, 256, 0, st>>>(p);
+  else ip2p_step_kernel<1><<<blocks, 256, 0, st>>>(p);
+  return (int)hipGetLastError();
+}
+
 // BlendedLatnetDiffusion._read_mask (:164-173): PIL NEAREST resize of the [H][W] mask to [h][w], then `mask < 0.5 -> 0, else 1` (for
 // uint8 values: non-zero -> 1).  PIL's nearest filter reads source pixel floor((i + 0.5) * H / h) (the centre of the destination pixel,
 // scaled): in integers floor((2 i + 1) H / (2 h)), clamped to the image.

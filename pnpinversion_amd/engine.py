@@ -821,6 +821,68 @@ class NativeEngine:
         return out
 
 
+    # ---- InstructPix2Pix (run_editing_instructpix2pix.py)
+    def unet_t(self, latents, t, context):
+        """pnpi_unet_forward at a float timestep: latents [rows, in_channels, h, w], context [rows, 77, D] (None: the rows of
+        text_kv_precompute) -> eps [rows, out_channels, h, w]"""
+        lat, ctx = self._f32(latents), (self._f32(context) if context is not None else None)
+        want = (self.cfg.in_channels, self.lat_hw, self.lat_hw)
+        if lat.dim() != 4 or lat.shape[1:] != want:
+            raise ValueError("latents must be [rows, %d, %d, %d], got %s" % (*want, tuple(lat.shape)))
+        out = torch.empty(lat.shape[0], self.cfg.out_channels, self.lat_hw, self.lat_hw, device=self.device)
+        self._call("pnpi_unet_forward_t", _p(lat), lat.shape[0], float(t), _p(ctx), _p(out))
+        self._keep = (lat, ctx)
+        return out
+
+    def ip2p_step(self, eps, z, noise, image, scalars, cfg_text, cfg_image, c_in_next=None):
+        """One step for nimg images (CFGDenoiser :46 + one iteration of sample_euler_ancestral): eps [nimg, 3, C, h, w], z / noise / image
+        [nimg, C, h, w], scalars the step's 6 floats (instructpix2pix.step_table) -> z' , or (z', inputs [nimg, 2, 2 C, h, w]) when c_in_next
+        is given: the next launch's [z' * c_in_next | image] and [z' * c_in_next | 0].  noise is not read when scalars[5] == 0."""
+        e, zs = self._f32(eps), self._f32(z)
+        if zs.dim() != 4 or e.shape != (zs.shape[0], 3, *zs.shape[1:]):
+            raise ValueError("eps must be [nimg, 3, C, h, w] and z [nimg, C, h, w], got %s and %s" % (tuple(e.shape), tuple(zs.shape)))
+        nz = self._f32(noise) if noise is not None else None
+        im = self._f32(image) if image is not None else None
+        for name, x in (("noise", nz), ("image", im)):
+            if x is not None and x.shape != zs.shape:
+                raise ValueError("%s must be [nimg, C, h, w] = %s, got %s" % (name, tuple(zs.shape), tuple(x.shape)))
+        sc = np.ascontiguousarray(np.asarray(scalars, dtype=np.float32).reshape(6))
+        out = torch.empty_like(zs)
+        nimg, ch = zs.shape[:2]
+        nxt = torch.empty(nimg, 2, 2 * ch, *zs.shape[2:], device=self.device) if c_in_next is not None else None
+        self._call("pnpi_ip2p_step", _p(e), _p(zs), _p(nz), _p(im), nimg, zs[0].numel(), float(cfg_text), float(cfg_image),
+                   sc.ctypes.data_as(C.POINTER(C.c_float)), float(c_in_next) if c_in_next is not None else 0.0, _p(out), _p(nxt))
+        self._keep = (e, zs, nz, im, sc)
+        return out if nxt is None else (out, nxt)
+
+    def ip2p_edit(self, z0, image, noise, context, scalars, cfg_text=7.5, cfg_image=1.5, trajectory=False):
+        """edit_instruct_pix2pix's sampler (:125-134) for nimg images, device-resident (pnpi_ip2p_edit).  z0 [nimg, 4, h, w] = randn *
+        sigmas[0], image [nimg, 4, h, w] the encoder's posterior mean (unscaled), noise [nsteps, nimg, 4, h, w] the draws in step order,
+        context [nimg, 3, 77, D] = [edit, null, null], scalars [nsteps, 6] (instructpix2pix.step_table) -> z [nimg, 4, h, w], or
+        (z, z after every step [nsteps, nimg, 4, h, w]) with trajectory"""
+        z, im, nz, ctx = self._f32(z0), self._f32(image), self._f32(noise), self._f32(context)
+        sc = np.ascontiguousarray(np.asarray(scalars, dtype=np.float32))
+        if sc.ndim != 2 or sc.shape[1] != 6:
+            raise ValueError("scalars must be [nsteps, 6], got %s" % (sc.shape,))
+        nsteps = sc.shape[0]
+        want = (self.cfg.out_channels, self.lat_hw, self.lat_hw)
+        if z.dim() != 4 or z.shape[1:] != want:
+            raise ValueError("z0 must be [nimg, %d, %d, %d], got %s" % (*want, tuple(z.shape)))
+        nimg = z.shape[0]
+        if im.shape != z.shape:
+            raise ValueError("image must be [nimg, 4, h, w] = %s, got %s" % (tuple(z.shape), tuple(im.shape)))
+        if nz.shape != (nsteps, *z.shape):
+            raise ValueError("noise must be [nsteps, nimg, 4, h, w] = %s, got %s" % ((nsteps, *z.shape), tuple(nz.shape)))
+        if ctx.shape != (nimg, 3, self.cfg.ctx_len, self.cfg.cross_dim):
+            raise ValueError("context must be [nimg, 3, %d, %d], got %s" % (self.cfg.ctx_len, self.cfg.cross_dim, tuple(ctx.shape)))
+        out = torch.empty_like(z)
+        traj = torch.empty(nsteps, *z.shape, device=self.device) if trajectory else None
+        self._call("pnpi_ip2p_edit", _p(z), _p(im), _p(nz), nimg, _p(ctx), float(cfg_text), float(cfg_image), nsteps,
+                   sc.ctypes.data_as(C.POINTER(C.c_float)), _p(out), _p(traj))
+        self._keep = (z, im, nz, ctx, sc)
+        return (out, traj) if trajectory else out
+
+
 def pnp_desc_default(lib, cfg, nsteps):
     """pnpi_pnp_desc_default without a context (host only, no GPU): the reference's conv site, q/k blocks and schedule for this model"""
     d = _capi.PnpDesc()
