@@ -1,6 +1,169 @@
 // api_backward.inc -- part of api.hip (one translation unit: included there, in this order; not compiled on its own).
-// reverse walk over the activation tape (null-text path): gradient w.r.t. the unconditional embedding
+// attention backward of one site, and the reverse walk over the activation tape (null-text path): gradient w.r.t. the unconditional embedding
 // ---------------------------------------------------------------------------------------------------- tape backward
+// Attention backward, materialised per (row, head) like the call-back path's forward (first version: generic GEMM launches and
+// transposes; a fused flash backward replaces it later).  q / k: [B*N][ld] views with the head's columns at off + h * Dp (pad columns
+// dh .. Dp are zero, as the forward guarantees); v: plain [B*Nk][ldvp] with the same head layout; d_o: [B*Nq][ldo], heads * dh wide.
+// Outputs dq / dk / dv in the layout of q / k / v (their pad columns are left untouched: clear the buffers first).
+//   S = scale q k^T, P = softmax(S);  dV = P^T dO;  dP = dO V^T;  dS = scale P (dP - rowsum(dP P));  dQ = dS K;  dK = dS^T Q.
+// scratch: Nq * Nk * 8 (S / P and dP, fp32) + 2 * Nq * ldp * 2 (P, dS as fp16) + 2 * Nk * ldq8 * 2 (their transposes) + dh * (ldp + 2 * ldq8) * 2
+// bytes (K^T, Q^T, dO^T), reused for every (row, head).
+static size_t attn_bwd_scratch_bytes(int Nq, int Nk, int dh) {
+  const size_t ldp = round_up_i(Nk, 8), ldq8 = round_up_i(Nq, 8);
+  return align_up((size_t)Nq * Nk * 4, 256) * 2 + align_up((size_t)Nq * ldp * 2, 256) * 2 + align_up((size_t)Nk * ldq8 * 2, 256) * 2 +
+         align_up((size_t)dh * ldp * 2, 256) + align_up((size_t)dh * ldq8 * 2, 256) * 2;
+}
+static int attn_bwd_materialized(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp,
+                                 int v_off, const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B,
+                                 half_t* dq, half_t* dk, half_t* dv, void* scratch, size_t scratch_bytes) {
+  const size_t per = attn_bwd_scratch_bytes(Nq, Nk, dh);
+  if (!scratch || scratch_bytes < per) return fail(c, PNPI_ENOMEM, "attention backward scratch too small");
+  if ((dh & 7) || (ldq & 7) || (ldk & 7) || (ldvp & 7) || (ldo & 7)) return fail(c, PNPI_ESHAPE, "attention backward: extents must be multiples of 8");
+  const int ldp = round_up_i(Nk, 8), ldq8 = round_up_i(Nq, 8);
+  // The heads of a row are independent problems of one shape: every step below is ONE launch over a group of `nb` heads (as many as
+  // the scratch holds; all of them with the tape's own scratch) -- a batched GEMM (grid z = head) or a row-wise kernel over nb * Nq rows.
+  // Head by head the same work was 13 launches of a few microseconds each per head: 3 300 launches per reverse walk.
+  const int nb_max = (int)std::min<size_t>((size_t)heads, scratch_bytes / per);
+  const size_t szS = align_up((size_t)Nq * Nk * 4, 256), szP = align_up((size_t)Nq * ldp * 2, 256), szT = align_up((size_t)Nk * ldq8 * 2, 256),
+               szK = align_up((size_t)dh * ldp * 2, 256), szQ = align_up((size_t)dh * ldq8 * 2, 256);
+  for (int b = 0; b < B; ++b)
+    for (int h0 = 0; h0 < heads; h0 += nb_max) {
+      const int nb = std::min(nb_max, heads - h0);
+      char* sp = (char*)scratch;
+      auto take = [&](size_t bytes_each) { char* r = sp; sp += bytes_each * nb; return r; };     // [nb] consecutive per-head buffers
+      float* S = (float*)take(szS);
+      float* dP = (float*)take(szS);
+      half_t* P16 = (half_t*)take(szP);
+      half_t* dS16 = (half_t*)take(szP);
+      half_t* PT = (half_t*)take(szT);
+      half_t* dST = (half_t*)take(szT);
+      half_t* Kt = (half_t*)take(szK);
+      half_t* Qt = (half_t*)take(szQ);
+      half_t* dOt = (half_t*)take(szQ);
+      const long eS = (long)(szS / 4), eP = (long)(szP / 2), eT = (long)(szT / 2), eK = (long)(szK / 2), eQ = (long)(szQ / 2);   // per-head strides in elements
+      const half_t* qh = q + (size_t)b * Nq * ldq + q_off + h0 * Dp;
+      const half_t* kh = k + (size_t)b * Nk * ldk + k_off + h0 * Dp;
+      const half_t* vh = v + (size_t)b * Nk * ldvp + v_off + h0 * Dp;
+      const half_t* doh = d_o + (size_t)b * Nq * ldo + h0 * dh;
+      GemmBatch gb; gb.n = nb;
+      VtOut vs; vs.outT = S; vs.col0 = 0; vs.ld = Nk; vs.f32 = 1; vs.rpb = Nk;            // S[q][key] = scale * sum_d k[key][d] q[q][d]
+      gb.sa = Dp; gb.sw = Dp; gb.sout = 0; gb.soutT = (long)szS;
+      CK(op_gemm(c, kh, ldk, Nk, dh, qh, ldq, Nq, nullptr, nullptr, 0, nullptr, Nq, scale, &vs, -1.0, 0, &gb));
+      VtOut vp; vp.outT = dP; vp.col0 = 0; vp.ld = Nk; vp.f32 = 1; vp.rpb = Nk;          // dP[q][key] = sum_d v[key][d] dO[q][d]
+      gb.sa = Dp; gb.sw = dh;
+      CK(op_gemm(c, vh, ldvp, Nk, dh, doh, ldo, Nq, nullptr, nullptr, 0, nullptr, Nq, 1.f, &vp, -1.0, 0, &gb));
+      if (szS == (size_t)Nq * Nk * 4 && szP == (size_t)Nq * ldp * 2) {
+        // the per-head buffers are dense: the row-wise kernels take all nb * Nq rows at once
+        CK(launch_softmax_rows_f32(S, (size_t)nb * Nq, Nk, c->st));
+        CK(launch_f32_rows_to_f16_padded(S, (size_t)nb * Nq, Nk, ldp, P16, c->st));
+        CK(launch_softmax_bwd_rows(S, dP, (size_t)nb * Nq, Nk, ldp, scale, dS16, c->st));
+      } else {
+        for (int i = 0; i < nb; ++i) {
+          CK(launch_softmax_rows_f32(S + i * eS, (size_t)Nq, Nk, c->st));
+          CK(launch_f32_rows_to_f16_padded(S + i * eS, (size_t)Nq, Nk, ldp, P16 + i * eP, c->st));
+          CK(launch_softmax_bwd_rows(S + i * eS, dP + i * eS, (size_t)Nq, Nk, ldp, scale, dS16 + i * eP, c->st));
+        }
+      }
+      CK(launch_transpose_f16(P16, ldp, Nq, Nk, PT, ldq8, c->st, nb, eP, eT));
+      CK(launch_transpose_f16(dS16, ldp, Nq, Nk, dST, ldq8, c->st, nb, eP, eT));
+      CK(launch_transpose_f16(kh, ldk, Nk, dh, Kt, ldp, c->st, nb, Dp, eK));
+      CK(launch_transpose_f16(qh, ldq, Nq, dh, Qt, ldq8, c->st, nb, Dp, eQ));
+      CK(launch_transpose_f16(doh, ldo, Nq, dh, dOt, ldq8, c->st, nb, dh, eQ));
+      gb.soutT = 0; gb.sout = Dp;
+      gb.sa = eP; gb.sw = eK;
+      CK(op_gemm(c, dS16, ldp, Nq, ldp, Kt, ldp, dh, nullptr, nullptr, 0, dq + (size_t)b * Nq * ldq + q_off + h0 * Dp, ldq, 1.f, nullptr, -1.0, 0, &gb));     // dQ = dS K
+      gb.sa = eT; gb.sw = eQ;
+      CK(op_gemm(c, dST, ldq8, Nk, ldq8, Qt, ldq8, dh, nullptr, nullptr, 0, dk + (size_t)b * Nk * ldk + k_off + h0 * Dp, ldk, 1.f, nullptr, -1.0, 0, &gb));   // dK = dS^T Q
+      CK(op_gemm(c, PT, ldq8, Nk, ldq8, dOt, ldq8, dh, nullptr, nullptr, 0, dv + (size_t)b * Nk * ldvp + v_off + h0 * Dp, ldvp, 1.f, nullptr, -1.0, 0, &gb)); // dV = P^T dO
+    }
+  return 0;
+}
+// Attention backward in flash form (attn.hip: attn_bwd_flash_kernel): one launch each for dQ (which also leaves D, and the per-query
+// log-sum-exp unless the forward did), dK and dV.  Workspace per batch row: 2 * heads * N floats (+ the fp32 partial sums of a split
+// cross-attention walk) -- at the 64 x 64 level 260 KB against the 8.6 GB-per-8-heads of the score matrices.
+// cross-attention (77 keys): dK / dV have one 128-row key tile per head, so the query walk is split over workgroups (fp32 partial sums,
+// added in a fixed order by a small reduce launch)
+static int attn_bwd_flash_nsplit(int Nq, int Nk) {
+  if (Nk > 128 || Nq < 256) return 1;
+  const int n = Nq / 128;
+  return n > 32 ? 32 : n;
+}
+static size_t attn_bwd_flash_scratch_bytes(int heads, int Nq, int Nk, int dh) {
+  const int ns = attn_bwd_flash_nsplit(Nq, Nk);
+  return (size_t)heads * 2 * align_up((size_t)Nq * 4, 256) + (ns > 1 ? align_up((size_t)ns * heads * Nk * dh * 4, 256) : 0);
+}
+static bool attn_bwd_flash_shape(int Nq, int Nk, int Dp, int dh) {
+  // tuning "attn_bwd_flash": 0 = the materialised form everywhere, 1 = flash form for self- and cross-attention (dQ with the forward's
+  // log-sum-exp where the tape has it), 2 = the same with the two-pass dQ always, 3 = self-attention only
+  const bool self = Nq == Nk, cross = !self && Nk <= 128 && Nk >= 8;
+  if (!g_attn_bwd_flash || !(self || (cross && g_attn_bwd_flash != 3))) return false;
+  return Nq >= 64 && Nq % 64 == 0 && (Dp == 32 || Dp == 64 || Dp == 96 || Dp == 160) && dh <= Dp && !(dh & 7);
+}
+static bool attn_bwd_flash_ok(int heads, int Nq, int Nk, int Dp, int dh, size_t scratch_bytes) {
+  return attn_bwd_flash_shape(Nq, Nk, Dp, dh) && scratch_bytes >= attn_bwd_flash_scratch_bytes(heads, Nq, Nk, dh);
+}
+static int attn_bwd_flash(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp,
+                          int v_off, const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B,
+                          half_t* dq, half_t* dk, half_t* dv, void* scratch, const float* lse_fwd, const half_t* o_fwd, int ld_ofwd) {
+  if ((ldq & 7) || (ldk & 7) || (ldvp & 7) || (ldo & 7) || (q_off & 7) || (k_off & 7) || (v_off & 7))
+    return fail(c, PNPI_ESHAPE, "attention backward: extents must be multiples of 8");
+  const size_t szF = align_up((size_t)Nq * 4, 256);
+  char* sp = (char*)scratch;
+  float* lse = (float*)sp; sp += szF * heads;
+  float* dsum = (float*)sp; sp += szF * heads;
+  float* part = (float*)sp;
+  const int nsplit = attn_bwd_flash_nsplit(Nq, Nk);
+  if (szF != (size_t)Nq * 4) return fail(c, PNPI_ESHAPE, "attention backward: Nq * 4 must be a multiple of 256");   // [heads][Nq] dense (Nq >= 64, % 64 == 0 in every caller)
+  for (int b = 0; b < B; ++b) {
+    const half_t* qh = q + (size_t)b * Nq * ldq + q_off;
+    const half_t* kh = k + (size_t)b * Nk * ldk + k_off;
+    const half_t* vh = v + (size_t)b * Nk * ldvp + v_off;
+    const half_t* doh = d_o + (size_t)b * Nq * ldo;
+    const BwdMat mq{qh, Dp, ldq, dh}, mk{kh, Dp, ldk, dh}, mv{vh, Dp, ldvp, dh}, mdo{doh, dh, ldo, dh};
+    AttnBwdP a{};
+    a.heads = heads; a.scale = scale; a.lse = lse; a.dsum = dsum; a.out_hs = Dp; a.out_w = dh;
+    a.b1 = mq; a.b2 = mdo; a.l1 = mk; a.l2 = mv; a.nb = Nq; a.nl = Nk;
+    a.out = dq + (size_t)b * Nq * ldq + q_off; a.out_ld = ldq;
+    if (lse_fwd && o_fwd && !(ld_ofwd & 7)) {     // the recording forward left the log-sum-exp and O: dQ without its first pass over the keys
+      a.lse = const_cast<float*>(lse_fwd) + (size_t)b * heads * Nq;       // read-only in this form
+      a.o = o_fwd + (size_t)b * Nq * ld_ofwd; a.o_hs = dh; a.o_ld = ld_ofwd;
+    }
+    CK(launch_attn_bwd_flash(a, 0, Dp, c->st));
+    // tile products of the three launches (dQ: S, dP, dQ -- twice S and dP without the forward's log-sum-exp; dK: S, dP, dK; dV: S, dV)
+    c->ctr.executed_attn_flops += 2.0 * heads * (double)Nq * Nk * Dp * ((a.o ? 3 : 5) + 3 + 2);
+    a.o = nullptr;
+    a.b1 = mk; a.b2 = mv; a.l1 = mq; a.l2 = mdo; a.nb = Nk; a.nl = Nq;
+    a.nsplit = nsplit; a.part = nsplit > 1 ? part : nullptr;
+    a.out = dk + (size_t)b * Nk * ldk + k_off; a.out_ld = ldk;
+    CK(launch_attn_bwd_flash(a, 1, Dp, c->st));
+    if (nsplit > 1) CK(launch_attn_bwd_reduce(a, c->st));
+    a.out = dv + (size_t)b * Nk * ldvp + v_off; a.out_ld = ldvp;
+    CK(launch_attn_bwd_flash(a, 2, Dp, c->st));
+    if (nsplit > 1) CK(launch_attn_bwd_reduce(a, c->st));
+  }
+  return 0;
+}
+// dq / dk / dv of one attention site: the flash form for self-attention, the materialised form otherwise
+static int attn_bwd(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp, int v_off,
+                    const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, half_t* dq, half_t* dk, half_t* dv,
+                    void* scratch, size_t scratch_bytes, const float* lse_fwd = nullptr, const half_t* o_fwd = nullptr, int ld_ofwd = 0) {
+  if (scratch && attn_bwd_flash_ok(heads, Nq, Nk, Dp, dh, scratch_bytes))
+    return attn_bwd_flash(c, q, ldq, q_off, k, ldk, k_off, v, ldvp, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch,
+                          g_attn_bwd_flash == 2 ? nullptr : lse_fwd, o_fwd, ld_ofwd);      // tuning value 2: always the two-pass dQ
+  return attn_bwd_materialized(c, q, ldq, q_off, k, ldk, k_off, v, ldvp, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch, scratch_bytes);
+}
+static int gn_bwd_workspace(pnpi_ctx* c, int B, int HW, int G, float** out) {
+  const size_t need = groupnorm_bwd2_scratch_floats(B, HW, G);
+  if (need > c->gn_bwd_ws_floats) {
+    CKH(hipStreamSynchronize(c->st));                      // a launch in flight may still read the old buffer
+    if (c->gn_bwd_ws) CKH(hipFree(c->gn_bwd_ws));
+    c->gn_bwd_ws = nullptr; c->gn_bwd_ws_floats = 0;
+    CKH(hipMalloc((void**)&c->gn_bwd_ws, need * sizeof(float)));
+    c->gn_bwd_ws_floats = need;
+  }
+  *out = c->gn_bwd_ws;
+  return 0;
+}
 static half_t* tape_galloc(pnpi_ctx* c, size_t n_halfs) {
   Tape& T = *c->tape;
   half_t* p = (half_t*)T.garena.alloc(n_halfs * sizeof(half_t));

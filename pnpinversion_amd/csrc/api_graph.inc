@@ -200,23 +200,31 @@ static int op_gemm(pnpi_ctx* c, const half_t* a, int lda, int M, int K, const ha
   return igemm_prof(c, p, alg_flops >= 0 ? alg_flops : 2.0 * M * (double)N * K * p.nbatch);
 }
 
-// ResnetBlock2D.forward (my_diffusers/models/resnet.py:331-365); x2 = skip tensor concatenated on the channel axis
-static int resnet_fwd(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, int B, int H, int W, int G,
-                      float eps, half_t* out, Stats s1 = Stats(), Stats s2 = Stats(), Stats* so = nullptr) {
-  const size_t mk = c->temp.mark();
+// The main branch of a ResNet block up to conv2's input: norm1 -> conv1 (+ the time-embedding bias) -> norm2 over B rows of x1 | x2
+static int resnet_main(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, int B, int H, int W, int G,
+                       float eps, Stats s1, Stats s2, half_t** t3) {
   const int HW = H * W;
   const size_t M = (size_t)B * HW;
   half_t* t1 = talloc(c, M * r.cin);
   CK(op_gn(c, x1, x2, C1, C2, B, HW, r.n1, G, eps, 1, t1, s1, s2));
   half_t* t2 = talloc(c, M * r.cout);
   const float* b1 = r.temb_off >= 0 ? c->bias_eff + r.temb_off : r.c1.b;
-  Stats st2, sto;
+  Stats st2;
   CK(op_conv(c, t1, r.cin, nullptr, 0, B, H, W, r.c1, 1, 1, 0, b1, nullptr, t2, H, W, -1, nullptr, &st2));
-  half_t* t3 = talloc(c, M * r.cout);
-  CK(op_gn(c, t2, nullptr, r.cout, 0, B, HW, r.n2, G, eps, 1, t3, st2));
+  *t3 = talloc(c, M * r.cout);
+  CK(op_gn(c, t2, nullptr, r.cout, 0, B, HW, r.n2, G, eps, 1, *t3, st2));
+  return 0;
+}
+// ResnetBlock2D.forward (my_diffusers/models/resnet.py:331-365); x2 = skip tensor concatenated on the channel axis
+static int resnet_fwd(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, int B, int H, int W, int G,
+                      float eps, half_t* out, Stats s1 = Stats(), Stats s2 = Stats(), Stats* so = nullptr) {
+  const size_t mk = c->temp.mark();
+  half_t* t3;
+  CKP(resnet_main(c, r, x1, C1, x2, C2, B, H, W, G, eps, s1, s2, &t3));
+  Stats sto;
   const half_t* sc = x1;
   if (r.has_sc) {      // conv2 below adds it as its residual
-    half_t* s = talloc(c, M * r.cout);
+    half_t* s = talloc(c, (size_t)B * H * W * r.cout);
     CK(op_conv(c, x1, C1, x2, C2, B, H, W, r.sc, 1, 0, 0, r.sc.b, nullptr, s, H, W));
     sc = s;
   }
@@ -249,14 +257,8 @@ static int resnet_fwd_pnp(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C
     }
     xs1 = g1; xs2 = g2; s1 = s2 = Stats();
   }
-  half_t* t1 = talloc(c, M * r.cin);
-  CK(op_gn(c, xs1, xs2, C1, C2, n, HW, r.n1, G, eps, 1, t1, s1, s2));
-  half_t* t2 = talloc(c, M * r.cout);
-  const float* b1 = r.temb_off >= 0 ? c->bias_eff + r.temb_off : r.c1.b;
-  Stats st2;
-  CK(op_conv(c, t1, r.cin, nullptr, 0, n, H, W, r.c1, 1, 1, 0, b1, nullptr, t2, H, W, -1, nullptr, &st2));
-  half_t* t3 = talloc(c, M * r.cout);
-  CK(op_gn(c, t2, nullptr, r.cout, 0, n, HW, r.n2, G, eps, 1, t3, st2));
+  half_t* t3;
+  CKP(resnet_main(c, r, xs1, C1, xs2, C2, n, H, W, G, eps, s1, s2, &t3));
   half_t* hsrc = talloc(c, M * r.cout);
   CK(op_conv(c, t3, r.cout, nullptr, 0, n, H, W, r.c2, 1, 1, 0, r.c2.b, nullptr, hsrc, H, W));
   if (!r.has_sc) return fail(c, PNPI_ESHAPE, "Plug-and-Play conv injection: the site has no shortcut convolution");   // a decoder ResNet concatenates its skip: cin != cout
@@ -269,9 +271,9 @@ static int resnet_fwd_pnp(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C
 // The hooked attention forward of models/p2p/attention_control.py:20-47, literally: sim = q k^T * scale -> softmax -> controller(attn,
 // is_cross, place) -> attn v, with the probabilities materialised in fp32 for a host callback (level-1 fallback for controllers
 // without a descriptor).  One GEMM pair per (row, head); rows are not redirected (the callback does the editing).
-static int attn_materialized(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* vt, int ldv,
-                             half_t* o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, int is_cross, int place,
-                             int layer) {
+static int attn_materialized(pnpi_ctx* c, const AttnP& a, int B, int is_cross, int place, int layer) {
+  const half_t *q = a.q, *k = a.k, *vt = a.vt;
+  const int ldq = a.ldq, q_off = a.q_off, ldk = a.ldk, k_off = a.k_off, ldv = a.ldv, ldo = a.ldo, heads = a.heads, Nq = a.Nq, Nk = a.Nk, Dp = a.Dp, dh = a.dh;
   const int ldp = round_up_i(Nk, 8);
   const size_t need = align_up((size_t)B * heads * Nq * Nk * sizeof(float), 256);
   // the fp16 copy of one (row, head) probability block (the MFMA operand of P V) lives behind the fp32 tensor in the caller's buffer
@@ -283,7 +285,7 @@ static int attn_materialized(pnpi_ctx* c, const half_t* q, int ldq, int q_off, c
       float* S = c->attn_buf + ((size_t)b * heads + h) * Nq * Nk;
       VtOut v; v.outT = S; v.col0 = 0; v.ld = Nk; v.f32 = 1; v.rpb = Nk;      // outT[q][key] = scale * sum_d K[key][d] Q[q][d]
       CK(op_gemm(c, k + (size_t)b * Nk * ldk + k_off + h * Dp, ldk, Nk, Dp, q + (size_t)b * Nq * ldq + q_off + h * Dp, ldq, Nq, nullptr,
-                 nullptr, 0, nullptr, Nq, scale, &v));
+                 nullptr, 0, nullptr, Nq, a.scale, &v));
     }
   CK(launch_softmax_rows_f32(c->attn_buf, (size_t)B * heads * Nq, Nk, c->st));
   CKH(hipStreamSynchronize(c->st));                 // the callback is host code: it sees finished probabilities
@@ -293,136 +295,196 @@ static int attn_materialized(pnpi_ctx* c, const half_t* q, int ldq, int q_off, c
       const float* S = c->attn_buf + ((size_t)b * heads + h) * Nq * Nk;
       CK(launch_f32_rows_to_f16_padded(S, Nq, Nk, ldp, p16, c->st));
       CK(op_gemm(c, p16, ldp, Nq, ldp, vt + ((size_t)b * heads + h) * Dp * (size_t)ldv, ldv, dh, nullptr, nullptr, 0,
-                 o + (size_t)b * Nq * ldo + h * dh, ldo));
+                 a.o + (size_t)b * Nq * ldo + h * dh, ldo));
     }
   return 0;
 }
-
-// SpatialTransformer + BasicTransformerBlock (my_diffusers/models/attention.py:140-200) with the hooked attention of
-// models/p2p/attention_control.py:20-47 and the controller semantics of :178-190, :269-282 fused into the kernels.
-// which row table a transformer block's self-attention takes at this step: 0 identity, 1 self-replace, 2 MasaCtrl
-static int self_attn_mode(pnpi_ctx* c, bool use_ctrl, int cur_step, int block_index, int N) {
+static int op_ln(pnpi_ctx* c, const half_t* x, int M, int C, const NormW& nw, half_t* out) {
+  if (c->dry) return 0;
+  if (taping(c)) { TapeOp o; o.kind = TK_LN; o.x1 = x; o.M = M; o.C1 = C; o.nw = &nw; o.eps = 1e-5f; o.out = out; c->tape->ops.push_back(o); }
+  PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)C * 2.0, launch_layernorm(x, M, C, 1e-5f, nw.g, nw.b, out, c->st));
+  return 0;
+}
+// One attention site of a transformer block: the fields AttnP, CrossEditP and the tape's TK_ATTN record share, written once.  The caller
+// adds the row table (and vt_perm / aug / lse where the site has them).
+static AttnP attn_site(const TransformerW& t, const half_t* q, int ldq, const half_t* k, int ldk, int k_off, const half_t* vt, int ldv,
+                       half_t* o, int Nq, int Nk, float scale) {
+  AttnP a; a.q = q; a.ldq = ldq; a.q_off = 0; a.k = k; a.ldk = ldk; a.k_off = k_off; a.vt = vt; a.ldv = ldv; a.rows = nullptr; a.nrows = 0;
+  a.o = o; a.ldo = t.C; a.heads = t.heads; a.Nq = Nq; a.Nk = Nk; a.Dp = t.Dp; a.dh = t.dh; a.scale = scale;
+  return a;
+}
+static CrossEditP cross_edit_site(const AttnP& a) {
+  CrossEditP e; e.q = a.q; e.ldq = a.ldq; e.q_off = a.q_off; e.k = a.k; e.ldk = a.ldk; e.k_off = a.k_off; e.vt = a.vt; e.ldv = a.ldv;
+  e.o = a.o; e.ldo = a.ldo; e.heads = a.heads; e.Nq = a.Nq; e.Nk = a.Nk; e.Dp = a.Dp; e.dh = a.dh; e.scale = a.scale;
+  return e;
+}
+// the TK_ATTN record of site `a` over B rows; v: the plain-layout tensor a.vt is the transposed copy of
+static void tape_attn(pnpi_ctx* c, const AttnP& a, const half_t* v, int ldv, int v_off, int B) {
+  TapeOp o; o.kind = TK_ATTN; o.q = a.q; o.ldq = a.ldq; o.q_off = a.q_off; o.k = a.k; o.ldk = a.ldk; o.k_off = a.k_off; o.v = v; o.ldv = ldv; o.v_off = v_off;
+  o.out = a.o; o.ldo = a.ldo; o.heads = a.heads; o.Nq = a.Nq; o.Nk = a.Nk; o.Dp = a.Dp; o.dh = a.dh; o.scale = a.scale; o.B = B; o.lse = a.lse;
+  c->tape->ops.push_back(o);
+}
+// What a transformer block's self-attention does at this step, decided ahead of its launch.  form: one flash launch over `rows`; that
+// launch plus the class-restricted kernel over `rows_tgt` (mask-guided MasaCtrl: source rows and rows of other images take the plain
+// launch unchanged, every target row runs over its source row's K / V with this level's resized masks, pnpi_masa_set_masks); or the
+// materialised probabilities handed to the host callback.  table: which rows `rows` redirects.
+enum { SA_FLASH = 0, SA_FLASH_MASKED = 1, SA_CALLBACK = 2 };
+enum { ST_IDENTITY = 0, ST_REPLACE = 1, ST_MASA = 2, ST_MASA_MASKED = 3, ST_PNP = 4 };
+struct SelfAttn {
+  int form = SA_FLASH, table = ST_IDENTITY;
+  const int* rows = nullptr; int nrows = 0;
+  const int* rows_tgt = nullptr; int nrows_tgt = 0; AttnMaskP mask{};      // SA_FLASH_MASKED
+  int err = 0; const char* msg = nullptr;                                  // the combination is refused: fail(c, err, msg)
+};
+// B: the rows in hand; dedup: they are the distinct latents of a "cfg_dedup" first half, which only the identity table can serve
+static SelfAttn self_attn_resolve(pnpi_ctx* c, bool use_ctrl, int cur_step, int block_index, int H, int W, int B, bool dedup) {
   const CtrlDev& cd = c->cd;
-  const bool edit = use_ctrl && cd.any_edit;
-  if (edit && cur_step >= cd.self_lo && cur_step < cd.self_hi && N <= cd.self_max_tokens) return 1;
+  SelfAttn s; s.rows = cd.rows_id; s.nrows = B;
+  if (keep_acts(c)) return s;      // a recording forward: one prompt row, no controller, no callback
+  auto refuse = [&s](int err, const char* msg) { s.err = err; s.msg = msg; return s; };
   const bool masa_step = cd.masa_step_list ? (cur_step >= 0 && cur_step < (int)cd.masa_step_on.size() && cd.masa_step_on[cur_step]) : cur_step >= cd.masa_start_step;
   const bool masa_layer = cd.masa_layer_mask ? ((cd.masa_layer_mask >> block_index) & 1u) != 0 && block_index < 31 : block_index >= cd.masa_start_layer;
-  return (use_ctrl && cd.masa_any && masa_step && masa_layer) ? 2 : 0;
+  if (use_ctrl && cd.any_edit && cur_step >= cd.self_lo && cur_step < cd.self_hi && H * W <= cd.self_max_tokens) { s.table = ST_REPLACE; s.rows = cd.rows_rep; }
+  else if (use_ctrl && cd.masa_any && masa_step && masa_layer) { s.table = ST_MASA; s.rows = cd.rows_masa; }
+  const bool redirects = s.table != ST_IDENTITY;
+  if (dedup && (redirects || c->attn_cb)) return refuse(PNPI_ESTATE, "cfg_dedup: this block's self-attention redirects rows");
+  // Plug-and-Play q/k injection (run_editing_pnp.py:190-201): {r, src, src, r} for the rows of every image, at every token count
+  if (c->pnp.on && c->pnp.qk && block_index < 32 && ((c->pnp.qk_mask >> block_index) & 1u)) {
+    if (dedup || c->attn_cb || redirects || B != 3 * c->pnp.nimg)
+      return refuse(PNPI_ESTATE, "Plug-and-Play q/k injection does not combine with cfg_dedup, a host callback or a controller");
+    s.table = ST_PNP; s.rows = c->pnp.rows;
+  }
+  if (c->attn_cb) s.form = SA_CALLBACK;       // rows are not redirected there: the callback does the editing
+  else if (s.table == ST_MASA && cd.masa_masked && !c->dry) {
+    int lev = -1;
+    for (size_t l = 0; l < c->mm.side.size(); ++l) if (c->mm.side[l] == H && H == W) lev = (int)l;
+    if (lev < 0) return refuse(PNPI_ESTATE, "mask-guided MasaCtrl: no resized mask for this self-attention level");
+    s.form = SA_FLASH_MASKED; s.table = ST_MASA_MASKED;
+    s.rows = cd.rows_masa_plain; s.nrows = cd.n_masa_plain; s.rows_tgt = cd.rows_masa_tgt; s.nrows_tgt = cd.n_masa_tgt;
+    s.mask.kcls = c->mm.s_at(lev); s.mask.qcls = c->mm.t_at(lev); s.mask.mrow = cd.masa_tgt_img;
+  }
+  return s;
 }
-// dd (tuning "cfg_dedup"): x and sx hold dd->U rows, one per distinct latent of the B-row launch.  Everything up to the cross-attention
-// query reads no text, so it runs on those rows; hs1, q2 and x are then expanded to the B rows (row r = compact row dmap[r]) for the
-// second half.  Only for a block whose self-attention takes the identity row table at this step.
-static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, int B, int H, int W, const half_t* ctx16,
-                           bool use_ctrl, int cur_step, half_t* out, Stats sx = Stats(), Stats* so = nullptr, const TfDedup* dd = nullptr) {
-  const pnpi_model_config& g = c->cfg;
-  const size_t mk = c->temp.mark();
-  const int block_index = c->tf_index++;    // transformer blocks in execution order (down 0.., mid, up ..15)
-  const int C = t.C, N = H * W, hd = t.heads * t.Dp, X = g.cross_dim, T = g.ctx_len;
-  const float scale = 1.0f / sqrtf((float)t.dh);
-  CtrlDev& cd = c->cd;
-  const bool edit = use_ctrl && cd.any_edit;
-  const int Bf = B, Mf = B * N;              // rows of the launch; B, M: the rows in hand (dd: of the text-independent first half)
-  if (dd) B = dd->U;
-  int M = B * N;
-  if (dd && ((N * C) % 8 || (N * hd) % 8)) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
-  // the sizing dry run takes the plain path and adds the three expanded tensors of the deduplicated one on top of it
-  if (c->dry && block_index == 0) { (void)talloc(c, (size_t)M * C); (void)talloc(c, (size_t)M * C); (void)talloc(c, (size_t)M * hd); }
 
-  half_t* g0 = talloc(c, (size_t)M * C);
-  CK(op_gn(c, x, nullptr, C, 0, B, N, t.gn, g.norm_groups, 1e-6f, 0, g0, sx));
-  half_t* hs = talloc(c, (size_t)M * C);
-  CK(op_conv(c, g0, C, nullptr, 0, B, H, W, t.proj_in, 1, 0, 0, t.proj_in.b, nullptr, hs, H, W));
-
-  // ---- self-attention
+// SpatialTransformer + BasicTransformerBlock (my_diffusers/models/attention.py:140-200) with the hooked attention of
+// models/p2p/attention_control.py:20-47 and the controller semantics of :178-190, :269-282 fused into the kernels: four stages over
+// one TfBlock.  A recording forward (null-text path: one prompt row, no controller) runs the same stages; where the backward needs a
+// plain layout the stage branches on `rec`: q | k | v as one row-major projection output (V^T for the flash kernel is a transposed
+// COPY) with the log-sum-exp kept, the text K / V projected inside the forward from the context, GEGLU unfused.
+struct TfBlock {
+  const TransformerW& t;
+  int H, W, N, C, hd;      // the map, its tokens, channels, heads * Dp
+  int block_index;         // transformer blocks in execution order (down 0.., mid, up ..15)
+  float scale;
+  int B, M, Bf, Mf;        // the rows in hand and their tokens (dd: of the text-independent first half, until tf_cross_attn expands them); of the launch
+  const TfDedup* dd;
+  bool rec, use_ctrl;      // rec = keep_acts: every temporary stays, TapeOp records are pushed while taping
+  int cur_step;
+};
+// ---- GroupNorm + proj_in
+static int tf_enter(pnpi_ctx* c, const TfBlock& s, const half_t* x, Stats sx, half_t** hs) {
+  half_t* g0 = talloc(c, (size_t)s.M * s.C);
+  CK(op_gn(c, x, nullptr, s.C, 0, s.B, s.N, s.t.gn, c->cfg.norm_groups, 1e-6f, 0, g0, sx));
+  *hs = talloc(c, (size_t)s.M * s.C);
+  CK(op_conv(c, g0, s.C, nullptr, 0, s.B, s.H, s.W, s.t.proj_in, 1, 0, 0, s.t.proj_in.b, nullptr, *hs, s.H, s.W));
+  return 0;
+}
+// ---- self-attention: ln1, the q | k | v projection, the launch self_attn_resolve chose, o1 (+ hs)
+static int tf_self_attn(pnpi_ctx* c, const TfBlock& s, const half_t* hs, half_t** hs1) {
+  const TransformerW& t = s.t;
+  const int B = s.B, M = s.M, N = s.N, C = s.C, hd = s.hd;
   half_t* n1 = talloc(c, (size_t)M * C);
-  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)C * 2.0, launch_layernorm(hs, M, C, 1e-5f, t.ln1.g, t.ln1.b, n1, c->st));
-  half_t* qk = talloc(c, (size_t)M * 2 * hd);
+  CK(op_ln(c, hs, M, C, t.ln1, n1));
+  const int ldq = (s.rec ? 3 : 2) * hd;      // q | k, and recording | v
+  half_t* qkv = talloc(c, (size_t)M * ldq);
   const int ldv = round_up_i(N, 8);
   half_t* vt = talloc(c, (size_t)B * hd * ldv);
-  // call-back path: P V runs over the padded key count, so the pad columns of V^T must be zeros -- cleared BEFORE the projection fills
-  // the real columns (only the 2 x 2 level of the narrow test configurations has a token count that is not a multiple of 8)
-  if (c->attn_cb && !c->dry && ldv != N) CKH(hipMemsetAsync(vt, 0, (size_t)B * hd * ldv * sizeof(half_t), c->st));
-  // the 4096-token sites run the 64-wide LDS-DMA kernel, which reads V^T in the permuted key order (one ds_read_b128 per P V fragment):
-  // the projection's epilogue writes it that way (not under a host callback: the materialised path reads plain V^T)
-  const int vperm = (g_vt_perm && !c->attn_cb && N % 16 == 0 && attn_flash_uses_dma64(t.Dp, N, 0)) ? 1 : 0;
-  {
-    VtOut v; v.outT = vt; v.col0 = 2 * hd; v.ld = ldv; v.f32 = 0; v.rpb = N; v.perm16 = vperm;
-    CK(op_gemm(c, n1, C, M, C, t.w_qkv, C, 3 * hd, t.b_qkv_aug, nullptr, 0, qk, 2 * hd, 1.f, &v, 2.0 * M * 3.0 * C * C));
-  }
   half_t* ao = talloc(c, (size_t)M * C);
-  {
-    AttnP a; a.q = qk; a.ldq = 2 * hd; a.q_off = 0; a.k = qk; a.ldk = 2 * hd; a.k_off = hd; a.vt = vt; a.ldv = ldv; a.vt_perm = vperm;
-    a.aug = (t.b_qkv_aug && g_attn_aug) ? 1 : 0;      // K / V column dh hold 1.0 (the projection above added b_qkv_aug)
-    a.o = ao; a.ldo = C; a.heads = t.heads; a.Nq = N; a.Nk = N; a.Dp = t.Dp; a.dh = t.dh; a.scale = scale;
-    const int mode = self_attn_mode(c, use_ctrl, cur_step, block_index, N);
-    const bool rep = mode == 1, masa = mode == 2;
-    if (dd && (mode != 0 || c->attn_cb)) return fail(c, PNPI_ESTATE, "cfg_dedup: this block's self-attention redirects rows");
-    a.rows = rep ? cd.rows_rep : (masa ? cd.rows_masa : cd.rows_id); a.nrows = B;
-    // Plug-and-Play q/k injection (run_editing_pnp.py:190-201): {r, src, src, r} for the rows of every image, at every token count
-    if (c->pnp.on && c->pnp.qk && block_index < 32 && ((c->pnp.qk_mask >> block_index) & 1u)) {
-      if (dd || c->attn_cb || mode != 0 || B != 3 * c->pnp.nimg)
-        return fail(c, PNPI_ESTATE, "Plug-and-Play q/k injection does not combine with cfg_dedup, a host callback or a controller");
-      a.rows = c->pnp.rows;
-    }
-    c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * N * t.Dp;
-    if (c->attn_cb && !c->dry) {
-      CKP(attn_materialized(c, qk, 2 * hd, 0, qk, 2 * hd, hd, vt, ldv, ao, C, t.heads, N, N, t.Dp, t.dh, scale, B, 0, t.place, 2 * block_index));
-    } else if (!c->dry && masa && !rep && cd.masa_masked) {
-      // mask-guided MasaCtrl: source rows (and rows of other images) take the plain launch unchanged; every target row runs the
-      // class-restricted kernel over its source row's K / V with this level's resized masks (pnpi_masa_set_masks)
-      int lev = -1;
-      for (size_t l = 0; l < c->mm.side.size(); ++l) if (c->mm.side[l] == H && H == W) lev = (int)l;
-      if (lev < 0) return fail(c, PNPI_ESTATE, "mask-guided MasaCtrl: no resized mask for this self-attention level");
-      AttnP ap = a; ap.rows = cd.rows_masa_plain; ap.nrows = cd.n_masa_plain;
-      PROFD(PNPI_KC_ATTN_FLASH, 4.0 * ap.nrows * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash(ap, c->st));
-      AttnP am = a; am.rows = cd.rows_masa_tgt; am.nrows = cd.n_masa_tgt;
-      AttnMaskP mk; mk.kcls = c->mm.s_at(lev); mk.qcls = c->mm.t_at(lev); mk.mrow = cd.masa_tgt_img;
-      PROFD(PNPI_KC_ATTN_FLASH, 4.0 * am.nrows * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash_masked(am, mk, c->st));
-    } else if (!c->dry) PROFD(PNPI_KC_ATTN_FLASH, 4.0 * B * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash(a, c->st));
+  AttnP a = attn_site(t, qkv, ldq, qkv, ldq, hd, vt, ldv, ao, N, N, s.scale);
+  if (s.rec) {
+    a.lse = (float*)talloc(c, (size_t)B * t.heads * N * 2);       // per-query log-sum-exp for the backward kernel
+    CK(op_gemm(c, n1, C, M, C, t.w_qkv, C, 3 * hd, nullptr, nullptr, 0, qkv, 3 * hd));
+    for (int b = 0; b < B && !c->dry; ++b) CK(launch_transpose_f16(qkv + (size_t)b * N * 3 * hd + 2 * hd, 3 * hd, N, hd, vt + (size_t)b * hd * ldv, ldv, c->st));
+  } else {
+    // call-back path: P V runs over the padded key count, so the pad columns of V^T must be zeros -- cleared BEFORE the projection fills
+    // the real columns (only the 2 x 2 level of the narrow test configurations has a token count that is not a multiple of 8)
+    if (c->attn_cb && !c->dry && ldv != N) CKH(hipMemsetAsync(vt, 0, (size_t)B * hd * ldv * sizeof(half_t), c->st));
+    // the 4096-token sites run the 64-wide LDS-DMA kernel, which reads V^T in the permuted key order (one ds_read_b128 per P V fragment):
+    // the projection's epilogue writes it that way (not under a host callback: the materialised path reads plain V^T)
+    a.vt_perm = (g_vt_perm && !c->attn_cb && N % 16 == 0 && attn_flash_uses_dma64(t.Dp, N, 0)) ? 1 : 0;
+    a.aug = (t.b_qkv_aug && g_attn_aug) ? 1 : 0;      // K / V column dh hold 1.0 (the projection below adds b_qkv_aug)
+    VtOut v; v.outT = vt; v.col0 = 2 * hd; v.ld = ldv; v.f32 = 0; v.rpb = N; v.perm16 = a.vt_perm;
+    CK(op_gemm(c, n1, C, M, C, t.w_qkv, C, 3 * hd, t.b_qkv_aug, nullptr, 0, qkv, 2 * hd, 1.f, &v, 2.0 * M * 3.0 * C * C));
   }
-  half_t* hs1 = talloc(c, (size_t)M * C);
-  CK(op_gemm(c, ao, C, M, C, t.o1.w, C, C, t.o1.b, hs, C, hs1, C));
-
-  // ---- cross-attention
+  const SelfAttn sa = self_attn_resolve(c, s.use_ctrl, s.cur_step, s.block_index, s.H, s.W, B, s.dd != nullptr);
+  if (sa.err) return fail(c, sa.err, sa.msg);
+  a.rows = sa.rows; a.nrows = sa.nrows;
+  if (!s.rec || !c->dry) c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * N * t.Dp;      // the recording forward's sizing run has never counted its attention
+  if (!c->dry && sa.form == SA_CALLBACK) CKP(attn_materialized(c, a, B, 0, t.place, 2 * s.block_index));
+  else if (!c->dry) {
+    PROFD(PNPI_KC_ATTN_FLASH, 4.0 * a.nrows * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash(a, c->st));
+    if (sa.form == SA_FLASH_MASKED) {
+      AttnP am = a; am.rows = sa.rows_tgt; am.nrows = sa.nrows_tgt;
+      PROFD(PNPI_KC_ATTN_FLASH, 4.0 * am.nrows * t.heads * (double)N * N * t.dh, 0.0, N, N, t.Dp, launch_attn_flash_masked(am, sa.mask, c->st));
+    }
+    if (taping(c)) tape_attn(c, a, qkv, 3 * hd, 2 * hd, B);
+  }
+  *hs1 = talloc(c, (size_t)M * C);
+  CK(op_gemm(c, ao, C, M, C, t.o1.w, C, C, t.o1.b, hs, C, *hs1, C));
+  return 0;
+}
+// ---- cross-attention: ln2, q2, the text K / V (cached, or projected here), the launch, the controller's cross edit, o2 (+ hs1).  A
+// deduplicated block leaves its compact rows behind q2: *x, like s.B / s.M, goes out at the rows of the launch; the GEMM pin ends there.
+static int tf_cross_attn(pnpi_ctx* c, TfBlock& s, const half_t* ctx16, const half_t** x, const half_t* hs1, half_t** hs2) {
+  const TransformerW& t = s.t;
+  const CtrlDev& cd = c->cd;
+  const int N = s.N, C = s.C, hd = s.hd, X = c->cfg.cross_dim, T = c->cfg.ctx_len;
+  const bool edit = s.use_ctrl && cd.any_edit && !s.rec;
+  int B = s.B, M = s.M;
   half_t* n2 = talloc(c, (size_t)M * C);
-  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)C * 2.0, launch_layernorm(hs1, M, C, 1e-5f, t.ln2.g, t.ln2.b, n2, c->st));
+  CK(op_ln(c, hs1, M, C, t.ln2, n2));
   half_t* q2 = talloc(c, (size_t)M * hd);
   CK(op_gemm(c, n2, C, M, C, t.w_q2, C, hd, nullptr, nullptr, 0, q2, hd, 1.f, nullptr, 2.0 * M * (double)C * C));
-  if (dd) {            // from here on every row has its own text: the three tensors the second half reads, at the rows of the launch
+  if (const TfDedup* dd = s.dd) {      // from here on every row has its own text: the three tensors the second half reads, at the rows of the launch
     pin_base(c);
-    B = Bf; M = Mf;
+    B = s.B = s.Bf; M = s.M = s.Mf;
     half_t *hs1f = talloc(c, (size_t)M * C), *q2f = talloc(c, (size_t)M * hd), *xf = talloc(c, (size_t)M * C);
     CK(launch_gather_rows_f16(hs1, dd->dmap, B, (size_t)N * C, hs1f, c->st));
     CK(launch_gather_rows_f16(q2, dd->dmap, B, (size_t)N * hd, q2f, c->st));
-    CK(launch_gather_rows_f16(x, dd->dmap, B, (size_t)N * C, xf, c->st));
-    hs1 = hs1f; q2 = q2f; x = xf;
+    CK(launch_gather_rows_f16(*x, dd->dmap, B, (size_t)N * C, xf, c->st));
+    hs1 = hs1f; q2 = q2f; *x = xf;
   }
   const int ldv2 = round_up_i(T, 8);
+  const int ldk2 = (s.rec ? 2 : 1) * hd;      // k, and recording | v
   half_t *k2, *vt2;
-  if (c->tkv.use) {     // projected once per loop by text_kv_precompute
-    k2 = c->tkv.k[block_index]; vt2 = c->tkv.vt[block_index];
+  if (c->tkv.use) {     // projected once per loop by text_kv_precompute (never while recording)
+    k2 = c->tkv.k[s.block_index]; vt2 = c->tkv.vt[s.block_index];
   } else {
-    k2 = talloc(c, (size_t)B * T * hd);
+    k2 = talloc(c, (size_t)B * T * ldk2);
     vt2 = talloc(c, (size_t)B * hd * ldv2);
-    // call-back path: the P V product runs over the padded key count, so the pad columns of V^T must be zeros (not stale arena bytes)
-    if (c->attn_cb && !c->dry && ldv2 != T) CKH(hipMemsetAsync(vt2, 0, (size_t)B * hd * ldv2 * sizeof(half_t), c->st));
-    VtOut v; v.outT = vt2; v.col0 = hd; v.ld = ldv2; v.f32 = 0; v.rpb = T;
-    CK(op_gemm(c, ctx16, X, B * T, X, t.w_kv2, X, 2 * hd, nullptr, nullptr, 0, k2, hd, 1.f, &v, 2.0 * B * T * 2.0 * C * X));
+    if (s.rec) {
+      CK(op_gemm(c, ctx16, X, B * T, X, t.w_kv2, X, 2 * hd, nullptr, nullptr, 0, k2, 2 * hd));
+      for (int b = 0; b < B && !c->dry; ++b) CK(launch_transpose_f16(k2 + (size_t)b * T * 2 * hd + hd, 2 * hd, T, hd, vt2 + (size_t)b * hd * ldv2, ldv2, c->st));
+    } else {
+      // call-back path: the P V product runs over the padded key count, so the pad columns of V^T must be zeros (not stale arena bytes)
+      if (c->attn_cb && !c->dry && ldv2 != T) CKH(hipMemsetAsync(vt2, 0, (size_t)B * hd * ldv2 * sizeof(half_t), c->st));
+      VtOut v; v.outT = vt2; v.col0 = hd; v.ld = ldv2; v.f32 = 0; v.rpb = T;
+      CK(op_gemm(c, ctx16, X, B * T, X, t.w_kv2, X, 2 * hd, nullptr, nullptr, 0, k2, hd, 1.f, &v, 2.0 * B * T * 2.0 * C * X));
+    }
   }
   half_t* ao2 = talloc(c, (size_t)M * C);
-  {
-    AttnP a; a.q = q2; a.ldq = hd; a.q_off = 0; a.k = k2; a.ldk = hd; a.k_off = 0; a.vt = vt2; a.ldv = ldv2;
-    a.o = ao2; a.ldo = C; a.heads = t.heads; a.Nq = N; a.Nk = T; a.Dp = t.Dp; a.dh = t.dh; a.scale = scale;
-    a.rows = edit ? cd.rows_plain : cd.rows_id; a.nrows = edit ? cd.n_plain : B;
-    c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * 96 * t.Dp;
-    if (c->attn_cb && !c->dry) {
-      CKP(attn_materialized(c, q2, hd, 0, k2, hd, 0, vt2, ldv2, ao2, C, t.heads, N, T, t.Dp, t.dh, scale, B, 1, t.place, 2 * block_index + 1));
-    } else if (!c->dry) PROFD(PNPI_KC_ATTN_FLASH, 4.0 * a.nrows * t.heads * (double)N * T * t.dh, 0.0, N, T, t.Dp, launch_attn_flash(a, c->st));
-    if (edit && !c->dry && !c->attn_cb) {
-      CrossEditP e; e.q = q2; e.ldq = hd; e.q_off = 0; e.k = k2; e.ldk = hd; e.k_off = 0; e.vt = vt2; e.ldv = ldv2;
-      e.o = ao2; e.ldo = C; e.heads = t.heads; e.Nq = N; e.Nk = T; e.Dp = t.Dp; e.dh = t.dh; e.scale = scale;
+  AttnP a = attn_site(t, q2, hd, k2, ldk2, 0, vt2, ldv2, ao2, N, T, s.scale);
+  if (s.rec) a.lse = (float*)talloc(c, (size_t)B * t.heads * N * 2);
+  a.rows = edit ? cd.rows_plain : cd.rows_id; a.nrows = edit ? cd.n_plain : B;
+  if (!s.rec || !c->dry) c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * 96 * t.Dp;
+  if (!c->dry && c->attn_cb && !s.rec) CKP(attn_materialized(c, a, B, 1, t.place, 2 * s.block_index + 1));
+  else if (!c->dry) {
+    PROFD(PNPI_KC_ATTN_FLASH, 4.0 * a.nrows * t.heads * (double)N * T * t.dh, 0.0, N, T, t.Dp, launch_attn_flash(a, c->st));
+    if (taping(c)) tape_attn(c, a, k2, 2 * hd, hd, B);
+    if (edit) {
+      CrossEditP e = cross_edit_site(a);
       e.pairs = cd.pairs; e.npairs = cd.npairs; e.mmatT = cd.mmatT;
-      int srow = cur_step < cd.n_alpha_rows ? cur_step : cd.n_alpha_rows - 1;
+      int srow = s.cur_step < cd.n_alpha_rows ? s.cur_step : cd.n_alpha_rows - 1;
       e.c1 = cd.coef + ((size_t)srow * 2 + 0) * cd.npairs * 96;
       e.c2 = cd.coef + ((size_t)srow * 2 + 1) * cd.npairs * 96;
       const bool lb = cd.lb_any && t.lb_slot0 >= 0 && N == c->unet.lb_tokens;
@@ -432,120 +494,120 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
       PROF(PNPI_KC_ATTN_EDIT, 4.0 * 2 * cd.npairs * t.heads * (double)N * T * t.dh, 0.0, launch_attn_cross_edit(e, c->st));
     }
   }
-  half_t* hs2 = talloc(c, (size_t)M * C);
-  CK(op_gemm(c, ao2, C, M, C, t.o2.w, C, C, t.o2.b, hs1, C, hs2, C));
-
-  // ---- GEGLU feed-forward
+  *hs2 = talloc(c, (size_t)M * C);
+  CK(op_gemm(c, ao2, C, M, C, t.o2.w, C, C, t.o2.b, hs1, C, *hs2, C));
+  return 0;
+}
+// ---- GEGLU feed-forward and the exit: ln3, ff1 with the GEGLU product, ff2 (+ hs2), proj_out (+ x) -- or those two as one launch
+static int tf_ff_exit(pnpi_ctx* c, const TfBlock& s, const half_t* x, const half_t* hs2, half_t* out, Stats* so) {
+  const TransformerW& t = s.t;
+  const int B = s.B, M = s.M, C = s.C, H = s.H, W = s.W;
   half_t* n3 = talloc(c, (size_t)M * C);
-  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)C * 2.0, launch_layernorm(hs2, M, C, 1e-5f, t.ln3.g, t.ln3.b, n3, c->st));
+  CK(op_ln(c, hs2, M, C, t.ln3, n3));
+  half_t* f1 = s.rec ? talloc(c, (size_t)M * 8 * C) : nullptr;      // recorded ahead of f2
   half_t* f2 = talloc(c, (size_t)M * 4 * C);
-  if (C % 64 == 0) {
+  if (!s.rec && C % 64 == 0) {
     // ff1 GEMM with the GEGLU product in its epilogue: [M][8C] never exists in memory
     CK(op_gemm(c, n3, C, M, C, t.ff1.w, C, 8 * C, t.ff1.b, nullptr, 0, f2, 4 * C, 1.f, nullptr, -1.0, 1));
   } else {
-    // narrow test configurations: the interleaved projection is materialised and combined by a small kernel
-    half_t* f1 = talloc(c, (size_t)M * 8 * C);
+    // recording (the backward needs the gate pre-activation) and narrow test configurations: materialised, combined by a small kernel
+    if (!f1) f1 = talloc(c, (size_t)M * 8 * C);
     CK(op_gemm(c, n3, C, M, C, t.ff1.w, C, 8 * C, t.ff1.b, nullptr, 0, f1, 8 * C));
     if (!c->dry) PROF(PNPI_KC_GEGLU, 0.0, 12.0 * M * (double)C * 2.0, launch_geglu(f1, M, 4 * C, f2, c->st));
+    if (taping(c)) { TapeOp o; o.kind = TK_GEGLU; o.x1 = f1; o.out = f2; o.M = M; o.N = 4 * C; c->tape->ops.push_back(o); }
   }
-  Stats qo;
   // ff2 + proj_out as one two-source 1 x 1 convolution over f2 | hs2 (K = 4C + C: both parts are whole 64-wide k-chunks).  Only with
   // folded weights that match the loaded ones (ff_fold_ready); the sizing dry run takes the two-launch path, which needs more memory
-  // (hs3), so the knob can be flipped on a live context
-  const bool fold = g_ff_fold && !c->dry && C % 64 == 0 && t.fo.w && c->warena_ref && c->warena_ref->ff_fold_ready && !keep_acts(c);
-  if (fold) {
-    CK(op_conv(c, f2, 4 * C, hs2, C, B, H, W, t.fo, 1, 0, 0, t.fo.b, x, out, H, W, -1, nullptr, &qo));
-  } else {
+  // (hs3), so the knob can be flipped on a live context; a recording forward keeps hs3
+  const bool fold = g_ff_fold && !c->dry && C % 64 == 0 && t.fo.w && c->warena_ref && c->warena_ref->ff_fold_ready && !s.rec;
+  if (fold) CK(op_conv(c, f2, 4 * C, hs2, C, B, H, W, t.fo, 1, 0, 0, t.fo.b, x, out, H, W, -1, nullptr, so));
+  else {
     half_t* hs3 = talloc(c, (size_t)M * C);
     CK(op_gemm(c, f2, 4 * C, M, 4 * C, t.ff2.w, 4 * C, C, t.ff2.b, hs2, C, hs3, C));
-    CK(op_conv(c, hs3, C, nullptr, 0, B, H, W, t.proj_out, 1, 0, 0, t.proj_out.b, x, out, H, W, -1, nullptr, &qo));
+    CK(op_conv(c, hs3, C, nullptr, 0, B, H, W, t.proj_out, 1, 0, 0, t.proj_out.b, x, out, H, W, -1, nullptr, so));
   }
-  if (so) *so = qo;
-  c->temp.release(mk);
   return 0;
 }
 
-// The same block while a tape is recording (null-text path: one prompt row, no controller): every intermediate the backward needs is
-// kept in its plain layout -- q | k | v as one row-major projection output (V^T for the flash kernel is a transposed COPY), the text
-// K / V projected inside the forward from the context (their gradient is the point of the exercise), GEGLU unfused.
-static int op_ln(pnpi_ctx* c, const half_t* x, int M, int C, const NormW& nw, half_t* out) {
-  if (c->dry) return 0;
-  if (taping(c)) { TapeOp o; o.kind = TK_LN; o.x1 = x; o.M = M; o.C1 = C; o.nw = &nw; o.eps = 1e-5f; o.out = out; c->tape->ops.push_back(o); }
-  PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)C * 2.0, launch_layernorm(x, M, C, 1e-5f, nw.g, nw.b, out, c->st));
+// dd (tuning "cfg_dedup"): x and sx hold dd->U rows, one per distinct latent of the B-row launch.  Everything up to the cross-attention
+// query reads no text, so it runs on those rows; hs1, q2 and x are then expanded to the B rows (row r = compact row dmap[r]) for the
+// second half.  Only for a block whose self-attention takes the identity row table at this step.  so (nullable): the output's GroupNorm sums.
+static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, int B, int H, int W, const half_t* ctx16,
+                           bool use_ctrl, int cur_step, half_t* out, Stats sx, Stats* so, const TfDedup* dd = nullptr) {
+  const size_t mk = c->temp.mark();
+  const int N = H * W, hd = t.heads * t.Dp, U = dd ? dd->U : B;
+  TfBlock s{t, H, W, N, t.C, hd, c->tf_index++, 1.0f / sqrtf((float)t.dh), U, U * N, B, B * N, dd, keep_acts(c), use_ctrl, cur_step};
+  if (dd && ((N * s.C) % 8 || (N * hd) % 8)) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
+  // the sizing dry run takes the plain path and adds the three expanded tensors of the deduplicated one on top of it
+  if (c->dry && s.block_index == 0 && !s.rec) { (void)talloc(c, (size_t)s.M * s.C); (void)talloc(c, (size_t)s.M * s.C); (void)talloc(c, (size_t)s.M * hd); }
+  half_t *hs, *hs1, *hs2;
+  CKP(tf_enter(c, s, x, sx, &hs));
+  CKP(tf_self_attn(c, s, hs, &hs1));
+  CKP(tf_cross_attn(c, s, ctx16, &x, hs1, &hs2));      // behind it s and x are at the rows of the launch
+  CKP(tf_ff_exit(c, s, x, hs2, out, so));
+  if (!s.rec) c->temp.release(mk);      // a recording forward keeps every activation for the backward pass
   return 0;
 }
-static int transformer_fwd_tape(pnpi_ctx* c, const TransformerW& t, const half_t* x, int B, int H, int W, const half_t* ctx16, half_t* out) {
+// TimestepEmbedding + the 22 time_emb_proj linears as three GEMVs: sinusoid row `sin_row` (device [C0]) -> conv1 bias + time embedding
+// of every ResNet, `row` (device [temb_total])
+static int temb_bias_row(pnpi_ctx* c, const float* sin_row, float* row) {
+  const UNetW& u = c->unet;
+  const int C0 = c->cfg.block_out_channels[0], TE = 4 * C0;
+  CK(launch_gemv(sin_row, C0, u.t1.w, TE, u.t1.b, nullptr, 0, c->temb_h, c->st));
+  CK(launch_gemv(c->temb_h, TE, u.t2.w, TE, u.t2.b, nullptr, 1, c->temb_emb, c->st));
+  CK(launch_gemv(c->temb_emb, TE, u.temb_w, u.temb_total, u.temb_b, u.conv1_b, 1, row, c->st));
+  return 0;
+}
+// A transformer block of the UNet behind *h (B rows of C channels): *h becomes its output and *s, the GroupNorm partial sums that travel
+// with *h, those of the output.  A recording forward neither consumes nor produces them.
+static int unet_transformer(pnpi_ctx* c, const TransformerW& t, half_t** h, int B, int H, int C, const half_t* ctx16, bool use_ctrl,
+                            int cur_step, Stats* s) {
+  half_t* out = palloc(c, (size_t)B * H * H * C);
+  const Stats sx = keep_acts(c) ? Stats() : *s;
+  *s = Stats();
+  CKP(transformer_fwd(c, t, *h, B, H, H, ctx16, use_ctrl, cur_step, out, sx, keep_acts(c) ? nullptr : s));
+  *h = out;
+  return 0;
+}
+// The text-independent prefix once per distinct latent (tuning "cfg_dedup"): conv_in, down_res[0][0] and, while block 0's self-attention
+// takes the identity row table, the first half of down_attn[0][0] on the ud.U rows of ud.lat_u.  *h / *hs: down_attn[0][0]'s B-row output.
+static int unet_dedup_prefix(pnpi_ctx* c, const UNetDedup& ud, int B, const half_t* ctx16, bool use_ctrl, int cur_step, half_t** h, Stats* hs) {
   const pnpi_model_config& g = c->cfg;
-  c->tf_index++;
-  const int C = t.C, N = H * W, M = B * N, hd = t.heads * t.Dp, X = g.cross_dim, T = g.ctx_len;
-  const float scale = 1.0f / sqrtf((float)t.dh);
-  half_t* g0 = talloc(c, (size_t)M * C);
-  CK(op_gn(c, x, nullptr, C, 0, B, N, t.gn, g.norm_groups, 1e-6f, 0, g0));
-  half_t* hs = talloc(c, (size_t)M * C);
-  CK(op_conv(c, g0, C, nullptr, 0, B, H, W, t.proj_in, 1, 0, 0, t.proj_in.b, nullptr, hs, H, W));
-  // ---- self-attention
-  half_t* n1 = talloc(c, (size_t)M * C);
-  CK(op_ln(c, hs, M, C, t.ln1, n1));
-  half_t* qkv = talloc(c, (size_t)M * 3 * hd);
-  CK(op_gemm(c, n1, C, M, C, t.w_qkv, C, 3 * hd, nullptr, nullptr, 0, qkv, 3 * hd));
-  const int ldv = round_up_i(N, 8);
-  half_t* vt = talloc(c, (size_t)B * hd * ldv);
-  half_t* ao = talloc(c, (size_t)M * C);
-  float* lse1 = (float*)talloc(c, (size_t)B * t.heads * N * 2);       // per-query log-sum-exp for the backward kernel
-  if (!c->dry) {
-    for (int b = 0; b < B; ++b) CK(launch_transpose_f16(qkv + (size_t)b * N * 3 * hd + 2 * hd, 3 * hd, N, hd, vt + (size_t)b * hd * ldv, ldv, c->st));
-    AttnP a; a.q = qkv; a.ldq = 3 * hd; a.q_off = 0; a.k = qkv; a.ldk = 3 * hd; a.k_off = hd; a.vt = vt; a.ldv = ldv;
-    a.o = ao; a.ldo = C; a.heads = t.heads; a.Nq = N; a.Nk = N; a.Dp = t.Dp; a.dh = t.dh; a.scale = scale; a.rows = c->cd.rows_id; a.nrows = B;
-    a.lse = lse1;
-    CK(launch_attn_flash(a, c->st));
-    c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * N * t.Dp;
-    if (taping(c)) {
-      TapeOp o; o.kind = TK_ATTN; o.q = qkv; o.ldq = 3 * hd; o.q_off = 0; o.k = qkv; o.ldk = 3 * hd; o.k_off = hd; o.v = qkv; o.ldv = 3 * hd; o.v_off = 2 * hd;
-      o.out = ao; o.ldo = C; o.heads = t.heads; o.Nq = N; o.Nk = N; o.Dp = t.Dp; o.dh = t.dh; o.scale = scale; o.B = B; o.lse = lse1;
-      c->tape->ops.push_back(o);
+  const UNetW& u = c->unet;
+  const int U = ud.U, H = g.sample_size, C0 = g.block_out_channels[0], oc = C0;
+  half_t* x0c = palloc(c, (size_t)U * H * H * 8);
+  CK(launch_nchw_f32_to_nhwc_f16(ud.lat_u, U, g.in_channels, H * H, 8, x0c, c->st));
+  // pinned row sharing: the compact prefix makes the choices of the logical launch's prefix (all rows under cfg_dedup = 2, its
+  // distinct latents under 1)
+  if (c->share_pin && c->share_U > 0) { c->pin_from = U; c->pin_to = g_cfg_dedup == 2 ? c->share_to : c->share_U; }
+  else if (g_cfg_dedup == 2) { c->pin_from = U; c->pin_to = B; }
+  half_t* hc = palloc(c, (size_t)U * H * H * C0);
+  Stats hcs, rcs;
+  CK(op_conv(c, x0c, 8, nullptr, 0, U, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, hc, H, H, -1, nullptr, &hcs));
+  half_t* rc = palloc(c, (size_t)U * H * H * oc);
+  CKP(resnet_fwd(c, u.down_res[0][0], hc, C0, nullptr, 0, U, H, H, g.norm_groups, 1e-5f, rc, hcs, Stats(), &rcs));
+  half_t* o2 = palloc(c, (size_t)B * H * H * oc);
+  if (self_attn_resolve(c, use_ctrl, cur_step, c->tf_index, H, H, U, false).table == ST_IDENTITY) {
+    const TfDedup td{U, ud.dmap};
+    CKP(transformer_fwd(c, u.down_attn[0][0], rc, B, H, H, ctx16, use_ctrl, cur_step, o2, rcs, hs, &td));   // unpins after its first half
+  } else {
+    // the self-attention redirects rows at this step: the prefix ends behind the ResNet, whose output and per-image GroupNorm
+    // partial sums are expanded to the rows of the launch
+    pin_base(c);
+    if (((size_t)H * H * oc) % 8) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
+    half_t* o = palloc(c, (size_t)B * H * H * oc);
+    CK(launch_gather_rows_f16(rc, ud.dmap, B, (size_t)H * H * oc, o, c->st));
+    Stats os;
+    if (rcs.p && rcs.rows > 0 && (H * H) % rcs.rows == 0) {
+      float* sp = stats_alloc(c, B * H * H, oc);
+      CK(launch_gather_rows_f32(rcs.p, ud.dmap, B, (size_t)(H * H / rcs.rows) * oc * 2, sp, c->st));
+      os.p = sp; os.rows = rcs.rows;
     }
+    CKP(transformer_fwd(c, u.down_attn[0][0], o, B, H, H, ctx16, use_ctrl, cur_step, o2, os, hs));
   }
-  half_t* hs1 = talloc(c, (size_t)M * C);
-  CK(op_gemm(c, ao, C, M, C, t.o1.w, C, C, t.o1.b, hs, C, hs1, C));
-  // ---- cross-attention
-  half_t* n2 = talloc(c, (size_t)M * C);
-  CK(op_ln(c, hs1, M, C, t.ln2, n2));
-  half_t* q2 = talloc(c, (size_t)M * hd);
-  CK(op_gemm(c, n2, C, M, C, t.w_q2, C, hd, nullptr, nullptr, 0, q2, hd));
-  half_t* kv2 = talloc(c, (size_t)B * T * 2 * hd);
-  CK(op_gemm(c, ctx16, X, B * T, X, t.w_kv2, X, 2 * hd, nullptr, nullptr, 0, kv2, 2 * hd));
-  const int ldv2 = round_up_i(T, 8);
-  half_t* vt2 = talloc(c, (size_t)B * hd * ldv2);
-  half_t* ao2 = talloc(c, (size_t)M * C);
-  float* lse2 = (float*)talloc(c, (size_t)B * t.heads * N * 2);
-  if (!c->dry) {
-    for (int b = 0; b < B; ++b) CK(launch_transpose_f16(kv2 + (size_t)b * T * 2 * hd + hd, 2 * hd, T, hd, vt2 + (size_t)b * hd * ldv2, ldv2, c->st));
-    AttnP a; a.q = q2; a.ldq = hd; a.q_off = 0; a.k = kv2; a.ldk = 2 * hd; a.k_off = 0; a.vt = vt2; a.ldv = ldv2;
-    a.o = ao2; a.ldo = C; a.heads = t.heads; a.Nq = N; a.Nk = T; a.Dp = t.Dp; a.dh = t.dh; a.scale = scale; a.rows = c->cd.rows_id; a.nrows = B;
-    a.lse = lse2;
-    CK(launch_attn_flash(a, c->st));
-    c->ctr.executed_attn_flops += 4.0 * B * t.heads * (double)N * 96 * t.Dp;
-    if (taping(c)) {
-      TapeOp o; o.kind = TK_ATTN; o.q = q2; o.ldq = hd; o.q_off = 0; o.k = kv2; o.ldk = 2 * hd; o.k_off = 0; o.v = kv2; o.ldv = 2 * hd; o.v_off = hd;
-      o.out = ao2; o.ldo = C; o.heads = t.heads; o.Nq = N; o.Nk = T; o.Dp = t.Dp; o.dh = t.dh; o.scale = scale; o.B = B; o.lse = lse2;
-      c->tape->ops.push_back(o);
-    }
-  }
-  half_t* hs2 = talloc(c, (size_t)M * C);
-  CK(op_gemm(c, ao2, C, M, C, t.o2.w, C, C, t.o2.b, hs1, C, hs2, C));
-  // ---- GEGLU feed-forward (unfused: the gate pre-activation is needed for its derivative)
-  half_t* n3 = talloc(c, (size_t)M * C);
-  CK(op_ln(c, hs2, M, C, t.ln3, n3));
-  half_t* f1 = talloc(c, (size_t)M * 8 * C);
-  CK(op_gemm(c, n3, C, M, C, t.ff1.w, C, 8 * C, t.ff1.b, nullptr, 0, f1, 8 * C));
-  half_t* f2 = talloc(c, (size_t)M * 4 * C);
-  if (!c->dry) {
-    CK(launch_geglu(f1, M, 4 * C, f2, c->st));
-    if (taping(c)) { TapeOp o; o.kind = TK_GEGLU; o.x1 = f1; o.out = f2; o.M = M; o.N = 4 * C; c->tape->ops.push_back(o); }
-  }
-  half_t* hs3 = talloc(c, (size_t)M * C);
-  CK(op_gemm(c, f2, 4 * C, M, 4 * C, t.ff2.w, 4 * C, C, t.ff2.b, hs2, C, hs3, C));
-  CK(op_conv(c, hs3, C, nullptr, 0, B, H, W, t.proj_out, 1, 0, 0, t.proj_out.b, x, out, H, W));
+  pin_base(c);
+  c->ctr.unet_dedup_prefix_rows += c->share_U > U ? c->share_U : U;      // under row sharing: the logical latents served (a mirrored full launch runs them all)
+  *h = o2;
   return 0;
 }
 
@@ -562,7 +624,7 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   if (!temb_row && (t < 0 || t >= g.n_train_timesteps)) return fail(c, PNPI_EINVAL, "timestep out of range");
   c->persist.reset(); c->temp.reset();
   c->tf_index = 0;
-  const int S = g.sample_size, n = g.n_blocks, C0 = g.block_out_channels[0], TE = 4 * C0, G = g.norm_groups;
+  const int S = g.sample_size, n = g.n_blocks, C0 = g.block_out_channels[0], G = g.norm_groups;
   const int B = rows;
   const float eps = 1e-5f;
   half_t* x0 = palloc(c, (size_t)B * S * S * 8);
@@ -579,33 +641,14 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
       if (!context) return fail(c, PNPI_EINVAL, "context is NULL and no text K/V cache is active");
       CK(launch_f32_to_f16(context, (size_t)B * g.ctx_len * g.cross_dim, ctx16, c->st));
     }
-    // conv1 bias + time embedding of every ResNet for this timestep (TimestepEmbedding + the 22 time_emb_proj linears as three
-    // GEMVs): a function of t and the weights only -> computed on the first forward at t, then read from the table
-    if (temb_row) {
-      float* row = bias_row ? bias_row : c->bias_scratch;
-      CK(launch_gemv(temb_row, C0, u.t1.w, TE, u.t1.b, nullptr, 0, c->temb_h, c->st));
-      CK(launch_gemv(c->temb_h, TE, u.t2.w, TE, u.t2.b, nullptr, 1, c->temb_emb, c->st));
-      CK(launch_gemv(c->temb_emb, TE, u.temb_w, u.temb_total, u.temb_b, u.conv1_b, 1, row, c->st));
-      c->bias_eff = row;
-    } else if (c->bias_tab && g_temb_cache) {
-      float* row = c->bias_tab + (size_t)t * u.temb_total;
-      if (!c->bias_valid[t]) {
-        CK(launch_gemv(c->temb_table + (size_t)t * C0, C0, u.t1.w, TE, u.t1.b, nullptr, 0, c->temb_h, c->st));
-        CK(launch_gemv(c->temb_h, TE, u.t2.w, TE, u.t2.b, nullptr, 1, c->temb_emb, c->st));
-        CK(launch_gemv(c->temb_emb, TE, u.temb_w, u.temb_total, u.temb_b, u.conv1_b, 1, row, c->st));
-        c->bias_valid[t] = 1;
-      }
-      c->bias_eff = row;
-    } else {
-      CK(launch_gemv(c->temb_table + (size_t)t * C0, C0, u.t1.w, TE, u.t1.b, nullptr, 0, c->temb_h, c->st));
-      CK(launch_gemv(c->temb_h, TE, u.t2.w, TE, u.t2.b, nullptr, 1, c->temb_emb, c->st));
-      CK(launch_gemv(c->temb_emb, TE, u.temb_w, u.temb_total, u.temb_b, u.conv1_b, 1, c->bias_scratch, c->st));
-      c->bias_eff = c->bias_scratch;
-    }
+    // conv1 bias + time embedding of every ResNet for this timestep: a function of t and the weights only -> computed on the first
+    // forward at t, then read from the table (not for a caller's row)
+    const bool cached = !temb_row && c->bias_tab && g_temb_cache;
+    c->bias_eff = cached ? c->bias_tab + (size_t)t * u.temb_total : (temb_row && bias_row) ? bias_row : c->bias_scratch;
+    if (!cached || !c->bias_valid[t]) CKP(temb_bias_row(c, temb_row ? temb_row : c->temb_table + (size_t)t * C0, c->bias_eff));
+    if (cached) c->bias_valid[t] = 1;
   }
-  // The text-independent prefix once per distinct latent (tuning "cfg_dedup"): conv_in, down_res[0][0] and, while block 0's
-  // self-attention takes the identity row table, the first half of down_attn[0][0].  Not for a recording forward (the tape walks
-  // full-row records), under a host attention callback, or in the sizing dry run (which sizes for both paths instead).
+  // unet_dedup_prefix: no recording forward (the tape walks full-row records), host callback or sizing dry run (which sizes for both paths)
   bool dedup = ud && g_cfg_dedup && !c->dry && ud->U > 0 && ud->U < rows && g.block_has_attn[0] && !keep_acts(c) && !c->attn_cb &&
                ud->lat_u && ud->hmap && ud->dmap && !c->pnp.on;      // the Plug-and-Play layout [source, x, x] redirects rows: never deduplicated
   if (c->pnp.on && (c->share_U > 0 || keep_acts(c) || c->attn_cb || use_ctrl || rows != 3 * c->pnp.nimg))
@@ -628,54 +671,16 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   for (int i = 0; i < n; ++i) {
     const int oc = g.block_out_channels[i];
     for (int j = 0; j < g.layers_per_block; ++j) {
-      if (dedup && i == 0 && j == 0) {
-        const int U = ud->U;
-        half_t* x0c = palloc(c, (size_t)U * S * S * 8);
-        CK(launch_nchw_f32_to_nhwc_f16(ud->lat_u, U, g.in_channels, S * S, 8, x0c, c->st));
-        // pinned row sharing: the compact prefix makes the choices of the logical launch's prefix (all rows under cfg_dedup = 2, its
-        // distinct latents under 1)
-        if (c->share_pin && c->share_U > 0) { c->pin_from = U; c->pin_to = g_cfg_dedup == 2 ? c->share_to : c->share_U; }
-        else if (g_cfg_dedup == 2) { c->pin_from = U; c->pin_to = B; }
-        half_t* hc = palloc(c, (size_t)U * H * H * C0);
-        Stats hcs, rcs, ns;
-        CK(op_conv(c, x0c, 8, nullptr, 0, U, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, hc, H, H, -1, nullptr, &hcs));
-        half_t* rc = palloc(c, (size_t)U * H * H * oc);
-        CKP(resnet_fwd(c, u.down_res[0][0], hc, ch, nullptr, 0, U, H, H, G, eps, rc, hcs, Stats(), &rcs));
-        half_t* o2 = palloc(c, (size_t)B * H * H * oc);
-        if (self_attn_mode(c, use_ctrl, cur_step, c->tf_index, H * H) == 0) {
-          const TfDedup td{U, ud->dmap};
-          CKP(transformer_fwd(c, u.down_attn[0][0], rc, B, H, H, ctx16, use_ctrl, cur_step, o2, rcs, &ns, &td));   // unpins after its first half
-        } else {
-          // the self-attention redirects rows at this step: the prefix ends behind the ResNet, whose output and per-image GroupNorm
-          // partial sums are expanded to the rows of the launch
-          pin_base(c);
-          if (((size_t)H * H * oc) % 8) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
-          half_t* o = palloc(c, (size_t)B * H * H * oc);
-          CK(launch_gather_rows_f16(rc, ud->dmap, B, (size_t)H * H * oc, o, c->st));
-          Stats os;
-          if (rcs.p && rcs.rows > 0 && (H * H) % rcs.rows == 0) {
-            float* sp = stats_alloc(c, B * H * H, oc);
-            CK(launch_gather_rows_f32(rcs.p, ud->dmap, B, (size_t)(H * H / rcs.rows) * oc * 2, sp, c->st));
-            os.p = sp; os.rows = rcs.rows;
-          }
-          CKP(transformer_fwd(c, u.down_attn[0][0], o, B, H, H, ctx16, use_ctrl, cur_step, o2, os, &ns));
-        }
-        pin_base(c);
-        c->ctr.unet_dedup_prefix_rows += c->share_U > U ? c->share_U : U;      // under row sharing: the logical latents served (a mirrored full launch runs them all)
-        h = o2; ch = oc; hs_ = ns;
+      if (dedup && i == 0 && j == 0) {      // down_res[0][0] and down_attn[0][0], their text-independent part on the distinct latents
+        CKP(unet_dedup_prefix(c, *ud, B, ctx16, use_ctrl, cur_step, &h, &hs_));
+        ch = oc;
         skips.push_back({h, ch, H, hs_});
         continue;
       }
       half_t* o = palloc(c, (size_t)B * H * H * oc);
-      Stats ns;
-      CKP(resnet_fwd(c, u.down_res[i][j], h, ch, nullptr, 0, B, H, H, G, eps, o, hs_, Stats(), &ns));
-      h = o; ch = oc; hs_ = ns;
-      if (g.block_has_attn[i]) {
-        half_t* o2 = palloc(c, (size_t)B * H * H * oc);
-        if (keep_acts(c)) { CKP(transformer_fwd_tape(c, u.down_attn[i][j], h, B, H, H, ctx16, o2)); ns = Stats(); }
-        else CKP(transformer_fwd(c, u.down_attn[i][j], h, B, H, H, ctx16, use_ctrl, cur_step, o2, hs_, &ns));
-        h = o2; hs_ = ns;
-      }
+      CKP(resnet_fwd(c, u.down_res[i][j], h, ch, nullptr, 0, B, H, H, G, eps, o, hs_, Stats(), &hs_));
+      h = o; ch = oc;
+      if (g.block_has_attn[i]) CKP(unet_transformer(c, u.down_attn[i][j], &h, B, H, oc, ctx16, use_ctrl, cur_step, &hs_));
       skips.push_back({h, ch, H, hs_});
     }
     if (i != n - 1) {
@@ -688,31 +693,24 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   }
   {
     half_t* o = palloc(c, (size_t)B * H * H * ch);
-    Stats n1, n2, n3;
-    CKP(resnet_fwd(c, u.mid_res[0], h, ch, nullptr, 0, B, H, H, G, eps, o, hs_, Stats(), &n1));
-    half_t* o2 = palloc(c, (size_t)B * H * H * ch);
-    if (keep_acts(c)) { CKP(transformer_fwd_tape(c, u.mid_attn, o, B, H, H, ctx16, o2)); n2 = Stats(); }
-    else CKP(transformer_fwd(c, u.mid_attn, o, B, H, H, ctx16, use_ctrl, cur_step, o2, n1, &n2));
+    CKP(resnet_fwd(c, u.mid_res[0], h, ch, nullptr, 0, B, H, H, G, eps, o, hs_, Stats(), &hs_));
+    CKP(unet_transformer(c, u.mid_attn, &o, B, H, ch, ctx16, use_ctrl, cur_step, &hs_));
     half_t* o3 = palloc(c, (size_t)B * H * H * ch);
-    CKP(resnet_fwd(c, u.mid_res[1], o2, ch, nullptr, 0, B, H, H, G, eps, o3, n2, Stats(), &n3));
-    h = o3; hs_ = n3;
+    CKP(resnet_fwd(c, u.mid_res[1], o, ch, nullptr, 0, B, H, H, G, eps, o3, hs_, Stats(), &hs_));
+    h = o3;
   }
   for (int i = 0; i < n; ++i) {
     const int oc = g.block_out_channels[n - 1 - i];
     for (int j = 0; j <= g.layers_per_block; ++j) {
       Act s = skips.back(); skips.pop_back();
       half_t* o = palloc(c, (size_t)B * H * H * oc);
-      Stats ns;
-      if (c->pnp.on && c->pnp.conv && c->pnp.up_res_index == c->pnp.conv_site) CKP(resnet_fwd_pnp(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s));
-      else CKP(resnet_fwd(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s, &ns));
+      if (c->pnp.on && c->pnp.conv && c->pnp.up_res_index == c->pnp.conv_site) {      // leaves no GroupNorm partial sums
+        CKP(resnet_fwd_pnp(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s));
+        hs_ = Stats();
+      } else CKP(resnet_fwd(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s, &hs_));
       c->pnp.up_res_index++;
-      h = o; ch = oc; hs_ = ns;
-      if (g.block_has_attn[n - 1 - i]) {
-        half_t* o2 = palloc(c, (size_t)B * H * H * oc);
-        if (keep_acts(c)) { CKP(transformer_fwd_tape(c, u.up_attn[i][j], h, B, H, H, ctx16, o2)); ns = Stats(); }
-        else CKP(transformer_fwd(c, u.up_attn[i][j], h, B, H, H, ctx16, use_ctrl, cur_step, o2, hs_, &ns));
-        h = o2; hs_ = ns;
-      }
+      h = o; ch = oc;
+      if (g.block_has_attn[n - 1 - i]) CKP(unet_transformer(c, u.up_attn[i][j], &h, B, H, oc, ctx16, use_ctrl, cur_step, &hs_));
     }
     if (i != n - 1) {
       const int Ho = H * 2;
@@ -731,169 +729,5 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   c->ctr.unet_sample_forwards += c->dry ? 0 : rows;
   c->ctr.unet_sample_forwards_cached_kv += (c->dry || !c->tkv.use) ? 0 : rows;
   if (c->persist.overflow || c->temp.overflow) return fail(c, PNPI_ENOMEM, "workspace overflow");
-  return 0;
-}
-
-// Attention backward, materialised per (row, head) like the call-back path's forward (first version: generic GEMM launches and
-// transposes; a fused flash backward replaces it later).  q / k: [B*N][ld] views with the head's columns at off + h * Dp (pad columns
-// dh .. Dp are zero, as the forward guarantees); v: plain [B*Nk][ldvp] with the same head layout; d_o: [B*Nq][ldo], heads * dh wide.
-// Outputs dq / dk / dv in the layout of q / k / v (their pad columns are left untouched: clear the buffers first).
-//   S = scale q k^T, P = softmax(S);  dV = P^T dO;  dP = dO V^T;  dS = scale P (dP - rowsum(dP P));  dQ = dS K;  dK = dS^T Q.
-// scratch: Nq * Nk * 8 (S / P and dP, fp32) + 2 * Nq * ldp * 2 (P, dS as fp16) + 2 * Nk * ldq8 * 2 (their transposes) + dh * (ldp + 2 * ldq8) * 2
-// bytes (K^T, Q^T, dO^T), reused for every (row, head).
-static size_t attn_bwd_scratch_bytes(int Nq, int Nk, int dh) {
-  const size_t ldp = round_up_i(Nk, 8), ldq8 = round_up_i(Nq, 8);
-  return align_up((size_t)Nq * Nk * 4, 256) * 2 + align_up((size_t)Nq * ldp * 2, 256) * 2 + align_up((size_t)Nk * ldq8 * 2, 256) * 2 +
-         align_up((size_t)dh * ldp * 2, 256) + align_up((size_t)dh * ldq8 * 2, 256) * 2;
-}
-static int attn_bwd_materialized(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp,
-                                 int v_off, const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B,
-                                 half_t* dq, half_t* dk, half_t* dv, void* scratch, size_t scratch_bytes) {
-  const size_t per = attn_bwd_scratch_bytes(Nq, Nk, dh);
-  if (!scratch || scratch_bytes < per) return fail(c, PNPI_ENOMEM, "attention backward scratch too small");
-  if ((dh & 7) || (ldq & 7) || (ldk & 7) || (ldvp & 7) || (ldo & 7)) return fail(c, PNPI_ESHAPE, "attention backward: extents must be multiples of 8");
-  const int ldp = round_up_i(Nk, 8), ldq8 = round_up_i(Nq, 8);
-  // The heads of a row are independent problems of one shape: every step below is ONE launch over a group of `nb` heads (as many as
-  // the scratch holds; all of them with the tape's own scratch) -- a batched GEMM (grid z = head) or a row-wise kernel over nb * Nq rows.
-  // Head by head the same work was 13 launches of a few microseconds each per head: 3 300 launches per reverse walk.
-  const int nb_max = (int)std::min<size_t>((size_t)heads, scratch_bytes / per);
-  const size_t szS = align_up((size_t)Nq * Nk * 4, 256), szP = align_up((size_t)Nq * ldp * 2, 256), szT = align_up((size_t)Nk * ldq8 * 2, 256),
-               szK = align_up((size_t)dh * ldp * 2, 256), szQ = align_up((size_t)dh * ldq8 * 2, 256);
-  for (int b = 0; b < B; ++b)
-    for (int h0 = 0; h0 < heads; h0 += nb_max) {
-      const int nb = std::min(nb_max, heads - h0);
-      char* sp = (char*)scratch;
-      auto take = [&](size_t bytes_each) { char* r = sp; sp += bytes_each * nb; return r; };     // [nb] consecutive per-head buffers
-      float* S = (float*)take(szS);
-      float* dP = (float*)take(szS);
-      half_t* P16 = (half_t*)take(szP);
-      half_t* dS16 = (half_t*)take(szP);
-      half_t* PT = (half_t*)take(szT);
-      half_t* dST = (half_t*)take(szT);
-      half_t* Kt = (half_t*)take(szK);
-      half_t* Qt = (half_t*)take(szQ);
-      half_t* dOt = (half_t*)take(szQ);
-      const long eS = (long)(szS / 4), eP = (long)(szP / 2), eT = (long)(szT / 2), eK = (long)(szK / 2), eQ = (long)(szQ / 2);   // per-head strides in elements
-      const half_t* qh = q + (size_t)b * Nq * ldq + q_off + h0 * Dp;
-      const half_t* kh = k + (size_t)b * Nk * ldk + k_off + h0 * Dp;
-      const half_t* vh = v + (size_t)b * Nk * ldvp + v_off + h0 * Dp;
-      const half_t* doh = d_o + (size_t)b * Nq * ldo + h0 * dh;
-      GemmBatch gb; gb.n = nb;
-      VtOut vs; vs.outT = S; vs.col0 = 0; vs.ld = Nk; vs.f32 = 1; vs.rpb = Nk;            // S[q][key] = scale * sum_d k[key][d] q[q][d]
-      gb.sa = Dp; gb.sw = Dp; gb.sout = 0; gb.soutT = (long)szS;
-      CK(op_gemm(c, kh, ldk, Nk, dh, qh, ldq, Nq, nullptr, nullptr, 0, nullptr, Nq, scale, &vs, -1.0, 0, &gb));
-      VtOut vp; vp.outT = dP; vp.col0 = 0; vp.ld = Nk; vp.f32 = 1; vp.rpb = Nk;          // dP[q][key] = sum_d v[key][d] dO[q][d]
-      gb.sa = Dp; gb.sw = dh;
-      CK(op_gemm(c, vh, ldvp, Nk, dh, doh, ldo, Nq, nullptr, nullptr, 0, nullptr, Nq, 1.f, &vp, -1.0, 0, &gb));
-      if (szS == (size_t)Nq * Nk * 4 && szP == (size_t)Nq * ldp * 2) {
-        // the per-head buffers are dense: the row-wise kernels take all nb * Nq rows at once
-        CK(launch_softmax_rows_f32(S, (size_t)nb * Nq, Nk, c->st));
-        CK(launch_f32_rows_to_f16_padded(S, (size_t)nb * Nq, Nk, ldp, P16, c->st));
-        CK(launch_softmax_bwd_rows(S, dP, (size_t)nb * Nq, Nk, ldp, scale, dS16, c->st));
-      } else {
-        for (int i = 0; i < nb; ++i) {
-          CK(launch_softmax_rows_f32(S + i * eS, (size_t)Nq, Nk, c->st));
-          CK(launch_f32_rows_to_f16_padded(S + i * eS, (size_t)Nq, Nk, ldp, P16 + i * eP, c->st));
-          CK(launch_softmax_bwd_rows(S + i * eS, dP + i * eS, (size_t)Nq, Nk, ldp, scale, dS16 + i * eP, c->st));
-        }
-      }
-      CK(launch_transpose_f16(P16, ldp, Nq, Nk, PT, ldq8, c->st, nb, eP, eT));
-      CK(launch_transpose_f16(dS16, ldp, Nq, Nk, dST, ldq8, c->st, nb, eP, eT));
-      CK(launch_transpose_f16(kh, ldk, Nk, dh, Kt, ldp, c->st, nb, Dp, eK));
-      CK(launch_transpose_f16(qh, ldq, Nq, dh, Qt, ldq8, c->st, nb, Dp, eQ));
-      CK(launch_transpose_f16(doh, ldo, Nq, dh, dOt, ldq8, c->st, nb, dh, eQ));
-      gb.soutT = 0; gb.sout = Dp;
-      gb.sa = eP; gb.sw = eK;
-      CK(op_gemm(c, dS16, ldp, Nq, ldp, Kt, ldp, dh, nullptr, nullptr, 0, dq + (size_t)b * Nq * ldq + q_off + h0 * Dp, ldq, 1.f, nullptr, -1.0, 0, &gb));     // dQ = dS K
-      gb.sa = eT; gb.sw = eQ;
-      CK(op_gemm(c, dST, ldq8, Nk, ldq8, Qt, ldq8, dh, nullptr, nullptr, 0, dk + (size_t)b * Nk * ldk + k_off + h0 * Dp, ldk, 1.f, nullptr, -1.0, 0, &gb));   // dK = dS^T Q
-      CK(op_gemm(c, PT, ldq8, Nk, ldq8, dOt, ldq8, dh, nullptr, nullptr, 0, dv + (size_t)b * Nk * ldvp + v_off + h0 * Dp, ldvp, 1.f, nullptr, -1.0, 0, &gb)); // dV = P^T dO
-    }
-  return 0;
-}
-// Attention backward in flash form (attn.hip: attn_bwd_flash_kernel): one launch each for dQ (which also leaves D, and the per-query
-// log-sum-exp unless the forward did), dK and dV.  Workspace per batch row: 2 * heads * N floats (+ the fp32 partial sums of a split
-// cross-attention walk) -- at the 64 x 64 level 260 KB against the 8.6 GB-per-8-heads of the score matrices.
-// cross-attention (77 keys): dK / dV have one 128-row key tile per head, so the query walk is split over workgroups (fp32 partial sums,
-// added in a fixed order by a small reduce launch)
-static int attn_bwd_flash_nsplit(int Nq, int Nk) {
-  if (Nk > 128 || Nq < 256) return 1;
-  const int n = Nq / 128;
-  return n > 32 ? 32 : n;
-}
-static size_t attn_bwd_flash_scratch_bytes(int heads, int Nq, int Nk, int dh) {
-  const int ns = attn_bwd_flash_nsplit(Nq, Nk);
-  return (size_t)heads * 2 * align_up((size_t)Nq * 4, 256) + (ns > 1 ? align_up((size_t)ns * heads * Nk * dh * 4, 256) : 0);
-}
-static bool attn_bwd_flash_shape(int Nq, int Nk, int Dp, int dh) {
-  // tuning "attn_bwd_flash": 0 = the materialised form everywhere, 1 = flash form for self- and cross-attention (dQ with the forward's
-  // log-sum-exp where the tape has it), 2 = the same with the two-pass dQ always, 3 = self-attention only
-  const bool self = Nq == Nk, cross = !self && Nk <= 128 && Nk >= 8;
-  if (!g_attn_bwd_flash || !(self || (cross && g_attn_bwd_flash != 3))) return false;
-  return Nq >= 64 && Nq % 64 == 0 && (Dp == 32 || Dp == 64 || Dp == 96 || Dp == 160) && dh <= Dp && !(dh & 7);
-}
-static bool attn_bwd_flash_ok(int heads, int Nq, int Nk, int Dp, int dh, size_t scratch_bytes) {
-  return attn_bwd_flash_shape(Nq, Nk, Dp, dh) && scratch_bytes >= attn_bwd_flash_scratch_bytes(heads, Nq, Nk, dh);
-}
-static int attn_bwd_flash(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp,
-                          int v_off, const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B,
-                          half_t* dq, half_t* dk, half_t* dv, void* scratch, const float* lse_fwd, const half_t* o_fwd, int ld_ofwd) {
-  if ((ldq & 7) || (ldk & 7) || (ldvp & 7) || (ldo & 7) || (q_off & 7) || (k_off & 7) || (v_off & 7))
-    return fail(c, PNPI_ESHAPE, "attention backward: extents must be multiples of 8");
-  const size_t szF = align_up((size_t)Nq * 4, 256);
-  char* sp = (char*)scratch;
-  float* lse = (float*)sp; sp += szF * heads;
-  float* dsum = (float*)sp; sp += szF * heads;
-  float* part = (float*)sp;
-  const int nsplit = attn_bwd_flash_nsplit(Nq, Nk);
-  if (szF != (size_t)Nq * 4) return fail(c, PNPI_ESHAPE, "attention backward: Nq * 4 must be a multiple of 256");   // [heads][Nq] dense (Nq >= 64, % 64 == 0 in every caller)
-  for (int b = 0; b < B; ++b) {
-    const half_t* qh = q + (size_t)b * Nq * ldq + q_off;
-    const half_t* kh = k + (size_t)b * Nk * ldk + k_off;
-    const half_t* vh = v + (size_t)b * Nk * ldvp + v_off;
-    const half_t* doh = d_o + (size_t)b * Nq * ldo;
-    const BwdMat mq{qh, Dp, ldq, dh}, mk{kh, Dp, ldk, dh}, mv{vh, Dp, ldvp, dh}, mdo{doh, dh, ldo, dh};
-    AttnBwdP a{};
-    a.heads = heads; a.scale = scale; a.lse = lse; a.dsum = dsum; a.out_hs = Dp; a.out_w = dh;
-    a.b1 = mq; a.b2 = mdo; a.l1 = mk; a.l2 = mv; a.nb = Nq; a.nl = Nk;
-    a.out = dq + (size_t)b * Nq * ldq + q_off; a.out_ld = ldq;
-    if (lse_fwd && o_fwd && !(ld_ofwd & 7)) {     // the recording forward left the log-sum-exp and O: dQ without its first pass over the keys
-      a.lse = const_cast<float*>(lse_fwd) + (size_t)b * heads * Nq;       // read-only in this form
-      a.o = o_fwd + (size_t)b * Nq * ld_ofwd; a.o_hs = dh; a.o_ld = ld_ofwd;
-    }
-    CK(launch_attn_bwd_flash(a, 0, Dp, c->st));
-    // tile products of the three launches (dQ: S, dP, dQ -- twice S and dP without the forward's log-sum-exp; dK: S, dP, dK; dV: S, dV)
-    c->ctr.executed_attn_flops += 2.0 * heads * (double)Nq * Nk * Dp * ((a.o ? 3 : 5) + 3 + 2);
-    a.o = nullptr;
-    a.b1 = mk; a.b2 = mv; a.l1 = mq; a.l2 = mdo; a.nb = Nk; a.nl = Nq;
-    a.nsplit = nsplit; a.part = nsplit > 1 ? part : nullptr;
-    a.out = dk + (size_t)b * Nk * ldk + k_off; a.out_ld = ldk;
-    CK(launch_attn_bwd_flash(a, 1, Dp, c->st));
-    if (nsplit > 1) CK(launch_attn_bwd_reduce(a, c->st));
-    a.out = dv + (size_t)b * Nk * ldvp + v_off; a.out_ld = ldvp;
-    CK(launch_attn_bwd_flash(a, 2, Dp, c->st));
-    if (nsplit > 1) CK(launch_attn_bwd_reduce(a, c->st));
-  }
-  return 0;
-}
-// dq / dk / dv of one attention site: the flash form for self-attention, the materialised form otherwise
-static int attn_bwd(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp, int v_off,
-                    const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, half_t* dq, half_t* dk, half_t* dv,
-                    void* scratch, size_t scratch_bytes, const float* lse_fwd = nullptr, const half_t* o_fwd = nullptr, int ld_ofwd = 0) {
-  if (scratch && attn_bwd_flash_ok(heads, Nq, Nk, Dp, dh, scratch_bytes))
-    return attn_bwd_flash(c, q, ldq, q_off, k, ldk, k_off, v, ldvp, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch,
-                          g_attn_bwd_flash == 2 ? nullptr : lse_fwd, o_fwd, ld_ofwd);      // tuning value 2: always the two-pass dQ
-  return attn_bwd_materialized(c, q, ldq, q_off, k, ldk, k_off, v, ldvp, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch, scratch_bytes);
-}
-static int gn_bwd_workspace(pnpi_ctx* c, int B, int HW, int G, float** out) {
-  const size_t need = groupnorm_bwd2_scratch_floats(B, HW, G);
-  if (need > c->gn_bwd_ws_floats) {
-    CKH(hipStreamSynchronize(c->st));                      // a launch in flight may still read the old buffer
-    if (c->gn_bwd_ws) CKH(hipFree(c->gn_bwd_ws));
-    c->gn_bwd_ws = nullptr; c->gn_bwd_ws_floats = 0;
-    CKH(hipMalloc((void**)&c->gn_bwd_ws, need * sizeof(float)));
-    c->gn_bwd_ws_floats = need;
-  }
-  *out = c->gn_bwd_ws;
   return 0;
 }
