@@ -423,6 +423,19 @@ int pnpi_ip2p_step(pnpi_ctx* ctx, const float* eps, const float* z, const float*
 int pnpi_ip2p_edit(pnpi_ctx* ctx, const float* z0, const float* image, const float* noise, int nimg, const float* context, float cfg_text,
                    float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out);
 
+/* ---- InstructDiffusion (run_editing_instructdiffusion.py: the same UNet function, sampler and step scalars as InstructPix2Pix) --------
+ * Rows [img][edit text + image, null text + image, edit text + zero image] (CFGDenoiser :37-48): the two distinct 8-channel inputs and the
+ * input map are InstructPix2Pix's, the third row pairs the zero image with the EDIT text, and the combine is symmetric around the mean of
+ * the two single-condition rows:
+ *   den = 0.5 * (den_1 + den_2) + cfg_text * (den_0 - den_1) + cfg_image * (den_0 - den_2)      summed left to right
+ * level 1, pnpi_ip2p_step with that combine: same arguments, same refusals, the same move after it, bit-exact against eager fp32 PyTorch. */
+int pnpi_instdiff_step(pnpi_ctx* ctx, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t row_elems,
+                       float cfg_text, float cfg_image, const float* sc6_host, float c_in_next, float* z_out, float* in_next);
+/* level 2, instruct_diffusion_edit's sampler (:110-120), device-resident: pnpi_ip2p_edit's arguments with context [nimg][3][77][768] =
+ * [edit, null, edit], the same launches per step (the compact prefix of "cfg_dedup" applies unchanged) and the same refusals. */
+int pnpi_instdiff_edit(pnpi_ctx* ctx, const float* z0, const float* image, const float* noise, int nimg, const float* context, float cfg_text,
+                       float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out);
+
 /* ---- kernel-level entry points (used by tests/ and bench.py to exercise single kernels) ------------------------- */
 int pnpi_op_conv(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nhwc_f16, int C1, int C2, int B, int H, int W,
                  int ksize, int stride, int pad, int upsample, int Ho, int Wo, const void* w_f16 /*[N][k*k*(C1+C2)]*/,

@@ -198,6 +198,9 @@ SYMBOLS = {
     "pnpi_unet_forward_t": (_i, [_vp, _vp, _i, _f, _vp, _vp]),                                  # UNet at k-diffusion's sigma_to_t(sigma)
     "pnpi_ip2p_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _fp, _f, _vp, _vp]),     # CFGDenoiser :46 + sample_euler_ancestral
     "pnpi_ip2p_edit": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _f, _i, _fp, _vp, _vp]),          # edit_instruct_pix2pix :125-134
+    # InstructDiffusion (run_editing_instructdiffusion.py)
+    "pnpi_instdiff_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _fp, _f, _vp, _vp]),  # CFGDenoiser :46-48 + sample_euler_ancestral
+    "pnpi_instdiff_edit": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _f, _i, _fp, _vp, _vp]),       # instruct_diffusion_edit :110-120
 }
 
 _lib = None

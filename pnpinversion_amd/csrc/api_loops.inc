@@ -779,15 +779,30 @@ static void temb_row_host(const pnpi_model_config& g, float t, float* row) {
     }
   }
 }
-static int ip2p_model_check(pnpi_ctx* c) {
+// The two instruction editors share everything but the third row's text and the combine (step.hip: ip2p_move)
+struct Ip2pKind {
+  int combine;
+  const char* name;          // in refusals
+  const char* rows_msg;      // the row-limit refusal names the kind's own row layout
+};
+static const Ip2pKind kIp2p = {IP2P_CHAIN, "InstructPix2Pix",
+                               "3 * nimg exceeds max_unet_rows (InstructPix2Pix runs [edit + image, null + image, null + no image] per image)"};
+static const Ip2pKind kInstDiff = {IP2P_SYMMETRIC, "InstructDiffusion",
+                                   "3 * nimg exceeds max_unet_rows (InstructDiffusion runs [edit + image, null + image, edit + no image] per image)"};
+static int ip2p_fail(pnpi_ctx* c, const Ip2pKind& k, const char* what) {
+  char msg[256];
+  snprintf(msg, sizeof msg, "%s %s", k.name, what);
+  return fail(c, PNPI_EINVAL, msg);
+}
+static int ip2p_model_check(pnpi_ctx* c, const Ip2pKind& k) {
   if (c->cfg.in_channels != 8 || c->cfg.out_channels != 4)
-    return fail(c, PNPI_EINVAL, "InstructPix2Pix needs a model with in_channels == 8 and out_channels == 4 (4 latent + 4 image-latent channels in, 4 out)");
+    return ip2p_fail(c, k, "needs a model with in_channels == 8 and out_channels == 4 (4 latent + 4 image-latent channels in, 4 out)");
   return 0;
 }
-static int ip2p_scalars_check(pnpi_ctx* c, const float* sc, int n) {
+static int ip2p_scalars_check(pnpi_ctx* c, const Ip2pKind& k, const float* sc, int n) {
   for (int i = 0; i < n; ++i) {
     const float* s = sc + 6 * (size_t)i;
-    if (!(s[0] > 0.f) || !(s[3] > 0.f)) return fail(c, PNPI_EINVAL, "InstructPix2Pix step scalars: sigma and c_in must be positive");
+    if (!(s[0] > 0.f) || !(s[3] > 0.f)) return ip2p_fail(c, k, "step scalars: sigma and c_in must be positive");
     if (!(s[4] >= 0.f) || !(s[4] <= (float)(c->cfg.n_train_timesteps - 1))) return fail(c, PNPI_EINVAL, "timestep out of range");
   }
   return 0;
@@ -810,30 +825,40 @@ int pnpi_unet_forward_t(pnpi_ctx* c, const float* latents, int rows, float t, co
 }
 // one step (level 1): eps [nimg][3][row_elems], z / noise / image / z_out [nimg][row_elems], sc6_host the step's scalars (c_in and t unread),
 // in_next (nullable) [nimg][2][2 * row_elems] scaled by c_in_next.  noise is not read when sc6_host[5] == 0 (sigma_next == 0).
-int pnpi_ip2p_step(pnpi_ctx* c, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t row_elems,
-                   float cfg_text, float cfg_image, const float* sc6_host, float c_in_next, float* z_out, float* in_next) {
+static int ip2p_step_impl(pnpi_ctx* c, const Ip2pKind& k, const float* eps, const float* z, const float* noise, const float* image, int nimg,
+                          size_t row_elems, float cfg_text, float cfg_image, const float* sc6_host, float c_in_next, float* z_out, float* in_next) {
   if (!c || !eps || !z || !sc6_host || !z_out || nimg <= 0 || row_elems == 0) return PNPI_EINVAL;
-  if (!(sc6_host[0] > 0.f)) return fail(c, PNPI_EINVAL, "InstructPix2Pix step scalars: sigma and c_in must be positive");
+  if (!(sc6_host[0] > 0.f)) return ip2p_fail(c, k, "step scalars: sigma and c_in must be positive");
   const int add_noise = sc6_host[5] != 0.f;
   if (add_noise && !noise) return fail(c, PNPI_EINVAL, "sigma_next > 0: the step needs its draw");
   if (in_next && !image) return fail(c, PNPI_EINVAL, "in_next needs the image latent");
-  CK(launch_ip2p_step(eps, z, noise, image, nimg, row_elems, cfg_text, cfg_image, sc6_host, add_noise, c_in_next, z_out, in_next, c->st));
+  CK(launch_ip2p_step(k.combine, eps, z, noise, image, nimg, row_elems, cfg_text, cfg_image, sc6_host, add_noise, c_in_next, z_out, in_next, c->st));
   return 0;
 }
-/* edit_instruct_pix2pix's sampler (:125-134) for nimg images, device-resident.  z0 [nimg][4 S^2] = randn * sigmas[0], image [nimg][4 S^2] the
- * encoder's posterior mean (not scaled), noise [nsteps][nimg][4 S^2] the draws in step order (the last is not read when its sigma_next is 0),
- * context [nimg][3][77][D] = [edit, null, null].  Per step one UNet launch of 3 * nimg rows on 2 * nimg distinct inputs (rows 0 and 1 share
- * theirs: the input map "cfg_dedup" compacts) and one ip2p_step launch.  trajectory_out (nullable) [nsteps][nimg][4 S^2]: z after every step. */
-int pnpi_ip2p_edit(pnpi_ctx* c, const float* z0, const float* image, const float* noise, int nimg, const float* context, float cfg_text,
-                   float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out) {
+int pnpi_ip2p_step(pnpi_ctx* c, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t row_elems,
+                   float cfg_text, float cfg_image, const float* sc6_host, float c_in_next, float* z_out, float* in_next) {
+  return ip2p_step_impl(c, kIp2p, eps, z, noise, image, nimg, row_elems, cfg_text, cfg_image, sc6_host, c_in_next, z_out, in_next);
+}
+int pnpi_instdiff_step(pnpi_ctx* c, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t row_elems,
+                       float cfg_text, float cfg_image, const float* sc6_host, float c_in_next, float* z_out, float* in_next) {
+  return ip2p_step_impl(c, kInstDiff, eps, z, noise, image, nimg, row_elems, cfg_text, cfg_image, sc6_host, c_in_next, z_out, in_next);
+}
+/* edit_instruct_pix2pix's sampler (:125-134) and instruct_diffusion_edit's (run_editing_instructdiffusion.py:110-120) for nimg images,
+ * device-resident.  z0 [nimg][4 S^2] = randn * sigmas[0], image [nimg][4 S^2] the encoder's posterior mean (not scaled), noise
+ * [nsteps][nimg][4 S^2] the draws in step order (the last is not read when its sigma_next is 0), context [nimg][3][77][D] = [edit, null, null]
+ * (InstructPix2Pix) or [edit, null, edit] (InstructDiffusion): the caller's rows, the loop reads them as given.  Per step one UNet launch of
+ * 3 * nimg rows on 2 * nimg distinct inputs (rows 0 and 1 share theirs: the input map "cfg_dedup" compacts; the map is the same for both kinds,
+ * the third row's zero image half is what both pair with their third text) and one ip2p_step launch with the kind's combine.  trajectory_out
+ * (nullable) [nsteps][nimg][4 S^2]: z after every step. */
+static int ip2p_edit_impl(pnpi_ctx* c, const Ip2pKind& k, const float* z0, const float* image, const float* noise, int nimg, const float* context,
+                          float cfg_text, float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out) {
   if (!c) return PNPI_EINVAL;
   if (nsteps <= 0 || nsteps > c->cfg.n_train_timesteps) return fail(c, PNPI_EINVAL, "need 1 <= nsteps <= n_train_timesteps");
   if (!z0 || !image || !noise || !context || !scalars_host || !z_out || nimg <= 0) return PNPI_EINVAL;
-  CKP(ip2p_model_check(c));
-  CKP(ip2p_scalars_check(c, scalars_host, nsteps));
+  CKP(ip2p_model_check(c, k));
+  CKP(ip2p_scalars_check(c, k, scalars_host, nsteps));
   Loop L(c);
-  CKP(loop_begin(L, nsteps, 3 * nimg, "3 * nimg exceeds max_unet_rows (InstructPix2Pix runs [edit + image, null + image, null + no image] per image)",
-                 nullptr, 0, 4, 2, 3, 0, true));
+  CKP(loop_begin(L, nsteps, 3 * nimg, k.rows_msg, nullptr, 0, 4, 2, 3, 0, true));
   const size_t E4 = L.E_out, N = (size_t)nimg * E4;
   const int C0 = c->cfg.block_out_channels[0];
   float* z = misc_f(c, N);
@@ -849,18 +874,26 @@ int pnpi_ip2p_edit(pnpi_ctx* c, const float* z0, const float* image, const float
   for (int i = 0; i < nsteps; ++i) temb_row_host(c->cfg, scalars_host[6 * (size_t)i + 4], rows_h.data() + (size_t)i * C0);
   CKP(upload(c, trows, rows_h.data(), rows_h.size() * sizeof(float)));
   L.temb_rows = trows;
-  CK(launch_ip2p_step(nullptr, z0, nullptr, image, nimg, E4, cfg_text, cfg_image, nullptr, 0, scalars_host[3], z, in2, c->st));
+  CK(launch_ip2p_step(k.combine, nullptr, z0, nullptr, image, nimg, E4, cfg_text, cfg_image, nullptr, 0, scalars_host[3], z, in2, c->st));
   CKP(L.kv.begin(context, L.rows));
   for (int i = 0; i < nsteps; ++i) {
     const float* sc = scalars_host + 6 * (size_t)i;
     CKP(loop_unet(L, in2, d_inmap, 0, context, false, i));
     const bool last = i + 1 == nsteps;
-    CK(launch_ip2p_step(L.eps, z, noise + (size_t)i * N, image, nimg, E4, cfg_text, cfg_image, sc, sc[5] != 0.f, last ? 0.f : sc[6 + 3], z,
-                        last ? nullptr : in2, c->st));
+    CK(launch_ip2p_step(k.combine, L.eps, z, noise + (size_t)i * N, image, nimg, E4, cfg_text, cfg_image, sc, sc[5] != 0.f,
+                        last ? 0.f : sc[6 + 3], z, last ? nullptr : in2, c->st));
     if (trajectory_out) CKH(hipMemcpyAsync(trajectory_out + (size_t)i * N, z, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
   }
   CKH(hipMemcpyAsync(z_out, z, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
   return 0;
+}
+int pnpi_ip2p_edit(pnpi_ctx* c, const float* z0, const float* image, const float* noise, int nimg, const float* context, float cfg_text,
+                   float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out) {
+  return ip2p_edit_impl(c, kIp2p, z0, image, noise, nimg, context, cfg_text, cfg_image, nsteps, scalars_host, z_out, trajectory_out);
+}
+int pnpi_instdiff_edit(pnpi_ctx* c, const float* z0, const float* image, const float* noise, int nimg, const float* context, float cfg_text,
+                       float cfg_image, int nsteps, const float* scalars_host, float* z_out, float* trajectory_out) {
+  return ip2p_edit_impl(c, kInstDiff, z0, image, noise, nimg, context, cfg_text, cfg_image, nsteps, scalars_host, z_out, trajectory_out);
 }
 
 // ---------------------------------------------------------------------------------------------------- null-text optimisation

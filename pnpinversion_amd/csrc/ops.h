@@ -227,9 +227,11 @@ int launch_bld_mask(const uint8_t* in, int n, int H, int W, int h, int w, float*
 int launch_pnp_step(const float* eps, const float* x, const float* src_next, int nimg, size_t E, float g, float a_t, float a_prev, float* x_out,
                     float* rows_next, hipStream_t st);
 // InstructPix2Pix: the three denoised rows, the two-scale CFG combine and the Euler-ancestral move in one launch (z_out may be z), and the next
-// launch's two distinct 8-channel inputs per image.  sc (host): [sigma, sigma_down - sigma, sigma_up]; eps == NULL: inputs only
-int launch_ip2p_step(const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t E, float g_text, float g_image,
-                     const float* sc, int add_noise, float c_in_next, float* z_out, float* in_next, hipStream_t st);
+// launch's two distinct 8-channel inputs per image.  sc (host): [sigma, sigma_down - sigma, sigma_up]; eps == NULL: inputs only.
+// combine: IP2P_CHAIN (InstructPix2Pix, third row null text + zero image) or IP2P_SYMMETRIC (InstructDiffusion, third row text + zero image)
+enum { IP2P_CHAIN = 0, IP2P_SYMMETRIC = 1 };
+int launch_ip2p_step(int combine, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t E, float g_text,
+                     float g_image, const float* sc, int add_noise, float c_in_next, float* z_out, float* in_next, hipStream_t st);
 // uint8 [n][H][W] -> uint8 0/1 [n][h][w]: F.interpolate(mode="nearest") indexing, source = min(floor(dst * (float)H / h), H - 1)
 int launch_masa_mask_level(const uint8_t* in, int n, int H, int W, int h, int w, uint8_t* out, hipStream_t st);
 

@@ -475,8 +475,9 @@ int launch_pnp_step(const float* eps, const float* x, const float* src_next, int
   return (int)hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------- InstructPix2Pix
-// Reference: run_editing_instructpix2pix.py, CFGDenoiser :33-46 around k-diffusion's CompVisDenoiser, and sample_euler_ancestral.  One step
+// ---------------------------------------------------------------------------------------------------- InstructPix2Pix, InstructDiffusion
+// Reference: run_editing_instructpix2pix.py, CFGDenoiser :33-46 around k-diffusion's CompVisDenoiser, and sample_euler_ancestral (and
+// run_editing_instructdiffusion.py :32-48: another third row and another combine, see ip2p_move; everything else below is shared).  One step
 // for nimg images in one launch, eps [nimg][3][E] = (edit text + image, null text + image, null text + zero image), sc = the step's host
 // scalars [sigma, sigma_down - sigma, sigma_up]:
 //   den_k = z + eps_k * (-sigma)                                                  CompVisDenoiser.forward: input + eps * c_out
@@ -492,15 +493,27 @@ struct Ip2pStepP {
   int add_noise;
   float *z_out, *in_next;
 };
+// COMBINE: how the three denoised rows become one (the rest of the step is shared).
+//   IP2P_CHAIN      run_editing_instructpix2pix.py :46, rows (text + image, null + image, null + zero image): a chain from the unconditional row
+//                     den_2 + g_text * (den_0 - den_1) + g_image * (den_1 - den_2)
+//   IP2P_SYMMETRIC  run_editing_instructdiffusion.py :46-48, rows (text + image, null + image, text + zero image): around the mean of the
+//                   two single-condition rows
+//                     0.5 * (den_1 + den_2) + g_text * (den_0 - den_1) + g_image * (den_0 - den_2)
+// both summed left to right as the reference's expression is evaluated.
+template <int COMBINE>
 __device__ __forceinline__ float ip2p_move(const Ip2pStepP& p, float z, float e0, float e1, float e2, float nz) {
   const float d0 = __fadd_rn(z, __fmul_rn(e0, p.neg_sigma)), d1 = __fadd_rn(z, __fmul_rn(e1, p.neg_sigma)), d2 = __fadd_rn(z, __fmul_rn(e2, p.neg_sigma));
-  const float den = __fadd_rn(__fadd_rn(d2, __fmul_rn(p.g_text, __fsub_rn(d0, d1))), __fmul_rn(p.g_image, __fsub_rn(d1, d2)));
+  float den;
+  if (COMBINE == IP2P_CHAIN)
+    den = __fadd_rn(__fadd_rn(d2, __fmul_rn(p.g_text, __fsub_rn(d0, d1))), __fmul_rn(p.g_image, __fsub_rn(d1, d2)));
+  else
+    den = __fadd_rn(__fadd_rn(__fmul_rn(0.5f, __fadd_rn(d1, d2)), __fmul_rn(p.g_text, __fsub_rn(d0, d1))), __fmul_rn(p.g_image, __fsub_rn(d0, d2)));
   const float d = __fdiv_rn(__fsub_rn(z, den), p.sigma);
   float zn = __fadd_rn(z, __fmul_rn(d, p.dt));
   if (p.add_noise) zn = __fadd_rn(zn, __fmul_rn(nz, p.up));
   return zn;
 }
-template <int V>
+template <int V, int COMBINE>
 __global__ void ip2p_step_kernel(const Ip2pStepP p) {
   const size_t EV = p.E / V, total = (size_t)p.nimg * EV;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -518,7 +531,7 @@ __global__ void ip2p_step_kernel(const Ip2pStepP p) {
         e0[0] = e[0]; e1[0] = e[p.E]; e2[0] = e[2 * p.E];
         if (p.add_noise) nz[0] = p.noise[at];
       }
-      for (int k = 0; k < V; ++k) zn[k] = ip2p_move(p, z[k], e0[k], e1[k], e2[k], p.add_noise ? nz[k] : 0.f);
+      for (int k = 0; k < V; ++k) zn[k] = ip2p_move<COMBINE>(p, z[k], e0[k], e1[k], e2[k], p.add_noise ? nz[k] : 0.f);
     } else {
       for (int k = 0; k < V; ++k) zn[k] = z[k];
     }
@@ -537,8 +550,9 @@ __global__ void ip2p_step_kernel(const Ip2pStepP p) {
     }
   }
 }
-int launch_ip2p_step(const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t E, float g_text, float g_image,
-                     const float* sc, int add_noise, float c_in_next, float* z_out, float* in_next, hipStream_t st) {
+int launch_ip2p_step(int combine, const float* eps, const float* z, const float* noise, const float* image, int nimg, size_t E, float g_text,
+                     float g_image, const float* sc, int add_noise, float c_in_next, float* z_out, float* in_next, hipStream_t st) {
+  if (combine != IP2P_CHAIN && combine != IP2P_SYMMETRIC) return -3;
   if (nimg <= 0 || E == 0 || !z || !z_out || (in_next && !image) || (eps && !sc) || (eps && add_noise && !noise)) return -3;
   if (eps && !(sc[0] > 0.f)) return -3;
   Ip2pStepP p;
@@ -551,8 +565,13 @@ int launch_ip2p_step(const float* eps, const float* z, const float* noise, const
   const size_t total = (size_t)nimg * (vec ? E / 4 : E);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 1024) blocks = 1024;
-  if (vec) ip2p_step_kernel<4><<<blocks, 256, 0, st>>>(p);
-  else ip2p_step_kernel<1><<<blocks, 256, 0, st>>>(p);
+  if (combine == IP2P_CHAIN) {
+    if (vec) ip2p_step_kernel<4, IP2P_CHAIN><<<blocks, 256, 0, st>>>(p);
+    else ip2p_step_kernel<1, IP2P_CHAIN><<<blocks, 256, 0, st>>>(p);
+  } else {
+    if (vec) ip2p_step_kernel<4, IP2P_SYMMETRIC><<<blocks, 256, 0, st>>>(p);
+    else ip2p_step_kernel<1, IP2P_SYMMETRIC><<<blocks, 256, 0, st>>>(p);
+  }
   return (int)hipGetLastError();
 }
 

@@ -834,7 +834,7 @@ class NativeEngine:
         self._keep = (lat, ctx)
         return out
 
-    def ip2p_step(self, eps, z, noise, image, scalars, cfg_text, cfg_image, c_in_next=None):
+    def ip2p_step(self, eps, z, noise, image, scalars, cfg_text, cfg_image, c_in_next=None, _symbol="pnpi_ip2p_step"):
         """One step for nimg images (CFGDenoiser :46 + one iteration of sample_euler_ancestral): eps [nimg, 3, C, h, w], z / noise / image
         [nimg, C, h, w], scalars the step's 6 floats (instructpix2pix.step_table) -> z' , or (z', inputs [nimg, 2, 2 C, h, w]) when c_in_next
         is given: the next launch's [z' * c_in_next | image] and [z' * c_in_next | 0].  noise is not read when scalars[5] == 0."""
@@ -850,12 +850,12 @@ class NativeEngine:
         out = torch.empty_like(zs)
         nimg, ch = zs.shape[:2]
         nxt = torch.empty(nimg, 2, 2 * ch, *zs.shape[2:], device=self.device) if c_in_next is not None else None
-        self._call("pnpi_ip2p_step", _p(e), _p(zs), _p(nz), _p(im), nimg, zs[0].numel(), float(cfg_text), float(cfg_image),
+        self._call(_symbol, _p(e), _p(zs), _p(nz), _p(im), nimg, zs[0].numel(), float(cfg_text), float(cfg_image),
                    sc.ctypes.data_as(C.POINTER(C.c_float)), float(c_in_next) if c_in_next is not None else 0.0, _p(out), _p(nxt))
         self._keep = (e, zs, nz, im, sc)
         return out if nxt is None else (out, nxt)
 
-    def ip2p_edit(self, z0, image, noise, context, scalars, cfg_text=7.5, cfg_image=1.5, trajectory=False):
+    def ip2p_edit(self, z0, image, noise, context, scalars, cfg_text=7.5, cfg_image=1.5, trajectory=False, _symbol="pnpi_ip2p_edit"):
         """edit_instruct_pix2pix's sampler (:125-134) for nimg images, device-resident (pnpi_ip2p_edit).  z0 [nimg, 4, h, w] = randn *
         sigmas[0], image [nimg, 4, h, w] the encoder's posterior mean (unscaled), noise [nsteps, nimg, 4, h, w] the draws in step order,
         context [nimg, 3, 77, D] = [edit, null, null], scalars [nsteps, 6] (instructpix2pix.step_table) -> z [nimg, 4, h, w], or
@@ -877,10 +877,21 @@ class NativeEngine:
             raise ValueError("context must be [nimg, 3, %d, %d], got %s" % (self.cfg.ctx_len, self.cfg.cross_dim, tuple(ctx.shape)))
         out = torch.empty_like(z)
         traj = torch.empty(nsteps, *z.shape, device=self.device) if trajectory else None
-        self._call("pnpi_ip2p_edit", _p(z), _p(im), _p(nz), nimg, _p(ctx), float(cfg_text), float(cfg_image), nsteps,
+        self._call(_symbol, _p(z), _p(im), _p(nz), nimg, _p(ctx), float(cfg_text), float(cfg_image), nsteps,
                    sc.ctypes.data_as(C.POINTER(C.c_float)), _p(out), _p(traj))
         self._keep = (z, im, nz, ctx, sc)
         return (out, traj) if trajectory else out
+
+    # ---- InstructDiffusion (run_editing_instructdiffusion.py): the same arguments, another third row and combine
+    def instdiff_step(self, eps, z, noise, image, scalars, cfg_text, cfg_image, c_in_next=None):
+        """ip2p_step with InstructDiffusion's combine (pnpi_instdiff_step): eps rows (text + image, null + image, text + zero image),
+        0.5 * (den_1 + den_2) + cfg_text * (den_0 - den_1) + cfg_image * (den_0 - den_2)"""
+        return self.ip2p_step(eps, z, noise, image, scalars, cfg_text, cfg_image, c_in_next, _symbol="pnpi_instdiff_step")
+
+    def instdiff_edit(self, z0, image, noise, context, scalars, cfg_text=5.0, cfg_image=1.25, trajectory=False):
+        """instruct_diffusion_edit's sampler (:110-120), device-resident (pnpi_instdiff_edit): ip2p_edit's arguments with context
+        [nimg, 3, 77, D] = [edit, null, edit]"""
+        return self.ip2p_edit(z0, image, noise, context, scalars, cfg_text, cfg_image, trajectory, _symbol="pnpi_instdiff_edit")
 
 
 def pnp_desc_default(lib, cfg, nsteps):

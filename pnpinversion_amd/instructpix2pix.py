@@ -115,8 +115,8 @@ class InstructPix2Pix:
         """pipe: a loaded NativePipeline on an 8-channel configuration (config.SD1_IP2P); max_unet_rows: 3 per image of an edit_images call"""
         cfg = pipe.engine.cfg
         if cfg.in_channels != 8 or cfg.out_channels != 4:
-            raise ValueError("InstructPix2Pix needs a model with in_channels = 8 and out_channels = 4 (config.SD1_IP2P), got in_channels = %d, "
-                             "out_channels = %d" % (cfg.in_channels, cfg.out_channels))
+            raise ValueError("%s needs a model with in_channels = 8 and out_channels = 4 (config.SD1_IP2P), got in_channels = %d, "
+                             "out_channels = %d" % (type(self).__name__, cfg.in_channels, cfg.out_channels))
         self.pipe, self.engine = pipe, pipe.engine
         self.schedule = schedule or SigmaSchedule()
         self.side = self.engine.lat_hw * cfg.vae_scale
@@ -142,6 +142,18 @@ class InstructPix2Pix:
             raise ValueError("the image fits to %d x %d, this context's latent needs %d x %d" % (width, height, self.side, self.side))
         return original, ImageOps.fit(original, (width, height), method=Image.Resampling.LANCZOS)          # :112
 
+    # what InstructDiffusion (instructdiffusion.py) does differently: the third text row, the loop's combine, the edit's way into the panel
+    def _rows(self, cond, null_token):
+        """[n, 77, D] each -> the three text rows per image [n, 3, 77, D] (:42)"""
+        return torch.stack([cond, null_token, null_token], 1)
+
+    def _loop(self, *args):
+        return self.engine.ip2p_edit(*args)
+
+    def _edited(self, x, original):
+        """the decoded uint8 [H, W, 3] edit as it enters the panel"""
+        return x
+
     @torch.no_grad()
     def edit_images(self, images, instructions, steps=50, cfg_text=7.5, cfg_image=1.5, noise=None, return_latents=False):
         """edit for len(images) (image, instruction) pairs in one loop call -> list of panels (uint8 [H, 4 W, 3])"""
@@ -152,7 +164,7 @@ class InstructPix2Pix:
         originals, fitted = zip(*[self._fit(im) for im in images])
         null_token = self._encode([""])                                                         # :104
         cond = torch.cat([self._encode([e]) for e in instructions])                             # :116
-        context = torch.stack([cond, null_token.expand(n, -1, -1), null_token.expand(n, -1, -1)], 1)       # :42
+        context = self._rows(cond, null_token.expand(n, -1, -1))                                # :42
         x = torch.stack([2 * torch.tensor(np.array(f)).float() / 255 - 1 for f in fitted]).permute(0, 3, 1, 2)     # :117-118
         m = eng.max_vae_images
         c_concat = torch.cat([eng.vae_encode(x[i:i + m]) for i in range(0, n, m)])              # :119 encode_first_stage(...).mode()
@@ -168,18 +180,18 @@ class InstructPix2Pix:
             d = torch.as_tensor(d).float()
             draws[:d.shape[0], i] = d.reshape(-1, *lat)[:steps]
         z0 = start * sigmas[0]                                                                  # :133
-        z = eng.ip2p_edit(z0, c_concat, draws, context, step_table(sigmas, self.schedule), cfg_text, cfg_image)    # :134
+        z = self._loop(z0, c_concat, draws, context, step_table(sigmas, self.schedule), cfg_text, cfg_image)      # :134
         scaled = 1. / VAE_SCALING * z                                                           # decode_first_stage
         x = torch.cat([eng.vae_decode(scaled[i:i + m]) for i in range(0, n, m)])                # :135
         x = torch.clamp((x + 1.0) / 2.0, min=0.0, max=1.0)                                      # :136
         x = (255.0 * x.permute(0, 2, 3, 1)).type(torch.uint8).cpu().numpy()                     # :137-138
         panels = []
         for i in range(n):
-            source = np.array(originals[i])
+            source, edited = np.array(originals[i]), self._edited(x[i], originals[i])
             image_instruct = txt_draw(f"edit prompt: {instructions[i]}", target_size=source.shape[:2])      # :140 (512 x 512 there)
-            if source.shape != x[i].shape:
-                raise ValueError("the panel needs a source image of the edit's size %s, got %s" % (x[i].shape, source.shape))
-            panels.append(np.concatenate((image_instruct, source, np.zeros_like(image_instruct), x[i]), axis=1))   # :142
+            if source.shape != edited.shape:
+                raise ValueError("the panel needs a source image of the edit's size %s, got %s" % (edited.shape, source.shape))
+            panels.append(np.concatenate((image_instruct, source, np.zeros_like(image_instruct), edited), axis=1))   # :142
         return (panels, z) if return_latents else panels
 
     @torch.no_grad()

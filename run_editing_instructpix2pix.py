@@ -6,8 +6,8 @@ and skip-if-exists resume): InstructPix2Pix, the benchmark's instruction-driven 
 Per image (run_editing_instructpix2pix.py:177-205): the mapping file's `editing_instruction`, 50 Euler-ancestral steps, text scale 7.5,
 image scale 1.5, setup_seed() before every image; panel instruction | source | black | edit.  Weights: --checkpoint <CompVis .ckpt> as the
 reference loads it (checkpoint.convert_ldm_state_dict; the vocabulary then comes from --tokenizer_dir), or --checkpoint_dir <diffusers
-directory>, or --synthetic_weights.  `--edit_method_list instruct-diffusion` (run_editing_instructdiffusion.py: the same sampler on another
-checkpoint) selects the same loop; InstructDiffusion's own preprocessing is out of scope."""
+directory>, or --synthetic_weights.  `--edit_method_list instruct-diffusion` here still means THIS editor's loop, rows and scales on another
+checkpoint, written to the folder `instruct-diffusion`; InstructDiffusion's own rows, combine and scales are run_editing_instructdiffusion.py."""
 import argparse
 import json
 import os
@@ -74,8 +74,9 @@ def load_weights(args, cfg, rank=0):
     return (*load_ldm_checkpoint(args.checkpoint), tok) if rank == 0 else (None, None, None, tok)
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def main(argv=None, parse=parse_args, editor_name="InstructPix2Pix", scales=(STEPS, CFG_TEXT, CFG_IMAGE)):
+    """parse / editor_name / scales: what run_editing_instructdiffusion.py, the same sweep around the other instruction editor, passes"""
+    args = parse(argv)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     prepare_env()
@@ -84,6 +85,7 @@ def main(argv=None):
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     from pnpinversion_amd.config import SD1_IP2P, SMALL64_IP2P
+    from pnpinversion_amd.instructdiffusion import InstructDiffusion
     from pnpinversion_amd.instructpix2pix import InstructPix2Pix
     from pnpinversion_amd.pipeline import NativePipeline
     cfg = SD1_IP2P if args.model_config == "sd1" else SMALL64_IP2P
@@ -93,7 +95,7 @@ def main(argv=None):
         pipe.load_state_dict(unet_sd, vae_sd, clip_sd=clip_sd)
     if world > 1:
         broadcast_weights(pipe.engine, src=0)
-    editor = InstructPix2Pix(pipe)
+    editor = {"InstructPix2Pix": InstructPix2Pix, "InstructDiffusion": InstructDiffusion}[editor_name](pipe)
 
     with open(os.path.join(args.data_path, "mapping_file.json")) as f:
         instructions = json.load(f)
@@ -101,7 +103,7 @@ def main(argv=None):
         for instruction, image_path, out_path in plan_work(args, instructions, method, rank, world):
             print(f"editing image [{image_path}] with [{method}]")
             setup_seed()
-            edited_image = editor.edit(image_path, instruction, STEPS, CFG_TEXT, CFG_IMAGE)
+            edited_image = editor.edit(image_path, instruction, *scales)
             os.makedirs(os.path.dirname(out_path), exist_ok=True)
             edited_image.save(out_path)
             print("finish")
