@@ -448,12 +448,20 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
                        const void* residual_f16, int N, void* out_nhwc_f16, int force_cfg, int force_split, float* stats_out,
                        int* tile_rows_out);
 /* process-wide kernel tuning knobs: variant A/B inside one process (tools/fwd_ab.py, tools/fwd_tune.py) and tests of non-default
- * variants; PNPI_EINVAL for an unknown key.  They are plain process globals read by every context's launches: set them while no other
- * thread is inside a pnpi_* call (the product never calls this; several contexts on several threads -- P2PEditor.edit_stream_in_flight --
- * only READ them).  A non-zero "igemm_vpp" / "igemm_sched" and "igemm_v128" / "igemm_v320" = 11, 12, 15 select ablation instances
- * that exist only in a library built with `python -m pnpinversion_amd.build --ablations` (-DPNPI_ABLATIONS=1 -> csrc/libpnpi_ablations.so,
- * loaded with PNPI_LIBRARY=<path>); the product library REJECTS those values here with PNPI_EINVAL -- and "attn_pipe" = 1 / 2 (round 6: the
- * half-tile software-pipelined forms of the 64-wide flash kernel, measured slower) likewise.
+ * variants.  One table holds them all -- key, built-in default, accepted range, the environment variable that seeds it, one-line
+ * description: PNPI_TUNING_KNOBS in pnpinversion_amd/csrc/tuning.h -- and pnpi_tuning_info enumerates it.  The environment is read once,
+ * when the library is loaded; a variable whose value the knob does not accept leaves the built-in default.
+ * pnpi_set_tuning: PNPI_EINVAL for an unknown key or a value outside the knob's range (the knob keeps its value).
+ * pnpi_get_tuning: the current value; PNPI_EINVAL for an unknown key.
+ * pnpi_tuning_info: row `index` of the table (0, 1, ... until PNPI_EINVAL): its key, its value at load (`initial`: the built-in default,
+ * or what the environment variable gave) and its current value; each pointer is nullable.
+ * pnpi_reset_tuning: every knob back to its value at load.
+ * All four are host-only and need no context.  The knobs are plain process globals read by every context's launches: set them while no
+ * other thread is inside a pnpi_* call (the product never sets one; several contexts on several threads --
+ * P2PEditor.edit_stream_in_flight -- only READ them).  A non-zero "igemm_vpp" / "igemm_sched" / "attn_pipe" and "igemm_v128" /
+ * "igemm_v320" = 11, 12, 15 select ablation instances that exist only in a library built with
+ * `python -m pnpinversion_amd.build --ablations` (-DPNPI_ABLATIONS=1 -> csrc/libpnpi_ablations.so, loaded with PNPI_LIBRARY=<path>); the
+ * product library REJECTS those values with PNPI_EINVAL instead of silently timing the default kernel.
  * "ff_fold" (1): each transformer block's ff2 GEMM and 1x1 proj_out run as one launch over folded weights [Wp W2 | Wp] derived at load
  * (same FLOPs, no hs3 round trip; fp16-rounding-level difference); 0 = the two launches.  May be switched on a live context.
  * "cfg_dedup" (1): in the loops that feed one latent to several UNet rows (classifier-free guidance: its unconditional and its
@@ -471,24 +479,17 @@ int pnpi_op_conv_stats(pnpi_ctx* ctx, const void* x1_nhwc_f16, const void* x2_nh
  * unet_shared_rows then stays put; under 1 the full launch of a recording context is configured as the compact launch would be, so the
  * context gives the same bits as one without a tape.  Other values are rejected.
  * May be switched on a live context.
- * Keys (default): "text_kv" (1) / "temb_cache" (1) per-loop caches; "gn_inline_rows" (0)
- * one-launch GroupNorm below this many rows; "igemm_dma" (1) LDS-DMA kernel family; "igemm_table" (1) measured tile table before the
- * cost model; "igemm_wide" (1) 128x320 / 128x256 tiles; "igemm_deep_rings" (1) deeper LDS rings on sparse launches; "igemm_vt_lds" (1)
- * transposed V^T epilogue through LDS; "igemm_bias_init" (1) bias as the accumulators' initial value; "igemm_sched" (0 / 1) hand-scheduled GEMM main loop (fragment
- * reads behind counted lgkmcnt waits, DMA instructions between the MFMAs); "attn_bwd_flash" (1) attention backward of the null-text path without the score matrices in memory (0: materialised everywhere, 2: flash form with the two-pass dQ even where the forward left its log-sum-exp, 3: flash form for self-attention only); "attn_vt_perm" (1) V^T of the 4096-token self-attention sites stored in the permuted key order the LDS-DMA flash kernel reads with one
- * 16-byte fragment load ("op_attention_vt_perm": pnpi_op_attention is handed such a V^T -- kernel tests); "igemm_res_late" (0) residual
- * added in the store loop; "igemm_force_cfg" (-1) / "igemm_force_split" (0) one tile id / split-K for every launch (sweeps);
- * "igemm_table_near" (1) nearest-row-count table entry for untabled M; "igemm_v128", "igemm_v64", "igemm_v256", "igemm_v320",
- * "igemm_v256n" variant of a tile id; "tile_order" (-1) XCD traversal order; "igemm_vpp" (0) ablations of the 8-wave ping-pong kernel
- * (1 no MFMAs, 2 no DMA, 3 DMA only, 4 MFMAs only -- all but 0 produce garbage, timing only); "igemm_tapin" (0) the ping-pong kernel
- * walks a 3 x 3 convolution's K channel-slab-major; "igemm_pp_only_m" / "_n" / "_k" (0) the table's ping-pong entries apply only to
- * launches with that M / N / K (n < 0: to none; tools/pp_bisect.py); "pp_rowtile" (1, or the PNPI_PP_ROWTILE variable) a ping-pong
- * launch takes the row height that fills the CUs at its launched M (pnpi_pp_rowtile_query; bit-identical to 0); "attn_aug" (1) the 40-wide flash self-attention carries the running
- * maximum and the row sum in the padding column of Q / K / V (0: explicit shift and sum on the VALU; the column is written either way and ignored);"op_gemm_vt_perm16" (0) pnpi_op_gemm stores its
- * transposed columns in the permuted key order of the 4096-token self-attention sites (token t of every aligned 16-token group at
- * t ^ 12 for the two middle quads; rpb % 16 == 0, fp16; kernel tests);"op_attention_aug" (0) pnpi_op_attention is handed K and V whose column 40 holds 1.0
- * and runs that kernel (kernel tests). */
+ * Keys (tests/test_tuning_host.py holds this list against the table): "text_kv", "temb_cache", "ff_fold", "cfg_dedup", "src_share",
+ * "attn_aug", "attn_vt_perm", "attn_bwd_flash", "op_attention_aug", "op_gemm_vt_perm16", "op_attention_vt_perm", "gn_nofuse";
+ * "igemm_dma", "igemm_v128", "igemm_v64", "igemm_v256", "igemm_v320", "igemm_v256n", "igemm_wide", "v128_bk64_tiles", "tile_order",
+ * "igemm_force_cfg", "igemm_force_split", "igemm_bias_init", "igemm_sched", "igemm_vpp", "igemm_tapin", "igemm_pp_only_n",
+ * "igemm_pp_only_k", "igemm_pp_only_m", "igemm_deep_rings", "igemm_vt_lds", "igemm_res_late", "igemm_table", "igemm_table_near",
+ * "pp_rowtile"; "gn_inline_rows", "gn_small_max", "gn_small_min", "gn_wide_below"; "attn_pipe", "attn_nodma", "attn_ksq4",
+ * "attn_noaug", "abf_prefetch". */
 int pnpi_set_tuning(const char* key, int value);
+int pnpi_get_tuning(const char* key, int* value);
+int pnpi_tuning_info(int index, const char** key, int* initial, int* current);
+int pnpi_reset_tuning(void);
 /* Host-only query of the measured tile table launch_igemm consults before its cost model (no device work; used by the CPU tests):
  * returns 1 for an exact {M, N, K, ksize} entry, 2 when the same layer (N, K, ksize) is listed at another row count and the entry
  * nearest in M (at most 4x away) is used, 0 for none; cfg / split / entry_m (each nullable) receive the entry. */

@@ -1,5 +1,6 @@
 """ctypes binding of libpnpi.so (include/pnpi.h).  There is no CPU fallback: if the HIP library is missing or a call
 fails, this module raises."""
+import contextlib
 import ctypes as C
 import os
 
@@ -128,6 +129,9 @@ SYMBOLS = {
     "pnpi_op_conv": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i]),
     "pnpi_op_conv_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _ip]),
     "pnpi_set_tuning": (_i, [C.c_char_p, _i]),
+    "pnpi_get_tuning": (_i, [C.c_char_p, _ip]),
+    "pnpi_tuning_info": (_i, [_i, C.POINTER(C.c_char_p), _ip, _ip]),
+    "pnpi_reset_tuning": (_i, []),
     "pnpi_tile_table_lookup": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pnpi_pp_rowtile_query": (_i, [_i, _i, _i, _i]),
     "pnpi_igemm_plan_query": (_i, [C.POINTER(IgemmLaunchDesc), C.POINTER(IgemmPlan)]),
@@ -240,6 +244,30 @@ def load_library(path=None):
     if path is None:
         _lib = lib
     return lib
+
+
+def get_tuning(lib, key):
+    v = C.c_int()
+    if lib.pnpi_get_tuning(key.encode(), v) != 0:
+        raise ValueError("unknown tuning key %r" % key)
+    return v.value
+
+
+@contextlib.contextmanager
+def tuning(lib, **knobs):
+    """Set process-wide tuning knobs (pnpi_set_tuning) for the block and put back what they held before it, also when the block raises.
+    A key or value the library rejects raises ValueError, after the knobs already set have been put back."""
+    saved = []
+    try:
+        for k, v in knobs.items():
+            old = get_tuning(lib, k)
+            if lib.pnpi_set_tuning(k.encode(), int(v)) != 0:
+                raise ValueError("tuning %s = %r: a value this build does not accept" % (k, v))
+            saved.append((k, old))
+        yield
+    finally:
+        for k, old in reversed(saved):
+            lib.pnpi_set_tuning(k.encode(), old)
 
 
 def check(lib, ctx, status):

@@ -19,9 +19,7 @@
 #include <string>
 
 #include "model.h"
-
-static int g_text_kv = 1;      // tuning "text_kv" = 0: project the text context inside every forward, as the reference does (A/B)
-static int g_temb_cache = 1;   // tuning "temb_cache" = 0: three GEMVs per forward
+#include "tuning.h"
 
 // ---------------------------------------------------------------------------------------------------- error helpers
 // explicit status + message
@@ -708,7 +706,7 @@ int pnpi_op_conv_stats(pnpi_ctx* c, const void* x1, const void* x2, int C1, int 
   if (!c || !stats_out || !tile_rows_out) return PNPI_EINVAL;
   return conv_hook(c, x1, x2, C1, C2, B, H, W, ksize, stride, pad, ups, Ho, Wo, w, bias, res, N, out, force_cfg, force_split, stats_out, tile_rows_out);
 }
-/* process-wide kernel tuning knobs (tile-variant A/B inside one process, tests of non-default variants) */
+/* host-only queries of tile selection (pnpi_set_tuning and its kin: tuning.hip) */
 int pnpi_tile_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split, int* entry_m) {
   return igemm_table_lookup(M, N, K, ksize, cfg, split, entry_m);
 }
@@ -733,23 +731,6 @@ int pnpi_igemm_plan_query(const pnpi_igemm_launch_desc* d, pnpi_igemm_plan* plan
   const IgemmPlan pl = igemm_plan(p, d->ws_bytes > 0, d->ws_bytes > 0 ? (size_t)d->ws_bytes : 0, d->force_cfg, d->force_split, d->sel_M);
   memcpy(plan, &pl, sizeof pl);
   return 0;
-}
-int pnpi_set_tuning(const char* key, int value) {
-  if (!key) return PNPI_EINVAL;
-  if (!strcmp(key, "text_kv")) { g_text_kv = value; return 0; }
-  if (!strcmp(key, "temb_cache")) { g_temb_cache = value; return 0; }
-  if (!strcmp(key, "gn_inline_rows")) { norm_set_tuning_gn_inline_rows(value); return 0; }
-  if (!strcmp(key, "attn_vt_perm")) { g_vt_perm = value; return 0; }
-  if (!strcmp(key, "attn_aug")) { g_attn_aug = value; return 0; }
-  if (!strcmp(key, "attn_pipe")) return attn_set_tuning_pipe(value) == 0 ? 0 : PNPI_EINVAL;
-  if (!strcmp(key, "ff_fold")) { g_ff_fold = value; return 0; }
-  if (!strcmp(key, "cfg_dedup")) { if (value < 0 || value > 2) return PNPI_EINVAL; g_cfg_dedup = value; return 0; }
-  if (!strcmp(key, "src_share")) { if (value < 0 || value > 2) return PNPI_EINVAL; g_src_share = value; return 0; }
-  if (!strcmp(key, "op_attention_aug")) { g_op_attention_aug = value; return 0; }
-  if (!strcmp(key, "op_attention_vt_perm")) { g_op_attention_vt_perm = value; return 0; }
-  if (!strcmp(key, "op_gemm_vt_perm16")) { g_op_gemm_vt_perm16 = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "attn_bwd_flash")) { g_attn_bwd_flash = value; return 0; }
-  return igemm_set_tuning(key, value) == 0 ? 0 : PNPI_EINVAL;
 }
 int pnpi_op_gemm(pnpi_ctx* c, const void* a, int lda, const void* w, int ldw, int M, int N, int K, float alpha, const float* bias,
                  const void* res, void* out, int ldo, int vt_col0, void* outT, int vt_ld, int vt_f32, int rpb, int force_cfg,

@@ -14,14 +14,13 @@ static void prof_close(pnpi_ctx* c, ProfRec& r, int cls, double flops, double by
 // [Wp W2 | Wp] (TransformerW::fo) -- nothing non-linear sits between them and hs3 has no other reader.  Same FLOPs, one launch, no
 // hs3 round trip.  0: the two launches.  Results differ at fp16-rounding level only (hs3 is no longer rounded between the GEMMs;
 // Wp W2 is rounded once at load).
-static int g_ff_fold = 1;
 // tuning "cfg_dedup": the rows of a classifier-free-guidance launch that share a latent (its unconditional and its conditional row) share
 // everything the UNet computes before its first cross-attention.  1 / 2: that prefix runs once per distinct latent (unet_fwd, UNetDedup)
 // and is expanded to the rows of the launch where the text comes in; 2 pins every prefix GEMM to the tile / split-K of its full-row
 // form, which makes the forward bit-identical to 0 (per-element accumulation order does not depend on the tile's position).  0: off.
 // Default 1: every prefix GEMM is planned on the rows it launches (igemm_plan at the launched M: the table's rows for the compact shapes,
 // tile_table.inc); against 2 that moves fp32 summation order only (panel pixels by up to 2 / 255, profiles/rowfit_ab.json).
-static int g_cfg_dedup = [] { const char* e = getenv("PNPI_CFG_DEDUP"); const int v = e ? atoi(e) : 1; return v >= 0 && v <= 2 ? v : 1; }();   // the variable: whole-benchmark A/B runs
+// PNPI_CFG_DEDUP: whole-benchmark A/B runs.
 // the distinct latents of a launch: lat_u fp32 [U][C][S][S]; row r of the launch is latent hmap[r] (host) = dmap[r] (device)
 struct UNetDedup { const float* lat_u; int U; const int* hmap; const int* dmap; };
 // tuning "src_share": pnpi_direct_edit runs the source rows that its offset, reconstruction and edit passes repeat bit for bit once
@@ -30,7 +29,6 @@ struct UNetDedup { const float* lat_u; int U; const int* hmap; const int* dmap; 
 // Default 1: the source rows of the three passes are one launch row, so they see the same arithmetic whatever tile is chosen, and the
 // 8-row launch takes the table's 8-row entries (text K/V projections included: they are planned at their launched M like every GEMM).
 // A context that holds a tape keeps the full launch, configured as the compact one (pnpi_direct_edit), so it gives the same bits.
-static int g_src_share = [] { const char* e = getenv("PNPI_SRC_SHARE"); const int v = e ? atoi(e) : 1; return v >= 0 && v <= 2 ? v : 1; }();
 // the GEMM pin outside the deduplicated prefix: none, or (pinned row sharing) compact rows -> logical rows
 static inline void pin_base(pnpi_ctx* c) {
   const bool on = c->share_pin && c->share_U > 0;
@@ -86,12 +84,6 @@ struct Tape {
   float* d_ctx = nullptr;                             // [rows * ctx_len * cross_dim] fp32
   void* attn_scratch = nullptr; size_t attn_scratch_bytes = 0;
 };
-static int g_attn_aug = 1;           // tuning "attn_aug" = 0: the 64-wide flash kernel ignores the augmented column (A/B)
-static int g_vt_perm = 1;            // tuning "attn_vt_perm": V^T of the 4096-token self-attention sites in the permuted key order (A/B)
-static int g_attn_bwd_flash = 1;     // tuning "attn_bwd_flash": self-attention backward without the [N][N] matrices in memory (0: the materialised form everywhere)
-static int g_op_attention_aug = 0;       // tuning "op_attention_aug": pnpi_op_attention is handed K / V^T with 1.0 in column / row dh (kernel tests)
-static int g_op_gemm_vt_perm16 = 0;      // tuning "op_gemm_vt_perm16": pnpi_op_gemm writes its transposed columns in the permuted key order (GemmP::vt_perm16; kernel tests)
-static int g_op_attention_vt_perm = 0;   // tuning "op_attention_vt_perm": pnpi_op_attention is handed a permuted V^T (kernel tests)
 static inline bool taping(pnpi_ctx* c) { return c->tape && c->tape->rec && !c->dry; }
 // a recording forward (or the dry run that sizes the arenas for one) keeps every activation and takes the plain-layout transformer block
 static inline bool keep_acts(pnpi_ctx* c) { return c->tape && c->tape->rec; }
@@ -117,8 +109,7 @@ static int op_gn(pnpi_ctx* c, const half_t* x1, const half_t* x2, int C1, int C2
   }
   const bool ok1 = s1.p && gn_stats_usable(HW, s1.rows);
   const bool ok2 = !x2 || (s2.p && gn_stats_usable(HW, s2.rows));
-  static const bool gn_nofuse = getenv("PNPI_GN_NOFUSE") != nullptr;   // ablation: always recompute the statistics
-  if (ok1 && ok2 && !gn_nofuse) {
+  if (ok1 && ok2 && !g_gn_nofuse) {
     PROFD(PNPI_KC_GROUPNORM, 0.0, 2.0 * B * HW * (double)(C1 + C2) * 2.0, B * HW, C1 + C2, 1,
           launch_groupnorm_fused(x1, x2, C1, C2, B, HW, G, eps, nw.g, nw.b, silu, out, s1.p, HW / s1.rows, s2.p,
                                  x2 ? HW / s2.rows : 1, c->gn_partial, c->st));

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "ops.h"
+#include "tuning.h"
 
 static constexpr int KV_TILE = 64;
 static constexpr int SV_LD = KV_TILE + 4;  // halfs; 136-byte rows: conflict-free ds_read_b64 over 32 rows
@@ -588,17 +589,11 @@ __global__ void __launch_bounds__(256) attn_flash_pipe64_kernel(AttnP p) {
   if (p.lse && w.qok && h == 0) p.lse[((size_t)w.orow * p.heads + w.head) * p.Nq + w.qtok] = mrun + __log2f(ltot);
   flash_store_o(p, w, h, O, inv);
 }
-static int g_attn_pipe = 0;
-int attn_set_tuning_pipe(int v) { g_attn_pipe = v; return 0; }
-#else
-static const int g_attn_pipe = 0;
-int attn_set_tuning_pipe(int v) { return v == 0 ? 0 : -2; }      // the instance exists only in the ablation library
 #endif
 
 // which launches the 64-wide LDS-DMA kernel takes (the producer of V^T may then write the permuted key order)
 bool attn_flash_uses_dma64(int Dp, int Nk, int causal) {
-  static const bool no_dma = getenv("PNPI_ATTN_NODMA") != nullptr;
-  return Dp == 64 && Nk % 64 == 0 && Nk >= 128 && !no_dma && !causal;
+  return Dp == 64 && Nk % 64 == 0 && Nk >= 128 && !g_attn_nodma && !causal;
 }
 
 // every 16-byte load of Q / K / V^T and every 8-byte store of O is aligned
@@ -612,10 +607,9 @@ int launch_attn_flash(const AttnP& p, hipStream_t st) {
   const int total = ((p.Nq + 127) / 128) * p.heads * p.nrows;
   dim3 grid((unsigned)(((total + 7) / 8) * 8), 1, 1);
   if (attn_flash_uses_dma64(p.Dp, p.Nk, p.causal)) {
-    static const bool ksq3 = !(getenv("PNPI_ATTN_KSQ4") != nullptr);      // PNPI_ATTN_KSQ4: always four k-steps (A/B)
-    static const bool no_aug = getenv("PNPI_ATTN_NOAUG") != nullptr;         // A/B: ignore AttnP::aug
-    if (p.aug && p.dh == 40 && ksq3 && !no_aug) {
-#ifdef PNPI_ABLATIONS
+    const bool ksq3 = !g_attn_ksq4;      // tuning "attn_ksq4": always four k-steps (A/B)
+    if (p.aug && p.dh == 40 && ksq3 && !g_attn_noaug) {
+#ifdef PNPI_ABLATIONS      // tuning "attn_pipe": the product library accepts 0 only
       if (p.vt_perm && g_attn_pipe == 1) attn_flash_pipe64_kernel<0><<<grid, 256, 0, st>>>(p);
       else if (p.vt_perm && g_attn_pipe == 2) attn_flash_pipe64_kernel<1><<<grid, 256, 0, st>>>(p);
       else
@@ -1348,10 +1342,9 @@ static int launch_abf(const AttnBwdP& p, int mode, hipStream_t st) {
   if (p.nsplit < 1 || (p.nsplit > 1 && (mode == 0 || !p.part))) return -3;
   const int T = ((p.nb + 127) >> 7) * p.heads * p.nsplit;
   const dim3 grid((unsigned)(((T + 7) / 8) * 8));
-  static const bool pf_on = !(getenv("PNPI_ABF_PREFETCH") && atoi(getenv("PNPI_ABF_PREFETCH")) == 0);   // PNPI_ABF_PREFETCH=0: never the register-prefetch variant (A/B)
   if constexpr (DP == 64 || DP == 96) {
-    // many loop tiles per workgroup and at most ~one workgroup per CU: prefetch the next tile into registers
-    if (pf_on && p.nl >= 8 * LT && T <= 512) {
+    // many loop tiles per workgroup and at most ~one workgroup per CU: prefetch the next tile into registers (tuning "abf_prefetch")
+    if (g_abf_prefetch && p.nl >= 8 * LT && T <= 512) {
       if (mode == 0) attn_bwd_flash_kernel<DP, LT, 0, true><<<grid, 256, 0, st>>>(p);
       else if (mode == 1) attn_bwd_flash_kernel<DP, LT, 1, true><<<grid, 256, 0, st>>>(p);
       else attn_bwd_flash_kernel<DP, LT, 2, true><<<grid, 256, 0, st>>>(p);

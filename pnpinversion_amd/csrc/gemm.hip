@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "ops.h"
+#include "tuning.h"
 #include "igemm_dma.inc"
 #include "igemm_pp.inc"
 
@@ -289,7 +290,6 @@ __global__ void __launch_bounds__(256) igemm_kernel(GemmP p_in) {
 //     drained by the vmcnt(0) the compiler puts in front of the one barrier per chunk.
 // Requires (C1 + C2) % 64 == 0 and C1 % 64 == 0 (every SD-1.x layer but the 4/3-channel stems, which stay on v1).
 // ------------------------------------------------------------------------------------------------------------------
-static int g_tile_order = -1;   // PNPI_TILE_ORDER: force 0 / 1 (ablation)
 static half_t* g_zero_page = nullptr;   // out-of-range lanes of igemm_dma_kernel read it (igemm_init)
 
 static thread_local int g_last_geom[7] = {0, 0, 0, 0, 0, 0, 0};   // template arguments of the most recent igemm_dma_kernel launch (all 0: the v1 kernel)
@@ -383,51 +383,10 @@ void gemm_defaults(GemmP& p) {
 static constexpr size_t lds_bytes(int BM, int BN) { return (size_t)(2 * BM + 2 * BN) * LDS_LD * sizeof(half_t); }
 
 static constexpr size_t ZERO_PAGE_BYTES = 128 << 10;   // >= 2 * (longest K + one chunk): out-of-range rows walk it like real rows
-static int g_wide = 1;      // PNPI_IGEMM_WIDE=0: never pick the 128x320 / 128x256 tiles (ablation)
-static int g_use_dma = 1;      // 0: register-staged v1 kernel everywhere
-static int g_use_table = 1;    // tuning "igemm_table" = 0: cost model only (no measured per-shape table)
-static int g_table_near = 1;   // tuning "igemm_table_near" = 0: exact {M, N, K, ksize} matches only (no nearest-row-count entry)
-static int g_res_late = 0;     // tuning "igemm_res_late" = 1: residual added in the store loop (fp16(fp16(acc + bias) + res)) instead of staged
-static int g_vt_lds = 1;       // tuning "igemm_vt_lds" = 0: transposed columns through the scalar epilogue (A/B)
-static int g_deep_rings = 1;   // tuning "igemm_deep_rings" = 0: shallow rings whatever the occupancy (A/B)
-static int g_bias_init = 1;     // 0: bias added in the epilogue (ablation)
-static int g_pp_only_n = 0, g_pp_only_k = 0, g_pp_only_m = 0;   // tuning "igemm_pp_only_{m,n,k}" > 0: table entries of the ping-pong kernel apply only to launches with that M / N / K (bisection of a wrong layer)
-static int g_tapin = 0;         // tuning "igemm_tapin" = 1: the ping-pong kernel walks 3 x 3 convolutions channel-slab-major (GemmP::k_order)
-static int g_varpp = 0;         // tuning "igemm_vpp": ablations of the ping-pong kernel (1 = no MFMAs, 2 = no DMA; both produce garbage)
-static int g_sched = 0;         // tuning "igemm_sched" = 1: the hand-scheduled main loop (igemm_dma_kernel<..., ABL = 4>) for the one-k-group tile configurations
-static int g_pp_rowtile = [] { const char* e = getenv("PNPI_PP_ROWTILE"); const int v = e ? atoi(e) : 1; return v == 0 ? 0 : 1; }();   // tuning "pp_rowtile": the ping-pong tile's row height follows the launched M (pp_rowtile_pick); 0: the table's tile as it stands
-static int g_force_split = 0;   // > 0 with igemm_force_cfg: split-K of every auto-configured launch (in-forward tuning sweeps)
 static thread_local int g_last_cfg = -1, g_last_split = 1;   // per thread: two contexts may launch from two threads   // what the most recent launch_igemm used (profiling dumps)
 void igemm_last_launch(int* cfg, int* split, int* geom) { *cfg = g_last_cfg; *split = g_last_split; for (int i = 0; i < 7; ++i) geom[i] = g_last_geom[i]; }
-static int g_force_cfg = -1;   // >= 0: every auto-configured launch uses this tile configuration (tests, whole-forward A/B)
-static int g_var128 = 2, g_var64 = 0, g_var256 = 0, g_var320 = 1, g_var256n = 1;
-static long g_v128_bk64_tiles = 0;   // PNPI_V128_BK64_TILES: tile count from which the 128x128 kernel switches to 128-byte rows   // tuning variants (PNPI_IGEMM_V128 / PNPI_IGEMM_V64)
-void igemm_set_dma(int on) { g_use_dma = on; }
-// process-wide tuning knobs (A/B measurements inside one process, tests of the non-default variants); 0 on success
-int igemm_set_tuning(const char* key, int v) {
-  struct { const char* k; int* p; } tab[] = {{"igemm_dma", &g_use_dma}, {"igemm_v128", &g_var128}, {"igemm_v64", &g_var64}, {"igemm_v256", &g_var256},
-                                             {"igemm_v320", &g_var320}, {"igemm_v256n", &g_var256n}, {"igemm_wide", &g_wide}, {"tile_order", &g_tile_order}, {"igemm_force_cfg", &g_force_cfg}, {"igemm_force_split", &g_force_split}, {"igemm_bias_init", &g_bias_init}, {"igemm_sched", &g_sched}, {"igemm_vpp", &g_varpp}, {"igemm_tapin", &g_tapin}, {"igemm_pp_only_n", &g_pp_only_n}, {"igemm_pp_only_k", &g_pp_only_k}, {"igemm_pp_only_m", &g_pp_only_m}, {"igemm_deep_rings", &g_deep_rings}, {"igemm_vt_lds", &g_vt_lds}, {"igemm_res_late", &g_res_late}, {"igemm_table", &g_use_table}, {"igemm_table_near", &g_table_near}, {"pp_rowtile", &g_pp_rowtile}};
-#ifndef PNPI_ABLATIONS
-  // the ablation instances (no MFMAs / no DMA / no fragment reads, the hand-scheduled 4-wave loop) exist only in a `build --ablations`
-  // library: a product build rejects their selectors here instead of silently timing the default kernel
-  if ((!strcmp(key, "igemm_sched") || !strcmp(key, "igemm_vpp")) && v != 0) return -2;
-  if ((!strcmp(key, "igemm_v128") || !strcmp(key, "igemm_v320")) && (v == 11 || v == 12 || v == 15)) return -2;
-#endif
-  for (auto& e : tab)
-    if (!strcmp(key, e.k)) { *e.p = v; return 0; }
-  return -1;
-}
 
 int igemm_init() {
-  if (const char* e = getenv("PNPI_IGEMM_DMA")) g_use_dma = atoi(e);
-  if (const char* e = getenv("PNPI_IGEMM_V128")) g_var128 = atoi(e);
-  if (const char* e = getenv("PNPI_IGEMM_V64")) g_var64 = atoi(e);
-  if (const char* e = getenv("PNPI_IGEMM_V256")) g_var256 = atoi(e);
-  if (const char* e = getenv("PNPI_IGEMM_V320")) g_var320 = atoi(e);
-  if (const char* e = getenv("PNPI_IGEMM_V256N")) g_var256n = atoi(e);
-  if (const char* e = getenv("PNPI_IGEMM_WIDE")) g_wide = atoi(e);
-  if (const char* e = getenv("PNPI_V128_BK64_TILES")) g_v128_bk64_tiles = atol(e);
-  if (const char* e = getenv("PNPI_TILE_ORDER")) g_tile_order = atoi(e);
   if (!g_zero_page) {
     HIP_CHECK_RET(hipMalloc((void**)&g_zero_page, ZERO_PAGE_BYTES));
     HIP_CHECK_RET(hipMemset(g_zero_page, 0, ZERO_PAGE_BYTES));

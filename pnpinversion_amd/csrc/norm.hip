@@ -5,6 +5,7 @@
 // All statistics are fp32; 16-byte (8 x fp16) vector accesses, NHWC so that a wavefront reads contiguous channels.
 #include <algorithm>
 #include "ops.h"
+#include "tuning.h"
 
 // ------------------------------------------------------------------------------------------------ GroupNorm
 // Three launches, all latency-lean:
@@ -244,10 +245,9 @@ __global__ void __launch_bounds__(NT) gn_small_kernel(const half_t* __restrict__
   }
 }
 
-static int gn_small_max() {     // elements per (sample, group) slice handled by the one-launch kernel (PNPI_GN_SMALL_MAX lowers it)
-  static const int v = getenv("PNPI_GN_SMALL_MAX") ? std::min(atoi(getenv("PNPI_GN_SMALL_MAX")), GN_SMALL_ELEMS) : GN_SMALL_ELEMS;
-  return v;
-}
+// elements per (sample, group) slice handled by the one-launch kernel (tuning "gn_small_max" lowers it)
+static_assert(GN_SMALL_ELEMS == 24576, "the default of \"gn_small_max\" in tuning.h");
+static int gn_small_max() { return std::min(g_gn_small_max, GN_SMALL_ELEMS); }
 // B (optional): at 48 rows and more (1536 blocks) only slices up to 8 192 elements take the one-launch kernel -- with six blocks per CU
 // the streaming statistics / finalize / apply passes are faster on the larger slices (96-row forward 94.2 -> 93.4 ms, no difference at 12 rows;
 // round 5, PNPI_GN_SMALL_MAX sweep)
@@ -260,16 +260,16 @@ static int launch_gn_small(const half_t* x1, const half_t* x2, int C1, int C2, i
                            const float* beta, int silu, half_t* out, hipStream_t st) {
   const int cpg = (C1 + C2) / G;
   static DeviceOnce attr_once;
-  // the launch asks for HW * cpg * 2 + cpg * 8 + 16 bytes (slice + gamma / beta + alignment slack): <= gn_small_max() * 2 + 8192 + 16
+  // the launch asks for HW * cpg * 2 + cpg * 8 + 16 bytes (slice + gamma / beta + alignment slack): <= GN_SMALL_ELEMS * 2 + 8192 + 16
+  // (set once per device, so for the largest gn_small_max() the knob can give)
   if (int r = once_per_device(attr_once, [&]() {
-        const int lim = gn_small_max() * 2 + 8192 + 16;
+        const int lim = GN_SMALL_ELEMS * 2 + 8192 + 16;
         int e = (int)hipFuncSetAttribute((const void*)gn_small_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
         return e ? e : (int)hipFuncSetAttribute((const void*)gn_small_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
       })) return r;
   // 1024-thread blocks: each (sample, group) slice is a latency chain load -> reduce -> normalise -> store, and four times
   // the lanes per slice shorten it at every row count measured (1 row: 16.2 -> 12.7 us per launch; 12 rows: 23.0 -> 20.7)
-  static const int wide_below = getenv("PNPI_GN_WIDE_BELOW") ? atoi(getenv("PNPI_GN_WIDE_BELOW")) : (1 << 30);
-  if (B * G < wide_below)
+  if (B * G < g_gn_wide_below)
     gn_small_kernel<1024><<<dim3(B, G), 1024, (size_t)HW * cpg * sizeof(half_t) + (size_t)cpg * 8 + 16, st>>>(x1, x2, C1, C2, HW, G, eps, gamma, beta, silu, out);
   else
     gn_small_kernel<256><<<dim3(B, G), 256, (size_t)HW * cpg * sizeof(half_t) + (size_t)cpg * 8 + 16, st>>>(x1, x2, C1, C2, HW, G, eps, gamma, beta, silu, out);
@@ -427,18 +427,14 @@ __global__ void __launch_bounds__(256) gn_fin_apply_kernel(const half_t* __restr
   }
 }
 
-static int g_gn_inline_rows = 0;   // statistics-fused GroupNorm: one launch (finalize inside apply) up to this many B*HW rows
-void norm_set_tuning_gn_inline_rows(int v) { g_gn_inline_rows = v; }
-
 int launch_groupnorm_fused(const half_t* x1, const half_t* x2, int C1, int C2, int B, int HW, int G, float eps, const float* gamma,
                            const float* beta, int silu, half_t* out, const float* st1, int tpb1, const float* st2, int tpb2,
                            float* scratch, hipStream_t st) {
   const int C = C1 + C2;
   if ((C & 7) || (C1 & 7) || C % G || G > 64) return -3;
   // the one-launch kernel runs one block per (sample, group) -- a few dozen blocks at one row -- yet measured equal to the
-  // two-launch path there (5.72 vs 5.75 ms per forward): no threshold by default
-  static const int small_min_blocks = getenv("PNPI_GN_SMALL_MIN") ? atoi(getenv("PNPI_GN_SMALL_MIN")) : 0;
-  if (gn_small_ok(C1, C2, HW, G, B) && B * G >= small_min_blocks)
+  // two-launch path there (5.72 vs 5.75 ms per forward): no threshold by default (tuning "gn_small_min")
+  if (gn_small_ok(C1, C2, HW, G, B) && B * G >= g_gn_small_min)
     return launch_gn_small(x1, x2, C1, C2, B, HW, G, eps, gamma, beta, silu, out, st);
   if ((long)B * HW <= g_gn_inline_rows) {
     // ~2 blocks per CU, each with enough pixels to amortise its own reduction of the partials

@@ -61,8 +61,6 @@ void igemm_last_launch(int* cfg, int* split, int* geom7);
 // measured tile table: 1 = exact {M, N, K, ksize} entry, 2 = the same layer at the nearest row count (<= 4x away in M), 0 = none (cost model)
 int igemm_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split, int* entry_m);
 int igemm_pp_rowtile_query(int cfg, int M, int N, int split);   // rows of the ping-pong tile launched for (cfg 16 / 17, M, N, split); host only
-int igemm_set_tuning(const char* key, int value);   // process-wide tuning knobs; 0 on success, -1 unknown key
-void igemm_set_dma(int on);  // 1 (default): LDS-DMA kernel where applicable; 0: register-staged v1 kernel everywhere
 
 // ---------------------------------------------------------------------------------------------------------------
 // Normalisation / elementwise
@@ -75,7 +73,6 @@ int launch_groupnorm(const half_t* x1, const half_t* x2, int C1, int C2, int B, 
 int launch_groupnorm_fused(const half_t* x1, const half_t* x2, int C1, int C2, int B, int HW, int G, float eps,
                            const float* gamma, const float* beta, int silu, half_t* out, const float* st1, int tpb1,
                            const float* st2, int tpb2, float* scratch, hipStream_t st);
-void norm_set_tuning_gn_inline_rows(int v);   // tuning "gn_inline_rows"
 // fp32 elements of `partial` (fused = false) / `scratch` (fused = true) that launch writes at most
 size_t groupnorm_scratch_floats(int C1, int C2, int B, int HW, int G, bool fused);
 int launch_layernorm(const half_t* x, int M, int C, float eps, const float* gamma, const float* beta, half_t* out,
@@ -134,7 +131,6 @@ struct AttnP {
   float* lse = nullptr;           // optional [out_row][heads][Nq]: log2-domain log-sum-exp of every query (recording forward of the null-text path)
 };
 int launch_attn_flash(const AttnP& p, hipStream_t st);
-int attn_set_tuning_pipe(int v);        // tuning "attn_pipe" (ablation builds only): the half-tile software-pipelined forms of the 64-wide LDS-DMA kernel
 bool attn_flash_uses_dma64(int Dp, int Nk, int causal);
 // Class-restricted self-attention (mask-guided MasaCtrl, models/masactrl/masactrl.py:138-193 for binary masks): query i attends only to the
 // keys j with kcls[j] == qcls[i]; a query whose class no key carries attends to all keys uniformly (the reference's softmax over logits

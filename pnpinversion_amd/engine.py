@@ -245,6 +245,10 @@ class NativeEngine:
     def reset_counters(self):
         self._call("pnpi_reset_counters")
 
+    def tuning(self, **knobs):
+        """with eng.tuning(key=value, ...): process-wide tuning knobs for the block (_capi.tuning)"""
+        return _capi.tuning(self.lib, **knobs)
+
     def masa_set_masks(self, mask_s=None, mask_t=None):
         """pnpi_masa_set_masks: attach binary masks [nimg, h, w] (or (h, w)) to the kind-2 controllers of this context; no arguments clears them."""
         if mask_s is None and mask_t is None:

@@ -44,6 +44,9 @@ class Ctx:
         st = getattr(self.lib, name)(self.h, *args)
         _capi.check(self.lib, self.h, st)
 
+    def tuning(self, **knobs):
+        return _capi.tuning(self.lib, **knobs)
+
     def close(self):
         if self.h:
             self.lib.pnpi_destroy(self.h)

@@ -83,9 +83,6 @@ WS_BYTES = 96 * MiB                 # pnpi_create's split-K workspace for up to 
 NO_VT = 1 << 30
 ROW_C, ROW_Z = 5, 6                 # the constructed (+-64) and the all-zero row of a; the constructed row of w is N - 3
 
-DEFAULT_TUNING = {"igemm_v128": 2, "igemm_v64": 0, "igemm_v256": 0, "igemm_v320": 1, "igemm_v256n": 1, "igemm_deep_rings": 1, "igemm_dma": 1,
-                  "igemm_bias_init": 1, "igemm_vt_lds": 1, "igemm_tapin": 0, "igemm_force_cfg": -1}
-
 # ------------------------------------------------------------------------------------------------ instance map
 PRODUCT_INSTANCES = frozenset([
     "v1<128,128,fast>", "v1<128,128,generic>", "v1<64,64,fast>", "v1<64,64,generic>",
@@ -309,16 +306,6 @@ def _build_cases():
 CASES = _build_cases()
 
 
-def set_tuning(lib, tune):
-    for k, v in dict(tune).items():
-        assert k in DEFAULT_TUNING and lib.pnpi_set_tuning(k.encode(), v) == 0, k
-
-
-def restore_tuning(lib):
-    for k, v in DEFAULT_TUNING.items():
-        lib.pnpi_set_tuning(k.encode(), v)
-
-
 def query_plan(lib, M, N, K, *, cfg, split=0, lda=None, ldw=None, ldo=None, bias=None, res=False, geglu=0, vt_col0=NO_VT, vt_ld=0, vt_f32=0, rpb=1,
                vt_perm16=0, ksize=1, C1=None, C2=0):
     """pnpi_igemm_plan_query under the tuning in force (the caller sets and restores it)"""
@@ -333,13 +320,10 @@ def query_plan(lib, M, N, K, *, cfg, split=0, lda=None, ldw=None, ldo=None, bias
 
 
 def case_plan(lib, case):
-    """the plan of a case in the poisoned layout of the GPU test (lda = K + 24, ldw = K + 8); sets the case's tuning and restores the defaults"""
-    set_tuning(lib, case.tune)
-    try:
+    """the plan of a case in the poisoned layout of the GPU test (lda = K + 24, ldw = K + 8), under the case's tuning"""
+    with _capi.tuning(lib, **dict(case.tune)):
         return query_plan(lib, case.M, case.N, case.K, cfg=case.cfg, split=case.split, lda=case.K + 24, ldw=case.K + 8, ldo=case.ldo, bias=case.bias,
                           res=case.res)
-    finally:
-        restore_tuning(lib)
 
 
 def check_case_plan(case, pl):
@@ -554,7 +538,6 @@ def _plan_fields(pl):
 
 
 def test_cases_reach_their_instances(lib):
-    restore_tuning(lib)
     defaults = [_plan_fields(query_plan(lib, M, N, K, cfg=-1, bias="a16")) for M, N, K in ((130, 136, 320), (1088, 1024, 320), (194, 328, 192))]
     reached = set()
     for case in CASES:
@@ -567,7 +550,7 @@ def test_cases_reach_their_instances(lib):
     assert reached == PRODUCT_INSTANCES, sorted(PRODUCT_INSTANCES - reached)
     assert len(set(c.name for c in CASES)) == len(CASES)
     assert all(c.M <= 1200 and c.N <= 1100 and c.K <= 1024 for c in CASES if not c.note.startswith("row index"))
-    # case_plan left the defaults in force: unforced launches plan as they did before the table's tunings were set
+    # case_plan left the knobs as it found them: unforced launches plan as they did before the table's tunings were set
     assert [_plan_fields(query_plan(lib, M, N, K, cfg=-1, bias="a16")) for M, N, K in ((130, 136, 320), (1088, 1024, 320), (194, 328, 192))] == defaults
 
 
@@ -579,12 +562,9 @@ def test_ping_pong_without_row_stores_falls_back_to_tile_0(lib):
     for rpb in (bm, 40):
         M, N = 3 * rpb, bn + 40
         for form, tune, col0, f32, want in (("lds", {}, bn, 0, 17), ("scalar", {"igemm_vt_lds": 0}, bn, 0, 0), ("f32", {}, 0, 1, 0)):
-            set_tuning(lib, tune)
-            try:
+            with _capi.tuning(lib, **tune):
                 pl = query_plan(lib, M, N, K, cfg=17, lda=K + 24, ldw=K + 8, ldo=col0 + 8 if col0 else N, bias="a16", vt_col0=col0, vt_ld=rpb + 8, vt_f32=f32,
                                 rpb=rpb)
-            finally:
-                restore_tuning(lib)
             assert (pl.err, pl.id) == (0, want), (rpb, form, pl.err, pl.id)
             assert instance_of(pl) == ("pp<192,320>" if want == 17 else "dma<128,128,32,8>"), (rpb, form, instance_of(pl))
 

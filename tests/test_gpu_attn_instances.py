@@ -96,16 +96,11 @@ class Case:
         lse = torch.full((self.out_rows, self.heads, self.Nq), LSE_CANARY, dtype=torch.float32, device=DEV) if want_lse else None
         rows_dev = torch.tensor(rows, dtype=torch.int32, device=DEV).reshape(-1, 4).contiguous()
         assert max(r[0] for r in rows) < self.out_rows - 1 and max(max(r[1:]) for r in rows) < self.B
-        assert ctx.lib.pnpi_set_tuning(b"op_attention_aug", int(self.aug)) == 0
-        assert ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", int(self.perm)) == 0
-        try:
+        with ctx.tuning(op_attention_aug=int(self.aug), op_attention_vt_perm=int(self.perm)):
             ctx.call("pnpi_op_attention_ex", ptr(self.fused), self.ld, self.q_off, ptr(self.fused), self.ld, self.k_off, ptr(self.vt), self.ldv,
                      ptr(o), self.ldo, self.heads, self.Nq, self.Nk, self.Dp, self.dh, self.scale, ptr(rows_dev), len(rows), causal,
                      ptr(lse) if want_lse else None)
             torch.cuda.synchronize()
-        finally:
-            ctx.lib.pnpi_set_tuning(b"op_attention_aug", 0)
-            ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", 0)
         return o, lse
 
     def check(self, tag, o, lse, rows, causal=0):

@@ -210,16 +210,13 @@ def test_attention_bwd_flash(ctx, B, heads, Nq, Nk, dh, Dp):
     nbytes = ctx.lib.pnpi_op_attention_bwd_scratch_bytes(Nq, Nk, dh) * heads + (64 << 20)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
     got = {}
-    try:
-        for flash in (1, 0):
-            assert ctx.lib.pnpi_set_tuning(b"attn_bwd_flash", flash) == 0
+    for flash in (1, 0):
+        with ctx.tuning(attn_bwd_flash=flash):
             dq, dk, dv = [torch.zeros_like(t) for t in (q, k, v)]
             ctx.call("pnpi_op_attention_bwd", ptr(q), heads * Dp, 0, ptr(k), heads * Dp, 0, ptr(v), heads * Dp, 0, ptr(d_o), heads * dh, heads, Nq, Nk, Dp,
                      dh, scale, B, ptr(dq), ptr(dk), ptr(dv), ptr(scratch), nbytes)
             torch.cuda.synchronize()
             got[flash] = (dq, dk, dv)
-    finally:
-        ctx.lib.pnpi_set_tuning(b"attn_bwd_flash", 1)
     for name, i, ref in (("dq", 0, qr.grad), ("dk", 1, kr.grad), ("dv", 2, vr.grad)):
         for flash in (1, 0):
             gh = got[flash][i].float().reshape(B, Nq if i == 0 else Nk, heads, Dp)
@@ -249,11 +246,10 @@ def test_context_gradient_same_with_forward_lse_and_two_pass_dq():
     got = {}
     try:
         for mode in (1, 2, 0):
-            assert eng.lib.pnpi_set_tuning(b"attn_bwd_flash", mode) == 0
-            eps, dctx = eng.unet_context_grad(lat, 500, ctx, d_eps)
-            got[mode] = (eps.clone(), dctx.clone())
+            with eng.tuning(attn_bwd_flash=mode):
+                eps, dctx = eng.unet_context_grad(lat, 500, ctx, d_eps)
+                got[mode] = (eps.clone(), dctx.clone())
     finally:
-        eng.lib.pnpi_set_tuning(b"attn_bwd_flash", 1)
         eng.close()
     assert torch.equal(got[1][0], got[2][0]) and torch.isfinite(got[1][1]).all() and got[1][1].abs().max() > 0
     assert rel_err(got[1][1], got[2][1]) < 1e-2, rel_err(got[1][1], got[2][1])

@@ -36,19 +36,6 @@ PROMPTS = [("a photograph of a mountain", "a watercolor photograph of a snowy mo
            ("a cat sitting on a wooden chair", "a small cat sitting on a old wooden chair", "cat", "small")]
 
 
-class Dedup:
-    """the process-wide knob for the length of a with-block; the default (2) afterwards"""
-
-    def __init__(self, eng, value):
-        self.lib, self.value = eng.lib, value
-
-    def __enter__(self):
-        assert self.lib.pnpi_set_tuning(b"cfg_dedup", self.value) == 0
-
-    def __exit__(self, *exc):
-        assert self.lib.pnpi_set_tuning(b"cfg_dedup", 2) == 0
-
-
 class Case:
     def __init__(self, cfg, blend):
         self.cfg = cfg
@@ -65,14 +52,14 @@ class Case:
             c = ac.make_controller(self.pipe, [src, tgt], False, {"default_": 0.4}, 0.6, ((bw,), (bw,)) if blend else None,
                                    {"words": (ew,), "values": (2,)}, num_ddim_steps=STEPS)
             self.ctrls.append(c.tables())
-        with Dedup(self.eng, 0):
+        with self.eng.tuning(cfg_dedup=0):
             self.traj = self.eng.ddim_invert(self.z0, self.ctx[:, 2], self.ts).clone()      # [STEPS + 1][2][4][S][S]
         self.memo = {}
 
     def direct_edit(self, mode, fresh=False):
         """(noise_loss, latents, rows through the compact prefix) of the two-pass lock-step edit of both images under cfg_dedup = mode"""
         if fresh or mode not in self.memo:
-            with Dedup(self.eng, mode):
+            with self.eng.tuning(cfg_dedup=mode):
                 self.eng.reset_counters()
                 nl, lats = self.eng.direct_edit(self.traj, self.ctx, [None, self.ctrls], self.ts, 7.5)
                 got = (nl.clone(), lats.clone(), self.eng.counters()["unet_dedup_prefix_rows"])
@@ -124,7 +111,7 @@ def test_other_row_maps(small64):
     """3. the pruned schedule (map [1, 0, 1], U = 2 of 3 per image), a P = 1 CFG loop and a loop without a map"""
     eng, got = small64.eng, {}
     for mode in (0, 2):
-        with Dedup(eng, mode):
+        with eng.tuning(cfg_dedup=mode):
             eng.reset_counters()
             pr = eng.direct_edit_pruned(small64.traj, small64.ctx, small64.ctrls, small64.ts, 7.5).clone()
             n_pr = eng.counters()["unet_dedup_prefix_rows"]

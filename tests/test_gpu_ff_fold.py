@@ -33,26 +33,13 @@ def _inputs(rows, seed):
     return lat, weights.synth_context(CFG, rows, seed=seed + 1)
 
 
-class Fold:
-    """the process-wide knob for the length of a with-block; the default (1) afterwards"""
-
-    def __init__(self, eng, value):
-        self.lib, self.value = eng.lib, value
-
-    def __enter__(self):
-        assert self.lib.pnpi_set_tuning(b"ff_fold", self.value) == 0
-
-    def __exit__(self, *exc):
-        assert self.lib.pnpi_set_tuning(b"ff_fold", 1) == 0
-
-
 def _forward(eng, fold, lat, t, ctx):
-    with Fold(eng, fold):
+    with eng.tuning(ff_fold=fold):
         return eng.unet(lat, t, ctx).clone()
 
 
 def _igemm_launches(eng, fold, lat, t, ctx):
-    with Fold(eng, fold):
+    with eng.tuning(ff_fold=fold):
         eng.profile_begin()
         eng.unet(lat, t, ctx)
         st = eng.profile_end()
@@ -177,7 +164,7 @@ def test_recording_forward_ignores_the_knob(model):
     got = {}
     eng.unet_context_grad(lat, 500, ctx, d_eps)          # the first recording forward of a context also sizes the tape's arenas (a counted dry run)
     for fold in (0, 1):
-        with Fold(eng, fold):
+        with eng.tuning(ff_fold=fold):
             eng.reset_counters()
             eng.profile_begin()
             eps, dctx = eng.unet_context_grad(lat, 500, ctx, d_eps)

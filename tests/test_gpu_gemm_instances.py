@@ -52,10 +52,10 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from pnpinversion_amd import _capi  # noqa: E402
 from tests.gpu_util import Ctx, ptr, rel_err  # noqa: E402
 from tests.test_gemm_bound_host import (CASES, GEGLU_TILES, KAPPA_G, NO_VT, bound_f16, bound_f32, bound_geglu, case_operands,  # noqa: E402
-                                        check_case_plan, gemm_inputs, geglu_ref64, geglu_shape, instance_of, query_plan, ref64, restore_tuning,
-                                        set_tuning, worst_ratio)
+                                        check_case_plan, gemm_inputs, geglu_ref64, geglu_shape, instance_of, query_plan, ref64, worst_ratio)
 
 DEV = "cuda"
 CANARY = -77.25              # exactly representable in fp16 and fp32
@@ -66,7 +66,6 @@ def ctx():
     c = Ctx()
     yield c
     c.close()
-    restore_tuning(c.lib)
 
 
 def poisoned(t, ld, spare_rows=1):
@@ -143,14 +142,11 @@ def run_gemm(ctx, M, N, K, a, w, bias, bias_how, res, alpha, ldo, cfg, split, vt
 def test_every_gemm_instance(ctx, case):
     lib = ctx.lib
     a, w, bias, res = case_operands(case)
-    set_tuning(lib, case.tune)
-    try:
+    with _capi.tuning(lib, **dict(case.tune)):
         pl = query_plan(lib, case.M, case.N, case.K, cfg=case.cfg, split=case.split, lda=case.K + 24, ldw=case.K + 8, ldo=case.ldo, bias=case.bias,
                         res=case.res)
         check_case_plan(case, pl)
         out, _ = run_gemm(ctx, case.M, case.N, case.K, a, w, bias, case.bias, res, case.alpha, case.ldo, case.cfg, case.split)
-    finally:
-        restore_tuning(lib)
     M, N = case.M, case.N
     ref, S = ref64(a.to(DEV), w.to(DEV), bias.to(DEV) if bias is not None else None, res.to(DEV) if res is not None else None, case.alpha)
     check(case.name, family_of(case), out[:M, :N], ref, S)
@@ -193,22 +189,15 @@ def test_transposed_outputs(ctx, famrow, tall, form):
     tune = dict(tune)
     if form == "scalar":
         tune["igemm_vt_lds"] = 0
-    set_tuning(lib, tune)
-    try:
+    with _capi.tuning(lib, **tune):
         pl = query_plan(lib, M, N, K, cfg=cfg, lda=K + 24, ldw=K + 8, ldo=ldo if ldo else N, bias="a16", vt_col0=col0, vt_ld=rpb + 8, vt_f32=int(f32),
                         rpb=rpb, vt_perm16=int(form == "perm16"))
         assert pl.err == 0
         assert pl.id == cfg and pl.epi_lds == int(form in ("lds", "perm16") and fam != "register-staged") and bool(pl.dma) == (fam != "register-staged"), (pl.id, pl.epi_lds, pl.dma)
-        if form == "perm16":
-            assert lib.pnpi_set_tuning(b"op_gemm_vt_perm16", 1) == 0
-        try:
+        with _capi.tuning(lib, op_gemm_vt_perm16=int(form == "perm16")):
             out, vt = run_gemm(ctx, M, N, K, a, w, bias, "a16", None, 1.0, ldo, cfg, 0, vt=(col0, Bn, rpb, f32))
-        finally:
-            lib.pnpi_set_tuning(b"op_gemm_vt_perm16", 0)
         if form == "perm16":
             out0, vt0 = run_gemm(ctx, M, N, K, a, w, bias, "a16", None, 1.0, ldo, cfg, 0, vt=(col0, Bn, rpb, f32))
-    finally:
-        restore_tuning(lib)
     tag = "%s-%s-rpb%d" % (fam, form, rpb)
     ref, S = ref64(a.to(DEV), w.to(DEV), bias.to(DEV), None, 1.0)
     if form == "perm16":           # the same bits as the plain launch, in the permuted order; the pad and the spare item untouched
@@ -299,16 +288,13 @@ def test_every_conv_instance(ctx, famrow, shape):
     bd = bias.to(DEV)
     rd = res.permute(0, 2, 3, 1).contiguous().to(DEV) if has_res else None
     out = torch.full((B + 1, Ho, Wo, N), CANARY, dtype=torch.half, device=DEV)
-    set_tuning(lib, tune)
-    try:
+    with _capi.tuning(lib, **tune):
         pl = query_plan(lib, M, N, K, cfg=cfg, bias="a16", res=has_res, ksize=ks, C1=C1, C2=C2)
         assert pl.err == 0 and pl.id == cfg and instance_of(pl) == instance, (pl.err, pl.id, instance_of(pl))
         assert pl.k_order == int(tune.get("igemm_tapin", 0) == 1 and ks == 3 and instance.startswith("pp"))
         ctx.call("pnpi_op_conv", ptr(x1[1:]), ptr(x2[1:]) if C2 else None, C1, C2, B, H, H, ks, stride, pad, ups, Ho, Wo, ptr(wp), ptr(bd), ptr(rd), N,
                  ptr(out), cfg, 0)
         torch.cuda.synchronize()
-    finally:
-        restore_tuning(lib)
     tag = "%s-%s" % (fam, sname)
     check(tag, "conv", out[:B].permute(0, 3, 1, 2), ref.to(DEV), S.to(DEV))
     written = torch.zeros_like(out, dtype=torch.bool)
@@ -327,14 +313,11 @@ def test_gemm_geglu_per_element(ctx, cfg):
     wbuf, wp = poisoned(w, K + 8)
     bbuf, bp = bias_at(bias, "a16")
     out = torch.full((M + 1, ldo), CANARY, dtype=torch.half, device=DEV)
-    assert lib.pnpi_set_tuning(b"igemm_force_cfg", cfg) == 0
-    try:
+    with _capi.tuning(lib, igemm_force_cfg=cfg):
         pl = query_plan(lib, M, N, K, cfg=-1, lda=K + 24, ldw=K + 8, ldo=ldo, bias="a16", geglu=1)
         assert (pl.err, pl.id, pl.epi_lds) == (0, cfg, 1), (pl.err, pl.id)
         ctx.call("pnpi_op_gemm_geglu", ap, K + 24, wp, K + 8, M, N, K, bp, ptr(out), ldo)
         torch.cuda.synchronize()
-    finally:
-        restore_tuning(lib)
     ref, slack = geglu_ref64(a.to(DEV), w.to(DEV), bias.to(DEV))
     got = out[:M, :I]
     r = worst_ratio(got, ref, bound_geglu(ref, slack, KAPPA_G))
@@ -380,14 +363,11 @@ def test_neighbouring_paths_bit_identical(ctx, name, M, N, K, group, split):
     ldo = (N + 7) // 8 * 8 + 8
     outs, names = [], []
     for cfg, tune, instance in group:
-        set_tuning(lib, tune)
-        try:
+        with _capi.tuning(lib, **tune):
             pl = query_plan(lib, M, N, K, cfg=cfg, split=split, lda=K + 24, ldw=K + 8, ldo=ldo, bias="a16", res=True)
             assert pl.err == 0 and pl.id == cfg and pl.split == max(split, 1), (cfg, pl.id, pl.split)
             assert instance_of(pl) == instance, (name, cfg, tune, instance_of(pl))      # the ring depth this row was written for
             out, _ = run_gemm(ctx, M, N, K, a, w, bias, "a16", res, 1.0, ldo, cfg, split)
-        finally:
-            restore_tuning(lib)
         outs.append(out)
         names.append(instance)
     assert len(set((cfg, instance) for cfg, _, instance in group)) == len(group), names       # no launch is compared with itself

@@ -46,11 +46,8 @@ def ctx():
 @pytest.fixture(params=[0, 1 << 20], ids=["finalize_tiles+apply", "fin_apply"])
 def inline(request, ctx):
     """tuning "gn_inline_rows": 0 = two launches (the default), 1 << 20 = the one-launch kernel for every case here"""
-    assert ctx.lib.pnpi_set_tuning(b"gn_inline_rows", request.param) == 0
-    try:
+    with ctx.tuning(gn_inline_rows=request.param):
         yield request.param
-    finally:
-        assert ctx.lib.pnpi_set_tuning(b"gn_inline_rows", 0) == 0
 
 
 def h16(*shape, scale=1.0, seed=0):

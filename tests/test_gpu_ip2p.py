@@ -41,19 +41,6 @@ def randn(seed, *shape):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
-class Dedup:
-    """the process-wide knob for the length of a with-block; the default (1) afterwards"""
-
-    def __init__(self, eng, value):
-        self.lib, self.value = eng.lib, value
-
-    def __enter__(self):
-        assert self.lib.pnpi_set_tuning(b"cfg_dedup", self.value) == 0
-
-    def __exit__(self, *exc):
-        assert self.lib.pnpi_set_tuning(b"cfg_dedup", 1) == 0
-
-
 @pytest.fixture(scope="module")
 def gold():
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "e2e_ip2p_tiny.npz"))
@@ -243,13 +230,13 @@ def test_ip2p_edit_equals_level1_steps_and_the_run_without_the_compact_prefix(pi
     sigmas, tab = table
     nimg = 2
     a = loop_inputs(nimg, 100, sigmas)
-    with Dedup(eng, 2):
+    with eng.tuning(cfg_dedup=2):
         got, traj = run_loop(eng, a, tab, trajectory=True)
         got, traj = got.cpu(), traj.cpu()
         eng.reset_counters()
         again = run_loop(eng, a, tab).cpu()
         c2 = eng.counters()
-    with Dedup(eng, 0):
+    with eng.tuning(cfg_dedup=0):
         eng.reset_counters()
         plain = run_loop(eng, a, tab).cpu()
         c0 = eng.counters()
@@ -388,7 +375,7 @@ def test_small64_two_steps_compact_prefix_is_bit_identical(sched):
         args = (randn(701, 1, 4, 64, 64) * sigmas[0], randn(702, 1, 4, 64, 64), randn(703, 2, 1, 4, 64, 64), torch.stack([ctx[0], ctx[1], ctx[1]])[None], tab)
         out = {}
         for mode in (2, 0):
-            with Dedup(eng, mode):
+            with eng.tuning(cfg_dedup=mode):
                 eng.reset_counters()
                 out[mode] = eng.ip2p_edit(*args, GT, GI).cpu()
                 c = eng.counters()

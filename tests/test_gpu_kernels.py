@@ -69,12 +69,9 @@ def test_gemm_wide_tile_variants(ctx, key, val, cfg):
     bias, res = torch.randn(N, device=DEV), h16(M, N, seed=23)
     out = torch.zeros(M, N, dtype=torch.half, device=DEV)
     lib = ctx.lib
-    assert lib.pnpi_set_tuning(key.encode(), val) == 0
-    try:
+    with ctx.tuning(**{key: val}):
         ctx.call("pnpi_op_gemm", ptr(a), K, ptr(w), K, M, N, K, 1.0, ptr(bias), ptr(res), ptr(out), N, 1 << 30, None, 0, 0, 1, cfg, 0)
         torch.cuda.synchronize()
-    finally:
-        assert lib.pnpi_set_tuning(key.encode(), 1) == 0
     ref = a.float() @ w.float().t() + bias + res.float()
     assert rel_err(out, ref) < 2e-3, rel_err(out, ref)
     assert lib.pnpi_set_tuning(b"no_such_knob", 1) != 0
@@ -95,15 +92,10 @@ def test_conv_epilogue_groupnorm_statistics(ctx, cfg, N, v320):
     stats = torch.full(((M + 63) // 64, N, 2), float("nan"), device=DEV)
     rows = C.c_int(0)
     xn, wp = nhwc(x), pack_w(w)
-    for key in (b"igemm_v320", b"igemm_v256n"):
-        assert ctx.lib.pnpi_set_tuning(key, v320) == 0
-    try:
+    with ctx.tuning(igemm_v320=v320, igemm_v256n=v320):
         ctx.call("pnpi_op_conv_stats", ptr(xn), None, Cin, 0, B, H, H, 3, 1, 1, 0, H, H, ptr(wp), ptr(bias), None, N, ptr(out), cfg, 0,
                  ptr(stats), C.byref(rows))
         torch.cuda.synchronize()
-    finally:
-        for key in (b"igemm_v320", b"igemm_v256n"):
-            ctx.lib.pnpi_set_tuning(key, 1)
     tr = rows.value
     assert tr == {1: 64, 8: 64, 11: 64, 12: 64, 6: 256, 7: 256, 16: 64, 17: 64}.get(cfg, 128)    # the ping-pong kernel: 64-row sub-blocks
     ref = F.conv2d(x.float(), w.float(), bias, padding=1)
@@ -155,12 +147,9 @@ def test_gemm_transposed_columns_through_lds_epilogue(ctx, cfg, col0, N, T, vt_l
     bias = torch.randn(N, device=DEV)
     out = torch.zeros(M, col0, dtype=torch.half, device=DEV)
     vt = torch.zeros(Bn, N - col0, T, dtype=torch.half, device=DEV)
-    assert ctx.lib.pnpi_set_tuning(b"igemm_vt_lds", vt_lds) == 0
-    try:
+    with ctx.tuning(igemm_vt_lds=vt_lds):
         ctx.call("pnpi_op_gemm", ptr(a), K, ptr(w), K, M, N, K, 1.0, ptr(bias), None, ptr(out), col0, col0, ptr(vt), T, 0, T, cfg, 0)
         torch.cuda.synchronize()
-    finally:
-        ctx.lib.pnpi_set_tuning(b"igemm_vt_lds", 1)
     ref = a.float() @ w.float().t() + bias
     assert rel_err(out, ref[:, :col0]) < 2e-3
     assert rel_err(vt, ref[:, col0:].reshape(Bn, T, N - col0).permute(0, 2, 1)) < 2e-3
@@ -319,11 +308,8 @@ def test_conv3x3(ctx, B, C1, C2, H, N, stride, pad, ups, cfg, split):
 def test_conv3x3_channel_slab_major_walk(ctx, B, C1, C2, H, N, stride, pad, ups, cfg, split):
     """The ping-pong kernel's other k order (tuning igemm_tapin: the nine filter taps of a 64-channel slab in a row, GemmP::k_order): same
     products, another summation order -- concat sources, stride 2, the folded upsample and split-K ranges of the permuted walk."""
-    assert ctx.lib.pnpi_set_tuning(b"igemm_tapin", 1) == 0
-    try:
+    with ctx.tuning(igemm_tapin=1):
         test_conv3x3(ctx, B, C1, C2, H, N, stride, pad, ups, cfg, split)
-    finally:
-        ctx.lib.pnpi_set_tuning(b"igemm_tapin", 0)
 
 
 def test_conv1x1_concat(ctx):
@@ -402,11 +388,8 @@ def test_geglu(ctx):
 def test_gemm_fused_geglu(ctx, M, K, I, force):
     """GEGLU.forward (my_diffusers/models/attention.py:331-333): proj -> chunk -> x * gelu(gate), fused into the GEMM epilogue
     of every tile configuration (force = tile configuration of launch_igemm; -1 = the cost model's choice)."""
-    assert ctx.lib.pnpi_set_tuning(b"igemm_force_cfg", force) == 0
-    try:
+    with ctx.tuning(igemm_force_cfg=force):
         _geglu_case(ctx, M, K, I)
-    finally:
-        ctx.lib.pnpi_set_tuning(b"igemm_force_cfg", -1)
 
 
 def _geglu_case(ctx, M, K, I):
@@ -482,12 +465,9 @@ def test_attention_flash_permuted_vt_and_its_producer(ctx, B, heads, N):
     scale = dh ** -0.5
     o = torch.zeros(B, N, heads * dh, dtype=torch.half, device=DEV)
     rows = torch.arange(B, dtype=torch.int32, device=DEV).repeat_interleave(4).reshape(B, 4).contiguous()
-    assert ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", 1) == 0
-    try:
+    with ctx.tuning(op_attention_vt_perm=1):
         ctx.call("pnpi_op_attention", ptr(qb), heads * Dp, 0, ptr(kb), heads * Dp, 0, ptr(vtp), ldv, ptr(o), heads * dh, heads, N, N, Dp, dh,
                  scale, ptr(rows), B)
-    finally:
-        ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", 0)
     ref = ((q.float() @ k.float().transpose(-1, -2) * scale).softmax(-1) @ v.float()).permute(0, 2, 1, 3).reshape(B, N, heads * dh)
     assert rel_err(o, ref) < 3e-3, rel_err(o, ref)
     o2 = torch.zeros_like(o)
@@ -525,14 +505,10 @@ def test_attention_flash_augmented_column(ctx, B, heads, N, perm):
             kk.view(B, N, heads, Dp)[..., dh] = 1.0
             vv.view(B, heads, Dp, -1)[:, :, dh, :] = 1.0
         o = torch.zeros(B, N, heads * dh, dtype=torch.half, device=DEV)
-        assert ctx.lib.pnpi_set_tuning(b"op_attention_aug", aug) == 0 and ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", perm) == 0
-        try:
+        with ctx.tuning(op_attention_aug=aug, op_attention_vt_perm=perm):
             ctx.call("pnpi_op_attention", ptr(qb), heads * Dp, 0, ptr(kk), heads * Dp, 0, ptr(vv), ldv, ptr(o), heads * dh, heads, N, N, Dp, dh, scale,
                      ptr(rows), B)
             torch.cuda.synchronize()
-        finally:
-            ctx.lib.pnpi_set_tuning(b"op_attention_aug", 0)
-            ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", 0)
         return o
 
     plain, aug = run(0), run(1)

@@ -96,12 +96,9 @@ def test_masked_attention_kernel_against_the_reference(ctx, gold, tag, perm, cas
     kcls = torch.from_numpy(g["%s_%s_mask_s" % (tag, case)]).reshape(1, N).contiguous().to(DEV)
     qcls = torch.from_numpy(g["%s_%s_mask_t" % (tag, case)]).reshape(1, N).contiguous().to(DEV)
     qb, kb, vt, ldv = pack(q, k, v, Dp, perm=bool(perm))
-    assert ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", perm) == 0
-    try:
+    with ctx.tuning(op_attention_vt_perm=perm):
         o = run_masked(ctx, qb, kb, vt, ldv, 1, N, N, Dp, dh, [[1, 1, 0, 0]], kcls, qcls, [0], 2)
         plain = run_masked(ctx, qb, kb, vt, ldv, 1, N, N, Dp, dh, [[1, 1, 0, 0]], None, None, None, 2, masked=False) if case == "rect" else None
-    finally:
-        ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", 0)
     assert torch.isfinite(o.float()).all()
     assert not o[0].any()                                        # only the listed output row is written
     ref_rows = torch.from_numpy(g["%s_%s_out" % (tag, case)]).to(DEV)

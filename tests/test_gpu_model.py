@@ -55,10 +55,8 @@ def test_text_kv_cache_and_timestep_bias_table_are_exact(tiny):
     cfg, usd, vsd, eng = tiny
     lat = _lat(cfg, 4, 41)
     ctx = weights.synth_context(cfg, 4, seed=42)
-    lib = eng.lib
-    lib.pnpi_set_tuning(b"temb_cache", 0)
-    ref = eng.unet(lat, 777, ctx).clone()
-    lib.pnpi_set_tuning(b"temb_cache", 1)
+    with eng.tuning(temb_cache=0):
+        ref = eng.unet(lat, 777, ctx).clone()
     first, again = eng.unet(lat, 777, ctx).clone(), eng.unet(lat, 777, ctx).clone()      # fills the table row, then reads it
     assert torch.equal(first, ref) and torch.equal(again, ref)
     eng.text_kv_precompute(ctx)
@@ -82,12 +80,9 @@ def test_text_kv_cache_and_timestep_bias_table_are_exact(tiny):
     ts = sch.timesteps.numpy()
     a = eng.ddim_invert(lat[:1], ctx[2:3], ts).clone()
     nl_a, lat_a = eng.direct_edit(a, ctx[None], [None], ts, 7.5)          # 8 rows: offsets + one guidance pass
-    lib.pnpi_set_tuning(b"text_kv", 0)
-    try:
+    with eng.tuning(text_kv=0):
         b = eng.ddim_invert(lat[:1], ctx[2:3], ts)
         nl_b, lat_b = eng.direct_edit(b, ctx[None], [None], ts, 7.5)
-    finally:
-        lib.pnpi_set_tuning(b"text_kv", 1)
     assert torch.equal(a, b) and torch.equal(nl_a, nl_b) and torch.equal(lat_a, lat_b)
 
 

@@ -138,14 +138,10 @@ def test_attention_row_table_source_q_k_own_v(kctx, N, dh, Dp, perm, aug):
     def run(rows):
         o = torch.zeros(3, N, heads * dh, dtype=torch.half, device=DEV)
         rows_t = torch.tensor(rows, dtype=torch.int32, device=DEV).contiguous()
-        assert ctx.lib.pnpi_set_tuning(b"op_attention_aug", aug) == 0 and ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", perm) == 0
-        try:
+        with ctx.tuning(op_attention_aug=aug, op_attention_vt_perm=perm):
             ctx.call("pnpi_op_attention", ptr(qb), heads * Dp, 0, ptr(kb), heads * Dp, 0, ptr(vt), ldv, ptr(o), heads * dh, heads, N, N, Dp, dh,
                      scale, ptr(rows_t), len(rows))
             torch.cuda.synchronize()
-        finally:
-            ctx.lib.pnpi_set_tuning(b"op_attention_aug", 0)
-            ctx.lib.pnpi_set_tuning(b"op_attention_vt_perm", 0)
         return o.view(3, N, heads, dh).permute(0, 2, 1, 3).float()
 
     got = run([[0, 0, 0, 0], [1, 0, 0, 1], [2, 0, 0, 2]])

@@ -178,16 +178,13 @@ def test_transposed_columns(ctx, new, perm):
     w = h16(N, K, scale=0.1, seed=5)
     bias = torch.randn(N, device=DEV)
     got = {}
-    assert ctx.lib.pnpi_set_tuning(b"op_gemm_vt_perm16", perm) == 0
-    try:
+    with ctx.tuning(op_gemm_vt_perm16=perm):
         for cfg in (new, old):
             out = torch.zeros(M, col0, dtype=torch.half, device=DEV)
             vt = torch.zeros(Bn, N - col0, T, dtype=torch.half, device=DEV)
             ctx.call("pnpi_op_gemm", ptr(a), K, ptr(w), K, M, N, K, 1.0, ptr(bias), None, ptr(out), col0, col0, ptr(vt), T, 0, T, cfg, 0)
             torch.cuda.synchronize()
             got[cfg] = (out, vt)
-    finally:
-        assert ctx.lib.pnpi_set_tuning(b"op_gemm_vt_perm16", 0) == 0
     assert torch.equal(got[new][0], got[old][0]) and torch.equal(got[new][1], got[old][1])
     ref = a.float() @ w.float().t() + bias
     assert rel_err(got[new][0], ref[:, :col0]) < 2e-3
@@ -222,15 +219,12 @@ def test_fused_geglu(ctx, new, M, K):
     wi = ilv32(w[:n_int].t(), w[n_int:].t()).t().contiguous()
     bi = ilv32(bias[:n_int][None], bias[n_int:][None])[0].contiguous()
     got = {}
-    try:
-        for cfg in (new, old):
-            assert ctx.lib.pnpi_set_tuning(b"igemm_force_cfg", cfg) == 0
+    for cfg in (new, old):
+        with ctx.tuning(igemm_force_cfg=cfg):
             out = torch.zeros(M, n_int, dtype=torch.half, device=DEV)
             ctx.call("pnpi_op_gemm_geglu", ptr(a), K, ptr(wi), K, M, 2 * n_int, K, ptr(bi), ptr(out), n_int)
             torch.cuda.synchronize()
             got[cfg] = out
-    finally:
-        assert ctx.lib.pnpi_set_tuning(b"igemm_force_cfg", -1) == 0
     assert torch.equal(got[new], got[old]), (got[new].float() - got[old].float()).abs().max().item()
     h = a.float() @ w.float().t() + bias
     e = rel_err(got[new], h[:, :n_int] * F.gelu(h[:, n_int:]))
@@ -239,19 +233,6 @@ def test_fused_geglu(ctx, new, M, K):
 
 # ------------------------------------------------------------------------------------------------ SD-1.x width: the rule in the forward
 STEPS = 2
-
-
-class Rowtile:
-    """the process-wide knob for the length of a with-block; the default (1) afterwards"""
-
-    def __init__(self, eng, value):
-        self.lib, self.value = eng.lib, value
-
-    def __enter__(self):
-        assert self.lib.pnpi_set_tuning(b"pp_rowtile", self.value) == 0
-
-    def __exit__(self, *exc):
-        assert self.lib.pnpi_set_tuning(b"pp_rowtile", 1) == 0
 
 
 def _kernels(path):
@@ -294,7 +275,7 @@ def test_sd1_eight_row_forward(sd1, tmp_path):
     ctx8 = weights.synth_context(SD1, 8, seed=52)
     got = {}
     for v in (0, 1):
-        with Rowtile(eng, v):
+        with eng.tuning(pp_rowtile=v):
             got[v] = _profiled(eng, tmp_path / ("fwd%d.csv" % v), lambda: eng.unet(lat, 500, ctx8).clone())
     print("8-row forward, ping-pong launches by tile: " + ", ".join(
         "pp_rowtile %d: %s" % (v, {k: n for k, n in got[v][1].items() if k.startswith("igemm_pp")}) for v in (0, 1)))
@@ -320,7 +301,7 @@ def test_sd1_two_step_direct_edit(sd1, tmp_path):
     traj = eng.ddim_invert(z0, ctx4[:, 2], ts).clone()
     got = {}
     for v in (0, 1):
-        with Rowtile(eng, v):
+        with eng.tuning(pp_rowtile=v):
             eng.reset_counters()
             (nl, lats), kern = _profiled(eng, tmp_path / ("edit%d.csv" % v), lambda: eng.direct_edit(traj, ctx4, [None, None], ts, 7.5))
             got[v] = (nl.clone(), lats.clone(), kern, eng.counters())

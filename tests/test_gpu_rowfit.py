@@ -55,14 +55,13 @@ def runs():
     got = []
     try:
         for mode in (2, 1, 1):
-            assert eng.lib.pnpi_set_tuning(b"src_share", mode) == 0 and eng.lib.pnpi_set_tuning(b"cfg_dedup", mode) == 0
-            eng.reset_counters()
-            nl, lats = eng.direct_edit(x_stars, ctx[None], [None, [ctrl.tables()]], ts, 7.5)
-            c = eng.counters()
+            with eng.tuning(src_share=mode, cfg_dedup=mode):
+                eng.reset_counters()
+                nl, lats = eng.direct_edit(x_stars, ctx[None], [None, [ctrl.tables()]], ts, 7.5)
+                c = eng.counters()
             assert c["unet_shared_rows"] == 4 * steps and c["unet_dedup_prefix_rows"] == 6 * steps, c      # 8 rows on 4 latents serve 12 on 6
             got.append((nl.cpu(), lats.cpu()))
     finally:
-        assert eng.lib.pnpi_set_tuning(b"src_share", 1) == 0 and eng.lib.pnpi_set_tuning(b"cfg_dedup", 1) == 0      # the defaults
         eng.close()
     return {"g": g, "steps": steps, "x_stars": x_stars, 2: got[0], 1: got[1], "again": got[2]}
 
@@ -112,10 +111,10 @@ def test_a_context_with_a_tape_gives_the_bits_it_gave_without(dedup):
                            (("mountain",), ("mountain",)), {"words": ("snowy",), "values": (2,)}, num_ddim_steps=steps)
 
     def run(share):
-        assert eng.lib.pnpi_set_tuning(b"src_share", share) == 0 and eng.lib.pnpi_set_tuning(b"cfg_dedup", dedup) == 0
-        eng.reset_counters()
-        nl, lats = eng.direct_edit(traj, ctx, [None, [c.tables()]], ts, 7.5)
-        return nl.cpu(), lats.cpu(), eng.counters()["unet_shared_rows"]
+        with eng.tuning(src_share=share, cfg_dedup=dedup):
+            eng.reset_counters()
+            nl, lats = eng.direct_edit(traj, ctx, [None, [c.tables()]], ts, 7.5)
+            return nl.cpu(), lats.cpu(), eng.counters()["unet_shared_rows"]
 
     try:
         traj = eng.ddim_invert(z0, ctx[:, 2], ts).clone()
@@ -123,7 +122,6 @@ def test_a_context_with_a_tape_gives_the_bits_it_gave_without(dedup):
         eng.unet_context_grad(z0, int(ts[0]), ctx[0, 2:3], torch.ones(1, 4, S, S))      # the context holds a tape from here on
         free_t, pinned_t = run(1), run(2)
     finally:
-        assert eng.lib.pnpi_set_tuning(b"src_share", 1) == 0 and eng.lib.pnpi_set_tuning(b"cfg_dedup", 1) == 0
         eng.close()
     assert free[2] == pinned[2] == 4 * steps and free_t[2] == pinned_t[2] == 0          # compact before, the full launch after
     print("SMALL64: mode 1 %s mode 2" % ("equals" if torch.equal(free[1], pinned[1]) else "differs from"))

@@ -34,19 +34,6 @@ PROMPTS = [("a photograph of a mountain", "a watercolor photograph of a snowy mo
            ("a cat sitting on a wooden chair", "a small cat sitting on a old wooden chair", "cat", "small")]
 
 
-class Knob:
-    """a process-wide tuning knob for the length of a with-block; its default afterwards"""
-
-    def __init__(self, eng, key, value, default=2):
-        self.lib, self.key, self.value, self.default = eng.lib, key.encode(), value, default
-
-    def __enter__(self):
-        assert self.lib.pnpi_set_tuning(self.key, self.value) == 0
-
-    def __exit__(self, *exc):
-        assert self.lib.pnpi_set_tuning(self.key, self.default) == 0
-
-
 class Case:
     def __init__(self, cfg, blend):
         self.cfg = cfg
@@ -77,7 +64,7 @@ class Case:
         """(noise_loss, latents, counters) of the lock-step edit under src_share = share"""
         key = (share, kind, nimg, npass, dedup, offset_rows)
         if fresh or key not in self.memo:
-            with Knob(self.eng, "src_share", share), Knob(self.eng, "cfg_dedup", dedup):
+            with self.eng.tuning(src_share=share, cfg_dedup=dedup):
                 self.eng.reset_counters()
                 nl, lats = self.eng.direct_edit(self.traj[:, :nimg], self.ctx[:nimg], self.passes(kind, nimg, npass), self.ts, GS,
                                                 offset_rows=offset_rows)
@@ -166,7 +153,7 @@ def _one_step_eps(case, share):
     prev = c_x x + c_e eps (DDIM, eta = 0), so eps = (prev - c_x x) / c_e in float64; the offset pass stores loss = target - prev."""
     eng, t = case.eng, int(case.ts[0])
     x, target = case.traj[-1, :1], case.traj[0, :1]                       # any start latent and any target serve
-    with Knob(eng, "src_share", share):
+    with eng.tuning(src_share=share):
         eng.reset_counters()
         nl, lats = eng.direct_edit(torch.stack([target, x]), case.ctx[:1], [None, None], case.ts[:1], 1.0)
         assert eng.counters()["unet_shared_rows"] == (4 if share else 0)

@@ -162,8 +162,5 @@ def test_sel_m_pins_the_choice_and_the_row_height_follows_the_launch(lib):
     assert (pl.err, pl.id, pl.split) == (0, 19, 1)
     assert (pl.bm, pl.bn, pl.gx, pl.gy, pl.gz) == (128, 320, 256, 1, 1)
     assert pl.sparse == 1                                 # occupancy is counted at sel_M: 384 units of 128 rows, two per CU
-    lib.pnpi_set_tuning(b"pp_rowtile", 0)
-    try:
+    with _capi.tuning(lib, pp_rowtile=0):
         assert plan(lib, 32768, 320, 2880, 3, bias=1, sel_M=49152).id == 17
-    finally:
-        lib.pnpi_set_tuning(b"pp_rowtile", 1)

@@ -54,5 +54,5 @@ def test_family_ids(lib):
 
 
 def test_knob_is_a_tuning_key(lib):
-    assert lib.pnpi_set_tuning(b"pp_rowtile", 0) == 0
-    assert lib.pnpi_set_tuning(b"pp_rowtile", 1) == 0
+    with _capi.tuning(lib, pp_rowtile=0), _capi.tuning(lib, pp_rowtile=1):      # both accepted (a rejected value raises)
+        assert _capi.get_tuning(lib, "pp_rowtile") == 1

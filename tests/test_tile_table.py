@@ -84,9 +84,6 @@ def test_runtime_lookup_exact_and_nearest_row_count():
     assert lib.pnpi_tile_table_lookup(4096, 320, 2880, 1, None, None, None) == 0
     assert lib.pnpi_tile_table_lookup(0, 320, 2880, 3, None, None, None) == 0
     # the nearest-entry rule can be switched off (A/B knob)
-    assert lib.pnpi_set_tuning(b"igemm_table_near", 0) == 0
-    try:
+    with _capi.tuning(lib, igemm_table_near=0):
         assert lib.pnpi_tile_table_lookup(20 * 4096, 320, 2880, 3, None, None, None) == 0
         assert lib.pnpi_tile_table_lookup(12 * 4096, 320, 2880, 3, None, None, None) == 1
-    finally:
-        assert lib.pnpi_set_tuning(b"igemm_table_near", 1) == 0
