@@ -611,6 +611,20 @@ int pnpi_op_attention_bwd_fwd(pnpi_ctx* ctx, const void* q, int ldq, int q_off, 
                               int v_off, const void* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, void* dq,
                               void* dk, void* dv, void* scratch, size_t scratch_bytes, const float* lse_fwd, const void* o_fwd,
                               int ld_ofwd);
+/* Host-only: everything pnpi_op_attention_bwd(_fwd) and the reverse walk decide for one attention site before they launch, without
+ * launching -- a pure function of the shape, the scratch the caller has (scratch_bytes; < 0: as much as the form asks for, 0: none) and
+ * the tuning knobs "attn_bwd_flash" / "abf_prefetch"; have_fwd: the forward's lse and O are handed over (ld_ofwd % 8 == 0).
+ * flash: 1 the flash kernel attn_bwd_flash_kernel<Dp, lt, mode, pf>, 0 the materialised form (lt 0); nsplit: shares of the dK / dV walk
+ * over the queries (> 1: fp32 partials and the reduce kernel), share_rows queries each (whole lt tiles), empty_shares of them beginning
+ * at or past Nq; pf_dq / pf_dk / pf_dv: the register-prefetch instance per launch; one_pass: dQ from the forward's lse and O;
+ * scratch_bytes: the workspace the flash form carves, or the materialised form's per head. */
+typedef struct {
+  int flash, lt, nsplit;
+  int pf_dq, pf_dk, pf_dv;
+  int one_pass, share_rows, empty_shares;
+  long long scratch_bytes;
+} pnpi_attn_bwd_plan;
+int pnpi_attn_bwd_plan_query(int heads, int Nq, int Nk, int Dp, int dh, long long scratch_bytes, int have_fwd, pnpi_attn_bwd_plan* plan);
 
 /* ---- differentiable UNet forward (null-text path; groundwork) ---------------------------------------------------------------
  * pnpi_unet_context_grad: eps = unet(latents [1][4][h][w], t, context [1][77][768]) with every activation recorded, then the reverse

@@ -86,6 +86,11 @@ class IgemmPlan(C.Structure):
                                        "bias_init", "res_late", "k_order", "stats", "stats_tile_rows", "cls", "dma", "fastk")]
 
 
+class AttnBwdPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("flash", "lt", "nsplit", "pf_dq", "pf_dk", "pf_dv", "one_pass", "share_rows", "empty_shares")] + \
+               [("scratch_bytes", C.c_longlong)]
+
+
 # every symbol include/pnpi.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
@@ -165,6 +170,7 @@ SYMBOLS = {
     "pnpi_op_attention_bwd_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "pnpi_op_attention_bwd_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, C.c_size_t,
                                        _vp, _vp, _i]),
+    "pnpi_attn_bwd_plan_query": (_i, [_i, _i, _i, _i, _i, C.c_longlong, _i, C.POINTER(AttnBwdPlan)]),
     "pnpi_edit_loop_uncond_steps": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.POINTER(C.c_int), _f, _i, _f, _vp, _i, _vp]),
     "pnpi_edit_loop_uncond_steps_recon": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.POINTER(C.c_int), _f, _i, _f, _vp, _i, C.POINTER(ReconDesc), _vp]),
     "pnpi_unet_context_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),

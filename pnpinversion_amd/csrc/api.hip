@@ -801,6 +801,16 @@ int pnpi_op_attention_bwd(pnpi_ctx* c, const void* q, int ldq, int q_off, const 
                                    scratch_bytes, nullptr, nullptr, 0);
 }
 size_t pnpi_op_attention_bwd_scratch_bytes(int Nq, int Nk, int dh) { return attn_bwd_scratch_bytes(Nq, Nk, dh); }
+/* host-only: what attn_bwd decides for this shape under the tuning in force (scratch_bytes < 0: as much as the form asks for) */
+int pnpi_attn_bwd_plan_query(int heads, int Nq, int Nk, int Dp, int dh, long long scratch_bytes, int have_fwd, pnpi_attn_bwd_plan* plan) {
+  if (!plan || heads <= 0 || Nq <= 0 || Nk <= 0 || Dp <= 0 || dh <= 0) return PNPI_EINVAL;
+  const AttnBwdPlan pl = attn_bwd_plan(heads, Nq, Nk, Dp, dh, scratch_bytes < 0 ? SIZE_MAX : (size_t)scratch_bytes, have_fwd != 0);
+  plan->flash = pl.flash; plan->lt = pl.lt; plan->nsplit = pl.nsplit;
+  plan->pf_dq = pl.pf[0]; plan->pf_dk = pl.pf[1]; plan->pf_dv = pl.pf[2];
+  plan->one_pass = pl.one_pass; plan->share_rows = pl.share_rows; plan->empty_shares = pl.empty_shares;
+  plan->scratch_bytes = pl.scratch_bytes;
+  return 0;
+}
 // ---- activation-gradient kernels (null-text path groundwork; tests/test_gpu_backward.py)
 int pnpi_op_layernorm_bwd(pnpi_ctx* c, const void* x, const void* dy, int M, int C, float eps, const float* gamma, void* dx) {
   CK(launch_layernorm_bwd((const half_t*)x, (const half_t*)dy, M, C, eps, gamma, (half_t*)dx, c->st));

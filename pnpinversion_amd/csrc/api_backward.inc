@@ -88,23 +88,35 @@ static int attn_bwd_flash_nsplit(int Nq, int Nk) {
   const int n = Nq / 128;
   return n > 32 ? 32 : n;
 }
-static size_t attn_bwd_flash_scratch_bytes(int heads, int Nq, int Nk, int dh) {
-  const int ns = attn_bwd_flash_nsplit(Nq, Nk);
-  return (size_t)heads * 2 * align_up((size_t)Nq * 4, 256) + (ns > 1 ? align_up((size_t)ns * heads * Nk * dh * 4, 256) : 0);
-}
-static bool attn_bwd_flash_shape(int Nq, int Nk, int Dp, int dh) {
-  // tuning "attn_bwd_flash": 0 = the materialised form everywhere, 1 = flash form for self- and cross-attention (dQ with the forward's
-  // log-sum-exp where the tape has it), 2 = the same with the two-pass dQ always, 3 = self-attention only
+// The one place that decides how an attention backward runs (ops.h AttnBwdPlan).  Pure: the shape, the scratch the caller has and the knobs
+//   "attn_bwd_flash": 0 = the materialised form everywhere, 1 = flash form for self- and cross-attention (dQ with the forward's
+//   log-sum-exp where the tape has it), 2 = the same with the two-pass dQ always, 3 = self-attention only;
+//   "abf_prefetch": 0 = never the register-prefetch instances.
+AttnBwdPlan attn_bwd_plan(int heads, int Nq, int Nk, int Dp, int dh, size_t scratch_bytes, bool have_fwd) {
+  AttnBwdPlan pl{};
+  pl.nsplit = 1; pl.share_rows = Nq;
+  pl.scratch_bytes = (long long)attn_bwd_scratch_bytes(Nq, Nk, dh);
   const bool self = Nq == Nk, cross = !self && Nk <= 128 && Nk >= 8;
-  if (!g_attn_bwd_flash || !(self || (cross && g_attn_bwd_flash != 3))) return false;
-  return Nq >= 64 && Nq % 64 == 0 && (Dp == 32 || Dp == 64 || Dp == 96 || Dp == 160) && dh <= Dp && !(dh & 7);
-}
-static bool attn_bwd_flash_ok(int heads, int Nq, int Nk, int Dp, int dh, size_t scratch_bytes) {
-  return attn_bwd_flash_shape(Nq, Nk, Dp, dh) && scratch_bytes >= attn_bwd_flash_scratch_bytes(heads, Nq, Nk, dh);
+  const int lt = attn_bwd_flash_lt(Dp);
+  if (!g_attn_bwd_flash || !(self || (cross && g_attn_bwd_flash != 3))) return pl;
+  if (!(Nq >= 64 && Nq % 64 == 0 && lt && dh <= Dp && !(dh & 7))) return pl;
+  const int ns = attn_bwd_flash_nsplit(Nq, Nk);
+  const size_t need = (size_t)heads * 2 * align_up((size_t)Nq * 4, 256) + (ns > 1 ? align_up((size_t)ns * heads * Nk * dh * 4, 256) : 0);
+  if (scratch_bytes < need) return pl;       // the caller's workspace does not hold lse, D and the partials: materialised (which needs its own)
+  pl.flash = 1; pl.lt = lt; pl.nsplit = ns; pl.scratch_bytes = (long long)need;
+  pl.one_pass = have_fwd && g_attn_bwd_flash != 2;
+  pl.share_rows = attn_bwd_share_rows(Nq, ns, lt);
+  for (int s = 0; s < ns; ++s) pl.empty_shares += s * pl.share_rows >= Nq;
+  // PF: 64- / 96-wide heads, many loop tiles per workgroup and at most ~one workgroup per CU (T workgroups of 128 block rows)
+  for (int mode = 0; mode < 3; ++mode) {
+    const int nb = mode ? Nk : Nq, nl = mode ? Nq : Nk, T = ((nb + 127) >> 7) * heads * (mode ? ns : 1);
+    pl.pf[mode] = (Dp == 64 || Dp == 96) && g_abf_prefetch && nl >= 8 * lt && T <= 512;
+  }
+  return pl;
 }
 static int attn_bwd_flash(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp,
                           int v_off, const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B,
-                          half_t* dq, half_t* dk, half_t* dv, void* scratch, const float* lse_fwd, const half_t* o_fwd, int ld_ofwd) {
+                          half_t* dq, half_t* dk, half_t* dv, void* scratch, const AttnBwdPlan& pl, const float* lse_fwd, const half_t* o_fwd, int ld_ofwd) {
   if ((ldq & 7) || (ldk & 7) || (ldvp & 7) || (ldo & 7) || (q_off & 7) || (k_off & 7) || (v_off & 7))
     return fail(c, PNPI_ESHAPE, "attention backward: extents must be multiples of 8");
   const size_t szF = align_up((size_t)Nq * 4, 256);
@@ -112,7 +124,7 @@ static int attn_bwd_flash(pnpi_ctx* c, const half_t* q, int ldq, int q_off, cons
   float* lse = (float*)sp; sp += szF * heads;
   float* dsum = (float*)sp; sp += szF * heads;
   float* part = (float*)sp;
-  const int nsplit = attn_bwd_flash_nsplit(Nq, Nk);
+  const int nsplit = pl.nsplit;
   if (szF != (size_t)Nq * 4) return fail(c, PNPI_ESHAPE, "attention backward: Nq * 4 must be a multiple of 256");   // [heads][Nq] dense (Nq >= 64, % 64 == 0 in every caller)
   for (int b = 0; b < B; ++b) {
     const half_t* qh = q + (size_t)b * Nq * ldq + q_off;
@@ -124,21 +136,21 @@ static int attn_bwd_flash(pnpi_ctx* c, const half_t* q, int ldq, int q_off, cons
     a.heads = heads; a.scale = scale; a.lse = lse; a.dsum = dsum; a.out_hs = Dp; a.out_w = dh;
     a.b1 = mq; a.b2 = mdo; a.l1 = mk; a.l2 = mv; a.nb = Nq; a.nl = Nk;
     a.out = dq + (size_t)b * Nq * ldq + q_off; a.out_ld = ldq;
-    if (lse_fwd && o_fwd && !(ld_ofwd & 7)) {     // the recording forward left the log-sum-exp and O: dQ without its first pass over the keys
+    if (pl.one_pass) {     // the recording forward left the log-sum-exp and O: dQ without its first pass over the keys
       a.lse = const_cast<float*>(lse_fwd) + (size_t)b * heads * Nq;       // read-only in this form
       a.o = o_fwd + (size_t)b * Nq * ld_ofwd; a.o_hs = dh; a.o_ld = ld_ofwd;
     }
-    CK(launch_attn_bwd_flash(a, 0, Dp, c->st));
+    CK(launch_attn_bwd_flash(a, 0, Dp, pl.pf[0], c->st));
     // tile products of the three launches (dQ: S, dP, dQ -- twice S and dP without the forward's log-sum-exp; dK: S, dP, dK; dV: S, dV)
-    c->ctr.executed_attn_flops += 2.0 * heads * (double)Nq * Nk * Dp * ((a.o ? 3 : 5) + 3 + 2);
+    c->ctr.executed_attn_flops += 2.0 * heads * (double)Nq * Nk * Dp * ((pl.one_pass ? 3 : 5) + 3 + 2);
     a.o = nullptr;
     a.b1 = mk; a.b2 = mv; a.l1 = mq; a.l2 = mdo; a.nb = Nk; a.nl = Nq;
     a.nsplit = nsplit; a.part = nsplit > 1 ? part : nullptr;
     a.out = dk + (size_t)b * Nk * ldk + k_off; a.out_ld = ldk;
-    CK(launch_attn_bwd_flash(a, 1, Dp, c->st));
+    CK(launch_attn_bwd_flash(a, 1, Dp, pl.pf[1], c->st));
     if (nsplit > 1) CK(launch_attn_bwd_reduce(a, c->st));
     a.out = dv + (size_t)b * Nk * ldvp + v_off; a.out_ld = ldvp;
-    CK(launch_attn_bwd_flash(a, 2, Dp, c->st));
+    CK(launch_attn_bwd_flash(a, 2, Dp, pl.pf[2], c->st));
     if (nsplit > 1) CK(launch_attn_bwd_reduce(a, c->st));
   }
   return 0;
@@ -147,9 +159,10 @@ static int attn_bwd_flash(pnpi_ctx* c, const half_t* q, int ldq, int q_off, cons
 static int attn_bwd(pnpi_ctx* c, const half_t* q, int ldq, int q_off, const half_t* k, int ldk, int k_off, const half_t* v, int ldvp, int v_off,
                     const half_t* d_o, int ldo, int heads, int Nq, int Nk, int Dp, int dh, float scale, int B, half_t* dq, half_t* dk, half_t* dv,
                     void* scratch, size_t scratch_bytes, const float* lse_fwd = nullptr, const half_t* o_fwd = nullptr, int ld_ofwd = 0) {
-  if (scratch && attn_bwd_flash_ok(heads, Nq, Nk, Dp, dh, scratch_bytes))
-    return attn_bwd_flash(c, q, ldq, q_off, k, ldk, k_off, v, ldvp, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch,
-                          g_attn_bwd_flash == 2 ? nullptr : lse_fwd, o_fwd, ld_ofwd);      // tuning value 2: always the two-pass dQ
+  const AttnBwdPlan pl = attn_bwd_plan(heads, Nq, Nk, Dp, dh, scratch ? scratch_bytes : 0, lse_fwd && o_fwd && !(ld_ofwd & 7));
+  if (pl.flash)
+    return attn_bwd_flash(c, q, ldq, q_off, k, ldk, k_off, v, ldvp, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch, pl,
+                          lse_fwd, o_fwd, ld_ofwd);
   return attn_bwd_materialized(c, q, ldq, q_off, k, ldk, k_off, v, ldvp, v_off, d_o, ldo, heads, Nq, Nk, Dp, dh, scale, B, dq, dk, dv, scratch, scratch_bytes);
 }
 static int gn_bwd_workspace(pnpi_ctx* c, int B, int HW, int G, float** out) {
@@ -344,8 +357,8 @@ static int tape_backward(pnpi_ctx* c, const half_t* d_out) {
           CK(launch_pad_heads_f16(dy, (size_t)o.B * o.Nq, o.heads, o.dh, o.Dp, dyp, c->st));
           dy = dyp; ldo_eff = o.heads * o.Dp;
         }
-        const size_t need = attn_bwd_flash_shape(o.Nq, o.Nk, o.Dp, dh_eff) ? attn_bwd_flash_scratch_bytes(o.heads, o.Nq, o.Nk, dh_eff)
-                                                                           : attn_bwd_scratch_bytes(o.Nq, o.Nk, dh_eff) * (size_t)o.heads;      // every head of a row in one set of launches
+        const AttnBwdPlan apl = attn_bwd_plan(o.heads, o.Nq, o.Nk, o.Dp, dh_eff, SIZE_MAX, false);      // what the form needs that the shape allows
+        const size_t need = apl.flash ? (size_t)apl.scratch_bytes : (size_t)apl.scratch_bytes * (size_t)o.heads;      // materialised: every head of a row in one set of launches
         if (need > T.attn_scratch_bytes) {
           if (T.attn_scratch) CKH(hipFree(T.attn_scratch));
           T.attn_scratch = nullptr; T.attn_scratch_bytes = 0;

@@ -1097,7 +1097,7 @@ __global__ void __launch_bounds__(256) attn_bwd_flash_kernel(AttnBwdP p) {
   const int brow = bt * 128 + wave * 32 + ql;
   const bool bok = brow < p.nb;
   // this workgroup's share of the loop rows (everything unless the launch is split; whole LT tiles)
-  const int lchunk = ((p.nl + p.nsplit - 1) / p.nsplit + LT - 1) / LT * LT;
+  const int lchunk = attn_bwd_share_rows(p.nl, p.nsplit, LT);
   const int l_begin = split * lchunk, l_end = min(p.nl, l_begin + lchunk);
 
   half8 f1[KS], f2[KS];
@@ -1338,31 +1338,33 @@ int launch_attn_bwd_reduce(const AttnBwdP& p, hipStream_t st) {
 }
 
 template <int DP, int LT>
-static int launch_abf(const AttnBwdP& p, int mode, hipStream_t st) {
+static int launch_abf(const AttnBwdP& p, int mode, bool pf, hipStream_t st) {
   if (p.nsplit < 1 || (p.nsplit > 1 && (mode == 0 || !p.part))) return -3;
   const int T = ((p.nb + 127) >> 7) * p.heads * p.nsplit;
   const dim3 grid((unsigned)(((T + 7) / 8) * 8));
   if constexpr (DP == 64 || DP == 96) {
-    // many loop tiles per workgroup and at most ~one workgroup per CU: prefetch the next tile into registers (tuning "abf_prefetch")
-    if (g_abf_prefetch && p.nl >= 8 * LT && T <= 512) {
+    // many loop tiles per workgroup and at most ~one workgroup per CU: prefetch the next tile into registers (attn_bwd_plan decides: pf)
+    if (pf) {
       if (mode == 0) attn_bwd_flash_kernel<DP, LT, 0, true><<<grid, 256, 0, st>>>(p);
       else if (mode == 1) attn_bwd_flash_kernel<DP, LT, 1, true><<<grid, 256, 0, st>>>(p);
       else attn_bwd_flash_kernel<DP, LT, 2, true><<<grid, 256, 0, st>>>(p);
       return (int)hipGetLastError();
     }
+  } else if (pf) {
+    return -3;        // no prefetch instance at this head width
   }
   if (mode == 0) attn_bwd_flash_kernel<DP, LT, 0><<<grid, 256, 0, st>>>(p);
   else if (mode == 1) attn_bwd_flash_kernel<DP, LT, 1><<<grid, 256, 0, st>>>(p);
   else attn_bwd_flash_kernel<DP, LT, 2><<<grid, 256, 0, st>>>(p);
   return (int)hipGetLastError();
 }
-int launch_attn_bwd_flash(const AttnBwdP& p, int mode, int Dp, hipStream_t st) {
+int launch_attn_bwd_flash(const AttnBwdP& p, int mode, int Dp, bool pf, hipStream_t st) {
   if (p.nb <= 0 || p.nl <= 0 || mode < 0 || mode > 2) return -3;
   switch (Dp) {
-    case 32: return launch_abf<32, 64>(p, mode, st);
-    case 64: return launch_abf<64, 64>(p, mode, st);
-    case 96: return launch_abf<96, 64>(p, mode, st);
-    case 160: return launch_abf<160, 32>(p, mode, st);
+    case 32: return launch_abf<32, attn_bwd_flash_lt(32)>(p, mode, pf, st);
+    case 64: return launch_abf<64, attn_bwd_flash_lt(64)>(p, mode, pf, st);
+    case 96: return launch_abf<96, attn_bwd_flash_lt(96)>(p, mode, pf, st);
+    case 160: return launch_abf<160, attn_bwd_flash_lt(160)>(p, mode, pf, st);
     default: return -1;
   }
 }

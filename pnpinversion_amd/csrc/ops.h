@@ -160,8 +160,27 @@ struct AttnBwdP {
   int nsplit = 1;                 // DK / DV with few keys (cross-attention): the loop rows are split over nsplit workgroups per (key tile, head), each
   float* part = nullptr;          // writing fp32 partial sums part[((split * heads + head) * nb + block_row) * out_w + d]; summed in order by
 };                                // launch_attn_bwd_reduce
+// Everything the backward of one attention site decides before it launches (api_backward.inc: attn_bwd_plan; a pure host function of the shape and
+// the tuning knobs "attn_bwd_flash" / "abf_prefetch"; pnpi_attn_bwd_plan_query hands it to the CPU tests).  attn_bwd, attn_bwd_flash and
+// launch_attn_bwd_flash run what it says.
+struct AttnBwdPlan {
+  int flash;                      // 1: attn_bwd_flash_kernel, 0: the materialised form
+  int lt;                         // loop-tile rows of the flash instance (64, or 32 at Dp 160); 0: materialised
+  int nsplit;                     // shares of the dK / dV query walk (> 1: fp32 partials + attn_bwd_reduce_kernel)
+  int pf[3];                      // per mode (dQ, dK, dV): the PF = true instance is launched
+  int one_pass;                   // dQ takes the forward's log-sum-exp and O: no first pass over the keys
+  int share_rows;                 // loop rows per share of the dK / dV walk (whole tiles; Nq when it is not split)
+  int empty_shares;               // shares that begin at or past Nq (their partials are zeros)
+  long long scratch_bytes;        // flash: the workspace attn_bwd_flash carves; materialised: attn_bwd_scratch_bytes of one head
+};
+constexpr int attn_bwd_flash_lt(int Dp) { return (Dp == 32 || Dp == 64 || Dp == 96) ? 64 : Dp == 160 ? 32 : 0; }   // 0: head width not instantiated
+// the loop rows of one share of a split walk: whole LT tiles (kernel and plan)
+__host__ __device__ constexpr int attn_bwd_share_rows(int nl, int nsplit, int LT) { return ((nl + nsplit - 1) / nsplit + LT - 1) / LT * LT; }
+// scratch_bytes: what the caller has (0: none); have_fwd: the forward's lse and O are there (O's leading dimension a multiple of 8)
+AttnBwdPlan attn_bwd_plan(int heads, int Nq, int Nk, int Dp, int dh, size_t scratch_bytes, bool have_fwd);
 int launch_attn_bwd_reduce(const AttnBwdP& p, hipStream_t st);
-int launch_attn_bwd_flash(const AttnBwdP& p, int mode /*0 DQ, 1 DK, 2 DV*/, int Dp, hipStream_t st);   // -1: head width not instantiated
+// pf: the plan's pf[mode]; -1: head width not instantiated
+int launch_attn_bwd_flash(const AttnBwdP& p, int mode /*0 DQ, 1 DK, 2 DV*/, int Dp, bool pf, hipStream_t st);
 
 // Cross-attention with the Prompt-to-Prompt edit fused in (one (src,tgt) row pair per grid.z entry).
 struct CrossEditP {
