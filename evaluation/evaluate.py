@@ -1,0 +1,232 @@
+"""PIE-Bench evaluation table (the reference's evaluation/evaluate.py): one CSV row per benchmark image, one column per
+(method folder, metric), for every column this library can compute:
+
+  psnr* / mse* / ssim*      pnpinversion_amd.metrics (numpy restatements of the torchmetrics definitions)
+  clip_similarity_*         on the device: pnpinversion_amd.clip_score.ClipScore (CLIP ViT-L/14 image tower + SD's own text tower)
+
+`structure_distance*` (DINO ViT self-similarity) and `lpips*` (SqueezeNet LPIPS) need networks that are not built here: asking for one of
+them ends the run with a message naming the column.  Arguments, the method-folder table, the right-hand 512 crop of non-square panels, the
+"nan" cells of empty masks and the CSV layout are the reference's.  The three CLIP columns of one (image, method) pair go to the device
+as ONE launch set (source image / source prompt, target image / target prompt, masked target image / target prompt).
+
+    python evaluation/evaluate.py --checkpoint_dir <SD-1.x dir> --clip_model_dir <clip-vit-large-patch14 dir> [--metrics ...]
+    python evaluation/evaluate.py --synthetic_weights ...        # seeded random towers: the numbers mean nothing, the plumbing runs
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+PIXEL_METRICS = ("psnr", "mse", "ssim")
+PARTS = ("", "_unedit_part", "_edit_part")
+CLIP_METRICS = ("clip_similarity_source_image", "clip_similarity_target_image", "clip_similarity_target_image_edit_part")
+NOT_BUILT = {"structure_distance": "DINO ViT structure distance", "lpips": "SqueezeNet LPIPS"}
+DEFAULT_METRICS = ["structure_distance", "psnr_unedit_part", "lpips_unedit_part", "mse_unedit_part", "ssim_unedit_part"] + list(CLIP_METRICS)
+
+
+def _folder_table():
+    """table key -> folder of the method's panels.  Keys are "<table number>_<method>"; the folder is output/<method>/annotation_images,
+    except that table 4 abbreviates null-text-inversion to null-text-inverse and tables 6 / 7 drop the "+p2p" of their folders."""
+    guidance = ["directinversion+p2p_guidance_%s_%s" % (i, f) for i in ("0", "1", "25", "5", "75") for f in ("1", "5", "25", "75")]
+    groups = [
+        ("1", ["ddim+p2p", "null-text-inversion+p2p_a800", "null-text-inversion+p2p_3090", "negative-prompt-inversion+p2p", "stylediffusion+p2p",
+               "directinversion+p2p", "ddim+masactrl", "directinversion+masactrl", "ddim+pix2pix-zero", "directinversion+pix2pix-zero", "ddim+pnp",
+               "directinversion+pnp"]),
+        ("2", ["instruct-pix2pix", "instruct-diffusion", "blended-latent-diffusion", "directinversion+p2p"]),
+        ("3", guidance),
+        ("4", ["null-text-inverse+p2p_a800", "null-text-inverse+p2p_3090", "null-text-inversion+proximal-guidance",
+               "negative-prompt-inversion+proximal-guidance", "edit-friendly-inversion+p2p", "edict+direct_forward", "edict+p2p", "directinversion+p2p"]),
+        ("5", ["ablation_directinversion_04+p2p", "ablation_directinversion_08+p2p", "ablation_null-latent-inversion+p2p_a800",
+               "ablation_null-latent-inversion+p2p_3090", "ablation_null-text-inversion_single_branch+p2p_a800",
+               "ablation_null-text-inversion_single_branch+p2p_3090"]),
+        ("6", ["ablation_directinversion_interval_%d" % k for k in (2, 5, 10, 24, 49)]),
+        ("7", ["ablation_directinversion_step_%d" % k for k in (20, 100, 500)]),
+        ("8", ["ablation_directinversion_add-source+p2p", "ablation_directinversion_add-target+p2p"]),
+    ]
+    table = {}
+    for num, methods in groups:
+        for m in methods:
+            folder = m.replace("null-text-inverse+", "null-text-inversion+") + ("+p2p" if num in ("6", "7") else "")
+            table["%s_%s" % (num, m)] = "output/%s/annotation_images" % folder
+    return table
+
+
+all_tgt_image_folders = _folder_table()
+
+
+def mask_decode(encoded_mask, image_shape=(512, 512)):
+    """PIE-Bench's run-length mask ((start, length) pairs over the flattened image) -> float 0 / 1 [H, W]; the one-pixel border is set,
+    as the reference does against annotation errors at the boundary"""
+    length = image_shape[0] * image_shape[1]
+    m = np.zeros(length)
+    for start, run in zip(encoded_mask[0::2], encoded_mask[1::2]):
+        m[start:start + min(run, length - start)] = 1
+    m = m.reshape(image_shape[0], image_shape[1])
+    m[0, :] = m[-1, :] = 1
+    m[:, 0] = m[:, -1] = 1
+    return m
+
+
+def _split(metric):
+    for part in ("_unedit_part", "_edit_part"):
+        if metric.endswith(part):
+            return metric[:-len(part)], part
+    return metric, ""
+
+
+def check_metrics(metrics):
+    for m in metrics:
+        base, _ = _split(m)
+        if base in NOT_BUILT:
+            raise SystemExit("column %r is not built: %s needs a network this library does not carry (computable columns: %s)"
+                             % (m, NOT_BUILT[base], ", ".join([p + s for p in PIXEL_METRICS for s in PARTS] + list(CLIP_METRICS))))
+        if m not in CLIP_METRICS and not (base in PIXEL_METRICS and m == base + _split(m)[1]):
+            raise SystemExit("unknown metric column %r" % m)
+
+
+class Calculator:
+    """the reference's MetricsCalculator protocol for the columns that are built"""
+
+    def __init__(self, scorer=None):
+        self.scorer = scorer
+
+    def calculate_clip_similarity(self, img, txt, mask=None):
+        from pnpinversion_amd import metrics
+        return metrics.calculate_clip_similarity(img, txt, mask, scorer=self.scorer)
+
+    def __getattr__(self, name):
+        from pnpinversion_amd import metrics
+        if name in ("calculate_psnr", "calculate_mse", "calculate_ssim"):
+            return getattr(metrics, name)
+        raise AttributeError(name)
+
+
+def calculate_metric(calc, metric, src_image, tgt_image, src_mask, tgt_mask, src_prompt, tgt_prompt):
+    """one cell; "nan" where the mask leaves nothing to measure"""
+    base, part = _split(metric)
+    if metric in CLIP_METRICS:
+        if metric == "clip_similarity_source_image":
+            return calc.calculate_clip_similarity(src_image, src_prompt, None)
+        if metric == "clip_similarity_target_image":
+            return calc.calculate_clip_similarity(tgt_image, tgt_prompt, None)
+        return "nan" if tgt_mask.sum() == 0 else calc.calculate_clip_similarity(tgt_image, tgt_prompt, tgt_mask)
+    if base in NOT_BUILT:
+        check_metrics([metric])
+    fn = lambda *a: getattr(calc, "calculate_" + base)(*a)
+    if part == "":
+        return fn(src_image, tgt_image, None, None)
+    ms, mt = (1 - src_mask, 1 - tgt_mask) if part == "_unedit_part" else (src_mask, tgt_mask)
+    return "nan" if ms.sum() == 0 or mt.sum() == 0 else fn(src_image, tgt_image, ms, mt)
+
+
+def clip_cells(scorer, metrics, src_image, tgt_image, tgt_mask, src_prompt, tgt_prompt):
+    """the CLIP columns of one (image, method) pair in one launch set -> {metric: value or "nan"}"""
+    want, imgs, prompts, masks = [], [], [], []
+    out = {}
+    for m in CLIP_METRICS:
+        if m not in metrics:
+            continue
+        if m == "clip_similarity_target_image_edit_part" and tgt_mask.sum() == 0:
+            out[m] = "nan"
+            continue
+        src = m == "clip_similarity_source_image"
+        want.append(m)
+        imgs.append(np.asarray(src_image if src else tgt_image).astype(np.uint8))
+        prompts.append(src_prompt if src else tgt_prompt)
+        masks.append(tgt_mask if m == "clip_similarity_target_image_edit_part" else None)
+    if want:
+        got = scorer.score(imgs, prompts, masks=masks if any(k is not None for k in masks) else None)
+        out.update({m: float(v) for m, v in zip(want, got)})
+    return out
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--annotation_mapping_file", type=str, default="data/mapping_file.json")
+    ap.add_argument("--metrics", nargs="+", type=str, default=DEFAULT_METRICS)
+    ap.add_argument("--src_image_folder", type=str, default="data/annotation_images")
+    ap.add_argument("--tgt_methods", nargs="+", type=str, default=[k for k in all_tgt_image_folders if k.startswith("1_")][:6])
+    ap.add_argument("--result_path", type=str, default="evaluation_result.csv")
+    ap.add_argument("--device", type=str, default="cuda")
+    ap.add_argument("--edit_category_list", nargs="+", type=str, default=[str(i) for i in range(10)])
+    ap.add_argument("--evaluate_whole_table", action="store_true")
+    # weights of the CLIP columns (not in the reference, which downloads openai/clip-vit-large-patch14)
+    ap.add_argument("--checkpoint_dir", type=str, default=None, help="Stable-Diffusion-1.x directory (diffusers layout): text tower + tokenizer")
+    ap.add_argument("--clip_model_dir", type=str, default=None, help="local clip-vit-large-patch14 directory: image tower + projections")
+    ap.add_argument("--synthetic_weights", action="store_true", help="seeded random towers and the word-level stand-in tokenizer")
+    return ap.parse_args(argv)
+
+
+def build_scorer(args):
+    """ClipScore on a text-only context (no UNet rows, no VAE images) from --checkpoint_dir + --clip_model_dir, or seeded weights"""
+    from pnpinversion_amd import checkpoint, weights
+    from pnpinversion_amd.clip_score import ClipScore
+    from pnpinversion_amd.config import SD1
+    from pnpinversion_amd.pipeline import NativePipeline
+    if bool(args.synthetic_weights) == bool(args.checkpoint_dir and args.clip_model_dir):
+        raise SystemExit("the clip_similarity_* columns need weights: --checkpoint_dir <SD-1.x dir> with --clip_model_dir <clip-vit-large-patch14 dir>, "
+                         "or --synthetic_weights (seeded random towers)")
+    dev = args.device if args.device != "cuda" else None
+    if args.synthetic_weights:
+        print(checkpoint.SYNTHETIC_WARNING, file=sys.stderr, flush=True)
+        pipe = NativePipeline(SD1, device=dev, max_unet_rows=0, max_vae_images=0, text_encoder="native")
+        pipe.engine.load_state_dict(clip_sd=weights.clip_state_dict(SD1, 0))
+        scorer = ClipScore(pipe, max_images=3)
+        scorer.load_synthetic(0)
+        return scorer
+    _, _, clip_sd, tok = checkpoint.load_checkpoint_dir(args.checkpoint_dir)
+    model_sd = checkpoint.load_clip_model_dir(args.clip_model_dir, text_sd=clip_sd)
+    pipe = NativePipeline(SD1, device=dev, max_unet_rows=0, max_vae_images=0, tokenizer=tok, text_encoder="native")
+    pipe.engine.load_state_dict(clip_sd=clip_sd)
+    scorer = ClipScore(pipe, max_images=3)
+    scorer.load_state_dict(model_sd)
+    return scorer
+
+
+def run(args, scorer=None):
+    from PIL import Image
+    metrics = list(args.metrics)
+    check_metrics(metrics)
+    if args.evaluate_whole_table:
+        folders = {k: v for k, v in all_tgt_image_folders.items() if k[0] in args.tgt_methods}
+    else:
+        folders = {k: all_tgt_image_folders[k] for k in args.tgt_methods}
+    if scorer is None and any(m in CLIP_METRICS for m in metrics):
+        scorer = build_scorer(args)
+    calc = Calculator(scorer)
+    with open(args.result_path, "w", newline="") as f:
+        csv.writer(f).writerow(["file_id"] + ["%s|%s" % (k, m) for k in folders for m in metrics])
+    with open(args.annotation_mapping_file) as f:
+        annotation = json.load(f)
+    for key, item in annotation.items():
+        if item["editing_type_id"] not in args.edit_category_list:
+            continue
+        print("evaluating image %s ..." % key)
+        mask = mask_decode(item["mask"])[:, :, None].repeat(3, axis=2)
+        src_prompt = item["original_prompt"].replace("[", "").replace("]", "")
+        tgt_prompt = item["editing_prompt"].replace("[", "").replace("]", "")
+        src_image = Image.open(os.path.join(args.src_image_folder, item["image_path"]))
+        row = [key]
+        for name, folder in folders.items():
+            tgt_image = Image.open(os.path.join(folder, item["image_path"]))
+            if tgt_image.size[0] != tgt_image.size[1]:            # a multi-panel output: the edit is the right-hand 512 x 512
+                w, h = tgt_image.size
+                tgt_image = tgt_image.crop((w - 512, h - 512, w, h))
+            clip = clip_cells(scorer, metrics, src_image, tgt_image, mask, src_prompt, tgt_prompt) if scorer is not None else {}
+            for m in metrics:
+                row.append(clip[m] if m in clip else calculate_metric(calc, m, src_image, tgt_image, mask, mask, src_prompt, tgt_prompt))
+        with open(args.result_path, "a+", newline="") as f:
+            csv.writer(f).writerow(row)
+
+
+if __name__ == "__main__":
+    _args = parse_args()
+    check_metrics(_args.metrics)
+    run(_args)

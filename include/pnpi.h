@@ -252,6 +252,56 @@ int pnpi_prox_threshold(pnpi_ctx* ctx, const float* eps, int nimg, int rows_per_
  * VAE entry points do not. */
 int pnpi_text_encode(pnpi_ctx* ctx, const int32_t* input_ids, int n, float* hidden_out);
 
+/* ---- CLIP similarity (evaluation/matrics_calculator.py:290-302: torchmetrics CLIPScore("openai/clip-vit-large-patch14") on
+ * uint8(img * mask)) ---------------------------------------------------------------------------------------------------------
+ * The image tower (transformers CLIPVisionTransformer), visual_projection and text_projection attached to a context that has the
+ * text tower: pnpi_model_config, pnpi_create and the shared weight arena are untouched, the tower's weights, tables and workspaces
+ * are an allocation of their own, freed by pnpi_destroy.  Weights arrive through pnpi_load_weights under the prefix "clipv." with
+ * transformers CLIPModel keys: vision_model.embeddings.{class_embedding, patch_embedding.weight, position_embedding.weight},
+ * vision_model.pre_layrnorm.* (upstream's spelling), vision_model.encoder.layers.N.*, vision_model.post_layernorm.*,
+ * visual_projection.weight, text_projection.weight.  Neither pnpi_missing_weights nor the UNet / VAE entry points look at them; the
+ * entry points below name every missing one in pnpi_last_error.  pnpi_mark_all_loaded does not mark them (they are not in the arena).
+ * Every entry point refuses, with a status and a message and before anything is launched: no tower attached (PNPI_ESTATE), missing
+ * weights (PNPI_ESTATE), n outside 1 .. max_images (PNPI_EINVAL), an S other than a square side with image_size <= S <= 8192
+ * (PNPI_ESHAPE), a mask byte other than 0 / 1 (PNPI_EINVAL; the masks are read back to the host for this check). */
+typedef struct {
+  int struct_size;                 /* = sizeof(pnpi_clipv_config), set by pnpi_clipv_config_vitl14 / the caller; a mismatch is PNPI_EINVAL */
+  int image_size;                  /* 224 */
+  int patch;                       /* 14 */
+  int width;                       /* 1024 */
+  int layers;                      /* 24 */
+  int heads;                       /* 16 */
+  int intermediate;                /* 4096 */
+  int proj_dim;                    /* 768 */
+} pnpi_clipv_config;
+void pnpi_clipv_config_vitl14(pnpi_clipv_config* cfg);
+/* PNPI_ESTATE if the context has no text tower (clip_layers = 0) or already has an image tower */
+int pnpi_clipv_attach(pnpi_ctx* ctx, const pnpi_clipv_config* cfg, int max_images);
+/* CLIPModel.get_image_features of CLIPProcessor(images): img_hwc device uint8 [n][S][S][3], mask_hw nullable device uint8 [n][S][S]
+ * (0 / 1, broadcast over the channels: uint8(img * mask) first); PIL's Image.resize(BICUBIC) to image_size (antialiased two-pass
+ * filter in PIL's 22-bit fixed point, a uint8 rounding after each pass: bit-exact), / 255, CLIP mean / std; patch embedding, class
+ * token, positions, pre_layrnorm, the encoder layers, post_layernorm on the class token, visual_projection.
+ * embed_out device fp32 [n][proj_dim], not normalised. */
+int pnpi_clip_image_embed(pnpi_ctx* ctx, const uint8_t* img_hwc, const uint8_t* mask_hw, int n, int S, float* embed_out);
+/* CLIPModel.get_text_features: the text tower's output (final LayerNorm included) at each row's EOS position -- the FIRST position
+ * holding the row's largest id, which is argmax(input_ids) of transformers for CLIP's vocabulary (EOS = vocab - 1) -- through
+ * text_projection.  input_ids device int32 [n][ctx_len]; embed_out device fp32 [n][proj_dim]. */
+int pnpi_clip_text_embed(pnpi_ctx* ctx, const int32_t* input_ids, int n, float* embed_out);
+/* CLIPScore per pair: score_out[i] = max(100 * cos(image_i, text_i), 0), device fp32 [n] */
+int pnpi_clip_score(pnpi_ctx* ctx, const uint8_t* img_hwc, const uint8_t* mask_hw, const int32_t* input_ids, int n, int S, float* score_out);
+/* kernel-level: the preprocessing alone, to out_size (a multiple of the attached tower's patch, <= S).  resized_out (nullable) device
+ * uint8 [n][out][out][3]: what PIL's resize gives; patches_f16_out (nullable) device fp16 [n][(out / patch)^2][Kp], Kp = 3 * patch^2
+ * rounded up to a multiple of 64: the normalised pixels as patch rows in the patch-embedding weight's (c, ky, kx) order, pad columns
+ * zero.  Needs no weights. */
+int pnpi_op_clip_preprocess(pnpi_ctx* ctx, const uint8_t* img_hwc, const uint8_t* mask_hw, int n, int S, int out_size,
+                            uint8_t* resized_out, void* patches_f16_out);
+/* Host-only, no context: the per-output-pixel tables the preprocessing kernels apply for in_size -> out_size (both passes use the same
+ * table for square images), as PIL's precompute_coeffs + normalize_coeffs_8bpc give them for BICUBIC.  Returns ksize (taps reserved per
+ * output pixel; 1 for in_size == out_size, where PIL copies) or PNPI_ESHAPE for out_size > in_size or in_size > 8192; bounds_out
+ * (nullable) [out_size][2] = (first source index, taps used), coef_out (nullable) [out_size][ksize] 22-bit fixed point.  Call once with
+ * NULLs for ksize.  One pass: acc = 2^21 + sum_j src[first + j] * coef[j];  out = clamp(acc >> 22, 0, 255). */
+int pnpi_clip_resize_tables(int in_size, int out_size, int* bounds_out, int* coef_out);
+
 /* ---- level 2: loop boundary (whole phases device-resident, no host round trip per step) ------------------------- */
 /* DirectInversion.ddim_loop (inversion.py:308-319): latents_out [nsteps+1][nimg][4][h][w]; timesteps_host = scheduler.timesteps */
 int pnpi_ddim_invert(pnpi_ctx* ctx, const float* z0, int nimg, const float* ctx_cond /*[nimg][77][768]*/, int nsteps,

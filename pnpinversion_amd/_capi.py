@@ -22,6 +22,15 @@ class ModelConfig(C.Structure):
     ]
 
 
+class ClipvConfig(C.Structure):
+    """pnpi_clipv_config: the CLIP image tower + projection width (pnpi_clipv_config_vitl14 fills ViT-L/14's)"""
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "image_size", "patch", "width", "layers", "heads", "intermediate", "proj_dim")]
+
+    @classmethod
+    def make(cls, image_size=224, patch=14, width=1024, layers=24, heads=16, intermediate=4096, proj_dim=768):
+        return cls(C.sizeof(cls), int(image_size), int(patch), int(width), int(layers), int(heads), int(intermediate), int(proj_dim))
+
+
 class NamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int), ("shape", C.c_int64 * 4)]
 
@@ -125,6 +134,14 @@ SYMBOLS = {
     "pnpi_cfg_ddim_prev": (_i, [_vp, _vp, _vp, _i, _i, _sz, _f, _i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, C.POINTER(ReconDesc)]),
     "pnpi_prox_threshold": (_i, [_vp, _vp, _i, _i, _sz, _f, _vp]),
     "pnpi_text_encode": (_i, [_vp, _vp, _i, _vp]),
+    # CLIP similarity (evaluation/matrics_calculator.py:290-302)
+    "pnpi_clipv_config_vitl14": (None, [C.POINTER(ClipvConfig)]),
+    "pnpi_clipv_attach": (_i, [_vp, C.POINTER(ClipvConfig), _i]),
+    "pnpi_clip_image_embed": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "pnpi_clip_text_embed": (_i, [_vp, _vp, _i, _vp]),
+    "pnpi_clip_score": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "pnpi_op_clip_preprocess": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pnpi_clip_resize_tables": (_i, [_i, _i, _ip, _ip]),
     "pnpi_ddim_invert": (_i, [_vp, _vp, _i, _vp, _i, _ip, _vp]),
     "pnpi_ddim_invert_cfg": (_i, [_vp, _vp, _i, _vp, _vp, _f, _i, _ip, _vp]),
     "pnpi_offset_calculate": (_i, [_vp, _vp, _i, _vp, _i, _ip, _f, _fp, _vp]),

@@ -12,8 +12,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libpnpi.so")
 LIB_ABLATIONS = os.path.join(CSRC, "libpnpi_ablations.so")
-SOURCES = ["gemm.hip", "norm.hip", "attn.hip", "step.hip", "bwd.hip", "api.hip", "tuning.hip"]
-HEADERS = ["common.h", "ops.h", "model.h", "tuning.h", "tile_table.inc", "igemm_dma.inc", "igemm_pp.inc", "api_weights.inc", "api_graph.inc", "api_backward.inc", "api_vae.inc", "api_ctrl.inc", "api_loops.inc", os.path.join("..", "..", "include", "pnpi.h")]
+SOURCES = ["gemm.hip", "norm.hip", "attn.hip", "step.hip", "bwd.hip", "clipscore.hip", "api.hip", "tuning.hip"]
+HEADERS = ["common.h", "ops.h", "model.h", "tuning.h", "tile_table.inc", "igemm_dma.inc", "igemm_pp.inc", "api_weights.inc", "api_graph.inc", "api_backward.inc", "api_vae.inc", "api_ctrl.inc", "api_clipscore.inc", "api_loops.inc", os.path.join("..", "..", "include", "pnpi.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-Wno-unused-value"]
 # Per-file flags.  step.hip: the reference rounds every multiply / add separately (no FMA contraction).  attn.hip: keep the MFMA
 # accumulators in VGPRs (gfx950's unified file) -- the softmax between the two MFMAs is VALU work on the S accumulators, and in
@@ -58,6 +58,9 @@ def build(force=False, verbose=True, ablations=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
+    srcs = [os.path.join(CSRC, s) for s in SOURCES]
+    if not force and not _stale(LIB, srcs + hdrs):
+        return LIB      # the library is newer than everything it is built from (a tree that travelled without its object files)
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -39,6 +39,31 @@ def load_checkpoint_dir(path):
     return unet, vae, clip, tok
 
 
+def load_clip_model_dir(path, text_sd=None, atol=1e-3):
+    """A local `openai/clip-vit-large-patch14` directory (model.safetensors or pytorch_model.bin: transformers CLIPModel) -> the state
+    dict ClipScore.load_state_dict takes: vision_model.*, visual_projection.weight, text_projection.weight.
+    text_sd: the CLIPTextModel state dict already loaded from the SD checkpoint (load_checkpoint_dir's third value).  CLIP similarity
+    runs the image tower of THIS directory against the text tower of THAT one, which is right only if they are the same network (SD-1.x
+    conditions on clip-vit-large-patch14's text tower): every text_model.* tensor here must match it within atol (fp16 checkpoints), or
+    ValueError names the first that does not.
+    Nothing offline can exercise this function -- no clip-vit-large-patch14 checkpoint exists on the build / GPU boxes; the tests run
+    seeded towers (weights.clipv_state_dict) through the same ClipScore.load_state_dict."""
+    if not os.path.isdir(path):
+        raise FileNotFoundError("CLIP model directory %r does not exist" % path)
+    sd = _load_sd(path, ("model.safetensors", "pytorch_model.bin"))
+    out = {k: v for k, v in sd.items() if (k.startswith("vision_model.") and "position_ids" not in k) or k in ("visual_projection.weight", "text_projection.weight")}
+    for need in ("vision_model.embeddings.class_embedding", "vision_model.pre_layrnorm.weight", "visual_projection.weight", "text_projection.weight"):
+        if need not in out:
+            raise KeyError("%s: no %s -- not a transformers CLIPModel checkpoint" % (path, need))
+    if text_sd is not None:
+        for k, v in text_sd.items():
+            mine = sd.get("text_model." + k)
+            if mine is None or mine.shape != v.shape or float((mine.float() - v.float()).abs().max()) > atol:
+                raise ValueError("the text tower of %s differs from the loaded Stable-Diffusion text encoder at %r: CLIP similarity would pair "
+                                 "an image tower with a text tower it was not trained with" % (path, k))
+    return out
+
+
 # ---- CompVis-layout checkpoints (what run_editing_instructpix2pix.py loads: one .ckpt whose state_dict holds model.diffusion_model.*,
 # first_stage_model.* and cond_stage_model.transformer.*) -> the diffusers-layout names load_state_dict takes
 _LDM_RES = {"in_layers.0": "norm1", "in_layers.2": "conv1", "emb_layers.1": "time_emb_proj", "out_layers.0": "norm2", "out_layers.3": "conv2",

@@ -1,12 +1,13 @@
 // libpnpi: C-ABI entry points + the static SD-1.x UNet / VAE graph executor and the device-resident DI / P2P loops.
 // See include/pnpi.h for the reference interface each entry point replaces.
-// One translation unit in seven files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the CLIP text encoder,
+// One translation unit in eight files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the CLIP text encoder,
 // kernel-level test hooks) includes, in order,
 //   api_weights.inc   weight slots of the packed arena and the model builder
 //   api_graph.inc     profiling records, activation tape, op wrappers, ResNet / transformer blocks, unet_fwd
 //   api_backward.inc  reverse walk over the tape (gradient w.r.t. the unconditional embedding)
 //   api_vae.inc       AutoencoderKL encoder / decoder graph
 //   api_ctrl.inc      per-loop text K / V cache, controller descriptor -> device tables
+//   api_clipscore.inc CLIP similarity: the image tower attached to a context, projections, preprocessing, score
 //   api_loops.inc     (last) the loop scaffold and the level-2 loops: DDIM / direct inversion, edit loops, edit-friendly DDPM, null-text
 #include <math.h>
 #include <stdio.h>
@@ -103,7 +104,8 @@ static int validate_config(pnpi_ctx* c) {
   return 0;
 }
 
-static int clip_fwd(pnpi_ctx* c, const int* ids, int n, float* out);
+static int clip_fwd(pnpi_ctx* c, const int* ids, int n, float* out, half_t** y16_out = nullptr);
+static void clipv_free(pnpi_ctx* c);
 
 static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device, void* hip_stream, int max_unet_rows, int max_vae_images, pnpi_ctx* parent);
 int pnpi_create(pnpi_ctx** out, const pnpi_model_config* cfg, int device, void* hip_stream, int max_unet_rows, int max_vae_images) {
@@ -263,6 +265,7 @@ void pnpi_destroy(pnpi_ctx* c) {
     for (auto& kv : c->tape->wd) (void)hipFree(kv.second);
     delete c->tape;
   }
+  clipv_free(c);
   delete c;
 }
 
@@ -309,7 +312,7 @@ int pnpi_missing_weights(const pnpi_ctx* c, char* names_out, size_t cap) {
   size_t used = 0;
   if (names_out && cap) names_out[0] = 0;
   for (auto& kv : c->slots)
-    if (!kv.second.loaded && kv.first.compare(0, 5, "clip.") != 0) {   // the text encoder reports through pnpi_text_encode
+    if (!kv.second.loaded && kv.first.compare(0, 5, "clip.") != 0 && kv.first.compare(0, 6, "clipv.") != 0) {   // the text encoder reports through pnpi_text_encode, the image tower through pnpi_clip_*
       ++missing;
       if (names_out && used + kv.first.size() + 2 < cap) {
         memcpy(names_out + used, kv.first.c_str(), kv.first.size());
@@ -330,7 +333,8 @@ int pnpi_weight_arena(pnpi_ctx* c, void** ptr, size_t* bytes) {
 
 int pnpi_mark_all_loaded(pnpi_ctx* c) {
   invalidate_derived(c);            // the arena was just overwritten by the broadcast
-  for (auto& kv : c->slots) kv.second.loaded = true;
+  for (auto& kv : c->slots)
+    if (kv.first.compare(0, 6, "clipv.") != 0) kv.second.loaded = true;      // the image tower is no part of the arena
   CK(build_ff_fold(c));             // derived after the broadcast, from the weights it delivered (a borrowing context leaves it to the owner)
   return 0;
 }
@@ -437,7 +441,8 @@ int pnpi_profile_end(pnpi_ctx* c, pnpi_kernel_stats* out) {
   return 0;
 }
 
-static bool is_clip_slot(const std::string& name) { return name.compare(0, 5, "clip.") == 0; }
+static bool is_clipv_slot(const std::string& name) { return name.compare(0, 6, "clipv.") == 0; }      // image tower + projections (pnpi_clipv_attach)
+static bool is_clip_slot(const std::string& name) { return name.compare(0, 5, "clip.") == 0 || is_clipv_slot(name); }
 static int check_ready(pnpi_ctx* c) {   // UNet / VAE entry points: the text encoder's weights are optional for them
   for (auto& kv : c->slots)
     if (!kv.second.loaded && !is_clip_slot(kv.first)) { c->err = "weights not loaded: " + kv.first; return PNPI_ESTATE; }
@@ -454,7 +459,7 @@ static int check_loop_ready(pnpi_ctx* c) {
 static int check_clip_ready(pnpi_ctx* c) {
   if (c->clip.layers.empty()) return fail(c, PNPI_ESTATE, "this context was built without a text encoder (clip_layers = 0)");
   for (auto& kv : c->slots)
-    if (!kv.second.loaded && is_clip_slot(kv.first)) { c->err = "weights not loaded: " + kv.first; return PNPI_ESTATE; }
+    if (!kv.second.loaded && is_clip_slot(kv.first) && !is_clipv_slot(kv.first)) { c->err = "weights not loaded: " + kv.first; return PNPI_ESTATE; }
   return 0;
 }
 
@@ -629,47 +634,54 @@ int pnpi_prox_threshold(pnpi_ctx* c, const float* eps, int nimg, int rpi, size_t
   return 0;
 }
 
+// One CLIPEncoderLayer (transformers modeling_clip.py), shared by the two towers: pre-LN self-attention (causal in the text tower, full in
+// the image tower) and the quick_gelu MLP, each with its residual; x [n * T][H] is updated in place.  rows: identity row table [n][4].
+static int clip_encoder_layer(pnpi_ctx* c, const ClipLayerW& L, half_t* x, int n, int T, int H, int heads, int I, int causal, const int* rows) {
+  const int M = n * T, dh = H / heads, ldv = round_up_i(T, 8);
+  const size_t mk = c->temp.mark();
+  half_t* h1 = talloc(c, (size_t)M * H);
+  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x, M, H, 1e-5f, L.ln1.g, L.ln1.b, h1, c->st));
+  half_t* qk = talloc(c, (size_t)M * 2 * H);
+  half_t* vt = talloc(c, (size_t)n * H * ldv);
+  {
+    VtOut v; v.outT = vt; v.col0 = 2 * H; v.ld = ldv; v.f32 = 0; v.rpb = T;
+    CK(op_gemm(c, h1, H, M, H, L.w_qkv, H, 3 * H, L.b_qkv, nullptr, 0, qk, 2 * H, 1.f, &v));
+  }
+  half_t* ao = talloc(c, (size_t)M * H);
+  {
+    AttnP a; a.q = qk; a.ldq = 2 * H; a.q_off = 0; a.k = qk; a.ldk = 2 * H; a.k_off = H; a.vt = vt; a.ldv = ldv;
+    a.o = ao; a.ldo = H; a.heads = heads; a.Nq = T; a.Nk = T; a.Dp = dh; a.dh = dh; a.scale = 1.0f / sqrtf((float)dh);
+    a.rows = rows; a.nrows = n; a.causal = causal;
+    if (!c->dry) PROFD(PNPI_KC_ATTN_FLASH, 4.0 * n * heads * (double)T * T * dh, 0.0, T, T, dh, launch_attn_flash(a, c->st));
+  }
+  half_t* x1 = talloc(c, (size_t)M * H);
+  CK(op_gemm(c, ao, H, M, H, L.out.w, H, H, L.out.b, x, H, x1, H));
+  half_t* h2 = talloc(c, (size_t)M * H);
+  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x1, M, H, 1e-5f, L.ln2.g, L.ln2.b, h2, c->st));
+  half_t* f = talloc(c, (size_t)M * I);
+  CK(op_gemm(c, h2, H, M, H, L.fc1.w, H, I, L.fc1.b, nullptr, 0, f, I));
+  if (!c->dry) CK(launch_quick_gelu(f, (size_t)M * I, c->st));
+  CK(op_gemm(c, f, I, M, I, L.fc2.w, I, H, L.fc2.b, x1, H, x, H));    // x <- x1 + mlp (x's old value is dead)
+  c->temp.release(mk);
+  return 0;
+}
+
 // CLIPTextModel.forward -> last_hidden_state (transformers modeling_clip.py: CLIPTextEmbeddings, CLIPEncoderLayer x L with a
-// causal mask, final_layer_norm); pre-LN blocks, quick_gelu MLP.  ids: device int32 [n][T]; out fp32 [n][T][H].
-static int clip_fwd(pnpi_ctx* c, const int* ids, int n, float* out) {
+// causal mask, final_layer_norm); pre-LN blocks, quick_gelu MLP.  ids: device int32 [n][T]; out fp32 [n][T][H] (nullable);
+// y16_out (nullable): the same rows in fp16, in the persistent workspace until the next forward resets it.
+static int clip_fwd(pnpi_ctx* c, const int* ids, int n, float* out, half_t** y16_out) {
   const ClipW& t = c->clip;
-  const int H = t.H, T = t.T, M = n * T, dh = H / t.heads;
+  const int H = t.H, T = t.T, M = n * T;
   c->persist.reset(); c->temp.reset();
   half_t* x = palloc(c, (size_t)M * H);
   if (!c->dry) CK(launch_embed_tokens(ids, M, T, H, t.vocab, t.tok, t.pos, x, c->st));
-  const int ldv = round_up_i(T, 8);
-  for (const ClipLayerW& L : t.layers) {
-    const size_t mk = c->temp.mark();
-    half_t* h1 = talloc(c, (size_t)M * H);
-    if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x, M, H, 1e-5f, L.ln1.g, L.ln1.b, h1, c->st));
-    half_t* qk = talloc(c, (size_t)M * 2 * H);
-    half_t* vt = talloc(c, (size_t)n * H * ldv);
-    {
-      VtOut v; v.outT = vt; v.col0 = 2 * H; v.ld = ldv; v.f32 = 0; v.rpb = T;
-      CK(op_gemm(c, h1, H, M, H, L.w_qkv, H, 3 * H, L.b_qkv, nullptr, 0, qk, 2 * H, 1.f, &v));
-    }
-    half_t* ao = talloc(c, (size_t)M * H);
-    {
-      AttnP a; a.q = qk; a.ldq = 2 * H; a.q_off = 0; a.k = qk; a.ldk = 2 * H; a.k_off = H; a.vt = vt; a.ldv = ldv;
-      a.o = ao; a.ldo = H; a.heads = t.heads; a.Nq = T; a.Nk = T; a.Dp = dh; a.dh = dh; a.scale = 1.0f / sqrtf((float)dh);
-      a.rows = c->rows_ident; a.nrows = n; a.causal = 1;
-      if (!c->dry) PROFD(PNPI_KC_ATTN_FLASH, 4.0 * n * t.heads * (double)T * T * dh, 0.0, T, T, dh, launch_attn_flash(a, c->st));
-    }
-    half_t* x1 = talloc(c, (size_t)M * H);
-    CK(op_gemm(c, ao, H, M, H, L.out.w, H, H, L.out.b, x, H, x1, H));
-    half_t* h2 = talloc(c, (size_t)M * H);
-    if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x1, M, H, 1e-5f, L.ln2.g, L.ln2.b, h2, c->st));
-    half_t* f = talloc(c, (size_t)M * t.I);
-    CK(op_gemm(c, h2, H, M, H, L.fc1.w, H, t.I, L.fc1.b, nullptr, 0, f, t.I));
-    if (!c->dry) CK(launch_quick_gelu(f, (size_t)M * t.I, c->st));
-    CK(op_gemm(c, f, t.I, M, t.I, L.fc2.w, t.I, H, L.fc2.b, x1, H, x, H));    // x <- x1 + mlp (x's old value is dead)
-    c->temp.release(mk);
-  }
+  for (const ClipLayerW& L : t.layers) CKP(clip_encoder_layer(c, L, x, n, T, H, t.heads, t.I, 1, c->rows_ident));
   half_t* y = palloc(c, (size_t)M * H);
   if (!c->dry) {
     PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x, M, H, 1e-5f, t.final_ln.g, t.final_ln.b, y, c->st));
-    CK(launch_f16_to_f32(y, (size_t)M * H, out, c->st));
+    if (out) CK(launch_f16_to_f32(y, (size_t)M * H, out, c->st));
   }
+  if (y16_out) *y16_out = y;
   return 0;
 }
 
@@ -679,6 +691,8 @@ int pnpi_text_encode(pnpi_ctx* c, const int32_t* input_ids, int n, float* hidden
   if (n > c->rows_ident_n) return fail(c, PNPI_EINVAL, "more prompts than max(max_unet_rows, 8)");
   return clip_fwd(c, (const int*)input_ids, n, hidden_out);
 }
+
+#include "api_clipscore.inc"
 
 // ---------------------------------------------------------------------------------------------------- kernel-level ops
 static int conv_hook(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int H, int W, int ksize, int stride, int pad, int ups,

@@ -127,6 +127,32 @@ struct ClipW {
   NormW final_ln;
 };
 
+// CLIP image tower + the two projections (pnpi_clipv_attach; transformers CLIPModel: vision_model, visual_projection, text_projection).
+// Everything it owns lives outside the context's own arenas: a context that never attaches one is unchanged.
+struct ClipVisionW {
+  pnpi_clipv_config cfg;
+  int max_images = 0;
+  int G = 0, NP = 0, T = 0, Kp = 0;       // patch grid side, patches, tokens (NP + 1), patch-row length 3 * patch^2 rounded up to 64
+  Bump arena;                             // weights (own allocation)
+  Bump persist, temp;                     // activation workspaces of the image forward (swapped into the context while it runs)
+  Bump bufs;                              // small persistent buffers below
+  half_t* w_patch = nullptr;              // [W][Kp] patch embedding, (c, ky, kx) columns, pad columns zero
+  float* cls = nullptr;                   // [W]
+  float* pos = nullptr;                   // [T][W]
+  NormW pre_ln, post_ln;
+  std::vector<ClipLayerW> layers;
+  half_t* w_vproj = nullptr;              // [proj][W]
+  half_t* w_tproj = nullptr;              // [proj][H_text]
+  int* rows_ident = nullptr;              // [max_images][4]
+  half_t *pool_img = nullptr, *ln_img = nullptr, *emb_img16 = nullptr, *pool_txt = nullptr, *emb_txt16 = nullptr;
+  float *emb_img = nullptr, *emb_txt = nullptr;   // [max_images][proj]
+  // PIL's bicubic coefficient tables per source size (built on the host at first use): bounds [out][2] = (first source index, count),
+  // coef [out][ksize] 22-bit fixed point
+  struct ResizeTab { int S, out, ksize; int* bounds; int* coef; };
+  std::vector<ResizeTab> tabs;
+  uint8_t* tmp_u8 = nullptr; size_t tmp_bytes = 0;   // the horizontal pass's output [n][S][out][3], grown on demand
+};
+
 struct Tensor4 { half_t* p; int B, H, W, C; };
 
 struct CtrlDev {
@@ -250,7 +276,8 @@ struct pnpi_ctx {
   UNetW unet;
   VaeW vae;
   ClipW clip;
-  int* rows_ident = nullptr;   // [max(max_rows, 8)][4] identity attention-row table (text encoder)
+  ClipVisionW* cv = nullptr;   // pnpi_clipv_attach; nullptr: no image tower
+  int* rows_ident = nullptr;  // [max(max_rows, 8)][4] identity attention-row table (text encoder)
   int rows_ident_n = 0;
   std::vector<float> ac;
   float final_alpha;

@@ -108,6 +108,24 @@ int launch_quick_gelu(half_t* x, size_t n, hipStream_t st);
 int launch_f16_to_f32(const half_t* in, size_t n, float* out, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
+// CLIP similarity (clipscore.hip): preprocessing, token assembly, pooled-row gather, cosine score
+// ---------------------------------------------------------------------------------------------------------------
+// PIL Image.resize(BICUBIC) on uint8 RGB in its 22-bit fixed point: bounds [out][2] = (first source index, taps), coef [out][ksize].
+// Horizontal pass: img [n][S][S][3] (* mask [n][S][S] 0 / 1, nullable) -> tmp [n][S][out][3]
+int launch_clip_resize_h(const uint8_t* img, const uint8_t* mask, int n, int S, int out, const int* bounds, const int* coef, int ksize,
+                         uint8_t* tmp, hipStream_t st);
+// Vertical pass: tmp -> resized [n][out][out][3] (nullable) and / or the normalised pixels as fp16 patch rows patches
+// [n][(out / patch)^2][Kp] in (c, ky, kx) order, columns 3 * patch^2 .. Kp zero (nullable)
+int launch_clip_resize_v(const uint8_t* tmp, int n, int S, int out, const int* bounds, const int* coef, int ksize, int patch, int Kp,
+                         uint8_t* resized, half_t* patches, hipStream_t st);
+// x [n][NP + 1][W]: row 0 = cls + pos[0], row 1 + p = pe[n][p] + pos[1 + p] (fp32 sums, one rounding); W % 8 == 0
+int launch_clip_assemble_tokens(const half_t* pe, const float* cls, const float* pos, int n, int NP, int W, half_t* x, hipStream_t st);
+// out [n][H] = x [n][T][H] at token 0 (ids == nullptr) or at the first position of each row's largest id (ids [n][T]); H % 8 == 0
+int launch_clip_gather_rows(const half_t* x, int n, int T, int H, const int* ids, half_t* out, hipStream_t st);
+// out[i] = max(100 * a_i . b_i / (|a_i| |b_i|), 0) in fp32, one wavefront per pair; a, b [n][D]
+int launch_clip_cosine(const float* a, const float* b, int n, int D, float* out, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------------------
 // Attention
 // ---------------------------------------------------------------------------------------------------------------
 // Key order of a "permuted" V^T (GemmP::vt_perm16 / AttnP::vt_perm): inside every aligned group of 16 tokens the two middle quads are

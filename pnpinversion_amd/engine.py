@@ -180,11 +180,12 @@ class NativeEngine:
         return t.to(device=self.device, dtype=torch.float32).contiguous()
 
     # ---- weights
-    def load_state_dict(self, unet_sd=None, vae_sd=None, chunk_bytes=1 << 30, clip_sd=None):
+    def load_state_dict(self, unet_sd=None, vae_sd=None, chunk_bytes=1 << 30, clip_sd=None, clipv_sd=None):
         """diffusers-layout state dicts (CPU or GPU tensors, fp32 or fp16); repacked on the device into the fp16 arena.
-        clip_sd: transformers CLIPTextModel state dict (optional; only pnpi_text_encode needs it)."""
+        clip_sd: transformers CLIPTextModel state dict (optional; only pnpi_text_encode needs it).
+        clipv_sd: transformers CLIPModel keys of the image tower and the two projections (after clipv_attach; see load_clipv_state_dict)."""
         items = []
-        for prefix, sd in (("unet.", unet_sd), ("vae.", vae_sd), ("clip.", clip_sd)):
+        for prefix, sd in (("unet.", unet_sd), ("vae.", vae_sd), ("clip.", clip_sd), ("clipv.", clipv_sd)):
             if sd:
                 items += [(prefix + k, v) for k, v in sd.items()]
         batch, keep, size = [], [], 0
@@ -367,6 +368,82 @@ class NativeEngine:
         out = torch.empty(n, T, self.cfg.cross_dim, device=self.device)
         self._call("pnpi_text_encode", _p(ids), n, _p(out))
         self._keep = ids
+        return out
+
+    # ---- CLIP similarity (pnpi_clipv_attach and the pnpi_clip_* entry points; clip_score.ClipScore is the user-facing object)
+    def clipv_attach(self, vcfg=None, max_images=8):
+        """Attach the CLIP image tower + projections (vcfg: _capi.ClipvConfig, default ViT-L/14) for up to max_images images per call."""
+        if vcfg is None:
+            vcfg = _capi.ClipvConfig()
+            self.lib.pnpi_clipv_config_vitl14(C.byref(vcfg))
+        self._call("pnpi_clipv_attach", C.byref(vcfg), int(max_images))
+        self.clipv_cfg, self.clipv_max_images = vcfg, int(max_images)
+
+    def load_clipv_state_dict(self, sd):
+        """transformers CLIPModel keys (vision_model.*, visual_projection.weight, text_projection.weight; text_model.* is ignored here)"""
+        wanted = {k: v for k, v in sd.items() if k.startswith("vision_model.") or k in ("visual_projection.weight", "text_projection.weight")}
+        self.load_state_dict(clipv_sd={k: v for k, v in wanted.items() if "position_ids" not in k})
+
+    def _clip_images(self, images, masks):
+        img = torch.as_tensor(images)
+        if img.dim() == 3:
+            img = img[None]
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3 or img.shape[1] != img.shape[2]:
+            raise ValueError("images must be uint8 [n, S, S, 3] (square panels), got %s %s" % (img.dtype, tuple(img.shape)))
+        img = img.to(self.device).contiguous()
+        m = None
+        if masks is not None:
+            m = torch.as_tensor(masks)
+            if m.dim() == 2:
+                m = m[None]
+            if m.dim() == 4:                      # evaluate.py's [S, S, 3] masks: one plane, broadcast over the channels by the kernel
+                if not bool((m == m[..., :1]).all()):
+                    raise ValueError("a mask with different channel planes is not supported")
+                m = m[..., 0]
+            if tuple(m.shape) != tuple(img.shape[:3]):
+                raise ValueError("masks must be [n, S, S], got %s for images %s" % (tuple(m.shape), tuple(img.shape)))
+            if not bool(((m == 0) | (m == 1)).all()):
+                raise ValueError("masks must hold 0 / 1 only")
+            m = m.to(self.device, dtype=torch.uint8).contiguous()
+        return img, m
+
+    def _clip_ids(self, input_ids):
+        ids = torch.as_tensor(input_ids).to(self.device, dtype=torch.int32).contiguous()
+        if ids.dim() != 2 or ids.shape[1] != self.cfg.ctx_len:
+            raise ValueError("input_ids must be [n, %d]" % self.cfg.ctx_len)
+        return ids
+
+    def clip_preprocess(self, images, masks=None, out_size=None, want_resized=True, want_patches=True):
+        """pnpi_op_clip_preprocess -> (resized uint8 [n, out, out, 3] or None, patch rows fp16 [n, (out / patch)^2, Kp] or None)"""
+        img, m = self._clip_images(images, masks)
+        n, S = img.shape[0], img.shape[1]
+        out = int(out_size or self.clipv_cfg.image_size)
+        p = self.clipv_cfg.patch
+        kp = (3 * p * p + 63) // 64 * 64
+        res = torch.empty(n, out, out, 3, dtype=torch.uint8, device=self.device) if want_resized else None
+        pat = torch.empty(n, max(out // p, 1) ** 2, kp, dtype=torch.float16, device=self.device) if want_patches else None
+        self._call("pnpi_op_clip_preprocess", _p(img), _p(m), n, S, out, _p(res), _p(pat))
+        return res, pat
+
+    def clip_image_embed(self, images, masks=None):
+        img, m = self._clip_images(images, masks)
+        out = torch.empty(img.shape[0], self.clipv_cfg.proj_dim, device=self.device)
+        self._call("pnpi_clip_image_embed", _p(img), _p(m), img.shape[0], img.shape[1], _p(out))
+        return out
+
+    def clip_text_embed(self, input_ids):
+        ids = self._clip_ids(input_ids)
+        out = torch.empty(ids.shape[0], self.clipv_cfg.proj_dim, device=self.device)
+        self._call("pnpi_clip_text_embed", _p(ids), ids.shape[0], _p(out))
+        return out
+
+    def clip_score(self, images, input_ids, masks=None):
+        img, m = self._clip_images(images, masks)
+        ids = self._clip_ids(input_ids)
+        if ids.shape[0] != img.shape[0]:
+            raise ValueError("%d images but %d prompts" % (img.shape[0], ids.shape[0]))
+        out = torch.empty(img.shape[0], device=self.device)
+        self._call("pnpi_clip_score", _p(img), _p(m), _p(ids), img.shape[0], img.shape[1], _p(out))
         return out
 
     def local_blend(self, latents, step_index):

@@ -95,3 +95,15 @@ def panel_report(panel, mask=None):
         out.update(psnr_unedit_part=calculate_psnr(edit, src, keep, keep), mse_unedit_part=calculate_mse(edit, src, keep, keep),
                    ssim_unedit_part=calculate_ssim(edit, src, keep, keep))
     return out
+
+
+def calculate_clip_similarity(img, txt, mask=None, *, scorer):
+    """matrics_calculator.py:290-302: CLIPScore of uint8(img * mask) against the prompt, on the device.  scorer: clip_score.ClipScore
+    (the reference holds its torchmetrics object in the calculator; here the caller passes the scorer).  mask: None, [S, S] or the
+    [S, S, 3] repeat evaluate.py builds, values 0 / 1."""
+    from .clip_score import _plane
+    a = np.asarray(img)
+    if a.ndim != 3 or a.shape[2] != 3:
+        a = np.asarray(img.convert("RGB")) if hasattr(img, "convert") else a
+    m = None if mask is None else _plane(mask)[None]
+    return float(scorer.score(a[None].astype(np.uint8), [txt], masks=m)[0].item())

@@ -15,6 +15,14 @@ import torch
 BOS, EOS = 49406, 49407
 
 
+def eos_positions(input_ids):
+    """The pooled position of CLIP's text tower per row: the FIRST position holding the row's largest id.  One rule for every tokenizer
+    here -- WordTokenizer and ClipBPETokenizer end a prompt with EOS = 49407 (the vocabulary's last id, larger than any other) and pad
+    with it -- and equal to transformers' `input_ids.argmax(-1)`; pnpi_clip_text_embed applies the same rule on the device."""
+    ids = np.asarray(input_ids)
+    return (ids == ids.max(axis=-1, keepdims=True)).argmax(axis=-1)
+
+
 class WordTokenizer:
     """CLIP conventions (BOS 49406, EOS/pad 49407, 77 positions) over a deterministic word-piece vocabulary: words longer
     than 6 characters are split into two pieces so that the multi-token paths of get_word_inds / seq_aligner are exercised."""

@@ -188,3 +188,32 @@ def clip_state_dict(cfg: ModelConfig, seed=0):
         _lin(sd, seed, "clip." + pre + ".mlp.fc2", I, H, gain=0.5)
     _norm(sd, seed, "clip.final_layer_norm", H)
     return {(k[5:] if k.startswith("clip.") else k): v for k, v in sd.items()}
+
+
+def clipv_state_dict(image_size=224, patch=14, width=1024, layers=24, heads=16, intermediate=4096, proj_dim=768, text_hidden=768, seed=0):
+    """The image tower and the two projections of transformers' CLIPModel (its state-dict keys: vision_model.*, visual_projection.weight,
+    text_projection.weight), seeded and fp16-representable like clip_state_dict -- no clip-vit-large-patch14 checkpoint exists offline.
+    Scales keep the activations O(1): the patch embedding is variance-preserving over normalised pixels, the residual branches shrink."""
+    del heads                                        # the head count shapes no tensor
+    sd = {}
+    vm = "vision_model."
+    T = (image_size // patch) ** 2 + 1
+    e = _gen(seed, "clipv.cls").standard_normal(width).astype(np.float32) * 0.5
+    sd[vm + "embeddings.class_embedding"] = torch.from_numpy(_fp16_round(e))
+    _w(sd, seed, vm + "embeddings.patch_embedding.weight", (width, 3, patch, patch), 3 * patch * patch)
+    e = _gen(seed, "clipv.pos").standard_normal((T, width)).astype(np.float32) * 0.5
+    sd[vm + "embeddings.position_embedding.weight"] = torch.from_numpy(_fp16_round(e))
+    _norm(sd, seed, vm + "pre_layrnorm", width)      # upstream's spelling
+    for l in range(layers):
+        pre = vm + "encoder.layers.%d" % l
+        _norm(sd, seed, pre + ".layer_norm1", width)
+        _norm(sd, seed, pre + ".layer_norm2", width)
+        for n in ("q_proj", "k_proj", "v_proj"):
+            _lin(sd, seed, pre + ".self_attn." + n, width, width, gain=1.2)
+        _lin(sd, seed, pre + ".self_attn.out_proj", width, width, gain=0.5)
+        _lin(sd, seed, pre + ".mlp.fc1", width, intermediate)
+        _lin(sd, seed, pre + ".mlp.fc2", intermediate, width, gain=0.5)
+    _norm(sd, seed, vm + "post_layernorm", width)
+    _lin(sd, seed, "visual_projection", width, proj_dim, bias=False)
+    _lin(sd, seed, "text_projection", text_hidden, proj_dim, bias=False)
+    return sd
