@@ -121,11 +121,42 @@ int pnpi_create_shared(pnpi_ctx** out, pnpi_ctx* parent, void* hip_stream, int m
   if (parent->warena_borrowed) return fail(parent, PNPI_ESTATE, "pnpi_create_shared: the parent itself borrows its weights; share from the owner");
   return create_impl(out, &parent->cfg, parent->device, hip_stream, max_unet_rows, max_vae_images, parent);
 }
+// dry runs of every graph at the context's row limits: the peaks of the two activation workspaces
+static int size_workspaces(pnpi_ctx* c, size_t* ppeak, size_t* tpeak) {
+  DryScope dry(c);
+  auto fresh = [c]() { c->persist = Bump(); c->temp = Bump(); };
+  auto keep = [&]() { *ppeak = std::max(*ppeak, c->persist.peak); *tpeak = std::max(*tpeak, c->temp.peak); };
+  *ppeak = *tpeak = 0;
+  if (c->max_rows > 0) {
+    fresh();
+    UNetCall k; k.rows = c->max_rows;
+    CKP(unet_fwd(c, k));
+    keep();
+  }
+  if (!c->clip.layers.empty()) {
+    fresh();
+    CKP(clip_fwd(c, nullptr, c->rows_ident_n, nullptr));
+    keep();
+  }
+  if (c->max_vae > 0) {
+    const int S = c->cfg.sample_size, F = 1 << (c->cfg.vae_n_blocks - 1);
+    fresh();
+    (void)palloc(c, (size_t)c->max_vae * S * F * S * F * 8);
+    CKP(vae_encode_fwd(c, nullptr, c->max_vae, S * F, S * F, nullptr));
+    keep();
+    fresh();
+    (void)palloc(c, (size_t)c->max_vae * S * S * 8);
+    (void)c->persist.alloc((size_t)c->max_vae * 3 * S * F * S * F * sizeof(float));
+    CKP(vae_decode_fwd(c, nullptr, c->max_vae, S, S, nullptr));
+    keep();
+  }
+  return 0;
+}
 static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device, void* hip_stream, int max_unet_rows, int max_vae_images, pnpi_ctx* parent) {
   pnpi_ctx* c = new pnpi_ctx();
   *out = c;
   c->cfg = *cfg; c->device = device; c->st = (hipStream_t)hip_stream; c->max_rows = max_unet_rows; c->max_vae = max_vae_images;
-  c->dry = true; c->sched_set = false; c->final_alpha = 0.f;
+  c->sched_set = false; c->final_alpha = 0.f;
   c->splitk_ws = nullptr; c->gn_partial = nullptr; c->temb_table = nullptr;
   memset(&c->ctr, 0, sizeof(c->ctr));
   CKP(validate_config(c));
@@ -167,7 +198,6 @@ static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device,
   CKH(hipMalloc((void**)&c->temb_row, C0 * sizeof(float)));
   CKH(hipMalloc((void**)&c->temb_emb, TE * sizeof(float)));
   CKH(hipMalloc((void**)&c->bias_scratch, (size_t)c->unet.temb_total * sizeof(float)));
-  c->bias_eff = c->bias_scratch;
   if (max_unet_rows > 0) {
     // per-timestep (conv1 bias + time embedding) table: [n_train][temb_total] fp32 (81 MB for SD-1.x), rows filled on first use
     CKH(hipMalloc((void**)&c->bias_tab, (size_t)g.n_train_timesteps * c->unet.temb_total * sizeof(float)));
@@ -206,43 +236,12 @@ static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device,
     CKH(hipMalloc((void**)&c->rows_ident, idt.size() * sizeof(int)));
     CKH(hipMemcpy(c->rows_ident, idt.data(), idt.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  // dry runs to size the activation workspaces
-  c->dry = true;
-  c->persist = Bump(); c->temp = Bump();
-  size_t ppeak = 0, tpeak = 0;
-  if (max_unet_rows > 0) {
-    int r = unet_fwd(c, nullptr, max_unet_rows, 0, nullptr, false, 0, nullptr);
-    if (r) return r;
-    ppeak = c->persist.peak; tpeak = c->temp.peak;
-  }
-  if (!c->clip.layers.empty()) {
-    c->persist.reset(); c->temp.reset(); c->persist.peak = 0; c->temp.peak = 0;
-    int r = clip_fwd(c, nullptr, c->rows_ident_n, nullptr);
-    if (r) return r;
-    if (c->persist.peak > ppeak) ppeak = c->persist.peak;
-    if (c->temp.peak > tpeak) tpeak = c->temp.peak;
-  }
-  if (max_vae_images > 0) {
-    const int S = g.sample_size, F = 1 << (g.vae_n_blocks - 1);
-    c->persist.reset(); c->temp.reset(); c->persist.peak = 0; c->temp.peak = 0;
-    (void)palloc(c, (size_t)max_vae_images * S * F * S * F * 8);
-    int r = vae_encode_fwd(c, nullptr, max_vae_images, S * F, S * F, nullptr);
-    if (r) return r;
-    if (c->persist.peak > ppeak) ppeak = c->persist.peak;
-    if (c->temp.peak > tpeak) tpeak = c->temp.peak;
-    c->persist.reset(); c->temp.reset(); c->persist.peak = 0; c->temp.peak = 0;
-    (void)palloc(c, (size_t)max_vae_images * S * S * 8);
-    (void)c->persist.alloc((size_t)max_vae_images * 3 * S * F * S * F * sizeof(float));
-    r = vae_decode_fwd(c, nullptr, max_vae_images, S, S, nullptr);
-    if (r) return r;
-    if (c->persist.peak > ppeak) ppeak = c->persist.peak;
-    if (c->temp.peak > tpeak) tpeak = c->temp.peak;
-  }
+  size_t ppeak, tpeak;
+  CKP(size_workspaces(c, &ppeak, &tpeak));
   ppeak = align_up(ppeak + (1 << 20), 4096); tpeak = align_up(tpeak + (1 << 20), 4096);
   CKH(hipMalloc((void**)&c->persist.base, ppeak));
   CKH(hipMalloc((void**)&c->temp.base, tpeak));
   c->persist.cap = ppeak; c->temp.cap = tpeak; c->persist.reset(); c->temp.reset();
-  c->dry = false;
   memset(&c->ctr, 0, sizeof(c->ctr));
   // identity attention-row table for the controller-free path
   CKP(setup_ctrl(c, nullptr, 0, max_unet_rows > 0 ? max_unet_rows : 1));
@@ -271,7 +270,7 @@ void pnpi_destroy(pnpi_ctx* c) {
 
 static void invalidate_derived(pnpi_ctx* c) {     // caches of functions of the weights
   std::fill(c->bias_valid.begin(), c->bias_valid.end(), 0);
-  c->tkv.rows = 0; c->tkv.use = false;
+  c->tkv.rows = 0;
   if (c->tape) { for (auto& kv : c->tape->wd) (void)hipFree(kv.second); c->tape->wd.clear(); }     // dgrad repacks of the old weights
 }
 
@@ -475,23 +474,26 @@ int pnpi_text_kv_precompute(pnpi_ctx* c, const float* context, int rows) {
   return text_kv_precompute(c, context, rows);
 }
 
+// the level-1 forwards' call: context == NULL reads the text K/V cache, which must hold this row count
+static int level1_call(pnpi_ctx* c, const float* latents, int rows, const float* context, float* eps_out, UNetCall& k) {
+  if (!context && c->tkv.rows != rows) return fail(c, PNPI_ESTATE, "context is NULL: call pnpi_text_kv_precompute for this row count first");
+  k.latents = latents; k.rows = rows; k.context = context; k.cached_kv = context == nullptr; k.eps_out = eps_out;
+  return 0;
+}
 int pnpi_unet_forward(pnpi_ctx* c, const float* latents, int rows, int rows_per_image, int t, const float* context,
                       const pnpi_ctrl_desc* ctrl_host, int cur_step, float* eps_out) {
   if (!c || !latents || !eps_out) return PNPI_EINVAL;
   CKP(check_ready(c));
-  if (!context && c->tkv.rows != rows) return fail(c, PNPI_ESTATE, "context is NULL: call pnpi_text_kv_precompute for this row count first");
+  UNetCall k; CKP(level1_call(c, latents, rows, context, eps_out, k));
   if (c->attn_cb && (!context || ctrl_host)) return fail(c, PNPI_EINVAL, "attention callback: pass the context, and no controller descriptor");
-  struct UseKV { pnpi_ctx* c; ~UseKV() { c->tkv.use = false; } } guard{c};
-  c->tkv.use = context == nullptr;
-  bool use_ctrl = false;
   if (ctrl_host) {
     if (rows_per_image != 4 || rows % 4) return fail(c, PNPI_EINVAL, "controllers need rows_per_image == 4");
     if (cur_step == 0 || c->cd.nimg != rows / 4) CKP(setup_ctrl(c, ctrl_host, rows / 4, rows));
-    use_ctrl = true;
   } else if (c->cd.any_edit || c->cd.nimg != 0) {
     CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
   }
-  return unet_fwd(c, latents, rows, t, context, use_ctrl, cur_step, eps_out);
+  k.t = t; k.use_ctrl = ctrl_host != nullptr; k.cur_step = cur_step;
+  return unet_fwd(c, k);
 }
 
 /* LocalBlend step_callback for level-1 drivers (attention_control.py:253-256): latents [nimg][2][4][h][w] in place */

@@ -246,7 +246,6 @@ static int raw_conv(pnpi_ctx* c, const half_t* x, int Cx, int B, int H, int W, i
 // (the one conv whose forward output is not an fp16 tensor).  Returns with T.d_ctx = d loss / d context (fp32, scaled like d_out).
 static int tape_backward(pnpi_ctx* c, const half_t* d_out) {
   Tape& T = *c->tape;
-  T.rec = false;
   const pnpi_model_config& g = c->cfg;
   for (size_t oi = T.ops.size(); oi-- > 0;) {
     const TapeOp& o = T.ops[oi];

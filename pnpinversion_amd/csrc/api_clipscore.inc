@@ -301,11 +301,9 @@ int pnpi_clipv_attach(pnpi_ctx* c, const pnpi_clipv_config* g, int max_images) {
   // workspaces: a dry run of the forward at max_images sizes them (no launch, counters untouched)
   {
     const pnpi_counters saved = c->ctr;
-    const bool was_dry = c->dry;
-    c->dry = true;
     v->persist = Bump(); v->temp = Bump();
-    const int r = clipv_fwd(c, nullptr, nullptr, max_images, g->image_size, v->emb_img16);
-    c->dry = was_dry; c->ctr = saved;
+    const int r = [&]() { DryScope dry(c); return clipv_fwd(c, nullptr, nullptr, max_images, g->image_size, v->emb_img16); }();
+    c->ctr = saved;
     if (r) { const std::string e = c->err; clipv_free(c); c->err = e; return r; }
     const size_t pb = align_up(v->persist.peak + (1 << 20), 4096), tb = align_up(v->temp.peak + (1 << 20), 4096);
     v->persist = Bump(); v->temp = Bump();

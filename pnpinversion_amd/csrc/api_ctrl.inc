@@ -18,14 +18,15 @@ static size_t text_kv_bytes(pnpi_ctx* c, int rows) {
   return total + 4096;
 }
 // K = context W_k^T, V^T = (context W_v^T)^T for the 16 cross-attention layers, `rows` context rows (fp32 [rows][T][X] on the device)
-static int text_kv_precompute(pnpi_ctx* c, const float* context, int rows) {
+// share: of the forwards that will read the cache -- pinned, the projections of the compact context rows are configured as at the logical rows
+static int text_kv_precompute(pnpi_ctx* c, const float* context, int rows, const UNetShare& share = UNetShare()) {
   const pnpi_model_config& g = c->cfg;
   TextKV& kv = c->tkv;
-  kv.rows = 0; kv.use = false;
+  kv.rows = 0;
   if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "text K/V precompute: rows out of range (max_unet_rows)");
   if (text_kv_bytes(c, rows) > kv.cap) return fail(c, PNPI_ENOMEM, "text K/V cache arena too small");
   const int T = g.ctx_len, X = g.cross_dim, ldv = round_up_i(T, 8);
-  pin_base(c);      // pinned row sharing: the projections of the compact context rows are configured as at the logical row count
+  UNetFlight fw(share); FlightScope pinned(c, &fw);
   c->persist.reset(); c->temp.reset();
   half_t* ctx16 = palloc(c, (size_t)rows * T * X);
   CK(launch_f32_to_f16(context, (size_t)rows * T * X, ctx16, c->st));

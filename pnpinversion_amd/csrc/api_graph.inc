@@ -29,11 +29,42 @@ struct UNetDedup { const float* lat_u; int U; const int* hmap; const int* dmap; 
 // Default 1: the source rows of the three passes are one launch row, so they see the same arithmetic whatever tile is chosen, and the
 // 8-row launch takes the table's 8-row entries (text K/V projections included: they are planned at their launched M like every GEMM).
 // A context that holds a tape keeps the full launch, configured as the compact one (pnpi_direct_edit), so it gives the same bits.
-// the GEMM pin outside the deduplicated prefix: none, or (pinned row sharing) compact rows -> logical rows
-static inline void pin_base(pnpi_ctx* c) {
-  const bool on = c->share_pin && c->share_U > 0;
-  c->pin_from = on ? c->share_from : 0; c->pin_to = on ? c->share_to : 0;
-}
+// U > 0: the launch of `from` rows serves `to` logical rows resting on U logical latents.  pin (= 2): every GEMM of the forward is
+// configured as at `to` rows (the prefix of "cfg_dedup" as at to / U rows), so each launch makes the choices of the full-row loop
+// (from > to: the full launch of a tape-holding context under "src_share" = 1, configured as the compact launch it replaces)
+struct UNetShare { int from = 0, to = 0, U = 0; bool pin = false; };
+// What a caller asks of ONE UNet forward (unet_fwd); nothing of it outlives the call.
+struct UNetCall {
+  const float* latents = nullptr;      // fp32 [rows][in_channels][S][S]
+  int rows = 0, t = 0, cur_step = 0;
+  const float* context = nullptr;      // fp32 [rows][ctx_len][cross_dim]; not read with cached_kv
+  bool use_ctrl = false;               // the controller tables of setup_ctrl act, at step cur_step
+  float* eps_out = nullptr;            // fp32 [rows][out_channels][S][S]
+  const UNetDedup* dedup = nullptr;    // the distinct latents behind the rows (the CFG loops); NULL = every row on its own
+  // temb_row (device [C0]): the sinusoid row of this forward, given by the caller (a fractional timestep); t is then not read, the three
+  // GEMVs run into bias_row (device [temb_total], NULL: the context's scratch row) and the per-timestep cache is neither read nor filled
+  const float* temb_row = nullptr; float* bias_row = nullptr;
+  bool cached_kv = false;              // read the text K / V of text_kv_precompute instead of projecting the context
+  bool record = false;                 // push every op on the context's tape and keep every activation (never with cached_kv)
+  const PnpState* pnp = nullptr;       // Plug-and-Play injection; NULL = none
+  UNetShare share;
+};
+// What the graph mutates while one forward runs: on unet_fwd's stack, reached by the op wrappers through pnpi_ctx::fw.  With fw == nullptr
+// (VAE, CLIP towers) no GEMM is pinned and nothing is recorded.
+struct UNetFlight {
+  int tf_index = 0, up_res_index = 0;  // transformer block counter (MasaCtrl start_layer, the K / V cache), decoder ResNet counter (Plug-and-Play)
+  // a GEMM over pin_from rows takes the tile / split-K its pin_to-row form gets: in the deduplicated prefix ("cfg_dedup" = 2), or throughout
+  int pin_from = 0, pin_to = 0;
+  const float* bias_eff = nullptr;     // [temb_total] conv1 bias + time embedding of this forward (points into bias_tab once cached)
+  bool cached_kv = false, record = false;
+  PnpState pnp;                        // off without UNetCall::pnp
+  UNetShare share;
+  explicit UNetFlight(const UNetShare& s) : share(s) { pin_base(); }
+  // the GEMM pin outside the deduplicated prefix: none, or (pinned row sharing) compact rows -> logical rows
+  void pin_base() { const bool on = share.pin && share.U > 0; pin_from = on ? share.from : 0; pin_to = on ? share.to : 0; }
+};
+struct FlightScope { pnpi_ctx* c; FlightScope(pnpi_ctx* c_, UNetFlight* f) : c(c_) { c->fw = f; } ~FlightScope() { c->fw = nullptr; } };
+struct DryScope { pnpi_ctx* c; bool prev; explicit DryScope(pnpi_ctx* c_) : c(c_), prev(c_->dry) { c->dry = true; } ~DryScope() { c->dry = prev; } };      // a sizing run
 struct TfDedup { int U; const int* dmap; };     // transformer_fwd: x holds U rows, the block's first half runs on them
 #define PROF(cls, flops, bytes, expr) PROFD(cls, flops, bytes, 0, 0, 0, expr)
 #define PROFD(cls, flops, bytes, d0, d1, d2, expr)            \
@@ -75,7 +106,6 @@ struct TapeOp {
 };
 struct Tape {
   std::vector<TapeOp> ops;
-  bool rec = false;                                   // recording (forward in flight)
   const half_t* no_grad_input = nullptr;              // the network input: its consumers' dgrad is skipped
   const half_t* ctx16 = nullptr;                      // the text context of this forward: gradients into it are summed in fp32
   Bump garena;                                        // gradient buffers + scratch of one backward
@@ -84,9 +114,9 @@ struct Tape {
   float* d_ctx = nullptr;                             // [rows * ctx_len * cross_dim] fp32
   void* attn_scratch = nullptr; size_t attn_scratch_bytes = 0;
 };
-static inline bool taping(pnpi_ctx* c) { return c->tape && c->tape->rec && !c->dry; }
 // a recording forward (or the dry run that sizes the arenas for one) keeps every activation and takes the plain-layout transformer block
-static inline bool keep_acts(pnpi_ctx* c) { return c->tape && c->tape->rec; }
+static inline bool keep_acts(pnpi_ctx* c) { return c->fw && c->fw->record; }
+static inline bool taping(pnpi_ctx* c) { return keep_acts(c) && !c->dry; }
 
 // ---------------------------------------------------------------------------------------------------- op wrappers
 // Per-channel GroupNorm partial sums attached to an activation by the GEMM that produced it ([tiles][C][2], `rows` per tile).
@@ -130,7 +160,8 @@ static int igemm_prof(pnpi_ctx* c, const GemmP& p, double alg_flops, Stats* so =
   // count (M = pin_from rows x tokens), so M / pin_from * pin_to is exactly the M of the same layer in the full-row launch.  A GEMM
   // whose M is no multiple of pin_from is not row-proportional (the one-row time-embedding products): it has the same M in the
   // full-row launch and stays unpinned (sel_M = 0), as there.
-  const int sel_M = (c->pin_to > 0 && p.M % c->pin_from == 0) ? (int)((long)p.M / c->pin_from * c->pin_to) : 0;
+  const UNetFlight* f = c->fw;
+  const int sel_M = (f && f->pin_to > 0 && p.M % f->pin_from == 0) ? (int)((long)p.M / f->pin_from * f->pin_to) : 0;
   if (c->prof_on) {
     ProfRec pr; prof_open(c, pr);
     int used = 0;
@@ -199,7 +230,7 @@ static int resnet_main(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, 
   half_t* t1 = talloc(c, M * r.cin);
   CK(op_gn(c, x1, x2, C1, C2, B, HW, r.n1, G, eps, 1, t1, s1, s2));
   half_t* t2 = talloc(c, M * r.cout);
-  const float* b1 = r.temb_off >= 0 ? c->bias_eff + r.temb_off : r.c1.b;
+  const float* b1 = r.temb_off >= 0 ? c->fw->bias_eff + r.temb_off : r.c1.b;
   Stats st2;
   CK(op_conv(c, t1, r.cin, nullptr, 0, B, H, W, r.c1, 1, 1, 0, b1, nullptr, t2, H, W, -1, nullptr, &st2));
   *t3 = talloc(c, M * r.cout);
@@ -232,7 +263,7 @@ static int resnet_fwd(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, c
 // epilogue has one).  The block's output carries no GroupNorm partial sums: its consumer recomputes the statistics.
 static int resnet_fwd_pnp(pnpi_ctx* c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, int B, int H, int W, int G,
                           float eps, half_t* out, Stats s1, Stats s2) {
-  const PnpState& ps = c->pnp;
+  const PnpState& ps = c->fw->pnp;
   const int HW = H * W, n = ps.nimg;
   if (B != 3 * n || !x2) return fail(c, PNPI_ESTATE, "Plug-and-Play conv injection: a decoder ResNet of a [img][3]-row launch expected");
   if (((size_t)HW * C1) % 8 || ((size_t)HW * C2) % 8 || ((size_t)HW * r.cout) % 8)
@@ -340,10 +371,11 @@ static SelfAttn self_attn_resolve(pnpi_ctx* c, bool use_ctrl, int cur_step, int 
   const bool redirects = s.table != ST_IDENTITY;
   if (dedup && (redirects || c->attn_cb)) return refuse(PNPI_ESTATE, "cfg_dedup: this block's self-attention redirects rows");
   // Plug-and-Play q/k injection (run_editing_pnp.py:190-201): {r, src, src, r} for the rows of every image, at every token count
-  if (c->pnp.on && c->pnp.qk && block_index < 32 && ((c->pnp.qk_mask >> block_index) & 1u)) {
-    if (dedup || c->attn_cb || redirects || B != 3 * c->pnp.nimg)
+  const PnpState& ps = c->fw->pnp;
+  if (ps.on && ps.qk && block_index < 32 && ((ps.qk_mask >> block_index) & 1u)) {
+    if (dedup || c->attn_cb || redirects || B != 3 * ps.nimg)
       return refuse(PNPI_ESTATE, "Plug-and-Play q/k injection does not combine with cfg_dedup, a host callback or a controller");
-    s.table = ST_PNP; s.rows = c->pnp.rows;
+    s.table = ST_PNP; s.rows = ps.rows;
   }
   if (c->attn_cb) s.form = SA_CALLBACK;       // rows are not redirected there: the callback does the editing
   else if (s.table == ST_MASA && cd.masa_masked && !c->dry) {
@@ -437,7 +469,7 @@ static int tf_cross_attn(pnpi_ctx* c, TfBlock& s, const half_t* ctx16, const hal
   half_t* q2 = talloc(c, (size_t)M * hd);
   CK(op_gemm(c, n2, C, M, C, t.w_q2, C, hd, nullptr, nullptr, 0, q2, hd, 1.f, nullptr, 2.0 * M * (double)C * C));
   if (const TfDedup* dd = s.dd) {      // from here on every row has its own text: the three tensors the second half reads, at the rows of the launch
-    pin_base(c);
+    c->fw->pin_base();
     B = s.B = s.Bf; M = s.M = s.Mf;
     half_t *hs1f = talloc(c, (size_t)M * C), *q2f = talloc(c, (size_t)M * hd), *xf = talloc(c, (size_t)M * C);
     CK(launch_gather_rows_f16(hs1, dd->dmap, B, (size_t)N * C, hs1f, c->st));
@@ -448,7 +480,7 @@ static int tf_cross_attn(pnpi_ctx* c, TfBlock& s, const half_t* ctx16, const hal
   const int ldv2 = round_up_i(T, 8);
   const int ldk2 = (s.rec ? 2 : 1) * hd;      // k, and recording | v
   half_t *k2, *vt2;
-  if (c->tkv.use) {     // projected once per loop by text_kv_precompute (never while recording)
+  if (c->fw->cached_kv) {     // projected once per loop by text_kv_precompute (never while recording)
     k2 = c->tkv.k[s.block_index]; vt2 = c->tkv.vt[s.block_index];
   } else {
     k2 = talloc(c, (size_t)B * T * ldk2);
@@ -527,7 +559,7 @@ static int transformer_fwd(pnpi_ctx* c, const TransformerW& t, const half_t* x, 
                            bool use_ctrl, int cur_step, half_t* out, Stats sx, Stats* so, const TfDedup* dd = nullptr) {
   const size_t mk = c->temp.mark();
   const int N = H * W, hd = t.heads * t.Dp, U = dd ? dd->U : B;
-  TfBlock s{t, H, W, N, t.C, hd, c->tf_index++, 1.0f / sqrtf((float)t.dh), U, U * N, B, B * N, dd, keep_acts(c), use_ctrl, cur_step};
+  TfBlock s{t, H, W, N, t.C, hd, c->fw->tf_index++, 1.0f / sqrtf((float)t.dh), U, U * N, B, B * N, dd, keep_acts(c), use_ctrl, cur_step};
   if (dd && ((N * s.C) % 8 || (N * hd) % 8)) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
   // the sizing dry run takes the plain path and adds the three expanded tensors of the deduplicated one on top of it
   if (c->dry && s.block_index == 0 && !s.rec) { (void)talloc(c, (size_t)s.M * s.C); (void)talloc(c, (size_t)s.M * s.C); (void)talloc(c, (size_t)s.M * hd); }
@@ -570,21 +602,22 @@ static int unet_dedup_prefix(pnpi_ctx* c, const UNetDedup& ud, int B, const half
   CK(launch_nchw_f32_to_nhwc_f16(ud.lat_u, U, g.in_channels, H * H, 8, x0c, c->st));
   // pinned row sharing: the compact prefix makes the choices of the logical launch's prefix (all rows under cfg_dedup = 2, its
   // distinct latents under 1)
-  if (c->share_pin && c->share_U > 0) { c->pin_from = U; c->pin_to = g_cfg_dedup == 2 ? c->share_to : c->share_U; }
-  else if (g_cfg_dedup == 2) { c->pin_from = U; c->pin_to = B; }
+  UNetFlight& f = *c->fw;
+  if (f.share.pin && f.share.U > 0) { f.pin_from = U; f.pin_to = g_cfg_dedup == 2 ? f.share.to : f.share.U; }
+  else if (g_cfg_dedup == 2) { f.pin_from = U; f.pin_to = B; }
   half_t* hc = palloc(c, (size_t)U * H * H * C0);
   Stats hcs, rcs;
   CK(op_conv(c, x0c, 8, nullptr, 0, U, H, H, u.conv_in, 1, 1, 0, u.conv_in.b, nullptr, hc, H, H, -1, nullptr, &hcs));
   half_t* rc = palloc(c, (size_t)U * H * H * oc);
   CKP(resnet_fwd(c, u.down_res[0][0], hc, C0, nullptr, 0, U, H, H, g.norm_groups, 1e-5f, rc, hcs, Stats(), &rcs));
   half_t* o2 = palloc(c, (size_t)B * H * H * oc);
-  if (self_attn_resolve(c, use_ctrl, cur_step, c->tf_index, H, H, U, false).table == ST_IDENTITY) {
+  if (self_attn_resolve(c, use_ctrl, cur_step, f.tf_index, H, H, U, false).table == ST_IDENTITY) {
     const TfDedup td{U, ud.dmap};
     CKP(transformer_fwd(c, u.down_attn[0][0], rc, B, H, H, ctx16, use_ctrl, cur_step, o2, rcs, hs, &td));   // unpins after its first half
   } else {
     // the self-attention redirects rows at this step: the prefix ends behind the ResNet, whose output and per-image GroupNorm
     // partial sums are expanded to the rows of the launch
-    pin_base(c);
+    f.pin_base();
     if (((size_t)H * H * oc) % 8) return fail(c, PNPI_ESHAPE, "cfg_dedup: row size is no multiple of 8 halfs");
     half_t* o = palloc(c, (size_t)B * H * H * oc);
     CK(launch_gather_rows_f16(rc, ud.dmap, B, (size_t)H * H * oc, o, c->st));
@@ -596,55 +629,57 @@ static int unet_dedup_prefix(pnpi_ctx* c, const UNetDedup& ud, int B, const half
     }
     CKP(transformer_fwd(c, u.down_attn[0][0], o, B, H, H, ctx16, use_ctrl, cur_step, o2, os, hs));
   }
-  pin_base(c);
-  c->ctr.unet_dedup_prefix_rows += c->share_U > U ? c->share_U : U;      // under row sharing: the logical latents served (a mirrored full launch runs them all)
+  f.pin_base();
+  c->ctr.unet_dedup_prefix_rows += f.share.U > U ? f.share.U : U;      // under row sharing: the logical latents served (a mirrored full launch runs them all)
   *h = o2;
   return 0;
 }
 
-// UNet2DConditionModel.forward (my_diffusers/models/unet_2d_condition.py:189-273)
-// ud (nullable): the distinct latents behind the rows and the row -> latent map (the CFG loops); NULL = every row on its own
-// temb_row (nullable, device [C0]): the sinusoid row of this forward, given by the caller (a fractional timestep); t is then not read, the
-// three GEMVs run into bias_row (device [temb_total], NULL: the context's scratch row) and the per-timestep cache is neither read nor filled
-static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const float* context, bool use_ctrl, int cur_step,
-                    float* eps_out, const UNetDedup* ud = nullptr, const float* temb_row = nullptr, float* bias_row = nullptr) {
+// UNet2DConditionModel.forward (my_diffusers/models/unet_2d_condition.py:189-273): the one forward `k` describes
+static int unet_fwd(pnpi_ctx* c, const UNetCall& k) {
   const pnpi_model_config& g = c->cfg;
   const UNetW& u = c->unet;
-  pin_base(c);
+  const int rows = k.rows, t = k.t, cur_step = k.cur_step;
+  const bool use_ctrl = k.use_ctrl; const UNetDedup* ud = k.dedup;
   if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "unet rows out of range (max_unet_rows)");
-  if (!temb_row && (t < 0 || t >= g.n_train_timesteps)) return fail(c, PNPI_EINVAL, "timestep out of range");
+  if (!k.temb_row && (t < 0 || t >= g.n_train_timesteps)) return fail(c, PNPI_EINVAL, "timestep out of range");
+  if (k.record && (!c->tape || k.cached_kv)) return fail(c, PNPI_ESTATE, "a recording forward needs the context's tape and projects its own text K/V");
+  UNetFlight fw(k.share);
+  fw.cached_kv = k.cached_kv; fw.record = k.record; fw.bias_eff = c->bias_scratch;
+  if (k.pnp) fw.pnp = *k.pnp;
+  const PnpState& pnp = fw.pnp;
+  FlightScope in_flight(c, &fw);      // the only place a forward's state is attached to the context, and where it ends
   c->persist.reset(); c->temp.reset();
-  c->tf_index = 0;
   const int S = g.sample_size, n = g.n_blocks, C0 = g.block_out_channels[0], G = g.norm_groups;
   const int B = rows;
   const float eps = 1e-5f;
   half_t* x0 = palloc(c, (size_t)B * S * S * 8);
   half_t* ctx16 = nullptr;
-  if (c->tkv.use && !c->dry) {
+  if (fw.cached_kv && !c->dry) {
     if (c->tkv.rows != B) return fail(c, PNPI_ESTATE, "text K/V cache holds a different row count than this forward");
   } else {
     ctx16 = palloc(c, (size_t)B * g.ctx_len * g.cross_dim);
   }
   if (taping(c)) { c->tape->no_grad_input = x0; c->tape->ctx16 = ctx16; }
   if (!c->dry) {
-    CK(launch_nchw_f32_to_nhwc_f16(latents, B, g.in_channels, S * S, 8, x0, c->st));
+    CK(launch_nchw_f32_to_nhwc_f16(k.latents, B, g.in_channels, S * S, 8, x0, c->st));
     if (ctx16) {
-      if (!context) return fail(c, PNPI_EINVAL, "context is NULL and no text K/V cache is active");
-      CK(launch_f32_to_f16(context, (size_t)B * g.ctx_len * g.cross_dim, ctx16, c->st));
+      if (!k.context) return fail(c, PNPI_EINVAL, "context is NULL and no text K/V cache is active");
+      CK(launch_f32_to_f16(k.context, (size_t)B * g.ctx_len * g.cross_dim, ctx16, c->st));
     }
     // conv1 bias + time embedding of every ResNet for this timestep: a function of t and the weights only -> computed on the first
     // forward at t, then read from the table (not for a caller's row)
-    const bool cached = !temb_row && c->bias_tab && g_temb_cache;
-    c->bias_eff = cached ? c->bias_tab + (size_t)t * u.temb_total : (temb_row && bias_row) ? bias_row : c->bias_scratch;
-    if (!cached || !c->bias_valid[t]) CKP(temb_bias_row(c, temb_row ? temb_row : c->temb_table + (size_t)t * C0, c->bias_eff));
+    const bool cached = !k.temb_row && c->bias_tab && g_temb_cache;
+    float* row = cached ? c->bias_tab + (size_t)t * u.temb_total : (k.temb_row && k.bias_row) ? k.bias_row : c->bias_scratch;
+    if (!cached || !c->bias_valid[t]) CKP(temb_bias_row(c, k.temb_row ? k.temb_row : c->temb_table + (size_t)t * C0, row));
     if (cached) c->bias_valid[t] = 1;
+    fw.bias_eff = row;
   }
   // unet_dedup_prefix: no recording forward (the tape walks full-row records), host callback or sizing dry run (which sizes for both paths)
-  bool dedup = ud && g_cfg_dedup && !c->dry && ud->U > 0 && ud->U < rows && g.block_has_attn[0] && !keep_acts(c) && !c->attn_cb &&
-               ud->lat_u && ud->hmap && ud->dmap && !c->pnp.on;      // the Plug-and-Play layout [source, x, x] redirects rows: never deduplicated
-  if (c->pnp.on && (c->share_U > 0 || keep_acts(c) || c->attn_cb || use_ctrl || rows != 3 * c->pnp.nimg))
+  bool dedup = ud && g_cfg_dedup && !c->dry && ud->U > 0 && ud->U < rows && g.block_has_attn[0] && !fw.record && !c->attn_cb &&
+               ud->lat_u && ud->hmap && ud->dmap && !pnp.on;      // the Plug-and-Play layout [source, x, x] redirects rows: never deduplicated
+  if (pnp.on && (fw.share.U > 0 || fw.record || c->attn_cb || use_ctrl || rows != 3 * pnp.nimg))
     return fail(c, PNPI_ESTATE, "Plug-and-Play forward: three rows per image, no src_share, tape, host callback or controller");
-  c->pnp.up_res_index = 0;
   for (int r = 0; dedup && r < rows; ++r) dedup = ud->hmap[r] >= 0 && ud->hmap[r] < ud->U;
   struct Act { half_t* p; int C, H; Stats s; };
   std::vector<Act> skips;
@@ -695,11 +730,11 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
     for (int j = 0; j <= g.layers_per_block; ++j) {
       Act s = skips.back(); skips.pop_back();
       half_t* o = palloc(c, (size_t)B * H * H * oc);
-      if (c->pnp.on && c->pnp.conv && c->pnp.up_res_index == c->pnp.conv_site) {      // leaves no GroupNorm partial sums
+      if (pnp.on && pnp.conv && fw.up_res_index == pnp.conv_site) {      // leaves no GroupNorm partial sums
         CKP(resnet_fwd_pnp(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s));
         hs_ = Stats();
       } else CKP(resnet_fwd(c, u.up_res[i][j], h, ch, s.p, s.C, B, H, H, G, eps, o, hs_, s.s, &hs_));
-      c->pnp.up_res_index++;
+      fw.up_res_index++;
       h = o; ch = oc;
       if (g.block_has_attn[n - 1 - i]) CKP(unet_transformer(c, u.up_attn[i][j], &h, B, H, oc, ctx16, use_ctrl, cur_step, &hs_));
     }
@@ -713,12 +748,12 @@ static int unet_fwd(pnpi_ctx* c, const float* latents, int rows, int t, const fl
   half_t* gno = palloc(c, (size_t)B * H * H * ch);
   CK(op_gn(c, h, nullptr, ch, 0, B, H * H, u.norm_out, G, eps, 1, gno, hs_));
   {
-    VtOut v; v.outT = eps_out; v.col0 = 0; v.ld = H * H; v.f32 = 1; v.rpb = H * H;
+    VtOut v; v.outT = k.eps_out; v.col0 = 0; v.ld = H * H; v.f32 = 1; v.rpb = H * H;
     CK(op_conv(c, gno, ch, nullptr, 0, B, H, H, u.conv_out, 1, 1, 0, u.conv_out.b, nullptr, nullptr, H, H, -1, &v));
   }
   c->ctr.unet_calls += c->dry ? 0 : 1;
   c->ctr.unet_sample_forwards += c->dry ? 0 : rows;
-  c->ctr.unet_sample_forwards_cached_kv += (c->dry || !c->tkv.use) ? 0 : rows;
+  c->ctr.unet_sample_forwards_cached_kv += (c->dry || !fw.cached_kv) ? 0 : rows;
   if (c->persist.overflow || c->temp.overflow) return fail(c, PNPI_ENOMEM, "workspace overflow");
   return 0;
 }

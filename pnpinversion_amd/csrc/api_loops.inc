@@ -5,19 +5,15 @@
 // The loops' text context is constant over their steps: project K / V once, then every forward of the loop reads the cache.
 struct LoopKV {
   pnpi_ctx* c;
-  bool armed = false;
+  bool armed = false;      // the loop's forwards read the cache (loop_unet: UNetCall::cached_kv)
   explicit LoopKV(pnpi_ctx* c_) : c(c_) {}
-  int begin(const float* context, int rows) {
-    if (!g_text_kv) return 0;
-    int r = text_kv_precompute(c, context, rows);
-    if (r) return r;
-    c->tkv.use = true;
-    armed = true;
+  int begin(const float* context, int rows, const UNetShare& share = UNetShare()) {
+    if (g_text_kv) { CKP(text_kv_precompute(c, context, rows, share)); armed = true; }
     return 0;
   }
   // a loop's projections belong to the loop's context: dropped at its end, so that a later pnpi_unet_forward(context = NULL) can
   // never silently read them (it fails and names pnpi_text_kv_precompute instead)
-  ~LoopKV() { if (armed) { c->tkv.use = false; c->tkv.rows = 0; } }
+  ~LoopKV() { if (armed) c->tkv.rows = 0; }
 };
 // What every loop sets up before its first step.  Scratch lives at the top of the controller arena (after the controller tables):
 //   loop_begin    entry checks, E / CE / ratio, the controller tables (setup_ctrl resets the arena)
@@ -33,12 +29,15 @@ struct Loop {
   const float* temb_rows = nullptr;            // [nsteps][C0] sinusoid rows of a loop at fractional timesteps (loop_unet: step's row) ...
   float* bias_row = nullptr;                   // ... and the loop-owned [temb_total] bias row its GEMVs write
   LoopKV kv;
+  UNetShare share; PnpState pnp;               // what loop_unet puts into every call: row sharing, the step's Plug-and-Play injection
   std::vector<int> maps;                       // host copy of all row maps, back to back
   std::vector<std::pair<int**, size_t>> map_dst;
   explicit Loop(pnpi_ctx* c_) : c(c_), kv(c_) {}
 };
-// the entry checks of loop_begin alone (a loop that builds its controller tables itself)
+// cds (nullable): controller descriptors of the nq (pseudo-)images of the launch, rows = rpi * nq (src_off, tgt_off, mask_nimg: setup_ctrl)
 // split_io: the loop keeps input rows (E) and prediction rows (E_out) apart; every other loop steps a latent by its own prediction
+struct LoopLayout { const pnpi_ctrl_desc* cds = nullptr; int nq = 0, rpi = 4, src_off = 2, tgt_off = 3, mask_nimg = 0; bool split_io = false; };
+// the entry checks of loop_begin alone (a loop that builds its controller tables itself)
 static int loop_entry(Loop& L, int nsteps, int rows, const char* too_many_rows, bool split_io = false) {
   pnpi_ctx* c = L.c;
   CKP(check_loop_ready(c));
@@ -50,12 +49,10 @@ static int loop_entry(Loop& L, int nsteps, int rows, const char* too_many_rows, 
   if (rows > c->max_rows) return fail(c, PNPI_EINVAL, too_many_rows);
   return 0;
 }
-// cds (nullable): controller descriptors of the nq (pseudo-)images of the launch, rows = rpi * nq
-static int loop_begin(Loop& L, int nsteps, int rows, const char* too_many_rows, const pnpi_ctrl_desc* cds = nullptr, int nq = 0, int rpi = 4,
-                      int src_off = 2, int tgt_off = 3, int mask_nimg = 0, bool split_io = false) {
+static int loop_begin(Loop& L, int nsteps, int rows, const char* too_many_rows, const LoopLayout& y = LoopLayout()) {
   pnpi_ctx* c = L.c;
-  CKP(loop_entry(L, nsteps, rows, too_many_rows, split_io));
-  return cds ? setup_ctrl(c, cds, nq, rows, rpi, src_off, tgt_off, mask_nimg) : setup_ctrl(c, nullptr, 0, c->max_rows);
+  CKP(loop_entry(L, nsteps, rows, too_many_rows, y.split_io));
+  return y.cds ? setup_ctrl(c, y.cds, y.nq, rows, y.rpi, y.src_off, y.tgt_off, y.mask_nimg) : setup_ctrl(c, nullptr, 0, c->max_rows);
 }
 static void loop_map(Loop& L, const std::vector<int>& m, int** dev) {      // *dev is valid after loop_commit
   L.map_dst.push_back({dev, L.maps.size()});
@@ -86,14 +83,18 @@ static int loop_commit(Loop& L, bool step_bufs = true) {
 // loop's committed maps) sends every row to its latent: unet_fwd gets both, and runs what depends on the latent alone once per latent
 static int loop_unet(Loop& L, const float* lat, const int* inmap, int t, const float* ctx, bool use_ctrl, int step) {
   pnpi_ctx* c = L.c;
-  const float* trow = L.temb_rows ? L.temb_rows + (size_t)step * c->cfg.block_out_channels[0] : nullptr;
-  if (!inmap) return unet_fwd(c, lat, L.rows, t, ctx, use_ctrl, step, L.eps, nullptr, trow, L.bias_row);
+  UNetCall k; k.latents = lat; k.rows = L.rows; k.t = t; k.context = ctx; k.use_ctrl = use_ctrl; k.cur_step = step; k.eps_out = L.eps;
+  k.cached_kv = L.kv.armed; k.share = L.share; k.pnp = L.pnp.on ? &L.pnp : nullptr;
+  if (L.temb_rows) { k.temb_row = L.temb_rows + (size_t)step * c->cfg.block_out_channels[0]; k.bias_row = L.bias_row; }
+  if (!inmap) return unet_fwd(c, k);
   CK(launch_gather_rows_f32(lat, inmap, L.rows, L.E, L.in, c->st));
+  k.latents = L.in;
   UNetDedup ud{lat, 0, nullptr, inmap};
   for (auto& m : L.map_dst)
     if (*m.first == inmap && m.second + (size_t)L.rows <= L.maps.size()) ud.hmap = L.maps.data() + m.second;
   for (int r = 0; ud.hmap && r < L.rows; ++r) ud.U = ud.hmap[r] + 1 > ud.U ? ud.hmap[r] + 1 : ud.U;
-  return unet_fwd(c, L.in, L.rows, t, ctx, use_ctrl, step, L.eps, ud.hmap ? &ud : nullptr, trow, L.bias_row);
+  if (ud.hmap) k.dedup = &ud;
+  return unet_fwd(c, k);
 }
 // dst rows [img][uncond, cond] (ctx_cond == NULL: [img][uncond])
 static int interleave_ctx(pnpi_ctx* c, float* dst, const float* ctx_uncond, const float* ctx_cond, int nimg, size_t CE) {
@@ -191,7 +192,8 @@ static int edit_loop_impl(pnpi_ctx* c, const float* x_T, int nimg, const float* 
   CKP(recon_check(c, recon));
   if (prox < 0 || prox > 2) return fail(c, PNPI_EINVAL, "prox must be 0 (none), 1 (l0) or 2 (l1)");
   Loop L(c);
-  CKP(loop_begin(L, nsteps, 4 * nimg, "nimg * 4 exceeds max_unet_rows", ctrl_host, nimg));
+  LoopLayout lay; lay.cds = ctrl_host; lay.nq = nimg;
+  CKP(loop_begin(L, nsteps, 4 * nimg, "nimg * 4 exceeds max_unet_rows", lay));
   const size_t E = L.E, CE = L.CE; const int rows = L.rows, S = c->cfg.sample_size;
   const bool use_ctrl = ctrl_host != nullptr;
   float* lat = misc_f(c, (size_t)nimg * 2 * E);
@@ -288,12 +290,6 @@ int pnpi_src_share_maps(int nimg, int npass, int* lsel, int* cmap, int* cctx, in
   if (compact_latents) *compact_latents = m.nlat;
   return 0;
 }
-// the context's row-sharing state lives for one pnpi_direct_edit call, whichever way that call returns
-struct ShareScope {
-  pnpi_ctx* c;
-  explicit ShareScope(pnpi_ctx* c_) : c(c_) {}
-  ~ShareScope() { c->share_from = c->share_to = c->share_U = 0; c->share_pin = false; pin_base(c); }
-};
 
 /* offset_calculate + npass guidance-forward passes of P2PEditor.edit_image_directinversion (p2p_editor.py:99-160) advanced in
  * lock step: every pass walks the same timesteps and pass p's step i needs only noise_loss[i], which the offset pass produces
@@ -320,7 +316,6 @@ int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* c
   // would be (the pin of 2, turned round), so a context gives the same bits with and without a tape -- as it does under 0 and 2
   const bool mirror = can_share && c->tape && g_src_share == 1;
   Loop L(c);
-  ShareScope scope(c);
   SrcShareMaps sm;
   const char* too_many = "(1 + npass) * nimg * 4 exceeds max_unet_rows";
   if (share) {
@@ -330,13 +325,11 @@ int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* c
     CKP(loop_entry(L, nsteps, rows, too_many));      // the logical rows are what max_unet_rows admits, whatever the knob says
     L.rows = sm.crows;
     CKP(setup_ctrl_rows(c, cds.data(), NI, sm.crows, rt.data(), nimg));
-    c->share_from = sm.crows; c->share_to = rows; c->share_U = 2 * NI; c->share_pin = share == 2;
+    L.share = UNetShare{sm.crows, rows, 2 * NI, share == 2};
   } else {
-    CKP(loop_begin(L, nsteps, rows, too_many, cds.data(), NI, 4, 2, 3, nimg));
-    if (mirror) {
-      src_share_maps(nimg, npass, sm);
-      c->share_from = rows; c->share_to = sm.crows; c->share_U = sm.nlat; c->share_pin = true;
-    }
+    LoopLayout lay; lay.cds = cds.data(); lay.nq = NI; lay.mask_nimg = nimg;
+    CKP(loop_begin(L, nsteps, rows, too_many, lay));
+    if (mirror) { src_share_maps(nimg, npass, sm); L.share = UNetShare{rows, sm.crows, sm.nlat, true}; }
   }
   const size_t E = L.E, CE = L.CE;
   float* lat = misc_f(c, (size_t)NI * 2 * E);
@@ -358,7 +351,7 @@ int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* c
   CKP(loop_commit(L));
   CK(launch_gather_rows_f32(lat_all + (size_t)nsteps * nimg * E, d_expand, NI * 2, E, lat, c->st));
   CK(launch_gather_rows_f32(context4, d_ctxmap, L.rows, CE, ctxrep, c->st));
-  CKP(L.kv.begin(ctxrep, L.rows));
+  CKP(L.kv.begin(ctxrep, L.rows, L.share));
   for (int i = 0; i < nsteps; ++i) {
     const int t = ts[i];
     const float* eps = L.eps;
@@ -370,7 +363,7 @@ int pnpi_direct_edit(pnpi_ctx* c, const float* lat_all, int nimg, const float* c
       // the counters keep counting the rows served; unet_shared_rows tells how many of them were not launched
       const uint64_t saved = (uint64_t)(rows - sm.crows);
       c->ctr.unet_sample_forwards += saved; c->ctr.unet_shared_rows += saved;
-      if (c->tkv.use) c->ctr.unet_sample_forwards_cached_kv += saved;
+      if (L.kv.armed) c->ctr.unet_sample_forwards_cached_kv += saved;
     } else {
       CKP(loop_unet(L, lat, d_inmap, t, ctxrep, true, i));
     }
@@ -403,7 +396,8 @@ int pnpi_direct_edit_pruned(pnpi_ctx* c, const float* lat_all, int nimg, const f
   std::vector<pnpi_ctrl_desc> none(nimg);
   memset(none.data(), 0, none.size() * sizeof(pnpi_ctrl_desc));
   Loop L(c);
-  CKP(loop_begin(L, nsteps, 3 * nimg, "3 * nimg exceeds max_unet_rows", ctrl_host ? ctrl_host : none.data(), nimg, 3, 1, 2));
+  LoopLayout lay; lay.cds = ctrl_host ? ctrl_host : none.data(); lay.nq = nimg; lay.rpi = 3; lay.src_off = 1; lay.tgt_off = 2;
+  CKP(loop_begin(L, nsteps, 3 * nimg, "3 * nimg exceeds max_unet_rows", lay));
   const size_t E = L.E, CE = L.CE; const int rows = L.rows;
   float* lat = misc_f(c, (size_t)nimg * 2 * E);      // [img][src, tgt]
   float* eps2 = misc_f(c, (size_t)nimg * 2 * E);     // [img][unc_tgt, cond_tgt]
@@ -549,7 +543,8 @@ int pnpi_ef_edit(pnpi_ctx* c, const float* xT, const float* zs, int nimg, int np
       if (ctrl_host[i].lb_enabled) return fail(c, PNPI_EINVAL, "LocalBlend is not supported by the edit-friendly edit");
   const int P = nprompts;
   Loop L(c);
-  CKP(loop_begin(L, nsteps_total, 2 * P * nimg, "2 * nprompts * nimg exceeds max_unet_rows", ctrl_host, nimg));
+  LoopLayout lay; lay.cds = ctrl_host; lay.nq = nimg;
+  CKP(loop_begin(L, nsteps_total, 2 * P * nimg, "2 * nprompts * nimg exceeds max_unet_rows", lay));
   const size_t E = L.E;
   float* lat = misc_f(c, (size_t)nimg * P * E);
   int *d_expand, *d_inmap;
@@ -660,12 +655,6 @@ static int pnp_check(pnpi_ctx* c, const pnpi_pnp_desc* d, int nimg) {
   if (d->conv_steps < 0 || d->qk_steps < 0) return fail(c, PNPI_EINVAL, "pnpi_pnp_desc: negative step count");
   return 0;
 }
-// the injection state lives for one call, whichever way that call returns
-struct PnpScope {
-  pnpi_ctx* c;
-  explicit PnpScope(pnpi_ctx* c_) : c(c_) {}
-  ~PnpScope() { c->pnp = PnpState(); }
-};
 // rows [3 nimg][4] = {r, source row of r's image, the same, r};  src_rows [nimg];  hrow [3 nimg]
 static void pnp_maps(int nimg, std::vector<int>& rows, std::vector<int>& src_rows, std::vector<int>& hrow) {
   rows.resize((size_t)nimg * 12); src_rows.resize(nimg); hrow.resize((size_t)nimg * 3);
@@ -678,9 +667,11 @@ static void pnp_maps(int nimg, std::vector<int>& rows, std::vector<int>& src_row
     }
   }
 }
-static void pnp_arm(pnpi_ctx* c, const pnpi_pnp_desc* d, int nimg, bool conv, bool qk) {
-  c->pnp.on = true; c->pnp.nimg = nimg; c->pnp.conv_site = d->conv_site; c->pnp.qk_mask = d->qk_block_mask;
-  c->pnp.conv = conv && d->conv_site >= 0; c->pnp.qk = qk && d->qk_block_mask != 0;
+// the injection parameters of one forward; s: the device tables of pnp_maps (rows, src_rows, hrow)
+static PnpState pnp_arm(const pnpi_pnp_desc* d, int nimg, bool conv, bool qk, PnpState s) {
+  s.on = true; s.nimg = nimg; s.conv_site = d->conv_site; s.qk_mask = d->qk_block_mask;
+  s.conv = conv && d->conv_site >= 0; s.qk = qk && d->qk_block_mask != 0;
+  return s;
 }
 
 int pnpi_pnp_step(pnpi_ctx* c, const float* eps, const float* x, int nimg, size_t row_elems, float guidance_scale, int t, int step_ratio,
@@ -699,9 +690,7 @@ int pnpi_unet_forward_pnp(pnpi_ctx* c, const float* latents, int nimg, int t, co
   CKP(pnp_check(c, desc, nimg));
   const int rows = 3 * nimg;
   if (c->attn_cb) return fail(c, PNPI_ESTATE, "an attention callback is installed: the Plug-and-Play forward takes its descriptor only");
-  if (!context && c->tkv.rows != rows) return fail(c, PNPI_ESTATE, "context is NULL: call pnpi_text_kv_precompute for this row count first");
-  struct UseKV { pnpi_ctx* c; ~UseKV() { c->tkv.use = false; } } guard{c};
-  c->tkv.use = context == nullptr;
+  UNetCall k; CKP(level1_call(c, latents, rows, context, eps_out, k));
   CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
   std::vector<int> rt, sr, hr;
   pnp_maps(nimg, rt, sr, hr);
@@ -710,10 +699,10 @@ int pnpi_unet_forward_pnp(pnpi_ctx* c, const float* latents, int nimg, int t, co
   std::vector<int> all(rt);
   all.insert(all.end(), sr.begin(), sr.end()); all.insert(all.end(), hr.begin(), hr.end());
   CKP(upload(c, d, all.data(), all.size() * sizeof(int)));
-  PnpScope scope(c);
-  pnp_arm(c, desc, nimg, conv_on != 0, qk_on != 0);
-  c->pnp.rows = d; c->pnp.src_rows = d + rt.size(); c->pnp.hrow = d + rt.size() + sr.size();
-  return unet_fwd(c, latents, rows, t, context, false, 0, eps_out);
+  PnpState tables; tables.rows = d; tables.src_rows = d + rt.size(); tables.hrow = d + rt.size() + sr.size();
+  const PnpState pnp = pnp_arm(desc, nimg, conv_on != 0, qk_on != 0, tables);
+  k.t = t; k.pnp = &pnp;
+  return unet_fwd(c, k);
 }
 
 int pnpi_pnp_edit(pnpi_ctx* c, const float* src_latents, const float* x_start, int nimg, const float* context, const pnpi_pnp_desc* desc,
@@ -732,8 +721,7 @@ int pnpi_pnp_edit(pnpi_ctx* c, const float* src_latents, const float* x_start, i
   L.eps = misc_f(c, 3 * N);
   std::vector<int> rt, sr, hr;
   pnp_maps(nimg, rt, sr, hr);
-  PnpScope scope(c);
-  loop_map(L, rt, &c->pnp.rows); loop_map(L, sr, &c->pnp.src_rows); loop_map(L, hr, &c->pnp.hrow);
+  loop_map(L, rt, &L.pnp.rows); loop_map(L, sr, &L.pnp.src_rows); loop_map(L, hr, &L.pnp.hrow);
   CKP(loop_commit(L, false));      // the rows of a launch are written in place by pnp_step: no gathered input buffer
   const size_t w = E * sizeof(float);
   CKH(hipMemcpyAsync(x, x_start, N * sizeof(float), hipMemcpyDeviceToDevice, c->st));
@@ -743,7 +731,7 @@ int pnpi_pnp_edit(pnpi_ctx* c, const float* src_latents, const float* x_start, i
   CKP(L.kv.begin(context, L.rows));
   for (int i = 0; i < nsteps; ++i) {
     const int t = ts[i];
-    pnp_arm(c, desc, nimg, i < desc->conv_steps, i < desc->qk_steps);
+    L.pnp = pnp_arm(desc, nimg, i < desc->conv_steps, i < desc->qk_steps, L.pnp);
     CKP(loop_unet(L, rows3, nullptr, t, context, false, i));
     float af, at; CKP(alphas_for(c, t, L.ratio, false, &af, &at));
     // CFG over rows 1 and 2, the DDIM step, and the next launch's rows [source latent of the next level, x, x]
@@ -814,14 +802,13 @@ int pnpi_unet_forward_t(pnpi_ctx* c, const float* latents, int rows, float t, co
   if (c->attn_cb) return fail(c, PNPI_ESTATE, "an attention callback is installed: pnpi_unet_forward_t runs no controller");
   if (!(t >= 0.f) || !(t <= (float)(c->cfg.n_train_timesteps - 1))) return fail(c, PNPI_EINVAL, "timestep out of range");
   if (rows <= 0 || rows > c->max_rows) return fail(c, PNPI_EINVAL, "unet rows out of range (max_unet_rows)");
-  if (!context && c->tkv.rows != rows) return fail(c, PNPI_ESTATE, "context is NULL: call pnpi_text_kv_precompute for this row count first");
-  struct UseKV { pnpi_ctx* c; ~UseKV() { c->tkv.use = false; } } guard{c};
-  c->tkv.use = context == nullptr;
+  UNetCall k; CKP(level1_call(c, latents, rows, context, eps_out, k));
   if (c->cd.any_edit || c->cd.nimg != 0) CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
   std::vector<float> row(c->cfg.block_out_channels[0]);
   temb_row_host(c->cfg, t, row.data());
   CKP(upload(c, c->temb_row, row.data(), row.size() * sizeof(float)));
-  return unet_fwd(c, latents, rows, 0, context, false, 0, eps_out, nullptr, c->temb_row, nullptr);
+  k.temb_row = c->temb_row;
+  return unet_fwd(c, k);
 }
 // one step (level 1): eps [nimg][3][row_elems], z / noise / image / z_out [nimg][row_elems], sc6_host the step's scalars (c_in and t unread),
 // in_next (nullable) [nimg][2][2 * row_elems] scaled by c_in_next.  noise is not read when sc6_host[5] == 0 (sigma_next == 0).
@@ -858,7 +845,8 @@ static int ip2p_edit_impl(pnpi_ctx* c, const Ip2pKind& k, const float* z0, const
   CKP(ip2p_model_check(c, k));
   CKP(ip2p_scalars_check(c, k, scalars_host, nsteps));
   Loop L(c);
-  CKP(loop_begin(L, nsteps, 3 * nimg, k.rows_msg, nullptr, 0, 4, 2, 3, 0, true));
+  LoopLayout lay; lay.split_io = true;
+  CKP(loop_begin(L, nsteps, 3 * nimg, k.rows_msg, lay));
   const size_t E4 = L.E_out, N = (size_t)nimg * E4;
   const int C0 = c->cfg.block_out_channels[0];
   float* z = misc_f(c, N);
@@ -910,15 +898,12 @@ static int tape_ensure(pnpi_ctx* c) {
   size_t pp, tp;
   {
     const Bump sp = c->persist, stmp = c->temp;
-    Tape* const prev = c->tape;
     c->persist = Bump(); c->temp = Bump();
     c->tape = T.get();
-    c->dry = true; T->rec = true;
-    const bool kv = c->tkv.use; c->tkv.use = false;
-    const int r = unet_fwd(c, nullptr, 1, 0, nullptr, false, 0, nullptr);
-    c->dry = false; T->rec = false; c->tkv.use = kv;
+    UNetCall k; k.rows = 1; k.record = true;
+    const int r = [&]() { DryScope dry(c); return unet_fwd(c, k); }();
     pp = align_up(c->persist.peak + (1 << 20), 4096); tp = align_up(c->temp.peak + (1 << 20), 4096);
-    c->persist = sp; c->temp = stmp; c->tape = prev;
+    c->persist = sp; c->temp = stmp; c->tape = nullptr;
     if (r) return r;
   }
   // gradients + dgrad scratch of one UNet row: about 2.8x the recorded activations at SD-1.x width (1.1 of 0.4 GB); 6x with a 64 MB floor
@@ -938,6 +923,12 @@ static int tape_ensure(pnpi_ctx* c) {
   c->tape = T.release();
   return 0;
 }
+// one row with its own context, no controller; record: onto the context's tape, cleared first (tape_backward walks it afterwards)
+static int unet_fwd_one(pnpi_ctx* c, const float* lat, int t, const float* context, float* eps_out, bool record) {
+  UNetCall k; k.latents = lat; k.rows = 1; k.t = t; k.context = context; k.eps_out = eps_out; k.record = record;
+  if (record) { Tape& T = *c->tape; T.ops.clear(); T.grads.clear(); T.garena.reset(); T.garena.overflow = false; }
+  return unet_fwd(c, k);
+}
 // eps = UNet(latents, t, context) for ONE row, and d_context = (d loss / d eps)^T (d eps / d context) for the given d loss / d eps
 // (fp32, the layout of eps; pre-multiplied by the caller's power-of-two loss scale -- activations' gradients travel in fp16).
 int pnpi_unet_context_grad(pnpi_ctx* c, const float* latents, int t, const float* context, const float* d_eps, float* eps_out, float* d_context_out) {
@@ -949,12 +940,7 @@ int pnpi_unet_context_grad(pnpi_ctx* c, const float* latents, int t, const float
   const size_t E = (size_t)g.in_channels * g.sample_size * g.sample_size, CE = (size_t)g.ctx_len * g.cross_dim;
   CKP(setup_ctrl(c, nullptr, 0, c->max_rows));
   float* eps = eps_out ? eps_out : misc_f(c, E);
-  T.ops.clear(); T.grads.clear(); T.garena.reset(); T.garena.overflow = false;
-  c->tkv.use = false;
-  T.rec = true;
-  int r = unet_fwd(c, latents, 1, t, context, false, 0, eps);
-  T.rec = false;
-  if (r) return r;
+  CKP(unet_fwd_one(c, latents, t, context, eps, true));
   half_t* d_out = tape_galloc(c, (size_t)g.sample_size * g.sample_size * 8);
   if (!d_out) return fail(c, PNPI_ENOMEM, "gradient arena overflow");
   CK(launch_nchw_f32_to_nhwc_f16(d_eps, 1, g.in_channels, g.sample_size * g.sample_size, 8, d_out, c->st));
@@ -979,19 +965,13 @@ static int null_inner_loop(pnpi_ctx* c, const NullOptBufs& b, const float* lat, 
   const float c_x = (float)(sa_p / sa_t), c_e = (float)(sb_p - sa_p * sb_t / sa_t);       // rec = c_x x + c_e eps
   const float lr = (float)(1e-2 * (1.0 - i / 100.0));
   int its = 0;
-  c->tkv.use = false;
-  int r = unet_fwd(c, lat, 1, t, ctx_cond, false, 0, b.eps2 + E);
-  if (r) return r;
+  CKP(unet_fwd_one(c, lat, t, ctx_cond, b.eps2 + E, false));
   CKH(hipMemsetAsync(b.am, 0, CE * sizeof(float), c->st));
   CKH(hipMemsetAsync(b.av, 0, CE * sizeof(float), c->st));
   for (int j = 0; j < num_inner_steps; ++j) {
     // forward with the tape recording; the loss head needs eps_u first, so forward and backward are two calls of the tape machinery
     Tape& T = *c->tape;
-    T.ops.clear(); T.grads.clear(); T.garena.reset(); T.garena.overflow = false;
-    T.rec = true;
-    r = unet_fwd(c, lat, 1, t, unc, false, 0, b.eps2);
-    T.rec = false;
-    if (r) return r;
+    CKP(unet_fwd_one(c, lat, t, unc, b.eps2, true));
     CK(launch_null_text_loss(b.eps2, b.eps2 + E, lat, target, (int)E, guidance_scale, c_x, c_e, scale, b.d_eps, b.loss_d, c->st));
     half_t* d_out = tape_galloc(c, (size_t)g.sample_size * g.sample_size * 8);
     if (!d_out) return fail(c, PNPI_ENOMEM, "gradient arena overflow");
@@ -1045,10 +1025,8 @@ int pnpi_null_text_optimize(pnpi_ctx* c, const float* ddim_latents, const float*
     if (iters_out) iters_out[i] = its;
     CKH(hipMemcpyAsync(uncond_out + (size_t)i * CE, unc, CE * sizeof(float), hipMemcpyDeviceToDevice, c->st));
     // latent_cur = prev_step(CFG(eps(unc), eps(cond)))   (get_noise_pred with the optimised embedding, inversion.py:221-224)
-    c->tkv.use = false;
-    int r = unet_fwd(c, lat, 1, t, unc, false, 0, b.eps2);
-    if (r) return r;
-    if (num_inner_steps == 0) { r = unet_fwd(c, lat, 1, t, ctx_cond, false, 0, b.eps2 + E); if (r) return r; }
+    CKP(unet_fwd_one(c, lat, t, unc, b.eps2, false));
+    if (num_inner_steps == 0) CKP(unet_fwd_one(c, lat, t, ctx_cond, b.eps2 + E, false));
     CK(launch_cfg_ddim_prev(cfg_step(L, b.eps2, lat, 1, 1, guidance_scale, a_t, a_p, lat), c->st));
   }
   return 0;
@@ -1095,16 +1073,14 @@ int pnpi_null_latent_calculate(pnpi_ctx* c, const float* ddim_latents, const flo
                           losses_out ? losses_out + (size_t)i * num_inner_steps : nullptr));
     if (iters_out) iters_out[i] = its;
     CKH(d2d(in4, cur, E)); CKH(d2d(in4 + E, cur, E)); CKH(d2d(in4 + 2 * E, cur + E, E)); CKH(d2d(in4 + 3 * E, cur + E, E));
-    c->tkv.use = false;
+    UNetCall k4; k4.latents = in4; k4.rows = 4; k4.t = t; k4.context = ctx4; k4.eps_out = eps4;
     // with the optimised embeddings -> opt
     CKH(d2d(ctx4, unc, CE)); CKH(d2d(ctx4 + 2 * CE, unc + CE, CE));
-    int r = unet_fwd(c, in4, 4, t, ctx4, false, 0, eps4);
-    if (r) return r;
+    CKP(unet_fwd(c, k4));
     CK(launch_cfg_ddim_prev(cfg_step(L, eps4, cur, 2, 1, guidance_scale, a_t, a_p, opt), c->st));
     // with the original ones -> plain; loss = opt - plain; latent_cur = plain + loss
     CKH(d2d(ctx4, context4, CE)); CKH(d2d(ctx4 + 2 * CE, context4 + CE, CE));
-    r = unet_fwd(c, in4, 4, t, ctx4, false, 0, eps4);
-    if (r) return r;
+    CKP(unet_fwd(c, k4));
     CfgStepP s = cfg_step(L, eps4, cur, 2, 1, guidance_scale, a_t, a_p, cur);
     s.target = opt; s.offset_out = noise_loss_out + (size_t)i * 2 * E;
     CK(launch_cfg_ddim_prev(s, c->st));

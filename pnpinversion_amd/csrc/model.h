@@ -46,7 +46,7 @@ struct ResnetW {
   NormW n1, n2;
   ConvW c1, c2, sc;
   bool has_sc;
-  int temb_off;   // >= 0: conv1 bias comes from the per-step bias_eff table at this offset; -1: static conv1 bias
+  int temb_off;   // >= 0: conv1 bias comes from the forward's bias row (UNetFlight::bias_eff) at this offset; -1: static conv1 bias
   int cin, cout;
 };
 
@@ -196,8 +196,7 @@ struct CtrlDev {
 struct TextKV {
   std::vector<half_t*> k, vt;     // per transformer block in execution order: [rows][T][hd], [rows][hd][ldv]
   char* base = nullptr; size_t cap = 0;
-  int rows = 0;                   // rows the cache holds (0 = invalid)
-  bool use = false;               // the forward in flight reads the cache instead of projecting the context
+  int rows = 0;                   // rows the cache holds (0 = invalid); a forward reads it when its call says so (UNetCall::cached_kv)
 };
 
 // Mask-guided MasaCtrl: the source / target masks of pnpi_masa_set_masks resized to every self-attention level, one class byte per
@@ -212,14 +211,13 @@ struct MasaMasks {
   const uint8_t* t_at(int l) const { return base + off[l] + (size_t)cap_img * side[l] * side[l]; }
 };
 
-// Plug-and-Play injection state of the forward in flight (pnpi_unet_forward_pnp, pnpi_pnp_edit): rows [img][source, negative, target].
+// Plug-and-Play injection parameters of one forward, the caller's (pnpi_unet_forward_pnp, pnpi_pnp_edit): rows [img][source, negative, target].
 // conv: the decoder ResNet `conv_site` (execution order) runs its main branch on the source rows only and every row adds its image's
 // result to its own shortcut; qk: the transformer blocks of qk_mask take the row table `rows` ({r, src, src, r}) in their self-attention.
 struct PnpState {
   bool on = false, conv = false, qk = false;
   int nimg = 0, conv_site = -1;
   unsigned qk_mask = 0;
-  int up_res_index = 0;           // decoder ResNet counter of the forward in flight
   int* rows = nullptr;            // [3 nimg][4] device
   int* src_rows = nullptr;        // [nimg] device: launch row of image i's source (3 i)
   int* hrow = nullptr;            // [3 nimg] device: launch row -> its image (r / 3)
@@ -227,7 +225,7 @@ struct PnpState {
 
 struct ProfRec { int cls; double flops, bytes; hipEvent_t a, b; int M, N, K, ksize; int cfg = -1, split = 0; int geom[7] = {0, 0, 0, 0, 0, 0, 0}; };
 
-struct Tape;   // activation tape of a differentiable forward (null-text path; api.hip)
+struct Tape; struct UNetFlight;   // api_graph.inc: activation tape of a differentiable forward (null-text path); what one UNet forward mutates while it runs
 
 struct pnpi_ctx {
   pnpi_model_config cfg;
@@ -235,16 +233,8 @@ struct pnpi_ctx {
   hipStream_t st;
   std::string err;
   int max_rows, max_vae;
-  bool dry;
-  int tf_index = 0;   // transformer block counter of the forward in flight (MasaCtrl start_layer)
-  // tuning "cfg_dedup" = 2, inside the deduplicated UNet prefix: a GEMM over pin_from rows takes the tile / split-K its pin_to-row form gets
-  int pin_from = 0, pin_to = 0;
-  // tuning "src_share", while pnpi_direct_edit launches its compact rows: share_U > 0 = the launch of share_from rows serves share_to
-  // logical rows resting on share_U logical latents.  share_pin (= 2): every GEMM of the forward is configured as at share_to rows
-  // (the prefix of "cfg_dedup" as at share_to / share_U rows), so each launch makes the choices of the full-row loop
-  // (share_from > share_to: the full launch of a tape-holding context under "src_share" = 1, configured as the compact launch it replaces)
-  int share_from = 0, share_to = 0, share_U = 0;
-  bool share_pin = false;
+  bool dry = false;             // sizing run: the graphs allocate and count, nothing is launched (DryScope)
+  UNetFlight* fw = nullptr;     // the UNet forward in flight (set and cleared by unet_fwd alone); nullptr in every other graph
   Bump warena, persist, temp, ctrl_arena;
   struct AugBias { float* p; int heads, Dp, dh; };
   std::vector<AugBias> aug_biases;                  // the b_qkv_aug vectors of this build (filled after the arena exists)
@@ -262,7 +252,6 @@ struct pnpi_ctx {
   float* temb_row = nullptr;   // [C0] the caller's sinusoid row of pnpi_unet_forward_t
   float* temb_h;          // [4*C0]
   float* temb_emb;        // [4*C0]
-  float* bias_eff;        // [temb_total] of the forward in flight (points into bias_tab once cached)
   float* bias_scratch;    // [temb_total]
   float* bias_tab = nullptr;          // [n_train][temb_total]: conv1 bias + time embedding per TIMESTEP, filled on first use -- it depends
   std::vector<char> bias_valid;       // on t and the weights only, so every later forward at that timestep launches no GEMV
@@ -284,10 +273,9 @@ struct pnpi_ctx {
   bool sched_set;
   pnpi_counters ctr;
   CtrlDev cd;
-  PnpState pnp;
   MasaMasks mm;
   std::vector<char> host_stage;
   bool prof_on = false;
   std::vector<ProfRec> prof;
-  Tape* tape = nullptr;          // non-null while a forward is being recorded for a backward pass
+  Tape* tape = nullptr;          // non-null once a recording forward ran on this context (UNetCall::record)
 };
