@@ -3,13 +3,17 @@
 
   psnr* / mse* / ssim*      pnpinversion_amd.metrics (numpy restatements of the torchmetrics definitions)
   clip_similarity_*         on the device: pnpinversion_amd.clip_score.ClipScore (CLIP ViT-L/14 image tower + SD's own text tower)
+  structure_distance*       on the device: pnpinversion_amd.structure_distance.StructureDistance (DINO ViT-B/8 key self-similarity)
 
-`structure_distance*` (DINO ViT self-similarity) and `lpips*` (SqueezeNet LPIPS) need networks that are not built here: asking for one of
-them ends the run with a message naming the column.  Arguments, the method-folder table, the right-hand 512 crop of non-square panels, the
-"nan" cells of empty masks and the CSV layout are the reference's.  The three CLIP columns of one (image, method) pair go to the device
-as ONE launch set (source image / source prompt, target image / target prompt, masked target image / target prompt).
+`lpips*` (SqueezeNet LPIPS) needs a network that is not built here, and `structure_distance*` is not built without DINO weights
+(--dino_checkpoint or --synthetic_weights): asking for such a column ends the run with a message naming it, before any file is opened.
+Arguments, the method-folder table, the right-hand 512 crop of non-square panels, the "nan" cells of empty masks and the CSV layout are
+the reference's.  The three CLIP columns of one (image, method) pair go to the device as ONE launch set (source image / source prompt,
+target image / target prompt, masked target image / target prompt), and so do its three structure columns (whole, unedited part, edited
+part: one tower pass over the six images).
 
-    python evaluation/evaluate.py --checkpoint_dir <SD-1.x dir> --clip_model_dir <clip-vit-large-patch14 dir> [--metrics ...]
+    python evaluation/evaluate.py --checkpoint_dir <SD-1.x dir> --clip_model_dir <clip-vit-large-patch14 dir> --dino_checkpoint <dino_vitbase8_pretrain.pth> [--metrics ...]
+    python evaluation/evaluate.py --dino_checkpoint <dino_vitbase8_pretrain.pth> --metrics structure_distance psnr_unedit_part   # no CLIP weights needed
     python evaluation/evaluate.py --synthetic_weights ...        # seeded random towers: the numbers mean nothing, the plumbing runs
 """
 import argparse
@@ -27,7 +31,8 @@ if ROOT not in sys.path:
 PIXEL_METRICS = ("psnr", "mse", "ssim")
 PARTS = ("", "_unedit_part", "_edit_part")
 CLIP_METRICS = ("clip_similarity_source_image", "clip_similarity_target_image", "clip_similarity_target_image_edit_part")
-NOT_BUILT = {"structure_distance": "DINO ViT structure distance", "lpips": "SqueezeNet LPIPS"}
+STRUCT_METRICS = ("structure_distance", "structure_distance_unedit_part", "structure_distance_edit_part")
+NOT_BUILT = {"lpips": "SqueezeNet LPIPS"}
 DEFAULT_METRICS = ["structure_distance", "psnr_unedit_part", "lpips_unedit_part", "mse_unedit_part", "ssim_unedit_part"] + list(CLIP_METRICS)
 
 
@@ -81,12 +86,23 @@ def _split(metric):
     return metric, ""
 
 
-def check_metrics(metrics):
+def has_dino_weights(args):
+    return bool(getattr(args, "dino_checkpoint", None) or getattr(args, "synthetic_weights", False))
+
+
+def check_metrics(metrics, dino=False):
+    """dino: DINO weights (or a scorer) are at hand, so the structure_distance* columns can be computed"""
+    computable = [p + s for p in PIXEL_METRICS for s in PARTS] + list(CLIP_METRICS)
     for m in metrics:
         base, _ = _split(m)
         if base in NOT_BUILT:
             raise SystemExit("column %r is not built: %s needs a network this library does not carry (computable columns: %s)"
-                             % (m, NOT_BUILT[base], ", ".join([p + s for p in PIXEL_METRICS for s in PARTS] + list(CLIP_METRICS))))
+                             % (m, NOT_BUILT[base], ", ".join(computable + list(STRUCT_METRICS))))
+        if m in STRUCT_METRICS:
+            if not dino:
+                raise SystemExit("column %r is not built without DINO weights: pass --dino_checkpoint <dino_vitbase8_pretrain.pth>, or "
+                                 "--synthetic_weights for a seeded random ViT (computable without them: %s)" % (m, ", ".join(computable)))
+            continue
         if m not in CLIP_METRICS and not (base in PIXEL_METRICS and m == base + _split(m)[1]):
             raise SystemExit("unknown metric column %r" % m)
 
@@ -94,12 +110,16 @@ def check_metrics(metrics):
 class Calculator:
     """the reference's MetricsCalculator protocol for the columns that are built"""
 
-    def __init__(self, scorer=None):
-        self.scorer = scorer
+    def __init__(self, scorer=None, struct_scorer=None):
+        self.scorer, self.struct_scorer = scorer, struct_scorer
 
     def calculate_clip_similarity(self, img, txt, mask=None):
         from pnpinversion_amd import metrics
         return metrics.calculate_clip_similarity(img, txt, mask, scorer=self.scorer)
+
+    def calculate_structure_distance(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
+        from pnpinversion_amd import metrics
+        return metrics.calculate_structure_distance(img_pred, img_gt, mask_pred, mask_gt, scorer=self.struct_scorer)
 
     def __getattr__(self, name):
         from pnpinversion_amd import metrics
@@ -117,7 +137,7 @@ def calculate_metric(calc, metric, src_image, tgt_image, src_mask, tgt_mask, src
         if metric == "clip_similarity_target_image":
             return calc.calculate_clip_similarity(tgt_image, tgt_prompt, None)
         return "nan" if tgt_mask.sum() == 0 else calc.calculate_clip_similarity(tgt_image, tgt_prompt, tgt_mask)
-    if base in NOT_BUILT:
+    if base in NOT_BUILT or (metric in STRUCT_METRICS and getattr(calc, "struct_scorer", None) is None):
         check_metrics([metric])
     fn = lambda *a: getattr(calc, "calculate_" + base)(*a)
     if part == "":
@@ -147,6 +167,27 @@ def clip_cells(scorer, metrics, src_image, tgt_image, tgt_mask, src_prompt, tgt_
     return out
 
 
+def struct_cells(scorer, metrics, src_image, tgt_image, src_mask, tgt_mask):
+    """the structure columns of one (image, method) pair in one launch set -> {metric: value or "nan"}; the reference's argument order
+    calculate_structure_distance(src_image, tgt_image, ...) and its "nan" rule for empty parts"""
+    want, pred, gt, mp, mg = [], [], [], [], []
+    out = {}
+    for m in STRUCT_METRICS:
+        if m not in metrics:
+            continue
+        part = _split(m)[1]
+        ms, mt = (None, None) if part == "" else ((1 - src_mask, 1 - tgt_mask) if part == "_unedit_part" else (src_mask, tgt_mask))
+        if part and (ms.sum() == 0 or mt.sum() == 0):
+            out[m] = "nan"
+            continue
+        want.append(m)
+        pred.append(src_image); gt.append(tgt_image); mp.append(ms); mg.append(mt)
+    if want:
+        got = scorer.distance(pred, gt, mp, mg)
+        out.update({m: float(v) for m, v in zip(want, got)})
+    return out
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--annotation_mapping_file", type=str, default="data/mapping_file.json")
@@ -161,6 +202,8 @@ def parse_args(argv=None):
     ap.add_argument("--checkpoint_dir", type=str, default=None, help="Stable-Diffusion-1.x directory (diffusers layout): text tower + tokenizer")
     ap.add_argument("--clip_model_dir", type=str, default=None, help="local clip-vit-large-patch14 directory: image tower + projections")
     ap.add_argument("--synthetic_weights", action="store_true", help="seeded random towers and the word-level stand-in tokenizer")
+    # weights of the structure columns (not in the reference, which downloads facebookresearch/dino:main dino_vitb8)
+    ap.add_argument("--dino_checkpoint", type=str, default=None, help="local dino_vitbase8_pretrain.pth: the DINO ViT-B/8 state dict")
     return ap.parse_args(argv)
 
 
@@ -190,17 +233,41 @@ def build_scorer(args):
     return scorer
 
 
-def run(args, scorer=None):
+def build_struct_scorer(args, engine=None):
+    """StructureDistance from --dino_checkpoint, or seeded weights; on the CLIP scorer's context when there is one, else on a context of
+    its own with no text tower, no UNet rows and no VAE images (the smallest model configuration: its weight arena is never loaded)"""
+    import dataclasses
+    from pnpinversion_amd import checkpoint
+    from pnpinversion_amd.structure_distance import StructureDistance
+    if args.dino_checkpoint and args.synthetic_weights:
+        raise SystemExit("--dino_checkpoint and --synthetic_weights are mutually exclusive")
+    if engine is None:
+        from pnpinversion_amd.config import TINY16
+        from pnpinversion_amd.engine import NativeEngine
+        engine = NativeEngine(dataclasses.replace(TINY16, clip_layers=0), device=args.device if args.device != "cuda" else None,
+                              max_unet_rows=0, max_vae_images=0)
+    scorer = StructureDistance(engine, max_pairs=3)
+    if args.dino_checkpoint:
+        scorer.load_state_dict(checkpoint.load_dino_checkpoint(args.dino_checkpoint))
+    else:
+        print(checkpoint.SYNTHETIC_WARNING, file=sys.stderr, flush=True)
+        scorer.load_synthetic(0)
+    return scorer
+
+
+def run(args, scorer=None, struct_scorer=None):
     from PIL import Image
     metrics = list(args.metrics)
-    check_metrics(metrics)
+    check_metrics(metrics, dino=struct_scorer is not None or has_dino_weights(args))
     if args.evaluate_whole_table:
         folders = {k: v for k, v in all_tgt_image_folders.items() if k[0] in args.tgt_methods}
     else:
         folders = {k: all_tgt_image_folders[k] for k in args.tgt_methods}
     if scorer is None and any(m in CLIP_METRICS for m in metrics):
         scorer = build_scorer(args)
-    calc = Calculator(scorer)
+    if struct_scorer is None and any(m in STRUCT_METRICS for m in metrics):
+        struct_scorer = build_struct_scorer(args, engine=getattr(scorer, "engine", None))
+    calc = Calculator(scorer, struct_scorer)
     with open(args.result_path, "w", newline="") as f:
         csv.writer(f).writerow(["file_id"] + ["%s|%s" % (k, m) for k in folders for m in metrics])
     with open(args.annotation_mapping_file) as f:
@@ -220,6 +287,8 @@ def run(args, scorer=None):
                 w, h = tgt_image.size
                 tgt_image = tgt_image.crop((w - 512, h - 512, w, h))
             clip = clip_cells(scorer, metrics, src_image, tgt_image, mask, src_prompt, tgt_prompt) if scorer is not None else {}
+            if struct_scorer is not None:
+                clip.update(struct_cells(struct_scorer, metrics, src_image, tgt_image, mask, mask))
             for m in metrics:
                 row.append(clip[m] if m in clip else calculate_metric(calc, m, src_image, tgt_image, mask, mask, src_prompt, tgt_prompt))
         with open(args.result_path, "a+", newline="") as f:
@@ -228,5 +297,5 @@ def run(args, scorer=None):
 
 if __name__ == "__main__":
     _args = parse_args()
-    check_metrics(_args.metrics)
+    check_metrics(_args.metrics, dino=has_dino_weights(_args))
     run(_args)

@@ -302,6 +302,56 @@ int pnpi_op_clip_preprocess(pnpi_ctx* ctx, const uint8_t* img_hwc, const uint8_t
  * NULLs for ksize.  One pass: acc = 2^21 + sum_j src[first + j] * coef[j];  out = clamp(acc >> 22, 0, 255). */
 int pnpi_clip_resize_tables(int in_size, int out_size, int* bounds_out, int* coef_out);
 
+/* ---- DINO structure distance (evaluation/matrics_calculator.py:385-405 -> LossG.calculate_global_ssim_loss :237-246 ->
+ * VitExtractor.get_keys_self_sim_from_input(layer_num = 11) :154-171, dino_vitb8) ---------------------------------------------
+ * The DINO ViT (facebookresearch/dino vision_transformer.py) attached to a context, which needs nothing else: no text tower, no UNet
+ * rows, no VAE images.  Weights, tables and workspaces are an allocation of their own, freed by pnpi_destroy; a context that never
+ * attaches is unchanged.  Weights arrive through pnpi_load_weights under the prefix "dino." with DINO's own state-dict keys: cls_token,
+ * pos_embed, patch_embed.proj.{weight, bias}, blocks.N.{norm1, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2}.{weight, bias}, norm.*.
+ * The metric reads the output of the LAST block's attn.qkv: of that block only norm1 and the K third of attn.qkv (rows width ..
+ * 2 * width - 1) are computed; its other tensors and the final norm.* have no slot -- they are accepted and dropped, neither missing
+ * nor an error.  pnpi_missing_weights, pnpi_mark_all_loaded and the UNet / VAE entry points do not look at "dino." slots.
+ * Preprocessing is the reference's: uint8 image (* 0 / 1 mask) as float 0..255, NOT divided by 255; torchvision 0.13's Resize on a tensor =
+ * two-tap bilinear, align_corners = False, no antialiasing; Normalize(ImageNet mean, std) on those 0..255 values.
+ * Every entry point refuses, with a status and a message and before anything is launched: nothing attached (PNPI_ESTATE), a second
+ * attach (PNPI_ESTATE), missing weights (PNPI_ESTATE, every name), n out of range (PNPI_EINVAL), an S outside 16 .. 8192
+ * (PNPI_ESHAPE), a mask byte other than 0 / 1 (PNPI_EINVAL; the masks are read back to the host), a NULL output (PNPI_EINVAL). */
+typedef struct {
+  int struct_size;                 /* = sizeof(pnpi_dino_config), set by pnpi_dino_config_vitb8 / the caller; a mismatch is PNPI_EINVAL */
+  int image_size;                  /* 224 */
+  int patch;                       /* 8 */
+  int width;                       /* 768 */
+  int layers;                      /* 12 */
+  int heads;                       /* 12 */
+  int intermediate;                /* 3072 */
+} pnpi_dino_config;
+void pnpi_dino_config_vitb8(pnpi_dino_config* cfg);
+/* up to max_pairs image pairs (2 * max_pairs images) per call */
+int pnpi_dino_attach(pnpi_ctx* ctx, const pnpi_dino_config* cfg, int max_pairs);
+/* the concatenated keys of the last block: img_hwc device uint8 [n][S][S][3], mask_hw nullable device uint8 [n][S][S];
+ * keys_out device fp32 [n][T][width], T = (image_size / patch)^2 + 1; n <= 2 * max_pairs */
+int pnpi_dino_keys(pnpi_ctx* ctx, const uint8_t* img_hwc, const uint8_t* mask_hw, int n, int S, float* keys_out);
+/* calculate_structure_distance for n pairs, n <= max_pairs: one tower pass over the 2 n images, one fused distance launch set.
+ * dist_out device fp32 [n]: mean over T^2 of (sim_pred - sim_gt)^2, sim[i][j] = k_i . k_j / max(|k_i| |k_j|, 1e-8). */
+int pnpi_structure_distance(pnpi_ctx* ctx, const uint8_t* img_pred, const uint8_t* mask_pred, const uint8_t* img_gt, const uint8_t* mask_gt,
+                            int n, int S, float* dist_out);
+/* kernel-level: the preprocessing alone, to out_size (a multiple of the attached tower's patch).  resized_f32_out (nullable) device
+ * fp32 [n][3][out][out], the resized 0..255 values; patches_f16_out (nullable) device fp16 [n][(out / patch)^2][3 * patch^2], the
+ * normalised values as patch rows in the patch-embedding weight's (c, ky, kx) order.  Needs no weights. */
+int pnpi_op_dino_preprocess(pnpi_ctx* ctx, const uint8_t* img_hwc, const uint8_t* mask_hw, int n, int S, int out_size,
+                            float* resized_f32_out, void* patches_f16_out);
+/* kernel-level: the fused self-similarity distance of n pairs of given key matrices, device fp16 [n][T][D], D % 32 == 0, 16-byte
+ * aligned; needs no attached tower.  dist_out device fp32 [n]; sim_a_out (nullable) device fp32 [n][T][T]: the map of keys_a, written
+ * by the debug variant of the same tile body.  The two maps of the distance never reach memory; the reduction order is fixed. */
+int pnpi_op_keys_selfsim_mse(pnpi_ctx* ctx, const void* keys_a_f16, const void* keys_b_f16, int n, int T, int D, float* dist_out,
+                             float* sim_a_out);
+/* Host-only, no context: the taps of the resize for in_size -> out_size per output index, by PyTorch's fp32 arithmetic
+ * (area_pixel_compute_source_index, align_corners = False): src = max(scale * (o + 0.5) - 0.5, 0), scale = in / out;
+ * idx0 = min(floor(src), in - 1), idx1 = idx0 + (idx0 < in - 1), lambda = weight of idx1 = clamp(src - idx0, 0, 1); the weight of
+ * idx0 is 1 - lambda in fp32.  in_size == out_size: idx0 = idx1 = o, lambda = 0.  Each output nullable, [out_size].
+ * Returns 0, or PNPI_ESHAPE for sizes outside 1 .. 8192. */
+int pnpi_dino_resize_taps(int in_size, int out_size, int* idx0_out, int* idx1_out, float* lambda_out);
+
 /* ---- level 2: loop boundary (whole phases device-resident, no host round trip per step) ------------------------- */
 /* DirectInversion.ddim_loop (inversion.py:308-319): latents_out [nsteps+1][nimg][4][h][w]; timesteps_host = scheduler.timesteps */
 int pnpi_ddim_invert(pnpi_ctx* ctx, const float* z0, int nimg, const float* ctx_cond /*[nimg][77][768]*/, int nsteps,

@@ -31,6 +31,15 @@ class ClipvConfig(C.Structure):
         return cls(C.sizeof(cls), int(image_size), int(patch), int(width), int(layers), int(heads), int(intermediate), int(proj_dim))
 
 
+class DinoConfig(C.Structure):
+    """pnpi_dino_config: the DINO ViT of the structure distance (pnpi_dino_config_vitb8 fills ViT-B/8's)"""
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "image_size", "patch", "width", "layers", "heads", "intermediate")]
+
+    @classmethod
+    def make(cls, image_size=224, patch=8, width=768, layers=12, heads=12, intermediate=3072):
+        return cls(C.sizeof(cls), int(image_size), int(patch), int(width), int(layers), int(heads), int(intermediate))
+
+
 class NamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int), ("shape", C.c_int64 * 4)]
 
@@ -142,6 +151,14 @@ SYMBOLS = {
     "pnpi_clip_score": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "pnpi_op_clip_preprocess": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pnpi_clip_resize_tables": (_i, [_i, _i, _ip, _ip]),
+    # DINO structure distance (evaluation/matrics_calculator.py:385-405, :237-246, :154-171)
+    "pnpi_dino_config_vitb8": (None, [C.POINTER(DinoConfig)]),
+    "pnpi_dino_attach": (_i, [_vp, C.POINTER(DinoConfig), _i]),
+    "pnpi_dino_keys": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "pnpi_structure_distance": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "pnpi_op_dino_preprocess": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pnpi_op_keys_selfsim_mse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pnpi_dino_resize_taps": (_i, [_i, _i, _ip, _ip, _fp]),
     "pnpi_ddim_invert": (_i, [_vp, _vp, _i, _vp, _i, _ip, _vp]),
     "pnpi_ddim_invert_cfg": (_i, [_vp, _vp, _i, _vp, _vp, _f, _i, _ip, _vp]),
     "pnpi_offset_calculate": (_i, [_vp, _vp, _i, _vp, _i, _ip, _f, _fp, _vp]),

@@ -175,6 +175,28 @@ def load_ldm_checkpoint(path):
     return convert_ldm_state_dict(pl_sd["state_dict"] if "state_dict" in pl_sd else pl_sd)
 
 
+def load_dino_checkpoint(path):
+    """dino_vitbase8_pretrain.pth (what torch.hub's facebookresearch/dino:main dino_vitb8 downloads): a plain state dict with DINO's own
+    keys -- cls_token, pos_embed, patch_embed.proj.*, blocks.N.*, norm.* -- as structure_distance.StructureDistance.load_state_dict
+    takes it.  A training checkpoint's "teacher" / "student" wrapper and its "module." / "backbone." prefixes are stripped; head.* is
+    dropped.  No such file exists offline, so this loader is untested here (the tests run weights.dino_state_dict)."""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    for wrap in ("teacher", "student", "state_dict"):
+        if isinstance(sd, dict) and wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    out = {}
+    for k, v in sd.items():
+        for pre in ("module.", "backbone."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        if not k.startswith("head."):
+            out[k] = v
+    if "cls_token" not in out or "pos_embed" not in out:
+        raise KeyError("%s holds no DINO VisionTransformer state dict (no cls_token / pos_embed)" % path)
+    return out
+
+
 SYNTHETIC_WARNING = ("WARNING: running on SEEDED SYNTHETIC (random) Stable-Diffusion weights and a word-level stand-in tokenizer -- the "
                      "saved panels are numerically meaningful (parity / timing) but are NOT edits of a trained model.  Pass "
                      "--checkpoint_dir <diffusers SD-1.x directory> for real weights.")

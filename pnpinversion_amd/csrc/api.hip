@@ -1,6 +1,6 @@
 // libpnpi: C-ABI entry points + the static SD-1.x UNet / VAE graph executor and the device-resident DI / P2P loops.
 // See include/pnpi.h for the reference interface each entry point replaces.
-// One translation unit in eight files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the CLIP text encoder,
+// One translation unit in nine files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the CLIP text encoder,
 // kernel-level test hooks) includes, in order,
 //   api_weights.inc   weight slots of the packed arena and the model builder
 //   api_graph.inc     profiling records, activation tape, op wrappers, ResNet / transformer blocks, unet_fwd
@@ -8,6 +8,7 @@
 //   api_vae.inc       AutoencoderKL encoder / decoder graph
 //   api_ctrl.inc      per-loop text K / V cache, controller descriptor -> device tables
 //   api_clipscore.inc CLIP similarity: the image tower attached to a context, projections, preprocessing, score
+//   api_structdist.inc DINO structure distance: the ViT attached to a context, preprocessing, keys, the fused distance
 //   api_loops.inc     (last) the loop scaffold and the level-2 loops: DDIM / direct inversion, edit loops, edit-friendly DDPM, null-text
 #include <math.h>
 #include <stdio.h>
@@ -106,6 +107,7 @@ static int validate_config(pnpi_ctx* c) {
 
 static int clip_fwd(pnpi_ctx* c, const int* ids, int n, float* out, half_t** y16_out = nullptr);
 static void clipv_free(pnpi_ctx* c);
+static void dino_free(pnpi_ctx* c);
 
 static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device, void* hip_stream, int max_unet_rows, int max_vae_images, pnpi_ctx* parent);
 int pnpi_create(pnpi_ctx** out, const pnpi_model_config* cfg, int device, void* hip_stream, int max_unet_rows, int max_vae_images) {
@@ -265,6 +267,8 @@ void pnpi_destroy(pnpi_ctx* c) {
     delete c->tape;
   }
   clipv_free(c);
+  dino_free(c);
+  (void)hipFree(c->ss_ws);
   delete c;
 }
 
@@ -311,7 +315,7 @@ int pnpi_missing_weights(const pnpi_ctx* c, char* names_out, size_t cap) {
   size_t used = 0;
   if (names_out && cap) names_out[0] = 0;
   for (auto& kv : c->slots)
-    if (!kv.second.loaded && kv.first.compare(0, 5, "clip.") != 0 && kv.first.compare(0, 6, "clipv.") != 0) {   // the text encoder reports through pnpi_text_encode, the image tower through pnpi_clip_*
+    if (!kv.second.loaded && kv.first.compare(0, 5, "clip.") != 0 && kv.first.compare(0, 6, "clipv.") != 0 && kv.first.compare(0, 5, "dino.") != 0) {   // the text encoder reports through pnpi_text_encode, the image tower through pnpi_clip_*, the DINO ViT through pnpi_dino_*
       ++missing;
       if (names_out && used + kv.first.size() + 2 < cap) {
         memcpy(names_out + used, kv.first.c_str(), kv.first.size());
@@ -333,7 +337,7 @@ int pnpi_weight_arena(pnpi_ctx* c, void** ptr, size_t* bytes) {
 int pnpi_mark_all_loaded(pnpi_ctx* c) {
   invalidate_derived(c);            // the arena was just overwritten by the broadcast
   for (auto& kv : c->slots)
-    if (kv.first.compare(0, 6, "clipv.") != 0) kv.second.loaded = true;      // the image tower is no part of the arena
+    if (kv.first.compare(0, 6, "clipv.") != 0 && kv.first.compare(0, 5, "dino.") != 0) kv.second.loaded = true;      // the image tower and the DINO ViT are no part of the arena
   CK(build_ff_fold(c));             // derived after the broadcast, from the weights it delivered (a borrowing context leaves it to the owner)
   return 0;
 }
@@ -442,9 +446,10 @@ int pnpi_profile_end(pnpi_ctx* c, pnpi_kernel_stats* out) {
 
 static bool is_clipv_slot(const std::string& name) { return name.compare(0, 6, "clipv.") == 0; }      // image tower + projections (pnpi_clipv_attach)
 static bool is_clip_slot(const std::string& name) { return name.compare(0, 5, "clip.") == 0 || is_clipv_slot(name); }
+static bool is_dino_slot(const std::string& name) { return name.compare(0, 5, "dino.") == 0; }      // DINO ViT (pnpi_dino_attach)
 static int check_ready(pnpi_ctx* c) {   // UNet / VAE entry points: the text encoder's weights are optional for them
   for (auto& kv : c->slots)
-    if (!kv.second.loaded && !is_clip_slot(kv.first)) { c->err = "weights not loaded: " + kv.first; return PNPI_ESTATE; }
+    if (!kv.second.loaded && !is_clip_slot(kv.first) && !is_dino_slot(kv.first)) { c->err = "weights not loaded: " + kv.first; return PNPI_ESTATE; }
   return 0;
 }
 // Level-2 entry points (whole loops in one call): they drive unet_fwd directly with kernel descriptors, so a host attention callback
@@ -638,11 +643,13 @@ int pnpi_prox_threshold(pnpi_ctx* c, const float* eps, int nimg, int rpi, size_t
 
 // One CLIPEncoderLayer (transformers modeling_clip.py), shared by the two towers: pre-LN self-attention (causal in the text tower, full in
 // the image tower) and the quick_gelu MLP, each with its residual; x [n * T][H] is updated in place.  rows: identity row table [n][4].
-static int clip_encoder_layer(pnpi_ctx* c, const ClipLayerW& L, half_t* x, int n, int T, int H, int heads, int I, int causal, const int* rows) {
+// DINO's Block (vision_transformer.py) is the same layer with ln_eps = 1e-6 and the erf-form GELU (gelu_erf = 1).
+static int clip_encoder_layer(pnpi_ctx* c, const ClipLayerW& L, half_t* x, int n, int T, int H, int heads, int I, int causal, const int* rows,
+                              float ln_eps = 1e-5f, int gelu_erf = 0) {
   const int M = n * T, dh = H / heads, ldv = round_up_i(T, 8);
   const size_t mk = c->temp.mark();
   half_t* h1 = talloc(c, (size_t)M * H);
-  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x, M, H, 1e-5f, L.ln1.g, L.ln1.b, h1, c->st));
+  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x, M, H, ln_eps, L.ln1.g, L.ln1.b, h1, c->st));
   half_t* qk = talloc(c, (size_t)M * 2 * H);
   half_t* vt = talloc(c, (size_t)n * H * ldv);
   {
@@ -659,10 +666,10 @@ static int clip_encoder_layer(pnpi_ctx* c, const ClipLayerW& L, half_t* x, int n
   half_t* x1 = talloc(c, (size_t)M * H);
   CK(op_gemm(c, ao, H, M, H, L.out.w, H, H, L.out.b, x, H, x1, H));
   half_t* h2 = talloc(c, (size_t)M * H);
-  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x1, M, H, 1e-5f, L.ln2.g, L.ln2.b, h2, c->st));
+  if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)H * 2.0, launch_layernorm(x1, M, H, ln_eps, L.ln2.g, L.ln2.b, h2, c->st));
   half_t* f = talloc(c, (size_t)M * I);
   CK(op_gemm(c, h2, H, M, H, L.fc1.w, H, I, L.fc1.b, nullptr, 0, f, I));
-  if (!c->dry) CK(launch_quick_gelu(f, (size_t)M * I, c->st));
+  if (!c->dry) CK(gelu_erf ? launch_gelu_erf(f, (size_t)M * I, c->st) : launch_quick_gelu(f, (size_t)M * I, c->st));
   CK(op_gemm(c, f, I, M, I, L.fc2.w, I, H, L.fc2.b, x1, H, x, H));    // x <- x1 + mlp (x's old value is dead)
   c->temp.release(mk);
   return 0;
@@ -695,6 +702,7 @@ int pnpi_text_encode(pnpi_ctx* c, const int32_t* input_ids, int n, float* hidden
 }
 
 #include "api_clipscore.inc"
+#include "api_structdist.inc"
 
 // ---------------------------------------------------------------------------------------------------- kernel-level ops
 static int conv_hook(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int H, int W, int ksize, int stride, int pad, int ups,

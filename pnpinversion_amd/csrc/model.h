@@ -153,6 +153,27 @@ struct ClipVisionW {
   uint8_t* tmp_u8 = nullptr; size_t tmp_bytes = 0;   // the horizontal pass's output [n][S][out][3], grown on demand
 };
 
+// DINO ViT for the structure distance (pnpi_dino_attach; facebookresearch/dino vision_transformer.py).  Like the CLIP image tower,
+// everything it owns lives outside the context's own arenas.
+struct DinoW {
+  pnpi_dino_config cfg;
+  int max_pairs = 0, max_images = 0;      // images per call = 2 * max_pairs
+  int G = 0, NP = 0, T = 0, K = 0;        // patch grid side, patches, tokens (NP + 1), patch-row length 3 * patch^2
+  Bump arena;                             // weights (own allocation)
+  Bump persist, temp;                     // activation workspaces of the forward (swapped into the context while it runs)
+  Bump bufs;                              // small persistent buffers below
+  half_t* w_patch = nullptr;              // [W][K] patch embedding, (c, ky, kx) columns
+  float* b_patch = nullptr;               // [W]
+  float* cls = nullptr;                   // [W]
+  float* pos = nullptr;                   // [T][W]
+  std::vector<ClipLayerW> layers;         // blocks 0 .. layers - 2 in full; of the last block only ln1, w_qkv, b_qkv exist
+  int* rows_ident = nullptr;              // [max_images][4]
+  half_t* keys16 = nullptr;               // [max_images][T][W]: the last block's keys
+  // resize taps per source size (built on the host at first use): idx0 | idx1 [out] ints, lam [out] floats, one allocation each
+  struct ResizeTab { int S, out; int* idx; float* lam; };
+  std::vector<ResizeTab> tabs;
+};
+
 struct Tensor4 { half_t* p; int B, H, W, C; };
 
 struct CtrlDev {
@@ -234,7 +255,7 @@ struct pnpi_ctx {
   std::string err;
   int max_rows, max_vae;
   bool dry = false;             // sizing run: the graphs allocate and count, nothing is launched (DryScope)
-  UNetFlight* fw = nullptr;     // the UNet forward in flight (set and cleared by unet_fwd alone); nullptr in every other graph
+  UNetFlight* fw = nullptr;     // the UNet forward in flight (set and cleared by unet_fwd; the DINO forward sets one for its GEMM pin alone); nullptr in every other graph
   Bump warena, persist, temp, ctrl_arena;
   struct AugBias { float* p; int heads, Dp, dh; };
   std::vector<AugBias> aug_biases;                  // the b_qkv_aug vectors of this build (filled after the arena exists)
@@ -266,6 +287,8 @@ struct pnpi_ctx {
   VaeW vae;
   ClipW clip;
   ClipVisionW* cv = nullptr;   // pnpi_clipv_attach; nullptr: no image tower
+  DinoW* dino = nullptr;       // pnpi_dino_attach; nullptr: no DINO ViT
+  float* ss_ws = nullptr; size_t ss_ws_floats = 0;   // norms and partial sums of the self-similarity distance (grown on demand)
   int* rows_ident = nullptr;  // [max(max_rows, 8)][4] identity attention-row table (text encoder)
   int rows_ident_n = 0;
   std::vector<float> ac;

@@ -126,6 +126,25 @@ int launch_clip_gather_rows(const half_t* x, int n, int T, int H, const int* ids
 int launch_clip_cosine(const float* a, const float* b, int n, int D, float* out, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
+// DINO structure distance (structdist.hip): preprocessing, token assembly, exact GELU, the fused key self-similarity distance
+// ---------------------------------------------------------------------------------------------------------------
+// Two-tap bilinear resize (taps idx0 / idx1 / lam [out] from the host, PyTorch align_corners = False) of img [n][S][S][3] (* mask
+// [n][S][S] 0 / 1, nullable) -> resized fp32 [n][3][out][out] in 0..255 (nullable) and / or (v - mean) / std as fp16 patch rows
+// [n][(out / patch)^2][3 * patch^2] in (c, ky, kx) order (nullable); patch even
+int launch_dino_preprocess(const uint8_t* img, const uint8_t* mask, int n, int S, int out, const int* idx0, const int* idx1, const float* lam,
+                           int patch, float* resized, half_t* patches, hipStream_t st);
+// x [n][NP + 1][W]: row 0 = cls + pos[0], row 1 + p = pe[n][p] + bias + pos[1 + p] (fp32 sums, one rounding); W % 8 == 0
+int launch_dino_assemble_tokens(const half_t* pe, const float* bias, const float* cls, const float* pos, int n, int NP, int W, half_t* x,
+                                hipStream_t st);
+int launch_gelu_erf(half_t* x, size_t n, hipStream_t st);      // erf-form GELU in place (gelu_f); n % 8 == 0, x 16-byte aligned
+// dist[p] = mean over T^2 of (sim(keys_a[p]) - sim(keys_b[p]))^2, sim[i][j] = x_i . x_j / max(|x_i| |x_j|, 1e-8); keys fp16 [n][T][D],
+// D % 32 == 0, 16-byte aligned; scratch: keys_selfsim_scratch_floats(n, T) floats; dist (nullable) needs keys_b; sim_a (nullable):
+// fp32 [n][T][T], the map of keys_a.  Fixed reduction order, no atomics.
+size_t keys_selfsim_scratch_floats(int n, int T);
+int launch_keys_selfsim_mse(const half_t* keys_a, const half_t* keys_b, int n, int T, int D, float* scratch, float* dist, float* sim_a,
+                            hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------------------
 // Attention
 // ---------------------------------------------------------------------------------------------------------------
 // Key order of a "permuted" V^T (GemmP::vt_perm16 / AttnP::vt_perm): inside every aligned group of 16 tokens the two middle quads are

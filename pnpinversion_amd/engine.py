@@ -180,12 +180,13 @@ class NativeEngine:
         return t.to(device=self.device, dtype=torch.float32).contiguous()
 
     # ---- weights
-    def load_state_dict(self, unet_sd=None, vae_sd=None, chunk_bytes=1 << 30, clip_sd=None, clipv_sd=None):
+    def load_state_dict(self, unet_sd=None, vae_sd=None, chunk_bytes=1 << 30, clip_sd=None, clipv_sd=None, dino_sd=None):
         """diffusers-layout state dicts (CPU or GPU tensors, fp32 or fp16); repacked on the device into the fp16 arena.
         clip_sd: transformers CLIPTextModel state dict (optional; only pnpi_text_encode needs it).
-        clipv_sd: transformers CLIPModel keys of the image tower and the two projections (after clipv_attach; see load_clipv_state_dict)."""
+        clipv_sd: transformers CLIPModel keys of the image tower and the two projections (after clipv_attach; see load_clipv_state_dict).
+        dino_sd: facebookresearch/dino VisionTransformer keys (after dino_attach; see load_dino_state_dict)."""
         items = []
-        for prefix, sd in (("unet.", unet_sd), ("vae.", vae_sd), ("clip.", clip_sd), ("clipv.", clipv_sd)):
+        for prefix, sd in (("unet.", unet_sd), ("vae.", vae_sd), ("clip.", clip_sd), ("clipv.", clipv_sd), ("dino.", dino_sd)):
             if sd:
                 items += [(prefix + k, v) for k, v in sd.items()]
         batch, keep, size = [], [], 0
@@ -445,6 +446,62 @@ class NativeEngine:
         out = torch.empty(img.shape[0], device=self.device)
         self._call("pnpi_clip_score", _p(img), _p(m), _p(ids), img.shape[0], img.shape[1], _p(out))
         return out
+
+    # ---- DINO structure distance (pnpi_dino_attach and the entry points behind it; structure_distance.StructureDistance is the user-facing object)
+    def dino_attach(self, cfg=None, max_pairs=4):
+        """Attach the DINO ViT (cfg: _capi.DinoConfig, default ViT-B/8) for up to max_pairs image pairs (2 * max_pairs images) per call."""
+        if cfg is None:
+            cfg = _capi.DinoConfig()
+            self.lib.pnpi_dino_config_vitb8(C.byref(cfg))
+        self._call("pnpi_dino_attach", C.byref(cfg), int(max_pairs))
+        self.dino_cfg, self.dino_max_pairs = cfg, int(max_pairs)
+
+    def load_dino_state_dict(self, sd):
+        """DINO's own state-dict keys.  The tensors the metric never reads (the last block's attn.proj / norm2 / mlp, norm.*, head.*) are dropped."""
+        self.load_state_dict(dino_sd=dict(sd))
+
+    def dino_tokens(self):
+        return (self.dino_cfg.image_size // self.dino_cfg.patch) ** 2 + 1
+
+    def dino_preprocess(self, images, masks=None, out_size=None, want_resized=True, want_patches=True):
+        """pnpi_op_dino_preprocess -> (resized fp32 [n, 3, out, out] in 0..255 or None, patch rows fp16 [n, (out / patch)^2, 3 patch^2] or None)"""
+        img, m = self._clip_images(images, masks)
+        n, S = img.shape[0], img.shape[1]
+        out = int(out_size or self.dino_cfg.image_size)
+        p = self.dino_cfg.patch
+        res = torch.empty(n, 3, out, out, dtype=torch.float32, device=self.device) if want_resized else None
+        pat = torch.empty(n, max(out // p, 1) ** 2, 3 * p * p, dtype=torch.float16, device=self.device) if want_patches else None
+        self._call("pnpi_op_dino_preprocess", _p(img), _p(m), n, S, out, _p(res), _p(pat))
+        return res, pat
+
+    def dino_keys(self, images, masks=None):
+        """-> fp32 [n, T, width]: the concatenated keys of the last block (the output of blocks[-1].attn.qkv, K third)"""
+        img, m = self._clip_images(images, masks)
+        out = torch.empty(img.shape[0], self.dino_tokens(), self.dino_cfg.width, device=self.device)
+        self._call("pnpi_dino_keys", _p(img), _p(m), img.shape[0], img.shape[1], _p(out))
+        return out
+
+    def structure_distance(self, pred, gt, mask_pred=None, mask_gt=None):
+        """-> fp32 [n]: calculate_structure_distance per pair, one tower pass over the 2 n images"""
+        a, ma = self._clip_images(pred, mask_pred)
+        b, mb = self._clip_images(gt, mask_gt)
+        if a.shape != b.shape:
+            raise ValueError("Image shapes should be the same: %s and %s" % (tuple(a.shape), tuple(b.shape)))
+        out = torch.empty(a.shape[0], device=self.device)
+        self._call("pnpi_structure_distance", _p(a), _p(ma), _p(b), _p(mb), a.shape[0], a.shape[1], _p(out))
+        return out
+
+    def keys_selfsim_mse(self, keys_a, keys_b, want_map=False):
+        """pnpi_op_keys_selfsim_mse on fp16 [n, T, D] key matrices -> (distance fp32 [n], the map of keys_a fp32 [n, T, T] or None)"""
+        ka = torch.as_tensor(keys_a).to(self.device, dtype=torch.float16).contiguous()
+        kb = torch.as_tensor(keys_b).to(self.device, dtype=torch.float16).contiguous()
+        if ka.dim() != 3 or ka.shape != kb.shape:
+            raise ValueError("keys must be two [n, T, D] tensors of one shape")
+        n, T, D = ka.shape
+        dist = torch.empty(n, device=self.device)
+        sim = torch.empty(n, T, T, device=self.device) if want_map else None
+        self._call("pnpi_op_keys_selfsim_mse", _p(ka), _p(kb), n, T, D, _p(dist), _p(sim))
+        return dist, sim
 
     def local_blend(self, latents, step_index):
         lat = self._f32(latents)

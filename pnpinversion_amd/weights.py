@@ -217,3 +217,33 @@ def clipv_state_dict(image_size=224, patch=14, width=1024, layers=24, heads=16, 
     _lin(sd, seed, "visual_projection", width, proj_dim, bias=False)
     _lin(sd, seed, "text_projection", text_hidden, proj_dim, bias=False)
     return sd
+
+
+def dino_state_dict(image_size=224, patch=8, width=768, layers=12, heads=12, intermediate=3072, seed=0):
+    """facebookresearch/dino VisionTransformer state dict (its own keys: cls_token, pos_embed, patch_embed.proj.*, blocks.N.*, norm.*),
+    seeded and fp16-representable like clipv_state_dict -- no dino_vitbase8_pretrain.pth exists offline.  The structure distance feeds
+    the ViT 0..255 pixels normalised with ImageNet mean / std (values of ~5.6e2 +- 3.3e2, up to 1.13e3), so the patch embedding is scaled
+    to give O(1) tokens from them: |w| uniform in 0.8e-4 .. 2.4e-4 with a random sign (rms 1.7e-4 -> tokens of ~1.5 rms over 3 p^2 = 192
+    inputs; the scale follows 192 / fan_in for other patch sizes).  Every weight stays in fp16's normal range, above 6.1e-5."""
+    del heads                                        # the head count shapes no tensor
+    sd = {}
+    T = (image_size // patch) ** 2 + 1
+    K = 3 * patch * patch
+    sd["cls_token"] = torch.from_numpy(_fp16_round(_gen(seed, "dino.cls").standard_normal((1, 1, width)).astype(np.float32) * 0.5))
+    sd["pos_embed"] = torch.from_numpy(_fp16_round(_gen(seed, "dino.pos").standard_normal((1, T, width)).astype(np.float32) * 0.5))
+    g = _gen(seed, "dino.patch_embed.proj.weight")
+    mag = g.uniform(0.8e-4, 2.4e-4, size=(width, 3, patch, patch)) * np.sqrt(192.0 / K)
+    sign = np.where(g.integers(0, 2, size=mag.shape) == 0, -1.0, 1.0)
+    sd["patch_embed.proj.weight"] = torch.from_numpy(_fp16_round((mag * sign).astype(np.float32)))
+    _b(sd, seed, "dino.patch_embed.proj.bias", width)
+    sd["patch_embed.proj.bias"] = sd.pop("dino.patch_embed.proj.bias")
+    for l in range(layers):
+        pre = "blocks.%d" % l
+        _norm(sd, seed, pre + ".norm1", width)
+        _lin(sd, seed, pre + ".attn.qkv", width, 3 * width, gain=1.2)
+        _lin(sd, seed, pre + ".attn.proj", width, width, gain=0.5)
+        _norm(sd, seed, pre + ".norm2", width)
+        _lin(sd, seed, pre + ".mlp.fc1", width, intermediate)
+        _lin(sd, seed, pre + ".mlp.fc2", intermediate, width, gain=0.5)
+    _norm(sd, seed, "norm", width)
+    return sd
