@@ -654,6 +654,15 @@ int pnpi_op_groupnorm_stats(pnpi_ctx* ctx, const void* x1, const void* x2, int C
 int pnpi_op_layernorm(pnpi_ctx* ctx, const void* x, int M, int C, float eps, const float* gamma, const float* beta, void* out);
 int pnpi_op_geglu(pnpi_ctx* ctx, const void* x, int M, int inner, void* out);
 int pnpi_op_softmax_rows(pnpi_ctx* ctx, void* x, int M, int N, int ld);
+/* kernel-level: launchers that no other entry point reaches on their own.  softmax_rows_f32: in place over [M][N] contiguous fp32 rows
+ * (the materialised attention scores of the controller call-back and of the backward).  f32_rows_to_f16_padded: in [M][N] fp32 -> out
+ * [M][ld] fp16, columns N .. ld zero (ld >= N).  gemv: out[n] = bias[n] + bias2[n] + sum_k act(x[k]) w[n][k] with x fp32 [K], w fp16
+ * [N][K], act = SiLU where silu_in != 0, K % 8 == 0; bias and bias2 nullable (the time-embedding MLP).  M, N, K <= 0: PNPI_EINVAL, as in
+ * pnpi_op_geglu and pnpi_op_softmax_rows. */
+int pnpi_op_softmax_rows_f32(pnpi_ctx* ctx, float* x, int M, int N);
+int pnpi_op_f32_rows_to_f16_padded(pnpi_ctx* ctx, const float* in, int M, int N, int ld, void* out_f16);
+int pnpi_op_gemv(pnpi_ctx* ctx, const float* x, int K, const void* w_f16, int N, const float* bias, const float* bias2, int silu_in,
+                 float* out);
 /* Activation-gradient kernels of the null-text / null-latent path (NullInversion.null_optimization's loss.backward(), inversion.py:
  * 196-225) -- groundwork, kernel-level only (no method string reaches them yet).  fp16 tensors in the forward's layouts.
  *   layernorm_bwd: dx of torch.nn.LayerNorm from the saved input;  groupnorm_bwd: dx (dense [B][HW][C1+C2]) of GroupNorm(+SiLU) over the

@@ -182,6 +182,9 @@ SYMBOLS = {
     "pnpi_op_layernorm": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     "pnpi_op_geglu": (_i, [_vp, _vp, _i, _i, _vp]),
     "pnpi_op_softmax_rows": (_i, [_vp, _vp, _i, _i, _i]),
+    "pnpi_op_softmax_rows_f32": (_i, [_vp, _vp, _i, _i]),
+    "pnpi_op_f32_rows_to_f16_padded": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "pnpi_op_gemv": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "pnpi_op_layernorm_bwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "pnpi_op_groupnorm_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
     "pnpi_op_groupnorm_bwd_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.c_size_t]),

@@ -801,11 +801,33 @@ int pnpi_op_layernorm(pnpi_ctx* c, const void* x, int M, int C, float eps, const
   return 0;
 }
 int pnpi_op_geglu(pnpi_ctx* c, const void* x, int M, int inner, void* out) {
+  if (!c || !x || !out || M <= 0 || inner <= 0) return PNPI_EINVAL;      // (a zero-block grid otherwise)
   CK(launch_geglu((const half_t*)x, M, inner, (half_t*)out, c->st));
   return 0;
 }
 int pnpi_op_softmax_rows(pnpi_ctx* c, void* x, int M, int N, int ld) {
+  if (!c || !x || M <= 0 || N <= 0) return PNPI_EINVAL;
+  if (ld < N) return fail(c, PNPI_ESHAPE, "softmax_rows: ld < N");
   CK(launch_softmax_rows((half_t*)x, M, N, ld, c->st));
+  return 0;
+}
+/* kernel-level forms of three launchers no other entry point reaches on their own (tests/test_gpu_norm_fwd_instances.py): the fp32 row
+ * softmax and the padded fp16 conversion of the materialised attention path (controller call-back, attention backward), and the GEMV of
+ * the time-embedding MLP. */
+int pnpi_op_softmax_rows_f32(pnpi_ctx* c, float* x, int M, int N) {
+  if (!c || !x || M <= 0 || N <= 0) return PNPI_EINVAL;
+  CK(launch_softmax_rows_f32(x, (size_t)M, N, c->st));
+  return 0;
+}
+int pnpi_op_f32_rows_to_f16_padded(pnpi_ctx* c, const float* in, int M, int N, int ld, void* out) {
+  if (!c || !in || !out || M <= 0 || N <= 0) return PNPI_EINVAL;
+  if (ld < N) return fail(c, PNPI_ESHAPE, "f32_rows_to_f16_padded: ld < N");
+  CK(launch_f32_rows_to_f16_padded(in, (size_t)M, N, ld, (half_t*)out, c->st));
+  return 0;
+}
+int pnpi_op_gemv(pnpi_ctx* c, const float* x, int K, const void* w, int N, const float* bias, const float* bias2, int silu_in, float* out) {
+  if (!c || !x || !w || !out || K <= 0 || N <= 0) return PNPI_EINVAL;
+  CK(launch_gemv(x, K, (const half_t*)w, N, bias, bias2, silu_in, out, c->st));
   return 0;
 }
 /* pnpi_op_attention_bwd with what the recording forward left (kernel tests of the hand-over): lse_fwd [B][heads][Nq] log2-domain

@@ -11,8 +11,10 @@
 // Three launches, all latency-lean:
 //   gn_stats    (B x nchunk blocks)  per-chunk partial (sum, sumsq) per group; each thread owns a fixed 8-channel vector and walks
 //                                    pixels four at a time (independent loads in flight); fixed-order reduction, no atomics
-//   gn_finalize (B blocks)           partials -> per-channel scale = rstd*gamma, shift = beta - mean*scale   ([B][C][2] fp32)
-//   gn_apply    (B x napply blocks)  y = x*scale + shift (+SiLU), 16-byte accesses
+//   gn_finalize (B blocks)           partials -> per-channel (scale = rstd*gamma, mean)   ([B][C][2] fp32)
+//   gn_apply    (B x napply blocks)  y = (x - mean)*scale + beta (+SiLU), 16-byte accesses.  Not x*scale + (beta - mean*scale): the shift
+//                                    is rounded at the magnitude of mean*scale, which a group of (nearly) constant values makes
+//                                    |mean| / sqrt(eps) -- an absolute error of 6e-5 on outputs of the size of beta at mean = -2, eps = 1e-6
 __global__ void __launch_bounds__(256) gn_stats_kernel(const half_t* __restrict__ x1, const half_t* __restrict__ x2, int C1,
                                                        int C2, int HW, int G, int nchunk, float* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -73,10 +75,9 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const half_t* __restrict_
   }
 }
 
-// One block per batch row: 8 lanes per group sum the chunk partials (fixed order), then scale/shift for every channel.
+// One block per batch row: 8 lanes per group sum the chunk partials (fixed order), then (scale, mean) for every channel.
 __global__ void __launch_bounds__(256) gn_finalize_kernel(const float* __restrict__ partial, int C, int HW, int G, int nchunk,
-                                                          float eps, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float* __restrict__ ss) {
+                                                          float eps, const float* __restrict__ gamma, float* __restrict__ ss) {
   __shared__ float s_mean[64], s_rstd[64];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int cpg = C / G;
@@ -103,18 +104,17 @@ __global__ void __launch_bounds__(256) gn_finalize_kernel(const float* __restric
   __syncthreads();
   for (int c = tid; c < C; c += blockDim.x) {
     int g = c / cpg;
-    float sc = s_rstd[g] * gamma[c];
-    ss[((size_t)b * C + c) * 2 + 0] = sc;
-    ss[((size_t)b * C + c) * 2 + 1] = beta[c] - s_mean[g] * sc;
+    ss[((size_t)b * C + c) * 2 + 0] = s_rstd[g] * gamma[c];
+    ss[((size_t)b * C + c) * 2 + 1] = s_mean[g];
   }
 }
 
-// y = x * scale + shift (+ SiLU).  A thread owns one 8-channel vector position (its 16 scale / shift values stay in registers)
+// y = (x - mean) * scale + beta (+ SiLU).  A thread owns one 8-channel vector position (its scale / mean / beta values stay in registers)
 // and walks pixels, four independent 16-byte loads in flight; a block covers `ppb` consecutive pixels of one batch item, so a
 // wavefront reads and writes whole contiguous rows.  No LDS, no barrier.
 __global__ void __launch_bounds__(256) gn_apply_kernel(const half_t* __restrict__ x1, const half_t* __restrict__ x2, int C1,
-                                                       int C2, int HW, int ppb, const float* __restrict__ ss, int silu,
-                                                       half_t* __restrict__ out) {
+                                                       int C2, int HW, int ppb, const float* __restrict__ ss,
+                                                       const float* __restrict__ beta, int silu, half_t* __restrict__ out) {
   const int C = C1 + C2, C8 = C >> 3;
   const int CL = C8 < 256 ? C8 : 256, TP = 256 / CL;
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -123,11 +123,13 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const half_t* __restrict_
   const int p0 = blockIdx.y * ppb, p1 = min(HW, p0 + ppb);
   for (int cv = tc; cv < C8; cv += CL) {
     const int c = cv * 8;
-    float sc[8], sh[8];
+    float sc[8], mn[8], be[8];
     {
       const floatx4* sp = reinterpret_cast<const floatx4*>(ss + ((size_t)b * C + c) * 2);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { floatx4 v = sp[j]; sc[2 * j] = v[0]; sh[2 * j] = v[1]; sc[2 * j + 1] = v[2]; sh[2 * j + 1] = v[3]; }
+      for (int j = 0; j < 4; ++j) { floatx4 v = sp[j]; sc[2 * j] = v[0]; mn[2 * j] = v[1]; sc[2 * j + 1] = v[2]; mn[2 * j + 1] = v[3]; }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) be[j] = beta[c + j];
     }
     const half_t* src; int ld, cc;
     if (c < C1) { src = x1; ld = C1; cc = c; } else { src = x2; ld = C2; cc = c - C1; }
@@ -137,7 +139,7 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const half_t* __restrict_
       half8 o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float f = (float)v[j] * sc[j] + sh[j];
+        float f = ((float)v[j] - mn[j]) * sc[j] + be[j];
         if (silu) f = silu_f(f);
         o[j] = (half_t)f;
       }
@@ -298,9 +300,9 @@ int launch_groupnorm(const half_t* x1, const half_t* x2, int C1, int C2, int B, 
   float* ss = partial + (size_t)B * nchunk * G * 2;
   size_t lds1 = (size_t)TP * C * 2 * sizeof(float);
   gn_stats_kernel<<<dim3(B, nchunk), 256, lds1, st>>>(x1, x2, C1, C2, HW, G, nchunk, partial);
-  gn_finalize_kernel<<<B, 256, 0, st>>>(partial, C, HW, G, nchunk, eps, gamma, beta, ss);
+  gn_finalize_kernel<<<B, 256, 0, st>>>(partial, C, HW, G, nchunk, eps, gamma, ss);
   const int ppb = gn_ppb(B, HW, C);
-  gn_apply_kernel<<<dim3(B, (HW + ppb - 1) / ppb), 256, 0, st>>>(x1, x2, C1, C2, HW, ppb, ss, silu, out);
+  gn_apply_kernel<<<dim3(B, (HW + ppb - 1) / ppb), 256, 0, st>>>(x1, x2, C1, C2, HW, ppb, ss, beta, silu, out);
   return (int)hipGetLastError();
 }
 
@@ -308,8 +310,7 @@ int launch_groupnorm(const half_t* x1, const half_t* x2, int C1, int C2, int B, 
 // One block per (batch item, group): cpg * tiles partial pairs are summed by 256 threads (fixed order: strided + tree).
 __global__ void __launch_bounds__(256) gn_finalize_tiles_kernel(const float* __restrict__ st1, int C1, int tpb1,
                                                                 const float* __restrict__ st2, int C2, int tpb2, int HW, int G,
-                                                                float eps, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, float* __restrict__ ss) {
+                                                                float eps, const float* __restrict__ gamma, float* __restrict__ ss) {
   __shared__ float s_s[4], s_q[4];
   const int C = C1 + C2, cpg = C / G;
   const int b = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
@@ -343,9 +344,8 @@ __global__ void __launch_bounds__(256) gn_finalize_tiles_kernel(const float* __r
   const float rstd = rsqrtf(var + eps);
   for (int cl = tid; cl < cpg; cl += 256) {
     const int c = g * cpg + cl;
-    const float sc = rstd * gamma[c];
-    ss[((size_t)b * C + c) * 2 + 0] = sc;
-    ss[((size_t)b * C + c) * 2 + 1] = beta[c] - mean * sc;
+    ss[((size_t)b * C + c) * 2 + 0] = rstd * gamma[c];
+    ss[((size_t)b * C + c) * 2 + 1] = mean;
   }
 }
 
@@ -391,12 +391,13 @@ __global__ void __launch_bounds__(256) gn_fin_apply_kernel(const half_t* __restr
   const int p0 = blockIdx.y * ppb, p1 = min(HW, p0 + ppb);
   for (int cv = tc; cv < C8; cv += CL) {
     const int c = cv * 8;
-    float sc[8], sh[8];
+    float sc[8], mn[8], be[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int g = (c + j) / cpg;
       sc[j] = s_rstd[g] * gamma[c + j];
-      sh[j] = beta[c + j] - s_mean[g] * sc[j];
+      mn[j] = s_mean[g];
+      be[j] = beta[c + j];
     }
     const half_t* src; int ld, cc;
     if (c < C1) { src = x1; ld = C1; cc = c; } else { src = x2; ld = C2; cc = c - C1; }
@@ -406,7 +407,7 @@ __global__ void __launch_bounds__(256) gn_fin_apply_kernel(const half_t* __restr
       half8 o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float f = (float)v[j] * sc[j] + sh[j];
+        float f = ((float)v[j] - mn[j]) * sc[j] + be[j];
         if (silu) f = silu_f(f);
         o[j] = (half_t)f;
       }
@@ -446,10 +447,10 @@ int launch_groupnorm_fused(const half_t* x1, const half_t* x2, int C1, int C2, i
                                                                      beta, silu, out);
     return (int)hipGetLastError();
   }
-  float* ss = scratch;   // [B][C][2]
-  gn_finalize_tiles_kernel<<<dim3(B, G), 256, 0, st>>>(st1, C1, tpb1, st2, C2, tpb2, HW, G, eps, gamma, beta, ss);
+  float* ss = scratch;   // [B][C][2]: (scale, mean)
+  gn_finalize_tiles_kernel<<<dim3(B, G), 256, 0, st>>>(st1, C1, tpb1, st2, C2, tpb2, HW, G, eps, gamma, ss);
   const int ppb = gn_ppb(B, HW, C);
-  gn_apply_kernel<<<dim3(B, (HW + ppb - 1) / ppb), 256, 0, st>>>(x1, x2, C1, C2, HW, ppb, ss, silu, out);
+  gn_apply_kernel<<<dim3(B, (HW + ppb - 1) / ppb), 256, 0, st>>>(x1, x2, C1, C2, HW, ppb, ss, beta, silu, out);
   return (int)hipGetLastError();
 }
 

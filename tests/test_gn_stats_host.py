@@ -4,7 +4,7 @@ computes (csrc/norm.hip: gn_finalize_tiles_kernel + gn_apply_kernel, or gn_fin_a
 The emulation: fp32 sums and sums of squares of the fp16 values over each m-tile's rows (64 / 128 / 256 rows per tile: what a
 convolution's epilogue hands over); fp32 sums of those over a group's tiles and channels in the order of either consumer (eight lanes
 per group, or 256 threads per group, each adding its share one after the other, then a tree); mean = s / n, var = max(q / n - mean^2,
-0), rstd = rsqrt(var + eps), y = x * (rstd gamma) + (beta - mean rstd gamma) in fp32, SiLU, one rounding to fp16.  The per-element
+0), rstd = rsqrt(var + eps), y = (x - mean) * (rstd gamma) + beta in fp32, SiLU, one rounding to fp16.  The per-element
 bound is  |y - ref| <= 2^-10 |ref| + 1e-3:  twice the half-ulp of the one fp16 rounding, plus an absolute floor for outputs near zero.
 
 Worst |y - ref| / bound over the tensor, observed with this file's seeds, 32 groups, SiLU on (over the three tile heights and the
@@ -82,8 +82,7 @@ def emulate(x, rows, groups, gamma, beta, eps, silu, st=None, order="lanes8"):
     var = torch.clamp(q / n - mean * mean, min=0.0)
     rstd = torch.rsqrt(var + torch.tensor(eps, dtype=torch.float32))
     sc = rstd.repeat_interleave(cpg, 1) * gamma.float()[None]             # [B, C]
-    sh = beta.float()[None] - mean.repeat_interleave(cpg, 1) * sc
-    y = x.float() * sc[:, None] + sh[:, None]
+    y = (x.float() - mean.repeat_interleave(cpg, 1)[:, None]) * sc[:, None] + beta.float()[None, None]
     if silu:
         y = y * torch.sigmoid(y)
     assert y.dtype == torch.float32
