@@ -15,10 +15,10 @@ vocab - 1 (the largest id there is) and pad with the same id, so the first maxim
 
 Real clip-vit-large-patch14 weights load through checkpoint.load_clip_model_dir; no such checkpoint exists offline, so that loader is
 untested here and the tests run seeded synthetic towers (weights.clipv_state_dict)."""
-import numpy as np
 import torch
 
 from . import _capi
+from .image_batches import chunks, stack_images, stack_masks
 
 
 class ClipScore:
@@ -51,55 +51,22 @@ class ClipScore:
         L = self.engine.cfg.ctx_len
         return torch.as_tensor(self.pipe.tokenizer(list(prompts), padding="max_length", max_length=L, truncation=True).input_ids)
 
-    @staticmethod
-    def _stack(images):
-        if isinstance(images, (list, tuple)):
-            images = np.stack([np.asarray(i) for i in images])
-        a = images if isinstance(images, torch.Tensor) else np.asarray(images)
-        return a[None] if a.ndim == 3 else a
-
-    def _chunks(self, n):
-        return [(i, min(i + self.max_images, n)) for i in range(0, n, self.max_images)]
-
     # ---- outputs
     def image_embed(self, images, masks=None):
         """uint8 [n, S, S, 3] (numpy / torch / list of PIL images), masks None or 0 / 1 [n, S, S] -> fp32 [n, proj_dim], not normalised"""
-        img = self._stack(images)
-        m = self._stack_masks(masks, img)
-        return torch.cat([self.engine.clip_image_embed(img[a:b], None if m is None else m[a:b]) for a, b in self._chunks(len(img))])
+        img = stack_images(images)
+        m = stack_masks(masks, img)
+        return torch.cat([self.engine.clip_image_embed(img[a:b], None if m is None else m[a:b]) for a, b in chunks(len(img), self.max_images)])
 
     def text_embed(self, prompts=None, input_ids=None):
         ids = self.tokenize(prompts) if input_ids is None else torch.as_tensor(input_ids)
-        return torch.cat([self.engine.clip_text_embed(ids[a:b]) for a, b in self._chunks(len(ids))])
+        return torch.cat([self.engine.clip_text_embed(ids[a:b]) for a, b in chunks(len(ids), self.max_images)])
 
     def score(self, images, prompts=None, masks=None, input_ids=None):
         """CLIPScore per (image, prompt) pair, one launch set per max_images pairs"""
-        img = self._stack(images)
-        m = self._stack_masks(masks, img)
+        img = stack_images(images)
+        m = stack_masks(masks, img)
         ids = self.tokenize(prompts) if input_ids is None else torch.as_tensor(input_ids)
         if len(ids) != len(img):
             raise ValueError("%d images but %d prompts" % (len(img), len(ids)))
-        return torch.cat([self.engine.clip_score(img[a:b], ids[a:b], None if m is None else m[a:b]) for a, b in self._chunks(len(img))])
-
-    @staticmethod
-    def _stack_masks(masks, img):
-        if masks is None:
-            return None
-        if isinstance(masks, (list, tuple)):
-            # a list may leave single entries None (whole image): those rows get a mask of ones
-            S = img.shape[1]
-            masks = np.stack([np.ones((S, S), np.uint8) if k is None else _plane(k) for k in masks])
-        m = masks if isinstance(masks, torch.Tensor) else np.asarray(masks)
-        return m[None] if m.ndim == 2 else m
-
-
-def _plane(mask):
-    """one mask as evaluate.py builds it ([S, S, 3], the plane repeated) or [S, S] -> uint8 [S, S]"""
-    a = np.asarray(mask)
-    if a.ndim == 3:
-        if not (a == a[..., :1]).all():
-            raise ValueError("a mask with different channel planes is not supported")
-        a = a[..., 0]
-    if not np.isin(a, (0, 1)).all():
-        raise ValueError("masks must hold 0 / 1 only")
-    return a.astype(np.uint8)
+        return torch.cat([self.engine.clip_score(img[a:b], ids[a:b], None if m is None else m[a:b]) for a, b in chunks(len(img), self.max_images)])

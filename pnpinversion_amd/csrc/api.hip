@@ -701,6 +701,7 @@ int pnpi_text_encode(pnpi_ctx* c, const int32_t* input_ids, int n, float* hidden
   return clip_fwd(c, (const int*)input_ids, n, hidden_out);
 }
 
+#include "api_vit.inc"
 #include "api_clipscore.inc"
 #include "api_structdist.inc"
 

@@ -1,7 +1,7 @@
-// api_clipscore.inc -- part of api.hip (one translation unit: included there behind the CLIP text encoder; not compiled on its own).
+// api_clipscore.inc -- part of api.hip (one translation unit: included there behind api_vit.inc; not compiled on its own).
 // CLIP similarity (evaluation/matrics_calculator.py:290-302): the image tower of transformers' CLIPModel attached to a context that has
-// the text tower, the two projections, CLIPProcessor's preprocessing and the score.  Everything here is allocated outside the
-// context's weight arena and workspaces; a context that never calls pnpi_clipv_attach is unchanged.
+// the text tower, the two projections, CLIPProcessor's preprocessing and the score.  What it shares with the DINO ViT (attach sequence, free, refusals,
+// token assembly) is in api_vit.inc; a context that never calls pnpi_clipv_attach is unchanged.
 // ---------------------------------------------------------------------------------------------------- PIL coefficient tables
 // precompute_coeffs + normalize_coeffs_8bpc of Pillow's libImaging/Resample.c for the bicubic filter (a = -0.5, support 2), in double
 // as there: the filter's support is stretched by the scale factor on a downscale (antialiasing), the weights of one output pixel
@@ -44,30 +44,24 @@ static int pil_bicubic_tables(int in_size, int out_size, std::vector<int>& bound
 }
 
 // ---------------------------------------------------------------------------------------------------- attach / free
-static void clipv_erase_slots(pnpi_ctx* c) {
-  for (auto it = c->slots.begin(); it != c->slots.end();) {
-    if (is_clipv_slot(it->first)) it = c->slots.erase(it); else ++it;
-  }
-}
 static void clipv_free(pnpi_ctx* c) {
   ClipVisionW* v = c->cv;
   if (!v) return;
+  tower_free(c, v);
   for (auto& t : v->tabs) { (void)hipFree(t.bounds); (void)hipFree(t.coef); }
-  void* bufs[] = {v->arena.base, v->persist.base, v->temp.base, v->bufs.base, v->tmp_u8};
-  for (void* b : bufs) (void)hipFree(b);
-  clipv_erase_slots(c);
+  (void)hipFree(v->tmp_u8);
   delete v;
   c->cv = nullptr;
 }
 
-// the tower's weight slots, allocated from v->arena through the context's own slot helpers (the arenas trade places for the build)
-static void clipv_build(pnpi_ctx* c, ClipVisionW* v) {
-  std::swap(c->warena, v->arena);
+// the tower's weight slots, through the context's own slot helpers (under TowerArena)
+static void clipv_build(pnpi_ctx* c) {
+  ClipVisionW* v = c->cv;
   const pnpi_clipv_config& g = v->cfg;
   const int W = g.width, P = g.proj_dim, Ht = c->clip.H, K = 3 * g.patch * g.patch;
   const std::string vm = "clipv.vision_model.";
-  v->w_patch = walloc_h(c, (size_t)W * v->Kp);
-  reg_mat(c, vm + "embeddings.patch_embedding.weight", v->w_patch, W, K, 1, v->Kp, K);      // [W][3][p][p] flattened = (c, ky, kx) columns
+  v->w_patch = walloc_h(c, (size_t)W * v->K);
+  reg_mat(c, vm + "embeddings.patch_embedding.weight", v->w_patch, W, K, 1, v->K, K);      // [W][3][p][p] flattened = (c, ky, kx) columns
   v->cls = walloc_f(c, W);
   reg_vec(c, vm + "embeddings.class_embedding", v->cls, W);
   v->pos = walloc_f(c, (size_t)v->T * W);
@@ -97,15 +91,19 @@ static void clipv_build(pnpi_ctx* c, ClipVisionW* v) {
   reg_mat(c, "clipv.visual_projection.weight", v->w_vproj, P, W, 1, W, W);
   v->w_tproj = walloc_h(c, (size_t)P * Ht);
   reg_mat(c, "clipv.text_projection.weight", v->w_tproj, P, Ht, 1, Ht, Ht);
-  std::swap(c->warena, v->arena);
 }
-
-// the image forward's workspaces take the place of the context's for its duration (palloc / talloc / op_gemm work on c->persist / c->temp)
-struct ClipvWorkspace {
-  pnpi_ctx* c; ClipVisionW* v;
-  ClipvWorkspace(pnpi_ctx* c_, ClipVisionW* v_) : c(c_), v(v_) { std::swap(c->persist, v->persist); std::swap(c->temp, v->temp); }
-  ~ClipvWorkspace() { std::swap(c->persist, v->persist); std::swap(c->temp, v->temp); }
-};
+// the tower's own small buffers
+static void clipv_bufs(pnpi_ctx* c, Bump& b) {
+  ClipVisionW* v = c->cv;
+  const size_t N = v->max_images, W = v->W, P = v->cfg.proj_dim, Ht = c->clip.H;
+  v->pool_img = (half_t*)b.alloc(N * W * sizeof(half_t));
+  v->ln_img = (half_t*)b.alloc(N * W * sizeof(half_t));
+  v->emb_img16 = (half_t*)b.alloc(N * P * sizeof(half_t));
+  v->pool_txt = (half_t*)b.alloc(N * Ht * sizeof(half_t));
+  v->emb_txt16 = (half_t*)b.alloc(N * P * sizeof(half_t));
+  v->emb_img = (float*)b.alloc(N * P * sizeof(float));
+  v->emb_txt = (float*)b.alloc(N * P * sizeof(float));
+}
 
 static int clipv_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int S, int out, uint8_t* resized, half_t* patches);
 
@@ -114,21 +112,16 @@ static int clipv_fwd(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n
   ClipVisionW* v = c->cv;
   const pnpi_clipv_config& g = v->cfg;
   const int W = g.width, T = v->T, NP = v->NP, M = n * T;
-  ClipvWorkspace ws(c, v);
+  TowerWorkspace ws(c, v);
   c->persist.reset(); c->temp.reset();
-  half_t* patches = palloc(c, (size_t)n * NP * v->Kp);
+  half_t* patches = palloc(c, (size_t)n * NP * v->K);
   if (!c->dry) CKP(clipv_preprocess(c, img, mask, n, S, g.image_size, nullptr, patches));
   half_t* x = palloc(c, (size_t)M * W);
   {
     const size_t mk = c->temp.mark();
-    half_t* pe = talloc(c, (size_t)n * NP * W);      // the bias-free stride-p convolution as a GEMM over patch rows (pad columns zero in both operands)
-    CK(op_gemm(c, patches, v->Kp, n * NP, v->Kp, v->w_patch, v->Kp, W, nullptr, nullptr, 0, pe, W, 1.f, nullptr,
-               2.0 * n * NP * (double)W * 3 * g.patch * g.patch));
     half_t* xa = talloc(c, (size_t)M * W);
-    if (!c->dry) {
-      CK(launch_clip_assemble_tokens(pe, v->cls, v->pos, n, NP, W, xa, c->st));
-      PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)W * 2.0, launch_layernorm(xa, M, W, 1e-5f, v->pre_ln.g, v->pre_ln.b, x, c->st));
-    }
+    CKP(vit_tokens(c, v, patches, n, 2.0 * n * NP * (double)W * 3 * g.patch * g.patch, xa));      // the pad columns do no work
+    if (!c->dry) PROF(PNPI_KC_LAYERNORM, 0.0, 2.0 * M * (double)W * 2.0, launch_layernorm(xa, M, W, 1e-5f, v->pre_ln.g, v->pre_ln.b, x, c->st));
     c->temp.release(mk);
   }
   for (const ClipLayerW& L : v->layers) CKP(clip_encoder_layer(c, L, x, n, T, W, g.heads, g.intermediate, 0, v->rows_ident));
@@ -140,6 +133,8 @@ static int clipv_fwd(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n
   if (c->persist.overflow || c->temp.overflow) return fail(c, PNPI_ENOMEM, "workspace overflow (CLIP image tower)");
   return 0;
 }
+
+static int clipv_dry_fwd(pnpi_ctx* c) { return clipv_fwd(c, nullptr, nullptr, c->cv->max_images, c->cv->cfg.image_size, c->cv->emb_img16); }
 
 // get_text_features: the text tower in chunks of what its row table holds, the EOS rows, text_projection: emb16 [n][proj] fp16
 static int clipv_text_fwd(pnpi_ctx* c, const int32_t* ids, int n, half_t* emb16) {
@@ -162,18 +157,7 @@ static int clipv_check_attached(pnpi_ctx* c) {
   return 0;
 }
 static int clipv_check_weights(pnpi_ctx* c, bool text_too) {
-  std::vector<std::string> miss;
-  for (auto& kv : c->slots)
-    if (!kv.second.loaded && is_clipv_slot(kv.first)) miss.push_back(kv.first);
-  if (!miss.empty()) {
-    std::sort(miss.begin(), miss.end());
-    c->err = "CLIP image tower weights not loaded (" + std::to_string(miss.size()) + "):";
-    for (const std::string& m : miss) {
-      if (c->err.size() + m.size() > 3800) { c->err += " ..."; break; }
-      c->err += " " + m;
-    }
-    return PNPI_ESTATE;
-  }
+  CKP(tower_check_weights(c, c->cv));
   if (text_too) CKP(check_clip_ready(c));
   return 0;
 }
@@ -182,14 +166,7 @@ static int clipv_check_images(pnpi_ctx* c, const uint8_t* img, const uint8_t* ma
   if (!img) return fail(c, PNPI_EINVAL, "img_hwc is NULL");
   if (n <= 0 || n > v->max_images) return fail(c, PNPI_EINVAL, "n must be 1 .. max_images of pnpi_clipv_attach");
   if (S < out || S > 8192) return fail(c, PNPI_ESHAPE, "unsupported image side: square S with image_size <= S <= 8192");
-  if (mask) {      // uint8(img * mask) is a keep / clear choice only for 0 / 1: read the masks back and look
-    const size_t nb = (size_t)n * S * S;
-    c->host_stage.resize(nb);
-    CKH(hipStreamSynchronize(c->st));
-    CKH(hipMemcpy(c->host_stage.data(), mask, nb, hipMemcpyDefault));
-    for (size_t i = 0; i < nb; ++i)
-      if ((unsigned char)c->host_stage[i] > 1) return fail(c, PNPI_EINVAL, "mask_hw holds a value other than 0 / 1");
-  }
+  if (mask) CKP(check_mask01(c, mask, (size_t)n * S * S));
   return 0;
 }
 // the device tables for S -> out and the horizontal pass's buffer; allocations and copies only, no launch
@@ -202,10 +179,10 @@ static int clipv_resize_prepare(pnpi_ctx* c, int n, int S, int out, const ClipVi
     ClipVisionW::ResizeTab t; t.S = S; t.out = out; t.bounds = nullptr; t.coef = nullptr;
     t.ksize = pil_bicubic_tables(S, out, bounds, coef);
     CKH(hipMalloc((void**)&t.bounds, bounds.size() * sizeof(int)));
-    CKH(hipMalloc((void**)&t.coef, coef.size() * sizeof(int)));
+    if (hipMalloc((void**)&t.coef, coef.size() * sizeof(int)) != hipSuccess) { (void)hipFree(t.bounds); return fail(c, PNPI_ENOMEM, "resize tables: allocation failed"); }
+    v->tabs.push_back(t);      // owned by the tower from here on (clipv_free)
     CKH(hipMemcpy(t.bounds, bounds.data(), bounds.size() * sizeof(int), hipMemcpyHostToDevice));
     CKH(hipMemcpy(t.coef, coef.data(), coef.size() * sizeof(int), hipMemcpyHostToDevice));
-    v->tabs.push_back(t);
     tab = &v->tabs.back();
   }
   const size_t need = (size_t)n * S * out * 3;
@@ -223,8 +200,7 @@ static int clipv_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask
   const ClipVisionW::ResizeTab* t = nullptr;
   CKP(clipv_resize_prepare(c, n, S, out, &t));
   CK(launch_clip_resize_h(img, mask, n, S, out, t->bounds, t->coef, t->ksize, v->tmp_u8, c->st));
-  CK(launch_clip_resize_v(v->tmp_u8, n, S, out, t->bounds, t->coef, t->ksize, v->cfg.patch, round_up_i(3 * v->cfg.patch * v->cfg.patch, 64),
-                          resized, patches, c->st));
+  CK(launch_clip_resize_v(v->tmp_u8, n, S, out, t->bounds, t->coef, t->ksize, v->cfg.patch, v->K, resized, patches, c->st));
   return 0;
 }
 
@@ -261,58 +237,10 @@ int pnpi_clipv_attach(pnpi_ctx* c, const pnpi_clipv_config* g, int max_images) {
   if (g->layers <= 0 || g->layers > 48 || g->intermediate <= 0 || g->intermediate % 8 || g->proj_dim <= 0 || g->proj_dim % 8)
     return fail(c, PNPI_ESHAPE, "layers must be 1 .. 48, intermediate and proj_dim multiples of 8");
   ClipVisionW* v = new ClipVisionW();
-  v->cfg = *g; v->max_images = max_images;
-  v->G = g->image_size / g->patch; v->NP = v->G * v->G; v->T = v->NP + 1; v->Kp = round_up_i(3 * g->patch * g->patch, 64);
+  v->name = "CLIP image tower"; v->prefix = "clipv.";
+  v->cfg = *g; v->max_images = max_images; v->W = g->width;
   c->cv = v;
-  auto bail = [&](int status, const char* what) { clipv_free(c); return fail(c, status, what); };
-  // weights: pass 1 measures, pass 2 places
-  clipv_build(c, v);
-  const size_t wbytes = align_up(v->arena.peak + 4096, 4096);
-  v->arena = Bump();
-  if (hipMalloc((void**)&v->arena.base, wbytes) != hipSuccess) return bail(PNPI_ENOMEM, "pnpi_clipv_attach: weight allocation failed");
-  v->arena.cap = wbytes;
-  if (hipMemsetAsync(v->arena.base, 0, wbytes, c->st) != hipSuccess) return bail(PNPI_EHIP, "pnpi_clipv_attach: memset failed");      // the pad columns of the patch embedding
-  clipv_build(c, v);
-  // small persistent buffers
-  const int W = g->width, P = g->proj_dim, Ht = c->clip.H;
-  for (int pass = 0; pass < 2; ++pass) {
-    Bump& b = v->bufs;
-    b.reset();
-    v->rows_ident = (int*)b.alloc((size_t)max_images * 4 * sizeof(int));
-    v->pool_img = (half_t*)b.alloc((size_t)max_images * W * sizeof(half_t));
-    v->ln_img = (half_t*)b.alloc((size_t)max_images * W * sizeof(half_t));
-    v->emb_img16 = (half_t*)b.alloc((size_t)max_images * P * sizeof(half_t));
-    v->pool_txt = (half_t*)b.alloc((size_t)max_images * Ht * sizeof(half_t));
-    v->emb_txt16 = (half_t*)b.alloc((size_t)max_images * P * sizeof(half_t));
-    v->emb_img = (float*)b.alloc((size_t)max_images * P * sizeof(float));
-    v->emb_txt = (float*)b.alloc((size_t)max_images * P * sizeof(float));
-    if (pass == 0) {
-      const size_t nb = align_up(b.peak + 256, 4096);
-      b = Bump();
-      if (hipMalloc((void**)&b.base, nb) != hipSuccess) return bail(PNPI_ENOMEM, "pnpi_clipv_attach: buffer allocation failed");
-      b.cap = nb;
-    }
-  }
-  {
-    std::vector<int> idt((size_t)max_images * 4);
-    for (int r = 0; r < max_images; ++r) idt[4 * r] = idt[4 * r + 1] = idt[4 * r + 2] = idt[4 * r + 3] = r;
-    if (hipMemcpy(v->rows_ident, idt.data(), idt.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return bail(PNPI_EHIP, "pnpi_clipv_attach: copy failed");
-  }
-  // workspaces: a dry run of the forward at max_images sizes them (no launch, counters untouched)
-  {
-    const pnpi_counters saved = c->ctr;
-    v->persist = Bump(); v->temp = Bump();
-    const int r = [&]() { DryScope dry(c); return clipv_fwd(c, nullptr, nullptr, max_images, g->image_size, v->emb_img16); }();
-    c->ctr = saved;
-    if (r) { const std::string e = c->err; clipv_free(c); c->err = e; return r; }
-    const size_t pb = align_up(v->persist.peak + (1 << 20), 4096), tb = align_up(v->temp.peak + (1 << 20), 4096);
-    v->persist = Bump(); v->temp = Bump();
-    if (hipMalloc((void**)&v->persist.base, pb) != hipSuccess || hipMalloc((void**)&v->temp.base, tb) != hipSuccess)
-      return bail(PNPI_ENOMEM, "pnpi_clipv_attach: workspace allocation failed");
-    v->persist.cap = pb; v->temp.cap = tb;
-  }
-  CKH(hipStreamSynchronize(c->st));
-  return 0;
+  return tower_attach(c, v, "pnpi_clipv_attach", g->image_size, g->patch, {clipv_build, clipv_bufs, clipv_dry_fwd, clipv_free});
 }
 
 int pnpi_op_clip_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int S, int out_size, uint8_t* resized_out,

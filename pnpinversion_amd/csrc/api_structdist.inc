@@ -1,7 +1,7 @@
 // api_structdist.inc -- part of api.hip (one translation unit: included there behind api_clipscore.inc; not compiled on its own).
 // DINO structure distance (evaluation/matrics_calculator.py:385-405 -> :237-246 -> :154-171): the DINO ViT attached to a context,
-// the reference's preprocessing, the keys of the last block and the fused self-similarity distance.  Everything here is allocated
-// outside the context's weight arena and workspaces; a context that never calls pnpi_dino_attach is unchanged.
+// the reference's preprocessing, the keys of the last block and the fused self-similarity distance.  What it shares with the CLIP
+// image tower (attach sequence, free, refusals, token assembly) is in api_vit.inc; a context that never calls pnpi_dino_attach is unchanged.
 // ---------------------------------------------------------------------------------------------------- resize taps (host)
 // PyTorch's compute_source_index_and_lambda for align_corners = False, opmath float (aten/src/ATen/native/UpSample.h)
 static void dino_resize_taps(int in_size, int out_size, int* idx0, int* idx1, float* lam) {
@@ -28,19 +28,15 @@ static void dino_resize_taps(int in_size, int out_size, int* idx0, int* idx1, fl
 static void dino_free(pnpi_ctx* c) {
   DinoW* v = c->dino;
   if (!v) return;
+  tower_free(c, v);
   for (auto& t : v->tabs) { (void)hipFree(t.idx); (void)hipFree(t.lam); }
-  void* bufs[] = {v->arena.base, v->persist.base, v->temp.base, v->bufs.base};
-  for (void* b : bufs) (void)hipFree(b);
-  for (auto it = c->slots.begin(); it != c->slots.end();) {
-    if (is_dino_slot(it->first)) it = c->slots.erase(it); else ++it;
-  }
   delete v;
   c->dino = nullptr;
 }
 
-// the ViT's weight slots, allocated from v->arena through the context's own slot helpers (the arenas trade places for the build)
-static void dino_build(pnpi_ctx* c, DinoW* v) {
-  std::swap(c->warena, v->arena);
+// the ViT's weight slots, through the context's own slot helpers (under TowerArena)
+static void dino_build(pnpi_ctx* c) {
+  DinoW* v = c->dino;
   const pnpi_dino_config& g = v->cfg;
   const int W = g.width;
   v->w_patch = walloc_h(c, (size_t)W * v->K);
@@ -56,7 +52,6 @@ static void dino_build(pnpi_ctx* c, DinoW* v) {
     const std::string pre = "dino.blocks." + std::to_string(l);
     const bool last = l == g.layers - 1;      // the hooked block: norm1 and the K third of attn.qkv, nothing else
     ClipLayerW L;
-    memset(&L, 0, sizeof L);
     L.ln1 = make_norm(c, pre + ".norm1", W);
     if (last) {
       L.w_qkv = walloc_h(c, (size_t)3 * W * W);      // the whole matrix is kept (one checkpoint tensor, one slot); rows W .. 2 W - 1 are read
@@ -75,15 +70,12 @@ static void dino_build(pnpi_ctx* c, DinoW* v) {
     }
     v->layers.push_back(L);
   }
-  std::swap(c->warena, v->arena);
 }
-
-// the forward's workspaces take the place of the context's for its duration (palloc / talloc / op_gemm work on c->persist / c->temp)
-struct DinoWorkspace {
-  pnpi_ctx* c; DinoW* v;
-  DinoWorkspace(pnpi_ctx* c_, DinoW* v_) : c(c_), v(v_) { std::swap(c->persist, v->persist); std::swap(c->temp, v->temp); }
-  ~DinoWorkspace() { std::swap(c->persist, v->persist); std::swap(c->temp, v->temp); }
-};
+// the tower's own small buffer
+static void dino_bufs(pnpi_ctx* c, Bump& b) {
+  DinoW* v = c->dino;
+  v->keys16 = (half_t*)b.alloc((size_t)v->max_images * v->T * v->W * sizeof(half_t));
+}
 
 static int dino_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int S, int out, float* resized, half_t* patches);
 
@@ -94,7 +86,7 @@ static int dino_fwd(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n,
   DinoW* v = c->dino;
   const pnpi_dino_config& g = v->cfg;
   const int W = g.width, T = v->T, NP = v->NP, nt = n + n2, M = nt * T;
-  DinoWorkspace ws(c, v);
+  TowerWorkspace ws(c, v);
   // every GEMM (M = nt x tokens) takes the tile / split-K of its max_images form: an image's keys do not depend on the batch it is in
   UNetFlight pin{UNetShare()};
   pin.pin_from = nt; pin.pin_to = v->max_images;
@@ -106,13 +98,7 @@ static int dino_fwd(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n,
     if (n2) CKP(dino_preprocess(c, img2, mask2, n2, S, g.image_size, nullptr, patches + (size_t)n * NP * v->K));
   }
   half_t* x = palloc(c, (size_t)M * W);
-  {
-    const size_t mk = c->temp.mark();
-    half_t* pe = talloc(c, (size_t)nt * NP * W);      // the stride-p convolution as a GEMM over patch rows; its bias joins in the assembly
-    CK(op_gemm(c, patches, v->K, nt * NP, v->K, v->w_patch, v->K, W, nullptr, nullptr, 0, pe, W));
-    if (!c->dry) CK(launch_dino_assemble_tokens(pe, v->b_patch, v->cls, v->pos, nt, NP, W, x, c->st));
-    c->temp.release(mk);
-  }
+  CKP(vit_tokens(c, v, patches, nt, -1.0, x));      // the convolution's bias joins in the assembly
   for (int l = 0; l + 1 < g.layers; ++l) CKP(clip_encoder_layer(c, v->layers[l], x, nt, T, W, g.heads, g.intermediate, 0, v->rows_ident, 1e-6f, 1));
   {
     const ClipLayerW& L = v->layers.back();
@@ -125,37 +111,18 @@ static int dino_fwd(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n,
   if (c->persist.overflow || c->temp.overflow) return fail(c, PNPI_ENOMEM, "workspace overflow (DINO ViT)");
   return 0;
 }
+static int dino_dry_fwd(pnpi_ctx* c) { return dino_fwd(c, nullptr, nullptr, c->dino->max_images, nullptr, nullptr, 0, c->dino->cfg.image_size, c->dino->keys16); }
 
 // ---------------------------------------------------------------------------------------------------- refusals (all before a launch)
 static int dino_check_attached(pnpi_ctx* c) {
   if (!c->dino) return fail(c, PNPI_ESTATE, "no DINO ViT attached to this context (pnpi_dino_attach)");
   return 0;
 }
-static int dino_check_weights(pnpi_ctx* c) {
-  std::vector<std::string> miss;
-  for (auto& kv : c->slots)
-    if (!kv.second.loaded && is_dino_slot(kv.first)) miss.push_back(kv.first);
-  if (miss.empty()) return 0;
-  std::sort(miss.begin(), miss.end());
-  c->err = "DINO ViT weights not loaded (" + std::to_string(miss.size()) + "):";
-  for (const std::string& m : miss) {
-    if (c->err.size() + m.size() > 3800) { c->err += " ..."; break; }
-    c->err += " " + m;
-  }
-  return PNPI_ESTATE;
-}
 static int dino_check_images(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int nmax, int S, const char* what) {
   if (!img) { c->err = std::string(what) + " is NULL"; return PNPI_EINVAL; }
   if (n <= 0 || n > nmax) return fail(c, PNPI_EINVAL, "n out of range: 1 .. max_pairs pairs, 1 .. 2 * max_pairs images of pnpi_dino_attach");
   if (S < 16 || S > 8192) return fail(c, PNPI_ESHAPE, "unsupported image side: square S with 16 <= S <= 8192");
-  if (mask) {      // img * mask is a keep / clear choice only for 0 / 1: read the masks back and look
-    const size_t nb = (size_t)n * S * S;
-    c->host_stage.resize(nb);
-    CKH(hipStreamSynchronize(c->st));
-    CKH(hipMemcpy(c->host_stage.data(), mask, nb, hipMemcpyDefault));
-    for (size_t i = 0; i < nb; ++i)
-      if ((unsigned char)c->host_stage[i] > 1) return fail(c, PNPI_EINVAL, "mask_hw holds a value other than 0 / 1");
-  }
+  if (mask) CKP(check_mask01(c, mask, (size_t)n * S * S));
   return 0;
 }
 // the device taps for S -> out; allocations and copies only, no launch
@@ -221,52 +188,10 @@ int pnpi_dino_attach(pnpi_ctx* c, const pnpi_dino_config* g, int max_pairs) {
   if (g->layers <= 0 || g->layers > 48 || g->intermediate <= 0 || g->intermediate % 8)
     return fail(c, PNPI_ESHAPE, "layers must be 1 .. 48, intermediate a multiple of 8");
   DinoW* v = new DinoW();
-  v->cfg = *g; v->max_pairs = max_pairs; v->max_images = 2 * max_pairs;
-  v->G = g->image_size / g->patch; v->NP = v->G * v->G; v->T = v->NP + 1; v->K = 3 * g->patch * g->patch;
+  v->name = "DINO ViT"; v->prefix = "dino.";
+  v->cfg = *g; v->max_pairs = max_pairs; v->max_images = 2 * max_pairs; v->W = g->width;
   c->dino = v;
-  auto bail = [&](int status, const char* what) { dino_free(c); return fail(c, status, what); };
-  // weights: pass 1 measures, pass 2 places
-  dino_build(c, v);
-  const size_t wbytes = align_up(v->arena.peak + 4096, 4096);
-  v->arena = Bump();
-  if (hipMalloc((void**)&v->arena.base, wbytes) != hipSuccess) return bail(PNPI_ENOMEM, "pnpi_dino_attach: weight allocation failed");
-  v->arena.cap = wbytes;
-  dino_build(c, v);
-  // small persistent buffers
-  const int W = g->width, NI = v->max_images;
-  for (int pass = 0; pass < 2; ++pass) {
-    Bump& b = v->bufs;
-    b.reset();
-    v->rows_ident = (int*)b.alloc((size_t)NI * 4 * sizeof(int));
-    v->keys16 = (half_t*)b.alloc((size_t)NI * v->T * W * sizeof(half_t));
-    if (pass == 0) {
-      const size_t nb = align_up(b.peak + 256, 4096);
-      b = Bump();
-      if (hipMalloc((void**)&b.base, nb) != hipSuccess) return bail(PNPI_ENOMEM, "pnpi_dino_attach: buffer allocation failed");
-      b.cap = nb;
-    }
-  }
-  {
-    std::vector<int> idt((size_t)NI * 4);
-    for (int r = 0; r < NI; ++r) idt[4 * r] = idt[4 * r + 1] = idt[4 * r + 2] = idt[4 * r + 3] = r;
-    if (hipMemcpy(v->rows_ident, idt.data(), idt.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return bail(PNPI_EHIP, "pnpi_dino_attach: copy failed");
-  }
-  // workspaces: a dry run of the forward at max_images sizes them (no launch, counters untouched)
-  {
-    const pnpi_counters saved = c->ctr;
-    v->persist = Bump(); v->temp = Bump();
-    const int r = [&]() { DryScope dry(c); return dino_fwd(c, nullptr, nullptr, NI, nullptr, nullptr, 0, g->image_size, v->keys16); }();
-    c->ctr = saved;
-    if (r) { const std::string e = c->err; dino_free(c); c->err = e; return r; }
-    const size_t pb = align_up(v->persist.peak + (1 << 20), 4096), tb = align_up(v->temp.peak + (1 << 20), 4096);
-    v->persist = Bump(); v->temp = Bump();
-    if (hipMalloc((void**)&v->persist.base, pb) != hipSuccess) return bail(PNPI_ENOMEM, "pnpi_dino_attach: workspace allocation failed");
-    v->persist.cap = pb;
-    if (hipMalloc((void**)&v->temp.base, tb) != hipSuccess) return bail(PNPI_ENOMEM, "pnpi_dino_attach: workspace allocation failed");
-    v->temp.cap = tb;
-  }
-  if (hipStreamSynchronize(c->st) != hipSuccess) return bail(PNPI_EHIP, "pnpi_dino_attach: synchronize failed");
-  return 0;
+  return tower_attach(c, v, "pnpi_dino_attach", g->image_size, g->patch, {dino_build, dino_bufs, dino_dry_fwd, dino_free});      // K = 3 patch^2: patch % 8 == 0
 }
 
 int pnpi_op_dino_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int S, int out_size, float* resized_out,
@@ -282,7 +207,7 @@ int pnpi_op_dino_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask
 int pnpi_dino_keys(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int S, float* keys_out) {
   if (!c) return PNPI_EINVAL;
   CKP(dino_check_attached(c));
-  CKP(dino_check_weights(c));
+  CKP(tower_check_weights(c, c->dino));
   if (!keys_out) return fail(c, PNPI_EINVAL, "keys_out is NULL");
   DinoW* v = c->dino;
   CKP(dino_check_images(c, img, mask, n, v->max_images, S, "img_hwc"));
@@ -295,7 +220,7 @@ int pnpi_structure_distance(pnpi_ctx* c, const uint8_t* img_pred, const uint8_t*
                             int n, int S, float* dist_out) {
   if (!c) return PNPI_EINVAL;
   CKP(dino_check_attached(c));
-  CKP(dino_check_weights(c));
+  CKP(tower_check_weights(c, c->dino));
   if (!dist_out) return fail(c, PNPI_EINVAL, "dist_out is NULL");
   DinoW* v = c->dino;
   CKP(dino_check_images(c, img_pred, mask_pred, n, v->max_pairs, S, "img_pred"));

@@ -163,38 +163,50 @@ int launch_clip_resize_v(const uint8_t* tmp, int n, int S, int out, const int* b
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// CLIPVisionEmbeddings: cat([class_embedding, patch_embeds]) + position_embedding, eight channels per thread
+// A ViT's token assembly: cat([class token, patch embeddings]) + position embedding, where pe is the bias-free GEMM over the patch
+// rows.  bias (nullable) is the convolution's: CLIP's patch embedding has none, DINO's is added here.  (pe [+ bias]) + pos in fp32,
+// one rounding to fp16; the class row takes no bias.  Eight channels per thread, 16-byte loads (W % 8 == 0, 16-byte aligned rows).
 // ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) clip_assemble_tokens_kernel(const half_t* __restrict__ pe, const float* __restrict__ cls,
-                                                                   const float* __restrict__ pos, int n, int NP, int W, half_t* __restrict__ x) {
+__device__ __forceinline__ void ldg_float8(const float* __restrict__ p, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__global__ void __launch_bounds__(256) vit_assemble_tokens_kernel(const half_t* __restrict__ pe, const float* __restrict__ bias,
+                                                                  const float* __restrict__ cls, const float* __restrict__ pos, int n, int NP,
+                                                                  int W, half_t* __restrict__ x) {
   const int W8 = W >> 3, T = NP + 1;
   const size_t total = (size_t)n * T * W8;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int c = (int)(i % W8) * 8;
     const size_t row = i / W8;
     const int t = (int)(row % T), b = (int)(row / T);
-    const float4 p0 = *reinterpret_cast<const float4*>(pos + (size_t)t * W + c), p1 = *reinterpret_cast<const float4*>(pos + (size_t)t * W + c + 4);
-    float v[8];
+    float v[8], pv[8];
     if (t == 0) {
-      const float4 c0 = *reinterpret_cast<const float4*>(cls + c), c1 = *reinterpret_cast<const float4*>(cls + c + 4);
-      v[0] = c0.x; v[1] = c0.y; v[2] = c0.z; v[3] = c0.w; v[4] = c1.x; v[5] = c1.y; v[6] = c1.z; v[7] = c1.w;
+      ldg_float8(cls + c, v);
     } else {
       const half8 h = ldg_half8(pe + ((size_t)b * NP + (t - 1)) * W + c);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
+      if (bias) {
+        float bv[8];
+        ldg_float8(bias + c, bv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] += bv[j];
+      }
     }
-    const float pv[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+    ldg_float8(pos + (size_t)t * W + c, pv);
     half8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (half_t)(v[j] + pv[j]);
     *reinterpret_cast<half8*>(x + row * W + c) = o;
   }
 }
-int launch_clip_assemble_tokens(const half_t* pe, const float* cls, const float* pos, int n, int NP, int W, half_t* x, hipStream_t st) {
+int launch_vit_assemble_tokens(const half_t* pe, const float* bias, const float* cls, const float* pos, int n, int NP, int W, half_t* x,
+                               hipStream_t st) {
   if (!pe || !cls || !pos || !x || n <= 0 || NP <= 0 || W <= 0 || (W & 7)) return -3;
   const size_t total = (size_t)n * (NP + 1) * (W >> 3);
   int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-  clip_assemble_tokens_kernel<<<blocks, 256, 0, st>>>(pe, cls, pos, n, NP, W, x);
+  vit_assemble_tokens_kernel<<<blocks, 256, 0, st>>>(pe, bias, cls, pos, n, NP, W, x);
   return (int)hipGetLastError();
 }
 

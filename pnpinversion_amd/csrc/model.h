@@ -115,9 +115,9 @@ struct VaeW {
 };
 
 struct ClipLayerW {
-  NormW ln1, ln2;
-  half_t* w_qkv; float* b_qkv;   // [3H][H] fused q | k | v (+ biases)
-  LinW out, fc1, fc2;
+  NormW ln1{}, ln2{};
+  half_t* w_qkv = nullptr; float* b_qkv = nullptr;   // [3H][H] fused q | k | v (+ biases)
+  LinW out{}, fc1{}, fc2{};
 };
 struct ClipW {
   int H = 0, heads = 0, I = 0, vocab = 0, T = 0;
@@ -127,23 +127,30 @@ struct ClipW {
   NormW final_ln;
 };
 
-// CLIP image tower + the two projections (pnpi_clipv_attach; transformers CLIPModel: vision_model, visual_projection, text_projection).
-// Everything it owns lives outside the context's own arenas: a context that never attaches one is unchanged.
-struct ClipVisionW {
-  pnpi_clipv_config cfg;
+// What the vision transformers attached to a context share (api_vit.inc): the geometry, the four allocations, the patch embedding, the
+// encoder layers.  Everything a tower owns lives outside the context's own arenas: a context that never attaches one is unchanged.
+struct VitTowerW {
+  const char* name = "";                  // in messages: "CLIP image tower", "DINO ViT"
+  const char* prefix = "";                // of its weight slots' names: "clipv.", "dino."
   int max_images = 0;
-  int G = 0, NP = 0, T = 0, Kp = 0;       // patch grid side, patches, tokens (NP + 1), patch-row length 3 * patch^2 rounded up to 64
+  int G = 0, NP = 0, T = 0, K = 0, W = 0; // patch grid side, patches, tokens (NP + 1), patch-row length 3 * patch^2 rounded up to 64, width
   Bump arena;                             // weights (own allocation)
-  Bump persist, temp;                     // activation workspaces of the image forward (swapped into the context while it runs)
-  Bump bufs;                              // small persistent buffers below
-  half_t* w_patch = nullptr;              // [W][Kp] patch embedding, (c, ky, kx) columns, pad columns zero
+  Bump persist, temp;                     // activation workspaces of the forward (swapped into the context while it runs)
+  Bump bufs;                              // small persistent buffers: rows_ident and the tower's own
+  half_t* w_patch = nullptr;              // [W][K] patch embedding, (c, ky, kx) columns, pad columns zero
+  float* b_patch = nullptr;               // [W], or nullptr: a bias-free patch embedding (CLIP)
   float* cls = nullptr;                   // [W]
   float* pos = nullptr;                   // [T][W]
-  NormW pre_ln, post_ln;
   std::vector<ClipLayerW> layers;
+  int* rows_ident = nullptr;              // [max_images][4]
+};
+
+// CLIP image tower + the two projections (pnpi_clipv_attach; transformers CLIPModel: vision_model, visual_projection, text_projection).
+struct ClipVisionW : VitTowerW {
+  pnpi_clipv_config cfg;
+  NormW pre_ln, post_ln;
   half_t* w_vproj = nullptr;              // [proj][W]
   half_t* w_tproj = nullptr;              // [proj][H_text]
-  int* rows_ident = nullptr;              // [max_images][4]
   half_t *pool_img = nullptr, *ln_img = nullptr, *emb_img16 = nullptr, *pool_txt = nullptr, *emb_txt16 = nullptr;
   float *emb_img = nullptr, *emb_txt = nullptr;   // [max_images][proj]
   // PIL's bicubic coefficient tables per source size (built on the host at first use): bounds [out][2] = (first source index, count),
@@ -153,21 +160,11 @@ struct ClipVisionW {
   uint8_t* tmp_u8 = nullptr; size_t tmp_bytes = 0;   // the horizontal pass's output [n][S][out][3], grown on demand
 };
 
-// DINO ViT for the structure distance (pnpi_dino_attach; facebookresearch/dino vision_transformer.py).  Like the CLIP image tower,
-// everything it owns lives outside the context's own arenas.
-struct DinoW {
+// DINO ViT for the structure distance (pnpi_dino_attach; facebookresearch/dino vision_transformer.py).  Of the last block only ln1,
+// w_qkv, b_qkv exist.
+struct DinoW : VitTowerW {
   pnpi_dino_config cfg;
-  int max_pairs = 0, max_images = 0;      // images per call = 2 * max_pairs
-  int G = 0, NP = 0, T = 0, K = 0;        // patch grid side, patches, tokens (NP + 1), patch-row length 3 * patch^2
-  Bump arena;                             // weights (own allocation)
-  Bump persist, temp;                     // activation workspaces of the forward (swapped into the context while it runs)
-  Bump bufs;                              // small persistent buffers below
-  half_t* w_patch = nullptr;              // [W][K] patch embedding, (c, ky, kx) columns
-  float* b_patch = nullptr;               // [W]
-  float* cls = nullptr;                   // [W]
-  float* pos = nullptr;                   // [T][W]
-  std::vector<ClipLayerW> layers;         // blocks 0 .. layers - 2 in full; of the last block only ln1, w_qkv, b_qkv exist
-  int* rows_ident = nullptr;              // [max_images][4]
+  int max_pairs = 0;                      // max_images = 2 * max_pairs
   half_t* keys16 = nullptr;               // [max_images][T][W]: the last block's keys
   // resize taps per source size (built on the host at first use): idx0 | idx1 [out] ints, lam [out] floats, one allocation each
   struct ResizeTab { int S, out; int* idx; float* lam; };

@@ -118,8 +118,10 @@ int launch_clip_resize_h(const uint8_t* img, const uint8_t* mask, int n, int S, 
 // [n][(out / patch)^2][Kp] in (c, ky, kx) order, columns 3 * patch^2 .. Kp zero (nullable)
 int launch_clip_resize_v(const uint8_t* tmp, int n, int S, int out, const int* bounds, const int* coef, int ksize, int patch, int Kp,
                          uint8_t* resized, half_t* patches, hipStream_t st);
-// x [n][NP + 1][W]: row 0 = cls + pos[0], row 1 + p = pe[n][p] + pos[1 + p] (fp32 sums, one rounding); W % 8 == 0
-int launch_clip_assemble_tokens(const half_t* pe, const float* cls, const float* pos, int n, int NP, int W, half_t* x, hipStream_t st);
+// x [n][NP + 1][W]: row 0 = cls + pos[0], row 1 + p = (pe[n][p] [+ bias]) + pos[1 + p] (fp32 sums, one rounding); bias nullable;
+// W % 8 == 0, every row 16-byte aligned.  Both attached ViTs (api_vit.inc).
+int launch_vit_assemble_tokens(const half_t* pe, const float* bias, const float* cls, const float* pos, int n, int NP, int W, half_t* x,
+                               hipStream_t st);
 // out [n][H] = x [n][T][H] at token 0 (ids == nullptr) or at the first position of each row's largest id (ids [n][T]); H % 8 == 0
 int launch_clip_gather_rows(const half_t* x, int n, int T, int H, const int* ids, half_t* out, hipStream_t st);
 // out[i] = max(100 * a_i . b_i / (|a_i| |b_i|), 0) in fp32, one wavefront per pair; a, b [n][D]
@@ -133,9 +135,6 @@ int launch_clip_cosine(const float* a, const float* b, int n, int D, float* out,
 // [n][(out / patch)^2][3 * patch^2] in (c, ky, kx) order (nullable); patch even
 int launch_dino_preprocess(const uint8_t* img, const uint8_t* mask, int n, int S, int out, const int* idx0, const int* idx1, const float* lam,
                            int patch, float* resized, half_t* patches, hipStream_t st);
-// x [n][NP + 1][W]: row 0 = cls + pos[0], row 1 + p = pe[n][p] + bias + pos[1 + p] (fp32 sums, one rounding); W % 8 == 0
-int launch_dino_assemble_tokens(const half_t* pe, const float* bias, const float* cls, const float* pos, int n, int NP, int W, half_t* x,
-                                hipStream_t st);
 int launch_gelu_erf(half_t* x, size_t n, hipStream_t st);      // erf-form GELU in place (gelu_f); n % 8 == 0, x 16-byte aligned
 // dist[p] = mean over T^2 of (sim(keys_a[p]) - sim(keys_b[p]))^2, sim[i][j] = x_i . x_j / max(|x_i| |x_j|, 1e-8); keys fp16 [n][T][D],
 // D % 32 == 0, 16-byte aligned; scratch: keys_selfsim_scratch_floats(n, T) floats; dist (nullable) needs keys_b; sim_a (nullable):

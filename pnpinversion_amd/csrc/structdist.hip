@@ -65,43 +65,6 @@ int launch_dino_preprocess(const uint8_t* img, const uint8_t* mask, int n, int S
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// DINO's token assembly: cat([cls_token, patch_embed(x)]) + pos_embed, where pe is the bias-free GEMM over the patch rows and the
-// convolution's bias is added here; eight channels per thread
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) dino_assemble_tokens_kernel(const half_t* __restrict__ pe, const float* __restrict__ bias,
-                                                                   const float* __restrict__ cls, const float* __restrict__ pos, int n, int NP,
-                                                                   int W, half_t* __restrict__ x) {
-  const int W8 = W >> 3, T = NP + 1;
-  const size_t total = (size_t)n * T * W8;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int c = (int)(i % W8) * 8;
-    const size_t row = i / W8;
-    const int t = (int)(row % T), b = (int)(row / T);
-    float v[8];
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = cls[c + j];
-    } else {
-      const half8 h = ldg_half8(pe + ((size_t)b * NP + (t - 1)) * W + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + bias[c + j];
-    }
-    half8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (half_t)(v[j] + pos[(size_t)t * W + c + j]);
-    *reinterpret_cast<half8*>(x + row * W + c) = o;
-  }
-}
-int launch_dino_assemble_tokens(const half_t* pe, const float* bias, const float* cls, const float* pos, int n, int NP, int W, half_t* x,
-                                hipStream_t st) {
-  if (!pe || !bias || !cls || !pos || !x || n <= 0 || NP <= 0 || W <= 0 || (W & 7)) return -3;
-  const size_t total = (size_t)n * (NP + 1) * (W >> 3);
-  int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-  dino_assemble_tokens_kernel<<<blocks, 256, 0, st>>>(pe, bias, cls, pos, n, NP, W, x);
-  return (int)hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // torch.nn.GELU() (erf form) in place, eight values per thread (n % 8 == 0: rows of a multiple-of-8 width)
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) gelu_erf_kernel(half_t* __restrict__ x, size_t n8) {

@@ -385,7 +385,7 @@ class NativeEngine:
         wanted = {k: v for k, v in sd.items() if k.startswith("vision_model.") or k in ("visual_projection.weight", "text_projection.weight")}
         self.load_state_dict(clipv_sd={k: v for k, v in wanted.items() if "position_ids" not in k})
 
-    def _clip_images(self, images, masks):
+    def _tower_images(self, images, masks):
         img = torch.as_tensor(images)
         if img.dim() == 3:
             img = img[None]
@@ -416,7 +416,7 @@ class NativeEngine:
 
     def clip_preprocess(self, images, masks=None, out_size=None, want_resized=True, want_patches=True):
         """pnpi_op_clip_preprocess -> (resized uint8 [n, out, out, 3] or None, patch rows fp16 [n, (out / patch)^2, Kp] or None)"""
-        img, m = self._clip_images(images, masks)
+        img, m = self._tower_images(images, masks)
         n, S = img.shape[0], img.shape[1]
         out = int(out_size or self.clipv_cfg.image_size)
         p = self.clipv_cfg.patch
@@ -427,7 +427,7 @@ class NativeEngine:
         return res, pat
 
     def clip_image_embed(self, images, masks=None):
-        img, m = self._clip_images(images, masks)
+        img, m = self._tower_images(images, masks)
         out = torch.empty(img.shape[0], self.clipv_cfg.proj_dim, device=self.device)
         self._call("pnpi_clip_image_embed", _p(img), _p(m), img.shape[0], img.shape[1], _p(out))
         return out
@@ -439,7 +439,7 @@ class NativeEngine:
         return out
 
     def clip_score(self, images, input_ids, masks=None):
-        img, m = self._clip_images(images, masks)
+        img, m = self._tower_images(images, masks)
         ids = self._clip_ids(input_ids)
         if ids.shape[0] != img.shape[0]:
             raise ValueError("%d images but %d prompts" % (img.shape[0], ids.shape[0]))
@@ -465,7 +465,7 @@ class NativeEngine:
 
     def dino_preprocess(self, images, masks=None, out_size=None, want_resized=True, want_patches=True):
         """pnpi_op_dino_preprocess -> (resized fp32 [n, 3, out, out] in 0..255 or None, patch rows fp16 [n, (out / patch)^2, 3 patch^2] or None)"""
-        img, m = self._clip_images(images, masks)
+        img, m = self._tower_images(images, masks)
         n, S = img.shape[0], img.shape[1]
         out = int(out_size or self.dino_cfg.image_size)
         p = self.dino_cfg.patch
@@ -476,15 +476,15 @@ class NativeEngine:
 
     def dino_keys(self, images, masks=None):
         """-> fp32 [n, T, width]: the concatenated keys of the last block (the output of blocks[-1].attn.qkv, K third)"""
-        img, m = self._clip_images(images, masks)
+        img, m = self._tower_images(images, masks)
         out = torch.empty(img.shape[0], self.dino_tokens(), self.dino_cfg.width, device=self.device)
         self._call("pnpi_dino_keys", _p(img), _p(m), img.shape[0], img.shape[1], _p(out))
         return out
 
     def structure_distance(self, pred, gt, mask_pred=None, mask_gt=None):
         """-> fp32 [n]: calculate_structure_distance per pair, one tower pass over the 2 n images"""
-        a, ma = self._clip_images(pred, mask_pred)
-        b, mb = self._clip_images(gt, mask_gt)
+        a, ma = self._tower_images(pred, mask_pred)
+        b, mb = self._tower_images(gt, mask_gt)
         if a.shape != b.shape:
             raise ValueError("Image shapes should be the same: %s and %s" % (tuple(a.shape), tuple(b.shape)))
         out = torch.empty(a.shape[0], device=self.device)

@@ -101,11 +101,11 @@ def calculate_clip_similarity(img, txt, mask=None, *, scorer):
     """matrics_calculator.py:290-302: CLIPScore of uint8(img * mask) against the prompt, on the device.  scorer: clip_score.ClipScore
     (the reference holds its torchmetrics object in the calculator; here the caller passes the scorer).  mask: None, [S, S] or the
     [S, S, 3] repeat evaluate.py builds, values 0 / 1."""
-    from .clip_score import _plane
+    from .image_batches import plane
     a = np.asarray(img)
     if a.ndim != 3 or a.shape[2] != 3:
         a = np.asarray(img.convert("RGB")) if hasattr(img, "convert") else a
-    m = None if mask is None else _plane(mask)[None]
+    m = None if mask is None else plane(mask)[None]
     return float(scorer.score(a[None].astype(np.uint8), [txt], masks=m)[0].item())
 
 
@@ -113,8 +113,8 @@ def calculate_structure_distance(img_pred, img_gt, mask_pred=None, mask_gt=None,
     """matrics_calculator.py:385-405: the DINO key self-similarity distance between img_pred * mask_pred and img_gt * mask_gt, on the
     device.  scorer: structure_distance.StructureDistance (the reference holds its LossG in the calculator; here the caller passes the
     scorer).  Masks: None, [S, S] or the [S, S, 3] repeat evaluate.py builds, values 0 / 1."""
-    from .structure_distance import _rgb
-    a, b = _rgb(img_pred), _rgb(img_gt)
+    from .image_batches import rgb
+    a, b = rgb(img_pred), rgb(img_gt)
     if a.shape != b.shape:
         raise ValueError("Image shapes should be the same.")
     return float(scorer.distance(a[None], b[None], [mask_pred], [mask_gt])[0].item())

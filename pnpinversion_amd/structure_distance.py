@@ -14,19 +14,10 @@ kernel forms both per tile and reduces (csrc/structdist.hip).
 Real dino_vitbase8_pretrain.pth weights load through checkpoint.load_dino_checkpoint; no such file exists offline, so that loader is
 untested here and the tests run seeded synthetic weights (weights.dino_state_dict).  Whether the real patch embedding keeps the
 ~1.1e3-valued normalised pixels inside fp16's range is likewise unverified offline."""
-import numpy as np
 import torch
 
 from . import _capi
-from .clip_score import _plane
-
-
-def _rgb(img):
-    """one image (PIL or array) -> uint8 [S, S, 3]"""
-    a = np.asarray(img)
-    if (a.ndim != 3 or a.shape[2] != 3) and hasattr(img, "convert"):
-        a = np.asarray(img.convert("RGB"))
-    return a.astype(np.uint8)
+from .image_batches import chunks, stack_images, stack_masks
 
 
 class StructureDistance:
@@ -50,45 +41,18 @@ class StructureDistance:
         self.load_state_dict(sd)
         return sd
 
-    # ---- inputs
-    @staticmethod
-    def _stack(images):
-        if isinstance(images, (list, tuple)):
-            images = np.stack([_rgb(i) for i in images])
-        a = images if isinstance(images, torch.Tensor) else np.asarray(images)
-        return a[None] if a.ndim == 3 else a
-
-    @staticmethod
-    def _stack_masks(masks, img):
-        """None, [n, S, S], [n, S, S, 3] or a list whose entries are None (whole image), [S, S] or the [S, S, 3] repeat -> uint8 [n, S, S]"""
-        if masks is None:
-            return None
-        if isinstance(masks, torch.Tensor):
-            masks = masks.cpu().numpy()
-        if not isinstance(masks, (list, tuple)):
-            masks = np.asarray(masks)
-            one = masks.ndim == 2 or (masks.ndim == 3 and tuple(masks.shape) == tuple(img.shape[1:]))      # [S, S], or one [S, S, 3] repeat
-            masks = [masks] if one else list(masks)
-        if all(k is None for k in masks):
-            return None
-        S = img.shape[1]
-        return np.stack([np.ones((S, S), np.uint8) if k is None else _plane(k) for k in masks])
-
-    def _chunks(self, n, per):
-        return [(i, min(i + per, n)) for i in range(0, n, per)]
-
     # ---- outputs
     def keys(self, images, masks=None):
         """uint8 [n, S, S, 3], masks None or 0 / 1 -> fp32 [n, T, width]: the concatenated keys of the last block"""
-        img = self._stack(images)
-        m = self._stack_masks(masks, img)
-        return torch.cat([self.engine.dino_keys(img[a:b], None if m is None else m[a:b]) for a, b in self._chunks(len(img), 2 * self.max_pairs)])
+        img = stack_images(images)
+        m = stack_masks(masks, img)
+        return torch.cat([self.engine.dino_keys(img[a:b], None if m is None else m[a:b]) for a, b in chunks(len(img), 2 * self.max_pairs)])
 
     def distance(self, pred, gt, mask_pred=None, mask_gt=None):
         """structure distance per (pred, gt) pair, one launch set per max_pairs pairs -> fp32 [n]"""
-        a, b = self._stack(pred), self._stack(gt)
+        a, b = stack_images(pred), stack_images(gt)
         if tuple(a.shape) != tuple(b.shape):
             raise ValueError("Image shapes should be the same.")
-        ma, mb = self._stack_masks(mask_pred, a), self._stack_masks(mask_gt, b)
+        ma, mb = stack_masks(mask_pred, a), stack_masks(mask_gt, b)
         return torch.cat([self.engine.structure_distance(a[i:j], b[i:j], None if ma is None else ma[i:j], None if mb is None else mb[i:j])
-                          for i, j in self._chunks(len(a), self.max_pairs)])
+                          for i, j in chunks(len(a), self.max_pairs)])

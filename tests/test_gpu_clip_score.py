@@ -209,6 +209,64 @@ def test_refusals(tiny, fx):
         no_text.close()
 
 
+def test_refused_attach_leaves_nothing_behind(tiny, fx):
+    """an attach that fails validation leaves the context without a tower: calls still say so, the slots are gone, a good attach works"""
+    img = fx.images
+    assert fx.vcfg["width"] % 7
+    eng = _engine(seed=int(fx.z["text_seed"]))
+    try:
+        eng.clipv_cfg = _vc(fx.vcfg)
+        missing = eng.missing_weights()
+        _refused(lambda: eng.clipv_attach(_vc(dict(fx.vcfg, heads=7)), 3), _capi.PNPI_ESHAPE, "heads")
+        _refused(lambda: eng.clip_image_embed(img), _capi.PNPI_ESTATE, "pnpi_clipv_attach")
+        assert eng.missing_weights() == missing
+        eng.clipv_attach(_vc(fx.vcfg), 3)
+        eng.load_clipv_state_dict(fx.vsd)
+        assert torch.equal(eng.clip_image_embed(img), tiny.clip_image_embed(img))
+        assert torch.equal(eng.clip_score(img[[0, 2]], fx.ids[:2], fx.masks), tiny.clip_score(img[[0, 2]], fx.ids[:2], fx.masks))
+    finally:
+        eng.close()
+
+
+# ---- 7. the CLIP image tower and the DINO ViT on one context: each swaps its arena and its workspaces in and out of the same context
+@pytest.fixture(scope="module")
+def dino_alone():
+    """the DINO fixture's tiny tower on a context of its own, built as the `tiny` fixture of tests/test_gpu_structure_distance.py is"""
+    from pnpinversion_amd.structure_distance import StructureDistance
+    from tests import test_gpu_structure_distance as d
+    dfx = d.Fixture()
+    eng = d._engine()
+    sc = StructureDistance(eng, d._dc(dfx.cfg), max_pairs=2)
+    sc.load_state_dict(dfx.sd)
+    yield dfx, eng
+    eng.close()
+
+
+def test_both_towers_on_one_context(tiny, fx, dino_alone):
+    from tests.test_gpu_structure_distance import _dc
+    dfx, dino = dino_alone
+    ids = fx.ids[[2, 0]]
+    pair = (dfx.images[:1], dfx.images[1:2], dfx.masks[:1], dfx.masks[:1])
+    want = [tiny.clip_score(fx.images[:2], ids), dino.structure_distance(*pair), dino.dino_keys(dfx.images[1:3]),
+            tiny.clip_score(fx.images[[0, 2]], ids, fx.masks), tiny.text_encode(fx.ids), tiny.clip_image_embed(fx.images[1:2])]
+    for life in range(2):                           # build, attach both, load, compute, destroy -- twice
+        eng = _engine(seed=int(fx.z["text_seed"]))
+        try:
+            missing = eng.missing_weights()
+            eng.clipv_attach(_vc(fx.vcfg), 2)
+            assert eng.missing_weights() == missing
+            eng.dino_attach(_dc(dfx.cfg), 1)
+            assert eng.missing_weights() == missing
+            eng.load_clipv_state_dict(fx.vsd)
+            eng.load_dino_state_dict(dfx.sd)
+            got = [eng.clip_score(fx.images[:2], ids), eng.structure_distance(*pair), eng.dino_keys(dfx.images[1:3]),
+                   eng.clip_score(fx.images[[0, 2]], ids, fx.masks), eng.text_encode(fx.ids), eng.clip_image_embed(fx.images[1:2])]
+            for i, (g, w) in enumerate(zip(got, want)):
+                assert torch.equal(g, w), "life %d, call %d differs from the single-tower context" % (life, i)
+        finally:
+            eng.close()
+
+
 def test_text_tower_unchanged_by_the_image_tower(tiny, fx):
     """a context without the tower behaves as before, and attaching one changes neither the text encoder's bits nor its launches"""
     plain = _engine(seed=int(fx.z["text_seed"]))

@@ -296,3 +296,23 @@ def test_lifecycle_and_refusals(tiny, fx):
         assert torch.equal(again.dino_keys(img[:2]), got)
     finally:
         again.close()
+
+
+def test_refused_attach_leaves_nothing_behind(tiny, fx):
+    """an attach that fails validation leaves the context without a ViT: calls still say so, the slots are gone, a good attach works"""
+    img = fx.images
+    assert fx.cfg["width"] % 3
+    eng = _engine()
+    try:
+        eng.dino_cfg = _dc(fx.cfg)
+        missing = eng.missing_weights()
+        _refused(lambda: eng.dino_attach(_dc(dict(fx.cfg, heads=3)), 2), _capi.PNPI_ESHAPE, "heads")
+        _refused(lambda: eng.dino_keys(img), _capi.PNPI_ESTATE, "pnpi_dino_attach")
+        assert eng.missing_weights() == missing
+        eng.dino_attach(_dc(fx.cfg), 2)
+        eng.load_dino_state_dict(fx.sd)
+        assert torch.equal(eng.dino_keys(img), tiny.engine.dino_keys(img))
+        pair = (img[:2], img[1:3], fx.masks, fx.masks)
+        assert torch.equal(eng.structure_distance(*pair), tiny.engine.structure_distance(*pair))
+    finally:
+        eng.close()
