@@ -189,67 +189,12 @@ __global__ void __launch_bounds__(256) igemm_kernel(GemmP p_in) {
       }
     }
     __syncthreads();
-    if (!p.geglu) {
-      // thread t owns the fixed 8-channel vector v = t % VPR and walks rows: per-channel sums for the GroupNorm that
-      // consumes this tensor fall out of the store loop (fp32 sums of the rounded fp16 values the consumer will read)
-      float cs[8], cq[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { cs[j] = 0.f; cq[j] = 0.f; }
-      for (int idx = tid; idx < BM * VPR; idx += 256) {
-        const int r = idx / VPR, v = idx - r * VPR;
-        const int m = m0 + r, n = n0 + v * 8;
-        if (m < p.M && n < p.N) {
-          const half8 val = *reinterpret_cast<const half8*>(sOut + r * OLD + v * 8);
-          *reinterpret_cast<half8*>(p.out + (size_t)m * p.ldo + n) = val;
-          if (p.stats) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { float f = (float)val[j]; cs[j] += f; cq[j] += f * f; }
-          }
-        }
-      }
-      if (p.stats) {
-        // lanes sharing a vector index are VPR apart: fold them inside the wave, then across the 4 waves through LDS
-        float* sSt = reinterpret_cast<float*>(sOut + BM * OLD);       // [4][BN][2]
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-#pragma unroll
-          for (int off = VPR; off < 64; off <<= 1) { cs[j] += __shfl_xor(cs[j], off, 64); cq[j] += __shfl_xor(cq[j], off, 64); }
-        }
-        const int lane_ = tid & 63, wv = tid >> 6;
-        if (lane_ < VPR) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            sSt[(wv * BN + lane_ * 8 + j) * 2 + 0] = cs[j];
-            sSt[(wv * BN + lane_ * 8 + j) * 2 + 1] = cq[j];
-          }
-        }
-        __syncthreads();
-        if (tid < BN && n0 + tid < p.N) {
-          float s = 0.f, q = 0.f;
-#pragma unroll
-          for (int w4 = 0; w4 < 4; ++w4) { s += sSt[(w4 * BN + tid) * 2]; q += sSt[(w4 * BN + tid) * 2 + 1]; }
-          float* dst = p.stats + ((size_t)blockIdx.x * p.N + n0 + tid) * 2;
-          dst[0] = s;
-          dst[1] = q;
-        }
-      }
-    } else {
-      // columns come in [x(32) | gate(32)] groups; the block's BN columns hold BN/2 outputs starting at column n0/2
-      constexpr int VPO = BN / 16;
-      for (int idx = tid; idx < BM * VPO; idx += 256) {
-        const int r = idx / VPO, v = idx - r * VPO;
-        const int m = m0 + r;
-        const int xc = (v >> 2) * 64 + (v & 3) * 8;     // local column of the x vector; its gate sits 32 columns further
-        const int no = (n0 >> 1) + v * 8;
-        if (m < p.M && no < (p.N >> 1)) {
-          half8 x = *reinterpret_cast<const half8*>(sOut + r * OLD + xc);
-          half8 gt = *reinterpret_cast<const half8*>(sOut + r * OLD + xc + 32);
-          half8 o8;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o8[j] = (half_t)((float)x[j] * gelu_f((float)gt[j]));
-          *reinterpret_cast<half8*>(p.out + (size_t)m * p.ldo + no) = o8;
-        }
-      }
+    // plain rows only: GEGLU and GroupNorm statistics launches never reach this kernel (igemm_plan gives them a DMA-family tile or fails)
+    for (int idx = tid; idx < BM * VPR; idx += 256) {
+      const int r = idx / VPR, v = idx - r * VPR;
+      const int m = m0 + r, n = n0 + v * 8;
+      if (m < p.M && n < p.N)
+        *reinterpret_cast<half8*>(p.out + (size_t)m * p.ldo + n) = *reinterpret_cast<const half8*>(sOut + r * OLD + v * 8);
     }
     return;
   }

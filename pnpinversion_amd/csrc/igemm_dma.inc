@@ -2,44 +2,9 @@
 // configurations of it to read their ISA without rebuilding every variant).
 #pragma once
 #include "ops.h"
+#include "igemm_epilogue.inc"
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-__device__ __forceinline__ void epilogue_store4(const GemmP& p, int m, int nb, const float* v, const float* bias) {
-  if (m >= p.M) return;
-  float o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    int n = nb + j;
-    float x = v[j] * p.alpha;
-    if (n < p.N) {
-      if (bias) x += bias[n];
-      if (p.res) x += (float)p.res[(size_t)m * p.ldres + n];
-    }
-    o[j] = x;
-  }
-  if (nb + 3 < p.vt_col0 && nb + 3 < p.N && (p.ldo & 3) == 0) {
-    half4 h;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = (half_t)o[j];
-    *reinterpret_cast<half4*>(p.out + (size_t)m * p.ldo + nb) = h;
-    return;
-  }
-  int b = 0, tok = m;
-  if (nb + 3 >= p.vt_col0) { b = m / p.rows_per_batch; tok = m - b * p.rows_per_batch; }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    int n = nb + j;
-    if (n >= p.N) continue;
-    if (n < p.vt_col0) {
-      p.out[(size_t)m * p.ldo + n] = (half_t)o[j];
-    } else {
-      size_t idx = ((size_t)b * (p.N - p.vt_col0) + (n - p.vt_col0)) * p.vt_ld + (p.vt_perm16 ? vt_perm16_pos(tok) : tok);
-      if (p.vt_f32) ((float*)p.outT)[idx] = o[j];
-      else ((half_t*)p.outT)[idx] = (half_t)o[j];
-    }
-  }
-}
 
 // A 16-byte LDS read the compiler does not track (ds_read_b128 in inline asm): the caller waits with its own counted
 // `s_waitcnt lgkmcnt(N)` + sched_barrier(0) before the first use (cdna_hip_programming.md 5.7, form iii).  hipcc's own waits are
@@ -610,22 +575,8 @@ igemm_dma_kernel(GemmP p_in, const half_t* __restrict__ zero_page) {
           }
         }
       } else {
-        // columns come in [x(32) | gate(32)] groups; the block's BN columns hold BN/2 outputs starting at column n0/2
         constexpr int VPO = BN / 16;
-        for (int idx = tid; idx < EROWS * VPO; idx += NT) {
-          const int r = idx / VPO, v = idx - r * VPO;
-          const int m = m0 + r0 + r;
-          const int xc = (v >> 2) * 64 + (v & 3) * 8;     // local column of the x vector; its gate sits 32 columns further
-          const int no = (n0 >> 1) + v * 8;
-          if (m < p.M && no < (p.N >> 1)) {
-            half8 x = *reinterpret_cast<const half8*>(sOut + r * OLD + xc);
-            half8 gt = *reinterpret_cast<const half8*>(sOut + r * OLD + xc + 32);
-            half8 o8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o8[j] = (half_t)((float)x[j] * gelu_f((float)gt[j]));
-            *reinterpret_cast<half8*>(p.out + (size_t)m * p.ldo + no) = o8;
-          }
-        }
+        for (int idx = tid; idx < EROWS * VPO; idx += NT) epilogue_geglu_vec<BN, OLD>(p, sOut, m0 + r0, n0, idx);
       }
       if (e + 1 < EPASS) __syncthreads();               // the next pass overwrites the staging rows
     }

@@ -517,20 +517,7 @@ igemm_pp_kernel(GemmP p_in) {
         }
       } else {
         constexpr int VPO = BN / 16;
-        for (int idx = tid; idx < EROWS * VPO; idx += NT) {
-          const int r = idx / VPO, v = idx - r * VPO;
-          const int m = m0 + r0 + r;
-          const int xc = (v >> 2) * 64 + (v & 3) * 8;
-          const int no = (n0 >> 1) + v * 8;
-          if (m < p.M && no < (p.N >> 1)) {
-            const half8 x = *reinterpret_cast<const half8*>(sOut + r * OLD + xc);
-            const half8 gt = *reinterpret_cast<const half8*>(sOut + r * OLD + xc + 32);
-            half8 o8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o8[j] = (half_t)((float)x[j] * gelu_f((float)gt[j]));
-            *reinterpret_cast<half8*>(p.out + (size_t)m * p.ldo + no) = o8;
-          }
-        }
+        for (int idx = tid; idx < EROWS * VPO; idx += NT) epilogue_geglu_vec<BN, OLD>(p, sOut, m0 + r0, n0, idx);
       }
       if (p.stats && !p.geglu) {
         // per (64-row sub-block, channel) sum / sum of squares of the stored fp16 values, combined in a FIXED order (rows ascending per
