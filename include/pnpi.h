@@ -609,7 +609,8 @@ int pnpi_pp_rowtile_query(int cfg, int M, int N, int split);
  * variant (ring depth folded in for ids 0 / 1) and 2 / 1 / 0 for at most one / two / more blocks per CU; bm x bn tiles on a
  * gx x gy x gz grid; epi_lds / bias_init / res_late / k_order: the epilogue flags the kernel gets; stats: requested statistics are
  * produced, stats_tile_rows rows per partial; cls: the kernel class pnpi_profile_end counts the launch in; dma 0: register-staged
- * fallback kernel (fastk: its 64-channel fast path). */
+ * fallback kernel (fastk: its 64-channel fast path); instance: the kernel instance that runs, an index for
+ * pnpi_igemm_instance_info (-1: err was set before one was chosen). */
 typedef struct {
   int M, N, K, ksize, C1, C2, ldx1, ldx2, ldw, ldo, ldres;
   int bias, bias_aligned16, residual, geglu, stats;
@@ -626,8 +627,16 @@ typedef struct {
   int epi_lds, bias_init, res_late, k_order;
   int stats, stats_tile_rows, cls;
   int dma, fastk;
+  int instance;
 } pnpi_igemm_plan;
 int pnpi_igemm_plan_query(const pnpi_igemm_launch_desc* desc, pnpi_igemm_plan* plan);
+/* Host-only: row `index` (0, 1, ...) of the table of kernel instances launch_igemm can run, which a plan's `instance` indexes.  name:
+ * "dma<BM,BN,BKT,NST[,wgmW][,kgK]>" (LDS-DMA kernel: tile, K step, ring stages; wave groups per k-group if not 2; k-groups if not 1),
+ * "pp<BM,BN>" (ping-pong kernel), "v1<BM,BN,fast|generic>" (register-staged kernel); ablation instances add ",ablA".  geom7: the
+ * seven integers the profiling records carry for a launch of it (the LDS-DMA kernel's BM, BN, BKT, NST, WGM, ABL, WK; the ping-pong
+ * kernel's BM, BN, MI0, NI0, ABL, 0, -1; all 0 for the register-staged kernel).  ablation_only: the row exists in a `build --ablations`
+ * library only.  Each output is nullable.  Returns PNPI_EINVAL past the end of the table. */
+int pnpi_igemm_instance_info(int index, const char** name, int* geom7, int* ablation_only);
 /* Host-only: the row maps of pnpi_direct_edit's shared-row launch ("src_share") for nimg images and npass guidance passes.  Logical row
  * 4 (p nimg + im) + k is row k of [unc_src, unc_tgt, cond_src, cond_tgt] of pass p (0 = the offset pass) of image im, on the logical
  * latent 2 (p nimg + im) + k % 2.  Outputs (each nullable): lsel [compact latent] -> logical latent, cmap [compact row] -> compact latent,

@@ -101,7 +101,7 @@ class IgemmLaunchDesc(C.Structure):
 
 class IgemmPlan(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("err", "id", "split", "kchunks_per_split", "variant", "sparse", "bm", "bn", "gx", "gy", "gz", "vt_col0", "epi_lds",
-                                       "bias_init", "res_late", "k_order", "stats", "stats_tile_rows", "cls", "dma", "fastk")]
+                                       "bias_init", "res_late", "k_order", "stats", "stats_tile_rows", "cls", "dma", "fastk", "instance")]
 
 
 class AttnBwdPlan(C.Structure):
@@ -174,6 +174,7 @@ SYMBOLS = {
     "pnpi_tile_table_lookup": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pnpi_pp_rowtile_query": (_i, [_i, _i, _i, _i]),
     "pnpi_igemm_plan_query": (_i, [C.POINTER(IgemmLaunchDesc), C.POINTER(IgemmPlan)]),
+    "pnpi_igemm_instance_info": (_i, [_i, C.POINTER(C.c_char_p), _ip, _ip]),
     "pnpi_src_share_maps": (_i, [_i, _i] + [C.POINTER(C.c_int)] * 6),
     "pnpi_op_gemm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "pnpi_op_gemm_geglu": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i]),

@@ -757,6 +757,9 @@ int pnpi_igemm_plan_query(const pnpi_igemm_launch_desc* d, pnpi_igemm_plan* plan
   memcpy(plan, &pl, sizeof pl);
   return 0;
 }
+int pnpi_igemm_instance_info(int index, const char** name, int* geom7, int* ablation_only) {
+  return igemm_instance_info(index, name, geom7, ablation_only) ? PNPI_EINVAL : 0;
+}
 int pnpi_op_gemm(pnpi_ctx* c, const void* a, int lda, const void* w, int ldw, int M, int N, int K, float alpha, const float* bias,
                  const void* res, void* out, int ldo, int vt_col0, void* outT, int vt_ld, int vt_f32, int rpb, int force_cfg,
                  int force_split) {

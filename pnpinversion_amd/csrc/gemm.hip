@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(256) igemm_kernel(GemmP p_in) {
 // ------------------------------------------------------------------------------------------------------------------
 static half_t* g_zero_page = nullptr;   // out-of-range lanes of igemm_dma_kernel read it (igemm_init)
 
-static thread_local int g_last_geom[7] = {0, 0, 0, 0, 0, 0, 0};   // template arguments of the most recent igemm_dma_kernel launch (all 0: the v1 kernel)
+static thread_local int g_last_geom[7] = {0, 0, 0, 0, 0, 0, 0};   // geom of the most recent launch's instance (kInstances; all 0: the v1 kernel)
 // What launch_dma and launch_pp share: the logical grid and the XCD traversal order into p, the launch grid flattened and rounded up
 // to 8 workgroups, the kernel's dynamic-LDS attribute once per device.
 static int dma_launch_prep(GemmP& p, dim3& grid, DeviceOnce& attr_once, const void* kernel, int lds) {
@@ -253,7 +253,6 @@ static int dma_launch_prep(GemmP& p, dim3& grid, DeviceOnce& attr_once, const vo
 template <int BM, int BN, int BKT, int NST, int WGM = 2, int ABL = 0, int WK = 1>
 static int launch_dma(GemmP p, dim3 grid, hipStream_t st) {
   using GEO = IgemmGeom<BM, BN, BKT, NST, WGM, ABL, WK>;
-  g_last_geom[0] = BM; g_last_geom[1] = BN; g_last_geom[2] = BKT; g_last_geom[3] = NST; g_last_geom[4] = WGM; g_last_geom[5] = ABL; g_last_geom[6] = WK;
   static DeviceOnce attr_once;
   if (int r = dma_launch_prep(p, grid, attr_once, (const void*)igemm_dma_kernel<BM, BN, BKT, NST, WGM, ABL, WK>, GEO::LDS)) return r;
   igemm_dma_kernel<BM, BN, BKT, NST, WGM, ABL, WK><<<grid, GEO::NT_ALL, GEO::LDS, st>>>(p, g_zero_page);
@@ -265,11 +264,22 @@ static int launch_dma(GemmP p, dim3 grid, hipStream_t st) {
 template <int BM, int BN, int MI0, int NI0, int ABL = 0>
 static int launch_pp(GemmP p, dim3 grid, hipStream_t st) {
   using GEO = PpGeom<BM, BN, MI0, NI0>;
-  g_last_geom[0] = BM; g_last_geom[1] = BN; g_last_geom[2] = MI0; g_last_geom[3] = NI0; g_last_geom[4] = ABL; g_last_geom[5] = 0; g_last_geom[6] = -1;   // [6] = -1: igemm_pp_kernel
   static DeviceOnce attr_once;
   if (int r = dma_launch_prep(p, grid, attr_once, (const void*)igemm_pp_kernel<BM, BN, MI0, NI0, ABL>, GEO::LDS)) return r;
   igemm_pp_kernel<BM, BN, MI0, NI0, ABL><<<grid, GEO::NT, GEO::LDS, st>>>(p);
   return 0;
+}
+
+// The register-staged v1 kernel: its launch, and its dynamic-LDS attribute (igemm_init sets it).
+static constexpr size_t lds_bytes(int BM, int BN) { return (size_t)(2 * BM + 2 * BN) * LDS_LD * sizeof(half_t); }
+template <int BM, int BN, bool FASTK>
+static int launch_v1(GemmP p, dim3 grid, hipStream_t st) {
+  igemm_kernel<BM, BN, FASTK><<<grid, 256, lds_bytes(BM, BN), st>>>(p);
+  return 0;
+}
+template <int BM, int BN, bool FASTK>
+static int init_v1() {
+  return (int)hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, FASTK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(BM, BN));
 }
 
 // Deterministic split-K combine: fixed slab order, then the common epilogue.
@@ -325,23 +335,9 @@ void gemm_defaults(GemmP& p) {
   p.k_order = 0; p.nbatch = 1; p.sx1 = 0; p.sw = 0; p.sout = 0; p.soutT = 0;
 }
 
-static constexpr size_t lds_bytes(int BM, int BN) { return (size_t)(2 * BM + 2 * BN) * LDS_LD * sizeof(half_t); }
-
 static constexpr size_t ZERO_PAGE_BYTES = 128 << 10;   // >= 2 * (longest K + one chunk): out-of-range rows walk it like real rows
 static thread_local int g_last_cfg = -1, g_last_split = 1;   // per thread: two contexts may launch from two threads   // what the most recent launch_igemm used (profiling dumps)
 void igemm_last_launch(int* cfg, int* split, int* geom) { *cfg = g_last_cfg; *split = g_last_split; for (int i = 0; i < 7; ++i) geom[i] = g_last_geom[i]; }
-
-int igemm_init() {
-  if (!g_zero_page) {
-    HIP_CHECK_RET(hipMalloc((void**)&g_zero_page, ZERO_PAGE_BYTES));
-    HIP_CHECK_RET(hipMemset(g_zero_page, 0, ZERO_PAGE_BYTES));
-  }
-  HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<128, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128)));
-  HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<128, 128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128)));
-  HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<64, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(64, 64)));
-  HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<64, 64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(64, 64)));
-  return 0;
-}
 
 // product tile configurations with one k-group: compiler-scheduled main loop, or (tuning "igemm_sched", in a `build --ablations` library:
 // tools/pp_ablate.py, tools/profile_pp.sh) the hand-scheduled ones
@@ -352,16 +348,155 @@ static constexpr bool kAblations = false;
 #endif
 template <int BM, int BN, int BKT, int NST>
 static int launch_dma_s(GemmP p, dim3 grid, hipStream_t st) {
-#ifdef PNPI_ABLATIONS
-  if (g_sched == 1) return launch_dma<BM, BN, BKT, NST, 2, 4>(p, grid, st);
-  if (g_sched == 2) return launch_dma<BM, BN, BKT, NST, 2, 5>(p, grid, st);
+#ifdef PNPI_ABLATIONS      // in place of the row's instance: the launch record shows the ABL that ran
+  if (g_sched == 1) { g_last_geom[5] = 4; return launch_dma<BM, BN, BKT, NST, 2, 4>(p, grid, st); }
+  if (g_sched == 2) { g_last_geom[5] = 5; return launch_dma<BM, BN, BKT, NST, 2, 5>(p, grid, st); }
 #endif
   return launch_dma<BM, BN, BKT, NST>(p, grid, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Kernel instances: one row per instance a build can launch.  igemm_plan names the row (kInstRules), launch_igemm calls its launch
+// function and records its geom (igemm_last_launch), pnpi_igemm_instance_info hands the table to the tests.
+//   name    "dma<BM,BN,BKT,NST[,wgmW][,kgK]>" (WGM = 2 and one k-group are left out), "pp<BM,BN>", "v1<BM,BN,fast|generic>"; an ablation
+//           instance adds ",ablA", A the kernel's ABL argument: "dma<128,128,32,3,abl1>", "pp<256,256,abl3>"
+//   geom    igemm_dma_kernel's <BM, BN, BKT, NST, WGM, ABL, WK>; igemm_pp_kernel's <BM, BN, MI0, NI0, ABL>, 0, -1; the v1 kernel: all 0
+//   launch  launch_dma_s: the instance, or under tuning "igemm_sched" (ablation library) its hand-scheduled form, which has no row
+//   init    igemm_init calls it (the v1 kernels' LDS attribute; the other kernels set theirs at their first launch on a device)
+// Product rows first; the instances of a `build --ablations` library in one block at the end.
+// ------------------------------------------------------------------------------------------------------------------
+using LaunchFn = int (*)(GemmP, dim3, hipStream_t);
+struct Instance { const char* name; int geom[7]; bool ablation_only; LaunchFn launch; int (*init)(); };
+template <int BM, int BN, int BKT, int NST, int WGM = 2, int ABL = 0, int WK = 1>
+static constexpr Instance dma_row(const char* name) { return {name, {BM, BN, BKT, NST, WGM, ABL, WK}, ABL != 0, launch_dma<BM, BN, BKT, NST, WGM, ABL, WK>, nullptr}; }
+template <int BM, int BN, int BKT, int NST>
+static constexpr Instance dma_s_row(const char* name) { return {name, {BM, BN, BKT, NST, 2, 0, 1}, false, launch_dma_s<BM, BN, BKT, NST>, nullptr}; }
+template <int BM, int BN, int MI0, int NI0, int ABL = 0>
+static constexpr Instance pp_row(const char* name) { return {name, {BM, BN, MI0, NI0, ABL, 0, -1}, ABL != 0, launch_pp<BM, BN, MI0, NI0, ABL>, nullptr}; }
+template <int BM, int BN, bool FASTK>
+static constexpr Instance v1_row(const char* name) { return {name, {0, 0, 0, 0, 0, 0, 0}, false, launch_v1<BM, BN, FASTK>, init_v1<BM, BN, FASTK>}; }
+static constexpr Instance kInstances[] = {
+  v1_row<128, 128, true>("v1<128,128,fast>"), v1_row<128, 128, false>("v1<128,128,generic>"),
+  v1_row<64, 64, true>("v1<64,64,fast>"), v1_row<64, 64, false>("v1<64,64,generic>"),
+  dma_s_row<128, 128, 64, 2>("dma<128,128,64,2>"),
+  dma_row<128, 128, 64, 3>("dma<128,128,64,3>"),
+  dma_s_row<128, 128, 32, 2>("dma<128,128,32,2>"),
+  dma_s_row<128, 128, 32, 3>("dma<128,128,32,3>"),
+  dma_row<128, 128, 32, 4>("dma<128,128,32,4>"),
+  dma_row<128, 128, 32, 8>("dma<128,128,32,8>"),        // 128 KB ring: sparse launches
+  dma_row<64, 64, 64, 2>("dma<64,64,64,2>"),
+  dma_s_row<64, 64, 64, 3>("dma<64,64,64,3>"),
+  dma_row<64, 64, 64, 4>("dma<64,64,64,4>"),
+  dma_row<64, 64, 64, 8>("dma<64,64,64,8>"),            // 128 KB ring: sparse launches
+  dma_row<64, 64, 32, 4>("dma<64,64,32,4>"),
+  dma_row<256, 128, 32, 2>("dma<256,128,32,2>"),
+  dma_row<256, 128, 32, 3>("dma<256,128,32,3>"),
+  dma_s_row<128, 320, 32, 2>("dma<128,320,32,2>"),      // 56 KB ring, two-pass epilogue, 2 blocks / CU
+  dma_row<128, 320, 32, 3>("dma<128,320,32,3>"),        // 84 KB ring = whole-tile epilogue, 1 block / CU
+  dma_row<128, 320, 32, 5>("dma<128,320,32,5>"),
+  dma_row<128, 320, 64, 2>("dma<128,320,64,2>"),        // 128-byte rows, 112 KB, 1 block / CU
+  dma_s_row<128, 256, 32, 2>("dma<128,256,32,2>"),      // 48 KB: two-pass epilogue, 3 blocks / CU by LDS
+  dma_row<128, 256, 32, 3>("dma<128,256,32,3>"),        // 72 KB, 2 blocks / CU
+  dma_row<128, 256, 32, 6>("dma<128,256,32,6>"),
+  dma_row<128, 256, 64, 2>("dma<128,256,64,2>"),
+  dma_row<256, 320, 64, 2, 4>("dma<256,320,64,2,wgm4>"),
+  dma_row<256, 256, 64, 2, 4>("dma<256,256,64,2,wgm4>"),
+  dma_row<64, 64, 64, 2, 2, 0, 4>("dma<64,64,64,2,kg4>"),
+  dma_row<128, 128, 32, 3, 2, 0, 2>("dma<128,128,32,3,kg2>"),
+  dma_row<128, 128, 64, 2, 2, 0, 2>("dma<128,128,64,2,kg2>"),
+  dma_row<64, 64, 64, 2, 2, 0, 2>("dma<64,64,64,2,kg2>"),
+  dma_row<64, 320, 32, 2>("dma<64,320,32,2>"),
+  pp_row<256, 256, 2, 4>("pp<256,256>"), pp_row<192, 320, 1, 4>("pp<192,320>"), pp_row<128, 320, 1, 4>("pp<128,320>"), pp_row<192, 256, 1, 4>("pp<192,256>"),
+#ifdef PNPI_ABLATIONS
+  dma_row<128, 128, 32, 3, 2, 1>("dma<128,128,32,3,abl1>"),      // DMA only
+  dma_row<128, 128, 32, 3, 2, 2>("dma<128,128,32,3,abl2>"),      // compute only
+  dma_row<128, 128, 32, 3, 2, 3>("dma<128,128,32,3,abl3>"),      // activation loads for tap 0 only
+  dma_row<128, 320, 32, 2, 2, 1>("dma<128,320,32,2,abl1>"),      // DMA only
+  dma_row<128, 320, 32, 2, 2, 2>("dma<128,320,32,2,abl2>"),      // compute only
+  // the tall ping-pong tiles without their MFMAs (1), without their DMA (2), DMA only (3), MFMAs only (4)
+  pp_row<256, 256, 2, 4, 1>("pp<256,256,abl1>"), pp_row<256, 256, 2, 4, 2>("pp<256,256,abl2>"), pp_row<256, 256, 2, 4, 3>("pp<256,256,abl3>"), pp_row<256, 256, 2, 4, 4>("pp<256,256,abl4>"),
+  pp_row<192, 320, 1, 4, 1>("pp<192,320,abl1>"), pp_row<192, 320, 1, 4, 2>("pp<192,320,abl2>"), pp_row<192, 320, 1, 4, 3>("pp<192,320,abl3>"), pp_row<192, 320, 1, 4, 4>("pp<192,320,abl4>"),
+#endif
+};
+static constexpr int kNumInstances = (int)(sizeof(kInstances) / sizeof(kInstances[0]));
+static constexpr bool str_eq(const char* a, const char* b) { for (; *a && *a == *b; ++a, ++b) {} return *a == *b; }
+static constexpr int inst(const char* name) {      // the row of that name; -1: none
+  for (int i = 0; i < kNumInstances; ++i)
+    if (str_eq(kInstances[i].name, name)) return i;
+  return -1;
+}
+int igemm_instance_info(int index, const char** name, int* geom7, int* ablation_only) {
+  if (index < 0 || index >= kNumInstances) return -1;
+  if (name) *name = kInstances[index].name;
+  if (ablation_only) *ablation_only = kInstances[index].ablation_only;
+  for (int i = 0; geom7 && i < 7; ++i) geom7[i] = kInstances[index].geom[i];
+  return 0;
+}
+
+int igemm_init() {
+  if (!g_zero_page) {
+    HIP_CHECK_RET(hipMalloc((void**)&g_zero_page, ZERO_PAGE_BYTES));
+    HIP_CHECK_RET(hipMemset(g_zero_page, 0, ZERO_PAGE_BYTES));
+  }
+  for (const Instance& in : kInstances)
+    if (in.init)
+      if (int r = in.init()) return r;
+  return 0;
+}
+
+// Which instance a plan runs: the first row that matches the tile id, the kernel path (the register-staged kernels by FASTK, or LDS-DMA),
+// the tile's knob (kTileDesc; DEF: whatever it holds) and the plan's occupancy class (`sparse`; ANY: whatever).  `reports` is what the
+// plan's variant field then shows (KEEP: the knob's value): ids 0 / 1 take their deep rings only from the default variant and report the
+// variant that names the same ring directly.  A variant without a row fails the plan (-10): the ping-pong tiles have rows for igemm_vpp
+// = 0 only, and in an ablation library the tall ones for 1 ... 4 and a default.
+enum { DEF = INT_MIN, KEEP = INT_MIN, ANY = -1 };
+enum InstPath { V1_FAST, V1_GENERIC, DMA };
+struct InstRule { int id; InstPath path; int variant, sparse, reports, inst; };
+static constexpr InstRule kInstRules[] = {
+  // id, path, variant, sparse, reports, instance
+#ifdef PNPI_ABLATIONS
+  {0, DMA, 11, ANY, KEEP, inst("dma<128,128,32,3,abl1>")}, {0, DMA, 12, ANY, KEEP, inst("dma<128,128,32,3,abl2>")}, {0, DMA, 15, ANY, KEEP, inst("dma<128,128,32,3,abl3>")},
+  {4, DMA, 11, ANY, KEEP, inst("dma<128,320,32,2,abl1>")}, {4, DMA, 12, ANY, KEEP, inst("dma<128,320,32,2,abl2>")},
+  {16, DMA, 1, ANY, KEEP, inst("pp<256,256,abl1>")}, {16, DMA, 2, ANY, KEEP, inst("pp<256,256,abl2>")}, {16, DMA, 3, ANY, KEEP, inst("pp<256,256,abl3>")},
+  {16, DMA, 4, ANY, KEEP, inst("pp<256,256,abl4>")}, {16, DMA, DEF, ANY, KEEP, inst("pp<256,256>")},
+  {17, DMA, 1, ANY, KEEP, inst("pp<192,320,abl1>")}, {17, DMA, 2, ANY, KEEP, inst("pp<192,320,abl2>")}, {17, DMA, 3, ANY, KEEP, inst("pp<192,320,abl3>")},
+  {17, DMA, 4, ANY, KEEP, inst("pp<192,320,abl4>")}, {17, DMA, DEF, ANY, KEEP, inst("pp<192,320>")},
+#endif
+  {0, V1_FAST, DEF, ANY, KEEP, inst("v1<128,128,fast>")}, {0, V1_GENERIC, DEF, ANY, KEEP, inst("v1<128,128,generic>")},
+  {1, V1_FAST, DEF, ANY, KEEP, inst("v1<64,64,fast>")}, {1, V1_GENERIC, DEF, ANY, KEEP, inst("v1<64,64,generic>")},
+  // the default variants of ids 0 / 1 by occupancy (igemm_plan: "Ring depth by occupancy")
+  {0, DMA, 2, 2, 8, inst("dma<128,128,32,8>")}, {0, DMA, 2, 1, 3, inst("dma<128,128,32,4>")}, {0, DMA, 2, ANY, KEEP, inst("dma<128,128,32,3>")},
+  {0, DMA, 1, ANY, KEEP, inst("dma<128,128,64,3>")}, {0, DMA, 3, ANY, KEEP, inst("dma<128,128,32,4>")}, {0, DMA, 4, ANY, KEEP, inst("dma<128,128,32,2>")},
+  {0, DMA, 8, ANY, KEEP, inst("dma<128,128,32,8>")}, {0, DMA, DEF, ANY, KEEP, inst("dma<128,128,64,2>")},
+  {1, DMA, 0, 2, 8, inst("dma<64,64,64,8>")}, {1, DMA, 0, 1, 2, inst("dma<64,64,64,4>")},
+  {1, DMA, 1, ANY, KEEP, inst("dma<64,64,64,2>")}, {1, DMA, 2, ANY, KEEP, inst("dma<64,64,64,4>")}, {1, DMA, 3, ANY, KEEP, inst("dma<64,64,32,4>")},
+  {1, DMA, 8, ANY, KEEP, inst("dma<64,64,64,8>")}, {1, DMA, DEF, ANY, KEEP, inst("dma<64,64,64,3>")},
+  {3, DMA, 1, ANY, KEEP, inst("dma<256,128,32,2>")}, {3, DMA, DEF, ANY, KEEP, inst("dma<256,128,32,3>")},
+  {4, DMA, 1, 2, KEEP, inst("dma<128,320,32,5>")}, {4, DMA, 0, ANY, KEEP, inst("dma<128,320,32,3>")}, {4, DMA, 2, ANY, KEEP, inst("dma<128,320,64,2>")},
+  {4, DMA, DEF, ANY, KEEP, inst("dma<128,320,32,2>")},
+  {5, DMA, 1, 2, KEEP, inst("dma<128,256,32,6>")}, {5, DMA, 0, ANY, KEEP, inst("dma<128,256,32,3>")}, {5, DMA, 2, ANY, KEEP, inst("dma<128,256,64,2>")},
+  {5, DMA, DEF, ANY, KEEP, inst("dma<128,256,32,2>")},
+  {6, DMA, DEF, ANY, KEEP, inst("dma<256,320,64,2,wgm4>")}, {7, DMA, DEF, ANY, KEEP, inst("dma<256,256,64,2,wgm4>")},
+  {8, DMA, DEF, ANY, KEEP, inst("dma<64,64,64,2,kg4>")}, {9, DMA, DEF, ANY, KEEP, inst("dma<128,128,32,3,kg2>")},
+  {10, DMA, DEF, ANY, KEEP, inst("dma<128,128,64,2,kg2>")}, {11, DMA, DEF, ANY, KEEP, inst("dma<64,64,64,2,kg2>")},
+  {12, DMA, DEF, ANY, KEEP, inst("dma<64,320,32,2>")}, {13, DMA, DEF, ANY, KEEP, inst("dma<128,128,32,2>")},
+  {14, DMA, DEF, ANY, KEEP, inst("dma<128,128,64,2>")}, {15, DMA, DEF, ANY, KEEP, inst("dma<128,256,64,2>")},
+  {18, DMA, DEF, ANY, KEEP, inst("dma<128,128,64,3>")},
+  {16, DMA, 0, ANY, KEEP, inst("pp<256,256>")}, {17, DMA, 0, ANY, KEEP, inst("pp<192,320>")},
+  {19, DMA, 0, ANY, KEEP, inst("pp<128,320>")}, {20, DMA, 0, ANY, KEEP, inst("pp<192,256>")},
+};
+static constexpr const InstRule* inst_rule(int id, InstPath path, int variant, int sparse) {
+  for (const InstRule& r : kInstRules)
+    if (r.id == id && r.path == path && (r.variant == DEF || r.variant == variant) && (r.sparse == ANY || r.sparse == sparse)) return &r;
+  return nullptr;
+}
+static_assert(inst_rule(0, DMA, 7, 2)->inst == inst("dma<128,128,64,2>") && inst_rule(0, DMA, 3, 2)->reports == KEEP, "an unnamed variant is the default; deep rings only from the default variant");
+static_assert(!inst_rule(19, DMA, 1, 0) && !inst_rule(20, DMA, 4, 2) && (inst_rule(16, DMA, 1, 0) != nullptr) == kAblations && (inst_rule(17, DMA, 7, 0) != nullptr) == kAblations,
+              "igemm_vpp: the short ping-pong tiles have no ablation instance, the tall ones in an ablation library only");
+
+// ------------------------------------------------------------------------------------------------------------------
 // Tile descriptors: one row per tile id (launch_igemm's force_cfg, the tools' CFG / NAME maps, csrc/tile_table.inc).  Everything the
-// launcher needs to know about a tile is a field here: a new tile is a row of this table (plus a case in igemm_dispatch if it has variants).
+// launcher needs to know about a tile is a field here: a new tile is a row of this table, its kInstances rows and its kInstRules rows.
 // Id 2 is no tile: it is the caller's alias for "id 1 with split-K chosen by the launcher".
 //   fam       FAM_V1: 4-wave LDS-DMA kernel that also exists as the register-staged v1 kernel (shapes the DMA kernels cannot take);
 //             FAM_DMA: 4-wave LDS-DMA kernel only (WGM x 2 waves per k-group); FAM_PP: the 8-wave ping-pong kernel (igemm_pp.inc)
@@ -372,32 +507,32 @@ static int launch_dma_s(GemmP p, dim3 grid, hipStream_t st) {
 //   alt       ping-pong tiles: the id of the other row height of the same BN (pp_rowtile_pick); -1 otherwise
 //   splits    takes split-K;  stats: takes a launch that produces statistics (the 192 x 256 tile cannot reproduce the 256 x 256 tile's
 //             statistics tree: 16 row groups over 3 sub-blocks)
-//   launch    the tile's kernel instance; nullptr: it has several, igemm_dispatch picks by the plan's variant
+//   knob      the tuning knob that holds the tile's variant (kInstRules); nullptr: the tile has one instance
 // ------------------------------------------------------------------------------------------------------------------
 enum TileFam { FAM_V1, FAM_DMA, FAM_PP };
-struct TileDesc { int id, bm, bn; TileFam fam; int kgroups; bool wide; int cls, stat_rows, alt; bool splits, stats; int (*launch)(GemmP, dim3, hipStream_t); };
+struct TileDesc { int id, bm, bn; TileFam fam; int kgroups; bool wide; int cls, stat_rows, alt; bool splits, stats; const int* knob; };
 static constexpr TileDesc kTileDesc[] = {
-  // id, bm, bn, fam, kgroups, wide, cls, stat_rows, alt, splits, stats, launch
-  {0, 128, 128, FAM_V1, 1, false, 0, 128, -1, true, true, nullptr},     // 64-byte rows x 3 stages; deeper rings on sparse launches (igemm_v128)
-  {1, 64, 64, FAM_V1, 1, false, 1, 64, -1, true, true, nullptr},        // (igemm_v64)
-  {3, 256, 128, FAM_DMA, 1, false, 0, 256, -1, false, true, nullptr},   // ablation: too few tiles at these sizes
-  {4, 128, 320, FAM_DMA, 1, true, 9, 128, -1, true, true, nullptr},     // (igemm_v320)
-  {5, 128, 256, FAM_DMA, 1, true, 9, 128, -1, true, true, nullptr},     // (igemm_v256n)
-  {6, 256, 320, FAM_DMA, 1, true, 9, 256, -1, true, true, launch_dma<256, 320, 64, 2, 4>},     // 6 / 7: 8 waves, 128-byte rows, two stages, one block per CU
-  {7, 256, 256, FAM_DMA, 1, true, 9, 256, -1, true, true, launch_dma<256, 256, 64, 2, 4>},
-  {8, 64, 64, FAM_DMA, 4, true, 1, 64, -1, true, true, launch_dma<64, 64, 64, 2, 2, 0, 4>},        // 16 waves: 4 k-groups
-  {9, 128, 128, FAM_DMA, 2, true, 0, 128, -1, true, true, launch_dma<128, 128, 32, 3, 2, 0, 2>},     // 8 waves: 2 k-groups, 96 KB
-  {10, 128, 128, FAM_DMA, 2, true, 0, 128, -1, true, true, launch_dma<128, 128, 64, 2, 2, 0, 2>},    // 8 waves: 2 k-groups, 128-byte rows, 128 KB
-  {11, 64, 64, FAM_DMA, 2, true, 1, 64, -1, true, true, launch_dma<64, 64, 64, 2, 2, 0, 2>},       // 8 waves: 2 k-groups, 64 KB (2 blocks / CU)
-  {12, 64, 320, FAM_DMA, 1, true, 9, 64, -1, true, true, launch_dma<64, 320, 32, 2>},      // 768 tiles on the 12-row 64 x 64 level = 3 per CU
-  {13, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, launch_dma_s<128, 128, 32, 2>},   // 32 KB two-stage ring (two-pass epilogue): 4 blocks / CU for the short-K layers
-  {14, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, launch_dma_s<128, 128, 64, 2>},   // 128-byte rows, half the barriers per k: 64 KB, 2 blocks / CU
-  {15, 128, 256, FAM_DMA, 1, true, 9, 128, -1, true, true, launch_dma<128, 256, 64, 2>},    // the same for the 128 x 256 tile: 96 KB, 1 block / CU
-  {16, 256, 256, FAM_PP, 1, true, 9, 64, 20, true, true, nullptr},
-  {17, 192, 320, FAM_PP, 1, true, 9, 64, 19, true, true, nullptr},
-  {18, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, launch_dma<128, 128, 64, 3>},   // 128-byte rows, three stages (96 KB, 1 block / CU): the one-wave launches of the 16 x 16 level
-  {19, 128, 320, FAM_PP, 1, true, 9, 64, 17, true, true, launch_pp<128, 320, 1, 4>},      // 19 / 20: the shorter ping-pong tiles: force_cfg or pp_rowtile_pick, never the table
-  {20, 192, 256, FAM_PP, 1, true, 9, 64, 16, true, false, launch_pp<192, 256, 1, 4>},
+  // id, bm, bn, fam, kgroups, wide, cls, stat_rows, alt, splits, stats, knob
+  {0, 128, 128, FAM_V1, 1, false, 0, 128, -1, true, true, &g_var128},     // 64-byte rows x 3 stages; deeper rings on sparse launches (igemm_v128)
+  {1, 64, 64, FAM_V1, 1, false, 1, 64, -1, true, true, &g_var64},        // (igemm_v64)
+  {3, 256, 128, FAM_DMA, 1, false, 0, 256, -1, false, true, &g_var256},   // ablation: too few tiles at these sizes
+  {4, 128, 320, FAM_DMA, 1, true, 9, 128, -1, true, true, &g_var320},     // (igemm_v320)
+  {5, 128, 256, FAM_DMA, 1, true, 9, 128, -1, true, true, &g_var256n},     // (igemm_v256n)
+  {6, 256, 320, FAM_DMA, 1, true, 9, 256, -1, true, true, nullptr},     // 6 / 7: 8 waves, 128-byte rows, two stages, one block per CU
+  {7, 256, 256, FAM_DMA, 1, true, 9, 256, -1, true, true, nullptr},
+  {8, 64, 64, FAM_DMA, 4, true, 1, 64, -1, true, true, nullptr},        // 16 waves: 4 k-groups
+  {9, 128, 128, FAM_DMA, 2, true, 0, 128, -1, true, true, nullptr},     // 8 waves: 2 k-groups, 96 KB
+  {10, 128, 128, FAM_DMA, 2, true, 0, 128, -1, true, true, nullptr},    // 8 waves: 2 k-groups, 128-byte rows, 128 KB
+  {11, 64, 64, FAM_DMA, 2, true, 1, 64, -1, true, true, nullptr},       // 8 waves: 2 k-groups, 64 KB (2 blocks / CU)
+  {12, 64, 320, FAM_DMA, 1, true, 9, 64, -1, true, true, nullptr},      // 768 tiles on the 12-row 64 x 64 level = 3 per CU
+  {13, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, nullptr},   // 32 KB two-stage ring (two-pass epilogue): 4 blocks / CU for the short-K layers
+  {14, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, nullptr},   // 128-byte rows, half the barriers per k: 64 KB, 2 blocks / CU
+  {15, 128, 256, FAM_DMA, 1, true, 9, 128, -1, true, true, nullptr},    // the same for the 128 x 256 tile: 96 KB, 1 block / CU
+  {16, 256, 256, FAM_PP, 1, true, 9, 64, 20, true, true, &g_varpp},
+  {17, 192, 320, FAM_PP, 1, true, 9, 64, 19, true, true, &g_varpp},
+  {18, 128, 128, FAM_DMA, 1, false, 0, 128, -1, true, true, nullptr},   // 128-byte rows, three stages (96 KB, 1 block / CU): the one-wave launches of the 16 x 16 level
+  {19, 128, 320, FAM_PP, 1, true, 9, 64, 17, true, true, &g_varpp},      // 19 / 20: the shorter ping-pong tiles: force_cfg or pp_rowtile_pick, never the table
+  {20, 192, 256, FAM_PP, 1, true, 9, 64, 16, true, false, &g_varpp},
 };
 static constexpr const TileDesc* tile_desc(int id) {      // nullptr: no such tile (id 2 included)
   return (id < 0 || id == 2 || id > 20) ? nullptr : &kTileDesc[id < 2 ? id : id - 1];
@@ -429,6 +564,24 @@ static constexpr bool tile_tables_consistent() {      // every id finds its own 
   return sizeof(kTileDesc) / sizeof(kTileDesc[0]) == 20;
 }
 static_assert(tile_tables_consistent(), "kTileDesc rows out of place, or tile_table.inc names an id without a row");
+// every rule names a tile and an instance; every instance has a rule; every tile has an instance at every occupancy whatever its knob
+// holds (a ping-pong tile: at igemm_vpp = 0), and a FAM_V1 tile both register-staged ones
+static constexpr bool inst_tables_consistent() {
+  bool used[kNumInstances] = {};
+  for (const InstRule& r : kInstRules) {
+    if (!tile_desc(r.id) || r.inst < 0) return false;
+    used[r.inst] = true;
+  }
+  for (bool u : used)
+    if (!u) return false;
+  for (const TileDesc& d : kTileDesc) {
+    for (int sparse = 0; sparse <= 2; ++sparse)
+      if (!inst_rule(d.id, DMA, d.fam == FAM_PP ? 0 : DEF, sparse)) return false;
+    if (d.fam == FAM_V1 && !(inst_rule(d.id, V1_FAST, DEF, 0) && inst_rule(d.id, V1_GENERIC, DEF, 0))) return false;
+  }
+  return true;
+}
+static_assert(inst_tables_consistent(), "kInstRules names no tile or no kInstances row, a row has no rule, or a tile has no default rule");
 // Table lookup: the exact {M, N, K, ksize}; else -- the same layer (N, K, ksize) at another row count, e.g. --batch_size 2 ... 7 of the
 // sweep driver -- the entry whose M is nearest in ratio, up to 4x away.  Held out of the table one row count at a time, the nearest
 // entry's configuration costs 13.3 / 10.1 / 6.7 / 5.2 ms per 12- / 8- / 4- / 3-row forward against 15.3 / 10.4 / 6.9 / 6.1 ms for the
@@ -505,10 +658,10 @@ static bool pp_eligible(const GemmP& p, const TileDesc* d, int split, bool dma_o
 // dereferenced (pointers are looked at for null / alignment only).  Order of decisions: forced tile (caller's force_cfg, else tuning
 // "igemm_force_cfg") | measured table at sel_M | cost model; then the fall-backs -- batched launches lose split-K and k-groups, shapes
 // the DMA kernels cannot take go to the v1 tiles, split-K is clamped to the workspace, a ping-pong tile the launch is not eligible for
-// becomes 128 x 128 -- then the ping-pong row height on the launched M, the epilogue, the grid and the ring depth.
+// becomes 128 x 128 -- then the ping-pong row height on the launched M, the epilogue, the grid, the occupancy class and the instance.
 IgemmPlan igemm_plan(GemmP p, bool have_ws, size_t ws_bytes, int force_cfg, int force_split, int sel_M) {
   IgemmPlan pl = {};
-  pl.id = -1; pl.split = 1; pl.stats_tile_rows = -1;
+  pl.id = -1; pl.split = 1; pl.stats_tile_rows = -1; pl.instance = -1;
   auto fail = [&](int err) { pl.err = err; return pl; };
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return fail(-2);
   const int Cin = p.C1 + p.C2;
@@ -621,94 +774,16 @@ IgemmPlan igemm_plan(GemmP p, bool have_ws, size_t ws_bytes, int force_cfg, int 
   // 8-deep ring (7 chunks in flight per block); two blocks per CU a 4-deep one; fuller launches the shallow rings that fit 3 blocks.
   const long units = (long)((selM + d->bm - 1) / d->bm) * pl.gy * pl.gz;
   pl.sparse = !g_deep_rings ? 0 : (units <= 256 ? 2 : (units <= 512 ? 1 : 0));
-  if (cpp) {
-    // igemm_vpp: the ablation instances exist in a `build --ablations` library only, and there for the tall tiles only
-    if (g_varpp && !(kAblations && pp_is_tall(d))) return fail(-10);
-    pl.variant = g_varpp;
-  } else if (dma_ok) {
-    switch (d->id) {     // the tiles with tuning variants; ids 0 and 1 fold the ring depth in
-    case 0:
-      pl.variant = g_var128;
-      // 128-byte rows with 2 stages (64 KB, 2 blocks / CU) beat 64-byte rows with 3 stages (48 KB, 3 blocks / CU) once every CU
-      // holds two blocks that cover for each other's exposed loads; below that the deeper ring wins
-      if (g_v128_bk64_tiles > 0 && pl.variant == 2 && units >= g_v128_bk64_tiles) pl.variant = 0;
-      if (pl.variant == 2 && pl.sparse) pl.variant = pl.sparse == 2 ? 8 : 3;
-      break;
-    case 1:
-      pl.variant = g_var64;
-      if (pl.variant == 0 && pl.sparse) pl.variant = pl.sparse == 2 ? 8 : 2;
-      break;
-    case 3: pl.variant = g_var256; break;
-    case 4: pl.variant = g_var320; break;
-    case 5: pl.variant = g_var256n; break;
-    }
-  }
+  // The instance (kInstRules): by the tile's knob and the occupancy class.  A variant without a row: -10
+  int variant = dma_ok && d->knob ? *d->knob : 0;
+  // 128-byte rows with 2 stages (64 KB, 2 blocks / CU) beat 64-byte rows with 3 stages (48 KB, 3 blocks / CU) once every CU
+  // holds two blocks that cover for each other's exposed loads; below that the deeper ring wins
+  if (d->id == 0 && g_v128_bk64_tiles > 0 && variant == 2 && units >= g_v128_bk64_tiles) variant = 0;
+  const InstRule* r = inst_rule(d->id, dma_ok ? DMA : (fast ? V1_FAST : V1_GENERIC), variant, pl.sparse);
+  if (!r) return fail(-10);
+  pl.variant = r->reports == KEEP ? variant : r->reports;
+  pl.instance = r->inst;
   return pl;
-}
-
-// The kernel instance of a plan: tile id, then the plan's variant where a tile has several.
-static int igemm_dispatch(const IgemmPlan& pl, const GemmP& p, hipStream_t st) {
-  const dim3 grid(pl.gx, pl.gy, pl.gz);
-  if (!pl.dma) {      // register-staged v1 kernel: ids 0 and 1
-    void (*const k)(GemmP) = pl.bm == 64 ? (pl.fastk ? igemm_kernel<64, 64, true> : igemm_kernel<64, 64, false>)
-                                         : (pl.fastk ? igemm_kernel<128, 128, true> : igemm_kernel<128, 128, false>);
-    k<<<grid, 256, lds_bytes(pl.bm, pl.bn), st>>>(p);
-    return 0;
-  }
-  if (const auto launch = tile_desc(pl.id)->launch) return launch(p, grid, st);
-  switch (pl.id) {
-    case 0: switch (pl.variant) {
-      case 1: return launch_dma<128, 128, 64, 3>(p, grid, st);
-      case 2: return launch_dma_s<128, 128, 32, 3>(p, grid, st);
-      case 3: return launch_dma<128, 128, 32, 4>(p, grid, st);
-      case 4: return launch_dma_s<128, 128, 32, 2>(p, grid, st);
-      case 8: return launch_dma<128, 128, 32, 8>(p, grid, st);       // 128 KB ring: sparse launches
-#ifdef PNPI_ABLATIONS
-      case 11: return launch_dma<128, 128, 32, 3, 2, 1>(p, grid, st);   // ablation: DMA only
-      case 12: return launch_dma<128, 128, 32, 3, 2, 2>(p, grid, st);   // ablation: compute only
-      case 15: return launch_dma<128, 128, 32, 3, 2, 3>(p, grid, st);   // ablation: activation loads for tap 0 only
-#endif
-      default: return launch_dma_s<128, 128, 64, 2>(p, grid, st);
-    }
-    case 1: switch (pl.variant) {
-      case 8: return launch_dma<64, 64, 64, 8>(p, grid, st);         // 128 KB ring: sparse launches
-      case 1: return launch_dma<64, 64, 64, 2>(p, grid, st);
-      case 2: return launch_dma<64, 64, 64, 4>(p, grid, st);
-      case 3: return launch_dma<64, 64, 32, 4>(p, grid, st);
-      default: return launch_dma_s<64, 64, 64, 3>(p, grid, st);
-    }
-    case 3: return pl.variant == 1 ? launch_dma<256, 128, 32, 2, 2>(p, grid, st) : launch_dma<256, 128, 32, 3, 2>(p, grid, st);
-    case 4:
-      if (pl.sparse == 2 && pl.variant == 1) return launch_dma<128, 320, 32, 5>(p, grid, st);
-      switch (pl.variant) {
-        case 0: return launch_dma<128, 320, 32, 3>(p, grid, st);       // 84 KB ring = whole-tile epilogue, 1 block / CU
-        case 2: return launch_dma<128, 320, 64, 2>(p, grid, st);       // 128-byte rows, 112 KB, 1 block / CU
-#ifdef PNPI_ABLATIONS
-        case 11: return launch_dma<128, 320, 32, 2, 2, 1>(p, grid, st);   // ablation: DMA only
-        case 12: return launch_dma<128, 320, 32, 2, 2, 2>(p, grid, st);   // ablation: compute only
-#endif
-        default: return launch_dma_s<128, 320, 32, 2>(p, grid, st);      // 56 KB ring, two-pass epilogue, 2 blocks / CU
-      }
-    case 5:
-      if (pl.sparse == 2 && pl.variant == 1) return launch_dma<128, 256, 32, 6>(p, grid, st);
-      switch (pl.variant) {
-        case 0: return launch_dma<128, 256, 32, 3>(p, grid, st);       // 72 KB, 2 blocks / CU
-        case 2: return launch_dma<128, 256, 64, 2>(p, grid, st);
-        default: return launch_dma_s<128, 256, 32, 2>(p, grid, st);      // 48 KB: two-pass epilogue, 3 blocks / CU by LDS
-      }
-#define LPP(...) (pl.id == 16 ? launch_pp<256, 256, 2, 4, __VA_ARGS__>(p, grid, st) : launch_pp<192, 320, 1, 4, __VA_ARGS__>(p, grid, st))
-    case 16: case 17: switch (pl.variant) {
-#ifdef PNPI_ABLATIONS
-      case 1: return LPP(1);     // ablations: no MFMAs
-      case 2: return LPP(2);     // no DMA
-      case 3: return LPP(3);     // DMA only
-      case 4: return LPP(4);     // MFMAs only
-#endif
-      default: return LPP(0);
-    }
-#undef LPP
-  }
-  return -2;
 }
 
 int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_cfg, int force_split, int* cfg_used,
@@ -717,13 +792,13 @@ int launch_igemm(GemmP p, float* ws, size_t ws_bytes, hipStream_t st, int force_
   if (pl.id < 0) return pl.err;      // rejected before a tile was chosen
   if (cfg_used) *cfg_used = pl.cls;
   g_last_cfg = pl.id; g_last_split = pl.split;
-  for (int i = 0; i < 7; ++i) g_last_geom[i] = 0;
+  for (int i = 0; i < 7; ++i) g_last_geom[i] = pl.instance < 0 ? 0 : kInstances[pl.instance].geom[i];
   if (stats_tile_rows && pl.stats_tile_rows >= 0) *stats_tile_rows = pl.stats_tile_rows;
   if (pl.err) return pl.err;
   p.vt_col0 = pl.vt_col0; p.splitk = pl.split; p.kchunks_per_split = pl.kchunks_per_split; p.slab = ws;
   p.epi_lds = pl.epi_lds; p.bias_init = pl.bias_init; p.res_late = pl.res_late; p.k_order = pl.k_order;
   if (!pl.stats) p.stats = nullptr;
-  if (int r = igemm_dispatch(pl, p, st)) return r;
+  if (int r = kInstances[pl.instance].launch(p, dim3(pl.gx, pl.gy, pl.gz), st)) return r;
   if (pl.split > 1) {
     size_t total = (size_t)p.M * ((p.N + 3) / 4);
     int blocks = (int)((total + 255) / 256);

@@ -53,10 +53,15 @@ struct IgemmPlan {
   int epi_lds, bias_init, res_late, k_order;   // the GemmP fields of the same names
   int stats, stats_tile_rows, cls;             // requested statistics survive; rows per partial (0: none); cfg_used class
   int dma, fastk;           // LDS-DMA kernel families (0: the register-staged v1 kernel, with FASTK = fastk)
+  int instance;             // the kernel instance that runs: an index for igemm_instance_info (-1: err before one was chosen)
 };
 IgemmPlan igemm_plan(GemmP p, bool have_ws, size_t ws_bytes, int force_cfg, int force_split, int sel_M);
 int igemm_init();  // sets dynamic-LDS attributes once
-// tile configuration id / split-K of the most recent launch_igemm and the <BM, BN, BKT, NST, WGM, ABL, WK> of its igemm_dma_kernel (profiling)
+// row `index` of the kernel instance table: name ("dma<128,128,32,8>", "pp<192,320>", "v1<64,64,fast>"), the seven geometry integers
+// igemm_last_launch reports for it, whether it exists in a `build --ablations` library only (each nullable); -1 past the end; host only
+int igemm_instance_info(int index, const char** name, int* geom7, int* ablation_only);
+// tile configuration id / split-K of the most recent launch_igemm and the geometry of its instance: igemm_dma_kernel's <BM, BN, BKT, NST,
+// WGM, ABL, WK>; igemm_pp_kernel's <BM, BN, MI0, NI0, ABL>, 0, -1; all 0 for the v1 kernel (profiling)
 void igemm_last_launch(int* cfg, int* split, int* geom7);
 // measured tile table: 1 = exact {M, N, K, ksize} entry, 2 = the same layer at the nearest row count (<= 4x away in M), 0 = none (cost model)
 int igemm_table_lookup(int M, int N, int K, int ksize, int* cfg, int* split, int* entry_m);

@@ -1,12 +1,13 @@
 """Where the per-element bound of tests/test_gpu_gemm_instances.py comes from, which kernel instance each of its cases runs, and what
 the bound catches that the kernel suite's relative L2 does not.
 
-Instance map.  instance_of(plan) is igemm_dispatch (csrc/gemm.hip) written out again from its rules: no LDS-DMA -> the register-staged
-igemm_kernel<BM, BN, FASTK> ("v1<128,128,fast>", "v1<64,64,generic>"); a tile with one instance -> that instance; ids 0 / 1 / 3 / 4 / 5 ->
-by the plan's variant (and sparse == 2 for the deep rings of ids 4 / 5); ids 16 / 17 / 19 / 20 -> the ping-pong kernel "pp<BM,BN>".  Names
-are "dma<BM,BN,BKT,NST>" with ",wgm4" for the 8-wave tiles and ",kg2" / ",kg4" for the k-group tiles.  launch_dma_s<...> is launch_dma<...>
-in a product build.  PRODUCT_INSTANCES is every instance a product build can dispatch (36); a scan of gemm.hip outside the PNPI_ABLATIONS
-blocks has to find exactly this set, so a tile added later fails here until it has cases.
+Instance map.  instance_name(lib, plan) is the row of the library's instance table (kInstances, csrc/gemm.hip, through
+pnpi_igemm_instance_info) that the plan query names in its `instance` field: the row launch_igemm launches, not a copy of its rules.  The
+register-staged igemm_kernel<BM, BN, FASTK> is "v1<128,128,fast>", "v1<64,64,generic>", ...; the ping-pong kernel "pp<BM,BN>"; the LDS-DMA
+kernel "dma<BM,BN,BKT,NST>" with ",wgm4" for the 8-wave tiles and ",kg2" / ",kg4" for the k-group tiles.  PRODUCT_INSTANCES is every
+instance a product build can launch (36), written out here: the table's rows outside its ablation block have to be exactly this set, so
+an instance added later fails here until it has cases; geom_of(), which reads an instance's geometry from its name, is held to the
+table's own integers for each of them.  tests/test_igemm_instances_host.py holds the rules that pick a row to a recording.
 
 Cases.  With BM x BN the tile, BKT its K step and NST its ring depth: M = BM + 2 and N = BN + 8 (one whole tile and a ragged one each way:
 the weight-row and output-row clamps are live), K = c BKT with c in {1, NST - 1, NST, NST + 1} (prologue only, exactly full, drain; the
@@ -64,10 +65,9 @@ residual at std 1 -- lets mutant 2 through (relative L2 3.9e-4, the unmutated em
 invisible to it; mutant 3, one wrong row of 1000, reaches 1.4e-2 and the others 9.7e-2 ... 4.1e-1).  test_old_criterion_is_blind
 asserts the list."""
 import collections
+import ctypes as C
 import functools
 import math
-import os
-import re
 
 import pytest
 import torch
@@ -96,30 +96,24 @@ PRODUCT_INSTANCES = frozenset([
     "dma<64,320,32,2>",
     "pp<256,256>", "pp<192,320>", "pp<128,320>", "pp<192,256>",
 ])
-_ONE_INSTANCE = {6: "dma<256,320,64,2,wgm4>", 7: "dma<256,256,64,2,wgm4>", 8: "dma<64,64,64,2,kg4>", 9: "dma<128,128,32,3,kg2>",
-                 10: "dma<128,128,64,2,kg2>", 11: "dma<64,64,64,2,kg2>", 12: "dma<64,320,32,2>", 13: "dma<128,128,32,2>",
-                 14: "dma<128,128,64,2>", 15: "dma<128,256,64,2>", 16: "pp<256,256>", 17: "pp<192,320>", 18: "dma<128,128,64,3>",
-                 19: "pp<128,320>", 20: "pp<192,256>"}
 
 
-def instance_of(pl):
-    """the kernel instance igemm_dispatch launches for a plan (fields id, variant, sparse, dma, fastk, bm of pnpi_igemm_plan)"""
-    if not pl.dma:
-        return "v1<%s,%s>" % ("64,64" if pl.bm == 64 else "128,128", "fast" if pl.fastk else "generic")
-    if pl.id in _ONE_INSTANCE:
-        return _ONE_INSTANCE[pl.id]
-    if pl.id == 0:
-        return "dma<128,128,%s>" % {1: "64,3", 2: "32,3", 3: "32,4", 4: "32,2", 8: "32,8"}.get(pl.variant, "64,2")
-    if pl.id == 1:
-        return "dma<64,64,%s>" % {8: "64,8", 1: "64,2", 2: "64,4", 3: "32,4"}.get(pl.variant, "64,3")
-    if pl.id == 3:
-        return "dma<256,128,32,2>" if pl.variant == 1 else "dma<256,128,32,3>"
-    if pl.id in (4, 5):
-        bn, deep = (320, 5) if pl.id == 4 else (256, 6)
-        if pl.sparse == 2 and pl.variant == 1:
-            return "dma<128,%d,32,%d>" % (bn, deep)
-        return "dma<128,%d,%s>" % (bn, {0: "32,3", 2: "64,2"}.get(pl.variant, "32,2"))
-    raise ValueError("no instance for tile id %d" % pl.id)
+Instance = collections.namedtuple("Instance", "name geom7 ablation_only")
+
+
+@functools.lru_cache(maxsize=None)
+def instance_table(lib):
+    """the library's kernel instance table (kInstances through pnpi_igemm_instance_info), in index order"""
+    rows, name, geom, abl = [], C.c_char_p(), (C.c_int * 7)(), C.c_int()
+    while lib.pnpi_igemm_instance_info(len(rows), name, geom, abl) == 0:
+        rows.append(Instance(name.value.decode(), tuple(geom), bool(abl.value)))
+    return tuple(rows)
+
+
+def instance_name(lib, pl):
+    """the kernel instance launch_igemm runs for a plan: the row pnpi_igemm_plan.instance names"""
+    assert pl.err == 0 and 0 <= pl.instance < len(instance_table(lib)), (pl.err, pl.instance)
+    return instance_table(lib)[pl.instance].name
 
 
 Geom = collections.namedtuple("Geom", "bm bn bkt nst wk")
@@ -136,61 +130,16 @@ def geom_of(instance):
     return Geom(bm, bn, int(args[2]), int(args[3]), wk)
 
 
-def scan_product_instances(src):
-    """template argument lists of launch_dma< / launch_dma_s< / launch_pp< / LPP( / igemm_kernel< in gemm.hip outside PNPI_ABLATIONS"""
-    keep, stack = [], []                               # per open conditional: True / False = an ablation-only / a product branch of a
-    for line in src.splitlines():                      # PNPI_ABLATIONS conditional, None = any other conditional (every branch kept)
-        m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif|else|endif)\b(.*)", line)
-        if m is None:
-            if True not in stack:
-                keep.append(line)
-            continue
-        word, rest = m.group(1), m.group(2)
-        if word in ("ifdef", "ifndef", "if"):
-            if "PNPI_ABLATIONS" not in rest:
-                stack.append(None)
-            else:
-                assert word != "if" and rest.split("//")[0].strip() == "PNPI_ABLATIONS", "a compound PNPI_ABLATIONS condition: %s" % line
-                stack.append(word == "ifdef")
-        elif word == "endif":
-            assert stack, "an #endif without its #if: %s" % line
-            stack.pop()
-        else:
-            assert stack and not (word == "elif" and stack[-1] is not None), "misplaced: %s" % line
-            if stack[-1] is not None:
-                stack[-1] = not stack[-1]
-    assert not stack, "an unterminated conditional"
-    text = "\n".join(keep)
-    found = set()
-
-    def ints(argstr):
-        parts = [a.strip() for a in argstr.split(",")]
-        return [int(a) for a in parts] if all(re.fullmatch(r"-?\d+", a) for a in parts) else None
-
-    for m in re.finditer(r"\blaunch_dma(?:_s)?<([^<>]*)>", text):
-        a = ints(m.group(1))
-        if a is None:
-            continue                                   # the templates' own definitions (<BM, BN, ...>)
-        a = a + [2, 0, 1][len(a) - 4:]                 # WGM = 2, ABL = 0, WK = 1
-        assert a[5] == 0, "an ablation instance outside PNPI_ABLATIONS: %s" % m.group(0)
-        found.add("dma<%d,%d,%d,%d%s%s>" % (a[0], a[1], a[2], a[3], ",wgm%d" % a[4] if a[4] != 2 else "", ",kg%d" % a[6] if a[6] > 1 else ""))
-    lpp_uses = [ints(m.group(1)) for m in re.finditer(r"\bLPP\(([^().]*)\)", text)]
-    for m in re.finditer(r"\blaunch_pp<([^<>]*)>", text):
-        args = m.group(1)
-        if "__VA_ARGS__" in args:                      # the LPP macro's two instances, once per LPP(...) use
-            for use in lpp_uses:
-                if use is not None:
-                    assert use == [0], "an ablation instance outside PNPI_ABLATIONS: LPP(%s)" % use
-                    a = ints(args.replace("__VA_ARGS__", str(use[0])))
-                    found.add("pp<%d,%d>" % (a[0], a[1]))
-            continue
-        a = ints(args)
-        if a is not None:
-            assert len(a) == 4 or a[4] == 0
-            found.add("pp<%d,%d>" % (a[0], a[1]))
-    for m in re.finditer(r"\bigemm_kernel<\s*(\d+)\s*,\s*(\d+)\s*,\s*(true|false)\s*>", text):
-        found.add("v1<%s,%s,%s>" % (m.group(1), m.group(2), "fast" if m.group(3) == "true" else "generic"))
-    return found
+def name_agrees_with_geom7(row):
+    """what geom_of() reads from a product row's name, and the name's wgm field, against the row's seven integers (LDS-DMA: BM, BN, BKT, NST,
+    WGM, ABL, WK; ping-pong: BM, BN, two quadrant counts the name does not hold, ABL, 0, -1; register-staged: all 0)"""
+    g, t = geom_of(row.name), row.geom7
+    if row.name.startswith("v1"):
+        return t == (0,) * 7
+    if row.name.startswith("pp"):
+        return (g.bm, g.bn) == t[:2] and t[4:] == (0, 0, -1)
+    wgm = [int(a[3:]) for a in row.name.rstrip(">").split(",")[4:] if a.startswith("wgm")]
+    return (g.bm, g.bn, g.bkt, g.nst, wgm[0] if wgm else 2, 0, g.wk) == t
 
 
 # ------------------------------------------------------------------------------------------------ case table
@@ -326,9 +275,9 @@ def case_plan(lib, case):
                           res=case.res)
 
 
-def check_case_plan(case, pl):
+def check_case_plan(lib, case, pl):
     assert pl.err == 0, (case.name, pl.err)
-    assert instance_of(pl) == case.instance, (case.name, instance_of(pl), pl.id, pl.variant, pl.sparse)
+    assert instance_name(lib, pl) == case.instance, (case.name, instance_name(lib, pl), pl.id, pl.variant, pl.sparse)
     assert pl.id == case.cfg, (case.name, pl.id)       # a forced ping-pong tile the launch is not eligible for would come back as id 0
     assert (pl.split, pl.epi_lds, pl.bias_init) == (max(case.split, 1), case.exp_epi_lds, case.exp_bias_init), (case.name, pl.split, pl.epi_lds, pl.bias_init)
     if case.split:
@@ -336,7 +285,7 @@ def check_case_plan(case, pl):
         assert pl.kchunks_per_split * (pl.split - 1) < nch < pl.kchunks_per_split * pl.split, case.name      # a short, non-empty last slice
 
 
-EmuPlan = collections.namedtuple("EmuPlan", "instance split kchunks_per_split bias_init res_late")
+EmuPlan = collections.namedtuple("EmuPlan", "name split kchunks_per_split bias_init res_late")
 
 
 def bias_init_of(case, pl):
@@ -403,7 +352,7 @@ def worst_ratio(got, ref, bound):
 def emulate(a, w, bias, res, alpha, plan, f32_out=False, mutant=None):
     """What the kernel instance of `plan` (EmuPlan) computes, in fp32 on the CPU, in its chunk order; see the module docstring.  Each
     chunk's product is torch's fp32 matmul, not the MFMA's internal order.  mutant: one of the mistakes 1 ... 8 of the docstring."""
-    g = geom_of(plan.instance)
+    g = geom_of(plan.name)
     M, K = a.shape
     N = w.shape[0]
     af, wf = a.float(), w.float()
@@ -517,20 +466,29 @@ def lib():
     return _capi.load_library()
 
 
-def test_source_scan_finds_the_product_instances():
-    path = os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "csrc", "gemm.hip")
-    with open(path) as f:
-        found = scan_product_instances(f.read())
-    assert found == PRODUCT_INSTANCES, (sorted(found - PRODUCT_INSTANCES), sorted(PRODUCT_INSTANCES - found))
+def is_product_library(lib):
+    """a product library refuses the tuning values that select ablation instances; a `build --ablations` one takes them"""
+    try:
+        with _capi.tuning(lib, igemm_vpp=1):
+            return False
+    except ValueError:
+        return True
 
 
-def test_source_scan_follows_nested_conditionals():
-    """another conditional's #else hides no product code, and its #endif inside an ablation block does not end the block"""
-    src = "\n".join(["#if defined(OTHER)", "launch_dma<128, 128, 32, 2>(p);", "#else", "launch_dma<128, 128, 32, 3>(p);", "#endif",
-                     "#ifdef PNPI_ABLATIONS", "#ifdef OTHER", "launch_dma<64, 64, 64, 2>(p);", "#else", "launch_dma<64, 64, 64, 3>(p);", "#endif",
-                     "launch_dma<64, 64, 64, 4>(p);", "#else  // product", "launch_pp<192, 320, 2, 4>(p);", "#endif",
-                     "#ifndef PNPI_ABLATIONS", "igemm_kernel<64, 64, true>", "#else", "igemm_kernel<128, 128, false>", "#endif"])
-    assert scan_product_instances(src) == {"dma<128,128,32,2>", "dma<128,128,32,3>", "pp<192,320>", "v1<64,64,fast>"}
+def test_instance_table_is_the_product_instances(lib):
+    """the rows a product build can launch are PRODUCT_INSTANCES (hand-written above: a new instance fails here until it has cases), each
+    row's seven integers are what its name says, and a product library holds no other row"""
+    rows = instance_table(lib)
+    product = [r for r in rows if not r.ablation_only]
+    assert len(product) == len(PRODUCT_INSTANCES) == 36
+    assert set(r.name for r in product) == PRODUCT_INSTANCES, (sorted(set(r.name for r in product) - PRODUCT_INSTANCES),
+                                                                sorted(PRODUCT_INSTANCES - set(r.name for r in product)))
+    for r in product:
+        assert name_agrees_with_geom7(r), r
+    assert rows[:len(product)] == tuple(product)                   # product rows first
+    if is_product_library(lib):
+        assert len(rows) == len(product), [r.name for r in rows if r.ablation_only]
+    assert lib.pnpi_igemm_instance_info(len(rows), None, None, None) == _capi.PNPI_EINVAL == lib.pnpi_igemm_instance_info(-1, None, None, None)
 
 
 def _plan_fields(pl):
@@ -542,11 +500,11 @@ def test_cases_reach_their_instances(lib):
     reached = set()
     for case in CASES:
         pl = case_plan(lib, case)
-        check_case_plan(case, pl)
+        check_case_plan(lib, case, pl)
         ep = emu_plan(case)
         assert (ep.split, ep.kchunks_per_split, ep.bias_init) == (pl.split, pl.kchunks_per_split, bias_init_of(case, pl)), case.name
         assert pl.res_late == 0
-        reached.add(instance_of(pl))
+        reached.add(instance_name(lib, pl))
     assert reached == PRODUCT_INSTANCES, sorted(PRODUCT_INSTANCES - reached)
     assert len(set(c.name for c in CASES)) == len(CASES)
     assert all(c.M <= 1200 and c.N <= 1100 and c.K <= 1024 for c in CASES if not c.note.startswith("row index"))
@@ -566,7 +524,7 @@ def test_ping_pong_without_row_stores_falls_back_to_tile_0(lib):
                 pl = query_plan(lib, M, N, K, cfg=17, lda=K + 24, ldw=K + 8, ldo=col0 + 8 if col0 else N, bias="a16", vt_col0=col0, vt_ld=rpb + 8, vt_f32=f32,
                                 rpb=rpb)
             assert (pl.err, pl.id) == (0, want), (rpb, form, pl.err, pl.id)
-            assert instance_of(pl) == ("pp<192,320>" if want == 17 else "dma<128,128,32,8>"), (rpb, form, instance_of(pl))
+            assert instance_name(lib, pl) == ("pp<192,320>" if want == 17 else "dma<128,128,32,8>"), (rpb, form, instance_name(lib, pl))
 
 
 def test_geglu_tiles_take_the_launch(lib):

@@ -1,4 +1,4 @@
-"""Every kernel instance igemm_dispatch can launch in a product build (csrc/gemm.hip, igemm_dma.inc, igemm_pp.inc), each against the
+"""Every kernel instance launch_igemm can launch in a product build (csrc/gemm.hip, igemm_dma.inc, igemm_pp.inc), each against the
 float64 value of alpha a w^T + bias + res under the per-element bound that tests/test_gemm_bound_host.py derives (applied unchanged), with
 the old relative L2 below 2e-3 kept beside it and guard bands checked bit for bit:
 
@@ -6,8 +6,8 @@ the old relative L2 below 2e-3 kept beside it and guard bands checked bit for bi
   * out has ldo = N rounded up to 8, plus 8 (N + 4 where the case asks for the scalar epilogue) and one spare row, filled with a canary
     that is exact in fp16; transposed outputs have vt_ld = rows_per_batch + 8 and one spare batch item; convolutions one NaN image before
     and after x and one spare output image;
-  * before every launch the plan query of the host file names the instance: a forced tile the launch is not eligible for (which would
-    silently run as tile 0) fails the test.
+  * before every launch the plan query names the instance the library will launch (its row of the instance table): a forced tile the
+    launch is not eligible for (which would silently run as tile 0) fails the test.
 
 Instance -> case: tests/test_gemm_bound_host.py CASES, one row per (instance, K chunk count, epilogue); the parametrised ids are
 "<instance>-<M>x<N>x<K>-<epilogue A ... G>[-s<split>]".  In short: every instance at M = BM + 2, N = BN + 8 and 1 / NST - 1 / NST / NST + 1
@@ -55,7 +55,7 @@ pytestmark = pytest.mark.gpu
 from pnpinversion_amd import _capi  # noqa: E402
 from tests.gpu_util import Ctx, ptr, rel_err  # noqa: E402
 from tests.test_gemm_bound_host import (CASES, GEGLU_TILES, KAPPA_G, NO_VT, bound_f16, bound_f32, bound_geglu, case_operands,  # noqa: E402
-                                        check_case_plan, gemm_inputs, geglu_ref64, geglu_shape, instance_of, query_plan, ref64, worst_ratio)
+                                        check_case_plan, gemm_inputs, geglu_ref64, geglu_shape, instance_name, query_plan, ref64, worst_ratio)
 
 DEV = "cuda"
 CANARY = -77.25              # exactly representable in fp16 and fp32
@@ -145,7 +145,7 @@ def test_every_gemm_instance(ctx, case):
     with _capi.tuning(lib, **dict(case.tune)):
         pl = query_plan(lib, case.M, case.N, case.K, cfg=case.cfg, split=case.split, lda=case.K + 24, ldw=case.K + 8, ldo=case.ldo, bias=case.bias,
                         res=case.res)
-        check_case_plan(case, pl)
+        check_case_plan(lib, case, pl)
         out, _ = run_gemm(ctx, case.M, case.N, case.K, a, w, bias, case.bias, res, case.alpha, case.ldo, case.cfg, case.split)
     M, N = case.M, case.N
     ref, S = ref64(a.to(DEV), w.to(DEV), bias.to(DEV) if bias is not None else None, res.to(DEV) if res is not None else None, case.alpha)
@@ -290,7 +290,7 @@ def test_every_conv_instance(ctx, famrow, shape):
     out = torch.full((B + 1, Ho, Wo, N), CANARY, dtype=torch.half, device=DEV)
     with _capi.tuning(lib, **tune):
         pl = query_plan(lib, M, N, K, cfg=cfg, bias="a16", res=has_res, ksize=ks, C1=C1, C2=C2)
-        assert pl.err == 0 and pl.id == cfg and instance_of(pl) == instance, (pl.err, pl.id, instance_of(pl))
+        assert pl.err == 0 and pl.id == cfg and instance_name(lib, pl) == instance, (pl.err, pl.id, instance_name(lib, pl))
         assert pl.k_order == int(tune.get("igemm_tapin", 0) == 1 and ks == 3 and instance.startswith("pp"))
         ctx.call("pnpi_op_conv", ptr(x1[1:]), ptr(x2[1:]) if C2 else None, C1, C2, B, H, H, ks, stride, pad, ups, Ho, Wo, ptr(wp), ptr(bd), ptr(rd), N,
                  ptr(out), cfg, 0)
@@ -366,7 +366,7 @@ def test_neighbouring_paths_bit_identical(ctx, name, M, N, K, group, split):
         with _capi.tuning(lib, **tune):
             pl = query_plan(lib, M, N, K, cfg=cfg, split=split, lda=K + 24, ldw=K + 8, ldo=ldo, bias="a16", res=True)
             assert pl.err == 0 and pl.id == cfg and pl.split == max(split, 1), (cfg, pl.id, pl.split)
-            assert instance_of(pl) == instance, (name, cfg, tune, instance_of(pl))      # the ring depth this row was written for
+            assert instance_name(lib, pl) == instance, (name, cfg, tune, instance_name(lib, pl))      # the ring depth this row was written for
             out, _ = run_gemm(ctx, M, N, K, a, w, bias, "a16", res, 1.0, ldo, cfg, split)
         outs.append(out)
         names.append(instance)
