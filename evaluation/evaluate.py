@@ -4,15 +4,18 @@
   psnr* / mse* / ssim*      pnpinversion_amd.metrics (numpy restatements of the torchmetrics definitions)
   clip_similarity_*         on the device: pnpinversion_amd.clip_score.ClipScore (CLIP ViT-L/14 image tower + SD's own text tower)
   structure_distance*       on the device: pnpinversion_amd.structure_distance.StructureDistance (DINO ViT-B/8 key self-similarity)
+  lpips*                    on the device: pnpinversion_amd.lpips.Lpips (SqueezeNet 1.1 features, torchmetrics >= 1.0's normalisation)
 
-`lpips*` (SqueezeNet LPIPS) needs a network that is not built here, and `structure_distance*` is not built without DINO weights
-(--dino_checkpoint or --synthetic_weights): asking for such a column ends the run with a message naming it, before any file is opened.
+`structure_distance*` is not built without DINO weights (--dino_checkpoint or --synthetic_weights) and `lpips*` is not built without
+LPIPS weights (--squeezenet_checkpoint with --lpips_checkpoint, or --synthetic_weights): asking for such a column ends the run with a
+message naming it, before any file is opened.
 Arguments, the method-folder table, the right-hand 512 crop of non-square panels, the "nan" cells of empty masks and the CSV layout are
 the reference's.  The three CLIP columns of one (image, method) pair go to the device as ONE launch set (source image / source prompt,
 target image / target prompt, masked target image / target prompt), and so do its three structure columns (whole, unedited part, edited
-part: one tower pass over the six images).
+part: one tower pass over the six images) and its three LPIPS columns (likewise).
 
-    python evaluation/evaluate.py --checkpoint_dir <SD-1.x dir> --clip_model_dir <clip-vit-large-patch14 dir> --dino_checkpoint <dino_vitbase8_pretrain.pth> [--metrics ...]
+    python evaluation/evaluate.py --checkpoint_dir <SD-1.x dir> --clip_model_dir <clip-vit-large-patch14 dir> --dino_checkpoint <dino_vitbase8_pretrain.pth> \
+                                  --squeezenet_checkpoint <squeezenet1_1-b8a52dc0.pth> --lpips_checkpoint <lpips squeeze.pth> [--metrics ...]
     python evaluation/evaluate.py --dino_checkpoint <dino_vitbase8_pretrain.pth> --metrics structure_distance psnr_unedit_part   # no CLIP weights needed
     python evaluation/evaluate.py --synthetic_weights ...        # seeded random towers: the numbers mean nothing, the plumbing runs
 """
@@ -32,7 +35,7 @@ PIXEL_METRICS = ("psnr", "mse", "ssim")
 PARTS = ("", "_unedit_part", "_edit_part")
 CLIP_METRICS = ("clip_similarity_source_image", "clip_similarity_target_image", "clip_similarity_target_image_edit_part")
 STRUCT_METRICS = ("structure_distance", "structure_distance_unedit_part", "structure_distance_edit_part")
-NOT_BUILT = {"lpips": "SqueezeNet LPIPS"}
+LPIPS_METRICS = ("lpips", "lpips_unedit_part", "lpips_edit_part")
 DEFAULT_METRICS = ["structure_distance", "psnr_unedit_part", "lpips_unedit_part", "mse_unedit_part", "ssim_unedit_part"] + list(CLIP_METRICS)
 
 
@@ -90,14 +93,21 @@ def has_dino_weights(args):
     return bool(getattr(args, "dino_checkpoint", None) or getattr(args, "synthetic_weights", False))
 
 
-def check_metrics(metrics, dino=False):
-    """dino: DINO weights (or a scorer) are at hand, so the structure_distance* columns can be computed"""
+def has_lpips_weights(args):
+    return bool((getattr(args, "squeezenet_checkpoint", None) and getattr(args, "lpips_checkpoint", None)) or getattr(args, "synthetic_weights", False))
+
+
+def check_metrics(metrics, dino=False, lpips=False):
+    """dino / lpips: DINO / LPIPS weights (or a scorer) are at hand, so the structure_distance* / lpips* columns can be computed"""
     computable = [p + s for p in PIXEL_METRICS for s in PARTS] + list(CLIP_METRICS)
     for m in metrics:
         base, _ = _split(m)
-        if base in NOT_BUILT:
-            raise SystemExit("column %r is not built: %s needs a network this library does not carry (computable columns: %s)"
-                             % (m, NOT_BUILT[base], ", ".join(computable + list(STRUCT_METRICS))))
+        if m in LPIPS_METRICS:
+            if not lpips:
+                raise SystemExit("column %r is not built without LPIPS weights: pass --squeezenet_checkpoint <squeezenet1_1 state dict> with "
+                                 "--lpips_checkpoint <the lpips package's squeeze.pth>, or --synthetic_weights for a seeded random network "
+                                 "(computable without them: %s)" % (m, ", ".join(computable)))
+            continue
         if m in STRUCT_METRICS:
             if not dino:
                 raise SystemExit("column %r is not built without DINO weights: pass --dino_checkpoint <dino_vitbase8_pretrain.pth>, or "
@@ -110,8 +120,8 @@ def check_metrics(metrics, dino=False):
 class Calculator:
     """the reference's MetricsCalculator protocol for the columns that are built"""
 
-    def __init__(self, scorer=None, struct_scorer=None):
-        self.scorer, self.struct_scorer = scorer, struct_scorer
+    def __init__(self, scorer=None, struct_scorer=None, lpips_scorer=None):
+        self.scorer, self.struct_scorer, self.lpips_scorer = scorer, struct_scorer, lpips_scorer
 
     def calculate_clip_similarity(self, img, txt, mask=None):
         from pnpinversion_amd import metrics
@@ -120,6 +130,10 @@ class Calculator:
     def calculate_structure_distance(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
         from pnpinversion_amd import metrics
         return metrics.calculate_structure_distance(img_pred, img_gt, mask_pred, mask_gt, scorer=self.struct_scorer)
+
+    def calculate_lpips(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
+        from pnpinversion_amd import metrics
+        return metrics.calculate_lpips(img_pred, img_gt, mask_pred, mask_gt, scorer=self.lpips_scorer)
 
     def __getattr__(self, name):
         from pnpinversion_amd import metrics
@@ -137,7 +151,8 @@ def calculate_metric(calc, metric, src_image, tgt_image, src_mask, tgt_mask, src
         if metric == "clip_similarity_target_image":
             return calc.calculate_clip_similarity(tgt_image, tgt_prompt, None)
         return "nan" if tgt_mask.sum() == 0 else calc.calculate_clip_similarity(tgt_image, tgt_prompt, tgt_mask)
-    if base in NOT_BUILT or (metric in STRUCT_METRICS and getattr(calc, "struct_scorer", None) is None):
+    if (metric in STRUCT_METRICS and getattr(calc, "struct_scorer", None) is None) or \
+       (metric in LPIPS_METRICS and getattr(calc, "lpips_scorer", None) is None):
         check_metrics([metric])
     fn = lambda *a: getattr(calc, "calculate_" + base)(*a)
     if part == "":
@@ -167,12 +182,12 @@ def clip_cells(scorer, metrics, src_image, tgt_image, tgt_mask, src_prompt, tgt_
     return out
 
 
-def struct_cells(scorer, metrics, src_image, tgt_image, src_mask, tgt_mask):
-    """the structure columns of one (image, method) pair in one launch set -> {metric: value or "nan"}; the reference's argument order
-    calculate_structure_distance(src_image, tgt_image, ...) and its "nan" rule for empty parts"""
+def _part_cells(score, names, metrics, src_image, tgt_image, src_mask, tgt_mask):
+    """the whole / unedited-part / edited-part columns `names` of one (image, method) pair in one call of score(pred, gt, mask_pred,
+    mask_gt) -> {metric: value or "nan"}; the reference's argument order (src_image, tgt_image, ...) and its "nan" rule for empty parts"""
     want, pred, gt, mp, mg = [], [], [], [], []
     out = {}
-    for m in STRUCT_METRICS:
+    for m in names:
         if m not in metrics:
             continue
         part = _split(m)[1]
@@ -183,9 +198,19 @@ def struct_cells(scorer, metrics, src_image, tgt_image, src_mask, tgt_mask):
         want.append(m)
         pred.append(src_image); gt.append(tgt_image); mp.append(ms); mg.append(mt)
     if want:
-        got = scorer.distance(pred, gt, mp, mg)
+        got = score(pred, gt, mp, mg)
         out.update({m: float(v) for m, v in zip(want, got)})
     return out
+
+
+def struct_cells(scorer, metrics, src_image, tgt_image, src_mask, tgt_mask):
+    """the structure columns of one (image, method) pair in one launch set"""
+    return _part_cells(scorer.distance, STRUCT_METRICS, metrics, src_image, tgt_image, src_mask, tgt_mask)
+
+
+def lpips_cells(scorer, metrics, src_image, tgt_image, src_mask, tgt_mask):
+    """the LPIPS columns of one (image, method) pair in one launch set"""
+    return _part_cells(scorer.score, LPIPS_METRICS, metrics, src_image, tgt_image, src_mask, tgt_mask)
 
 
 def parse_args(argv=None):
@@ -204,6 +229,9 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic_weights", action="store_true", help="seeded random towers and the word-level stand-in tokenizer")
     # weights of the structure columns (not in the reference, which downloads facebookresearch/dino:main dino_vitb8)
     ap.add_argument("--dino_checkpoint", type=str, default=None, help="local dino_vitbase8_pretrain.pth: the DINO ViT-B/8 state dict")
+    # weights of the LPIPS columns (not in the reference, whose torchmetrics downloads both)
+    ap.add_argument("--squeezenet_checkpoint", type=str, default=None, help="local squeezenet1_1-b8a52dc0.pth: torchvision's squeezenet1_1 state dict")
+    ap.add_argument("--lpips_checkpoint", type=str, default=None, help="local squeeze.pth of the lpips package: the seven lin layers")
     return ap.parse_args(argv)
 
 
@@ -235,18 +263,12 @@ def build_scorer(args):
 
 def build_struct_scorer(args, engine=None):
     """StructureDistance from --dino_checkpoint, or seeded weights; on the CLIP scorer's context when there is one, else on a context of
-    its own with no text tower, no UNet rows and no VAE images (the smallest model configuration: its weight arena is never loaded)"""
-    import dataclasses
+    its own (_smallest_engine)"""
     from pnpinversion_amd import checkpoint
     from pnpinversion_amd.structure_distance import StructureDistance
     if args.dino_checkpoint and args.synthetic_weights:
         raise SystemExit("--dino_checkpoint and --synthetic_weights are mutually exclusive")
-    if engine is None:
-        from pnpinversion_amd.config import TINY16
-        from pnpinversion_amd.engine import NativeEngine
-        engine = NativeEngine(dataclasses.replace(TINY16, clip_layers=0), device=args.device if args.device != "cuda" else None,
-                              max_unet_rows=0, max_vae_images=0)
-    scorer = StructureDistance(engine, max_pairs=3)
+    scorer = StructureDistance(engine if engine is not None else _smallest_engine(args), max_pairs=3)
     if args.dino_checkpoint:
         scorer.load_state_dict(checkpoint.load_dino_checkpoint(args.dino_checkpoint))
     else:
@@ -255,10 +277,36 @@ def build_struct_scorer(args, engine=None):
     return scorer
 
 
-def run(args, scorer=None, struct_scorer=None):
+def _smallest_engine(args):
+    """a context with no text tower, no UNet rows and no VAE images (the smallest model configuration: its weight arena is never loaded)"""
+    import dataclasses
+    from pnpinversion_amd.config import TINY16
+    from pnpinversion_amd.engine import NativeEngine
+    return NativeEngine(dataclasses.replace(TINY16, clip_layers=0), device=args.device if args.device != "cuda" else None,
+                        max_unet_rows=0, max_vae_images=0)
+
+
+def build_lpips_scorer(args, engine=None):
+    """Lpips from --squeezenet_checkpoint + --lpips_checkpoint, or seeded weights; on the context that is already there (the CLIP or the
+    structure scorer's), else on the smallest one"""
+    from pnpinversion_amd import checkpoint
+    from pnpinversion_amd.lpips import Lpips
+    real = bool(args.squeezenet_checkpoint and args.lpips_checkpoint)
+    if real and args.synthetic_weights:
+        raise SystemExit("--squeezenet_checkpoint / --lpips_checkpoint and --synthetic_weights are mutually exclusive")
+    scorer = Lpips(engine if engine is not None else _smallest_engine(args), max_pairs=3)
+    if real:
+        scorer.load_state_dict(checkpoint.load_lpips_checkpoint(args.squeezenet_checkpoint, args.lpips_checkpoint))
+    else:
+        print(checkpoint.SYNTHETIC_WARNING, file=sys.stderr, flush=True)
+        scorer.load_synthetic(0)
+    return scorer
+
+
+def run(args, scorer=None, struct_scorer=None, lpips_scorer=None):
     from PIL import Image
     metrics = list(args.metrics)
-    check_metrics(metrics, dino=struct_scorer is not None or has_dino_weights(args))
+    check_metrics(metrics, dino=struct_scorer is not None or has_dino_weights(args), lpips=lpips_scorer is not None or has_lpips_weights(args))
     if args.evaluate_whole_table:
         folders = {k: v for k, v in all_tgt_image_folders.items() if k[0] in args.tgt_methods}
     else:
@@ -267,7 +315,9 @@ def run(args, scorer=None, struct_scorer=None):
         scorer = build_scorer(args)
     if struct_scorer is None and any(m in STRUCT_METRICS for m in metrics):
         struct_scorer = build_struct_scorer(args, engine=getattr(scorer, "engine", None))
-    calc = Calculator(scorer, struct_scorer)
+    if lpips_scorer is None and any(m in LPIPS_METRICS for m in metrics):
+        lpips_scorer = build_lpips_scorer(args, engine=getattr(scorer, "engine", None) or getattr(struct_scorer, "engine", None))
+    calc = Calculator(scorer, struct_scorer, lpips_scorer)
     with open(args.result_path, "w", newline="") as f:
         csv.writer(f).writerow(["file_id"] + ["%s|%s" % (k, m) for k in folders for m in metrics])
     with open(args.annotation_mapping_file) as f:
@@ -289,6 +339,8 @@ def run(args, scorer=None, struct_scorer=None):
             clip = clip_cells(scorer, metrics, src_image, tgt_image, mask, src_prompt, tgt_prompt) if scorer is not None else {}
             if struct_scorer is not None:
                 clip.update(struct_cells(struct_scorer, metrics, src_image, tgt_image, mask, mask))
+            if lpips_scorer is not None:
+                clip.update(lpips_cells(lpips_scorer, metrics, src_image, tgt_image, mask, mask))
             for m in metrics:
                 row.append(clip[m] if m in clip else calculate_metric(calc, m, src_image, tgt_image, mask, mask, src_prompt, tgt_prompt))
         with open(args.result_path, "a+", newline="") as f:
@@ -297,5 +349,5 @@ def run(args, scorer=None, struct_scorer=None):
 
 if __name__ == "__main__":
     _args = parse_args()
-    check_metrics(_args.metrics, dino=has_dino_weights(_args))
+    check_metrics(_args.metrics, dino=has_dino_weights(_args), lpips=has_lpips_weights(_args))
     run(_args)

@@ -352,6 +352,40 @@ int pnpi_op_keys_selfsim_mse(pnpi_ctx* ctx, const void* keys_a_f16, const void* 
  * Returns 0, or PNPI_ESHAPE for sizes outside 1 .. 8192. */
 int pnpi_dino_resize_taps(int in_size, int out_size, int* idx0_out, int* idx1_out, float* lambda_out);
 
+/* ---- LPIPS, SqueezeNet backbone (evaluation/matrics_calculator.py:324-342 -> torchmetrics
+ * LearnedPerceptualImagePatchSimilarity(net_type = "squeeze")) ------------------------------------------------------------------
+ * torchvision's squeezenet1_1().features 0 .. 12 and the seven 1 x 1 `lin` layers attached to a context, which needs nothing else: no
+ * text tower, no UNet rows, no VAE images.  Weights and workspaces are an allocation of their own, freed by pnpi_destroy; a context
+ * that never attaches is unchanged.  Weights arrive through pnpi_load_weights under the prefix "lpips.": torchvision's keys
+ * features.0.{weight, bias}, features.N.{squeeze, expand1x1, expand3x3}.{weight, bias} for N in 3, 4, 6, 7, 9, 10, 11, 12, and
+ * lin0.weight .. lin6.weight ([1][C][1][1], no bias).  pnpi_missing_weights, pnpi_mark_all_loaded and the UNet / VAE entry points do
+ * not look at "lpips." slots.
+ * Computed per image: x = ((uint8 / 255) * mask) * 2 - 1 (a cleared pixel is -1), (x - shift) / scale with shift (-.030, -.088, -.188),
+ * scale (.458, .448, .450), no resize; seven taps = the outputs of features 1, 4, 7, 9, 10, 11, 12 (64, 128, 256, 384, 384, 512, 512
+ * channels; the max pools are ceil_mode).  Per pair and tap: a^ = a / sqrt(1e-8 + sum_c a_c^2) per pixel (torchmetrics >= 1.0's form:
+ * the eps under the root), d = sum_c w_c (a^_c - b^_c)^2, the tap's term is the mean of d over the pixels; the score is the sum of the
+ * seven terms.  Activations are fp16, sums fp32; reductions run in a fixed order (the same call twice gives the same bits) and every
+ * convolution takes the tile of its max_pairs form (a pair's score does not depend on the batch it is in).
+ * Every entry point refuses, with a status and a message and before anything is launched: nothing attached (PNPI_ESTATE), a second
+ * attach (PNPI_ESTATE), missing weights (PNPI_ESTATE, every name), n out of range (PNPI_EINVAL), an S outside 17 .. 8192 (PNPI_ESHAPE;
+ * below 17 the third max pool has no window), a mask byte other than 0 / 1 (PNPI_EINVAL; the masks are read back to the host), a NULL
+ * output (PNPI_EINVAL).  The workspaces are sized for 512 x 512 images at attach and grow at the first call with a larger S. */
+/* up to max_pairs image pairs (2 * max_pairs images) per call; a refused attach leaves nothing behind */
+int pnpi_lpips_attach(pnpi_ctx* ctx, int max_pairs);
+/* LPIPS of n pairs, n <= max_pairs: one pass of the network over the 2 n images, then the seven fused tap distances.  img_* device
+ * uint8 [n][S][S][3], mask_* nullable device uint8 [n][S][S]; score_out device fp32 [n] */
+int pnpi_lpips(pnpi_ctx* ctx, const uint8_t* img_pred, const uint8_t* mask_pred, const uint8_t* img_gt, const uint8_t* mask_gt, int n, int S,
+               float* score_out);
+/* one tap's feature map (tests): out_f32 device fp32 [n][H_tap][H_tap][C_tap] (NHWC), tap 0 .. 6; n <= 2 * max_pairs.
+ * H_0 = (S - 3) / 2 + 1; each ceil-mode pool: H -> ceil((H - 3) / 2) + 1, one less if that window would start outside the map */
+int pnpi_lpips_features(pnpi_ctx* ctx, const uint8_t* img_hwc, const uint8_t* mask_hw, int n, int S, int tap, float* out_f32);
+/* kernel-level: one tap's distance for n pairs of given feature maps, device fp16 [n][HW][C], C % 8 == 0 (else PNPI_ESHAPE), 16-byte
+ * aligned; w device fp32 [C], any sign; needs no attached network.  out device fp32 [n].  The normalised maps never reach memory. */
+int pnpi_op_lpips_layer(pnpi_ctx* ctx, const void* a_f16, const void* b_f16, const float* w, int n, int HW, int C, float* out);
+/* kernel-level: MaxPool2d(3, stride 2, ceil_mode = True) on device fp16 NHWC [n][H][H][C] -> [n][Ho][Ho][C], overhanging windows clipped
+ * to the map; C % 8 == 0, H >= 2, 16-byte aligned; needs no attached network */
+int pnpi_op_maxpool3s2_ceil(pnpi_ctx* ctx, const void* x_f16, int n, int H, int C, void* out_f16);
+
 /* ---- level 2: loop boundary (whole phases device-resident, no host round trip per step) ------------------------- */
 /* DirectInversion.ddim_loop (inversion.py:308-319): latents_out [nsteps+1][nimg][4][h][w]; timesteps_host = scheduler.timesteps */
 int pnpi_ddim_invert(pnpi_ctx* ctx, const float* z0, int nimg, const float* ctx_cond /*[nimg][77][768]*/, int nsteps,

@@ -159,6 +159,12 @@ SYMBOLS = {
     "pnpi_op_dino_preprocess": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pnpi_op_keys_selfsim_mse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pnpi_dino_resize_taps": (_i, [_i, _i, _ip, _ip, _fp]),
+    # LPIPS, SqueezeNet backbone (evaluation/matrics_calculator.py:324-342)
+    "pnpi_lpips_attach": (_i, [_vp, _i]),
+    "pnpi_lpips": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "pnpi_lpips_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "pnpi_op_lpips_layer": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "pnpi_op_maxpool3s2_ceil": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "pnpi_ddim_invert": (_i, [_vp, _vp, _i, _vp, _i, _ip, _vp]),
     "pnpi_ddim_invert_cfg": (_i, [_vp, _vp, _i, _vp, _vp, _f, _i, _ip, _vp]),
     "pnpi_offset_calculate": (_i, [_vp, _vp, _i, _vp, _i, _ip, _f, _fp, _vp]),

@@ -197,6 +197,41 @@ def load_dino_checkpoint(path):
     return out
 
 
+def lpips_keys():
+    """the state-dict keys lpips.Lpips.load_state_dict needs"""
+    from . import weights
+    keys = ["features.0.weight", "features.0.bias"]
+    for idx, _, _, _ in weights.LPIPS_FIRES:
+        keys += ["features.%d.%s.%s" % (idx, part, t) for part in ("squeeze", "expand1x1", "expand3x3") for t in ("weight", "bias")]
+    return keys + ["lin%d.weight" % k for k in range(len(weights.LPIPS_TAP_CHANNELS))]
+
+
+def load_lpips_checkpoint(squeezenet_pth, lin_pth):
+    """The two files torchmetrics' LPIPS(net_type="squeeze") rests on, merged into what lpips.Lpips.load_state_dict takes:
+      squeezenet_pth  torchvision's squeezenet1_1 state dict (squeezenet1_1-b8a52dc0.pth): features.N.{weight, bias} and
+                      features.N.{squeeze, expand1x1, expand3x3}.{weight, bias} are kept under their own names, classifier.* is ignored
+      lin_pth         the lpips package's squeeze.pth: lin{k}.model.1.weight [1, C, 1, 1] -> lin{k}.weight
+    Any other key of either file, and any needed key that neither holds, raises KeyError with the names.  Neither file exists
+    offline: the key mapping is tested on stand-ins written with torch.save, real weights are unverified, and so is whether the real
+    network's activations stay inside fp16's range."""
+    import re
+    out, unknown = {}, []
+    for k, v in torch.load(squeezenet_pth, map_location="cpu", weights_only=True).items():
+        if k.startswith("classifier."):
+            continue
+        (out.__setitem__(k, v) if k.startswith("features.") else unknown.append("%s: %s" % (os.path.basename(squeezenet_pth), k)))
+    for k, v in torch.load(lin_pth, map_location="cpu", weights_only=True).items():
+        m = re.fullmatch(r"lin(\d)\.model\.1\.weight", k)
+        (out.__setitem__("lin%s.weight" % m.group(1), v) if m else unknown.append("%s: %s" % (os.path.basename(lin_pth), k)))
+    want = lpips_keys()
+    unknown += [k for k in out if k not in want]
+    out = {k: v for k, v in out.items() if k in want}
+    missing = [k for k in want if k not in out]
+    if unknown or missing:
+        raise KeyError("LPIPS checkpoint: unknown keys %s; missing keys %s" % (sorted(set(unknown)), missing))
+    return out
+
+
 SYNTHETIC_WARNING = ("WARNING: running on SEEDED SYNTHETIC (random) Stable-Diffusion weights and a word-level stand-in tokenizer -- the "
                      "saved panels are numerically meaningful (parity / timing) but are NOT edits of a trained model.  Pass "
                      "--checkpoint_dir <diffusers SD-1.x directory> for real weights.")

@@ -1,6 +1,6 @@
 // libpnpi: C-ABI entry points + the static SD-1.x UNet / VAE graph executor and the device-resident DI / P2P loops.
 // See include/pnpi.h for the reference interface each entry point replaces.
-// One translation unit in nine files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the CLIP text encoder,
+// One translation unit in ten files: this one (error helpers, the C ABI: context life cycle, level-1 operators, the CLIP text encoder,
 // kernel-level test hooks) includes, in order,
 //   api_weights.inc   weight slots of the packed arena and the model builder
 //   api_graph.inc     profiling records, activation tape, op wrappers, ResNet / transformer blocks, unet_fwd
@@ -9,6 +9,7 @@
 //   api_ctrl.inc      per-loop text K / V cache, controller descriptor -> device tables
 //   api_clipscore.inc CLIP similarity: the image tower attached to a context, projections, preprocessing, score
 //   api_structdist.inc DINO structure distance: the ViT attached to a context, preprocessing, keys, the fused distance
+//   api_lpips.inc     LPIPS: SqueezeNet 1.1 features attached to a context, the seven taps, the fused tap distance
 //   api_loops.inc     (last) the loop scaffold and the level-2 loops: DDIM / direct inversion, edit loops, edit-friendly DDPM, null-text
 #include <math.h>
 #include <stdio.h>
@@ -108,6 +109,7 @@ static int validate_config(pnpi_ctx* c) {
 static int clip_fwd(pnpi_ctx* c, const int* ids, int n, float* out, half_t** y16_out = nullptr);
 static void clipv_free(pnpi_ctx* c);
 static void dino_free(pnpi_ctx* c);
+static void lpips_free(pnpi_ctx* c);
 
 static int create_impl(pnpi_ctx** out, const pnpi_model_config* cfg, int device, void* hip_stream, int max_unet_rows, int max_vae_images, pnpi_ctx* parent);
 int pnpi_create(pnpi_ctx** out, const pnpi_model_config* cfg, int device, void* hip_stream, int max_unet_rows, int max_vae_images) {
@@ -268,7 +270,9 @@ void pnpi_destroy(pnpi_ctx* c) {
   }
   clipv_free(c);
   dino_free(c);
+  lpips_free(c);
   (void)hipFree(c->ss_ws);
+  (void)hipFree(c->lp_ws);
   delete c;
 }
 
@@ -315,7 +319,7 @@ int pnpi_missing_weights(const pnpi_ctx* c, char* names_out, size_t cap) {
   size_t used = 0;
   if (names_out && cap) names_out[0] = 0;
   for (auto& kv : c->slots)
-    if (!kv.second.loaded && kv.first.compare(0, 5, "clip.") != 0 && kv.first.compare(0, 6, "clipv.") != 0 && kv.first.compare(0, 5, "dino.") != 0) {   // the text encoder reports through pnpi_text_encode, the image tower through pnpi_clip_*, the DINO ViT through pnpi_dino_*
+    if (!kv.second.loaded && kv.first.compare(0, 5, "clip.") != 0 && kv.first.compare(0, 6, "clipv.") != 0 && kv.first.compare(0, 5, "dino.") != 0 && kv.first.compare(0, 6, "lpips.") != 0) {   // the text encoder reports through pnpi_text_encode, the image tower through pnpi_clip_*, the DINO ViT through pnpi_dino_*, LPIPS through pnpi_lpips*
       ++missing;
       if (names_out && used + kv.first.size() + 2 < cap) {
         memcpy(names_out + used, kv.first.c_str(), kv.first.size());
@@ -337,7 +341,7 @@ int pnpi_weight_arena(pnpi_ctx* c, void** ptr, size_t* bytes) {
 int pnpi_mark_all_loaded(pnpi_ctx* c) {
   invalidate_derived(c);            // the arena was just overwritten by the broadcast
   for (auto& kv : c->slots)
-    if (kv.first.compare(0, 6, "clipv.") != 0 && kv.first.compare(0, 5, "dino.") != 0) kv.second.loaded = true;      // the image tower and the DINO ViT are no part of the arena
+    if (kv.first.compare(0, 6, "clipv.") != 0 && kv.first.compare(0, 5, "dino.") != 0 && kv.first.compare(0, 6, "lpips.") != 0) kv.second.loaded = true;      // the image tower, the DINO ViT and the LPIPS network are no part of the arena
   CK(build_ff_fold(c));             // derived after the broadcast, from the weights it delivered (a borrowing context leaves it to the owner)
   return 0;
 }
@@ -446,7 +450,7 @@ int pnpi_profile_end(pnpi_ctx* c, pnpi_kernel_stats* out) {
 
 static bool is_clipv_slot(const std::string& name) { return name.compare(0, 6, "clipv.") == 0; }      // image tower + projections (pnpi_clipv_attach)
 static bool is_clip_slot(const std::string& name) { return name.compare(0, 5, "clip.") == 0 || is_clipv_slot(name); }
-static bool is_dino_slot(const std::string& name) { return name.compare(0, 5, "dino.") == 0; }      // DINO ViT (pnpi_dino_attach)
+static bool is_dino_slot(const std::string& name) { return name.compare(0, 5, "dino.") == 0 || name.compare(0, 6, "lpips.") == 0; }      // DINO ViT (pnpi_dino_attach), LPIPS network (pnpi_lpips_attach)
 static int check_ready(pnpi_ctx* c) {   // UNet / VAE entry points: the text encoder's weights are optional for them
   for (auto& kv : c->slots)
     if (!kv.second.loaded && !is_clip_slot(kv.first) && !is_dino_slot(kv.first)) { c->err = "weights not loaded: " + kv.first; return PNPI_ESTATE; }
@@ -704,6 +708,7 @@ int pnpi_text_encode(pnpi_ctx* c, const int32_t* input_ids, int n, float* hidden
 #include "api_vit.inc"
 #include "api_clipscore.inc"
 #include "api_structdist.inc"
+#include "api_lpips.inc"
 
 // ---------------------------------------------------------------------------------------------------- kernel-level ops
 static int conv_hook(pnpi_ctx* c, const void* x1, const void* x2, int C1, int C2, int B, int H, int W, int ksize, int stride, int pad, int ups,

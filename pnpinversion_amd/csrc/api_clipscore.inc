@@ -92,9 +92,10 @@ static void clipv_build(pnpi_ctx* c) {
   v->w_tproj = walloc_h(c, (size_t)P * Ht);
   reg_mat(c, "clipv.text_projection.weight", v->w_tproj, P, Ht, 1, Ht, Ht);
 }
-// the tower's own small buffers
+// the row table and the tower's own small buffers
 static void clipv_bufs(pnpi_ctx* c, Bump& b) {
   ClipVisionW* v = c->cv;
+  vit_bufs(v, b);
   const size_t N = v->max_images, W = v->W, P = v->cfg.proj_dim, Ht = c->clip.H;
   v->pool_img = (half_t*)b.alloc(N * W * sizeof(half_t));
   v->ln_img = (half_t*)b.alloc(N * W * sizeof(half_t));
@@ -240,7 +241,7 @@ int pnpi_clipv_attach(pnpi_ctx* c, const pnpi_clipv_config* g, int max_images) {
   v->name = "CLIP image tower"; v->prefix = "clipv.";
   v->cfg = *g; v->max_images = max_images; v->W = g->width;
   c->cv = v;
-  return tower_attach(c, v, "pnpi_clipv_attach", g->image_size, g->patch, {clipv_build, clipv_bufs, clipv_dry_fwd, clipv_free});
+  return vit_attach(c, v, "pnpi_clipv_attach", g->image_size, g->patch, {clipv_build, clipv_bufs, clipv_dry_fwd, clipv_free});
 }
 
 int pnpi_op_clip_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int S, int out_size, uint8_t* resized_out,

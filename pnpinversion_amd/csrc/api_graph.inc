@@ -183,14 +183,14 @@ static float* stats_alloc(pnpi_ctx* c, int M, int N) {   // worst case: 64-row t
 
 static int op_conv(pnpi_ctx* c, const half_t* x1, int C1, const half_t* x2, int C2, int B, int H, int W, const ConvW& w, int stride,
                    int pad, int ups, const float* bias, const half_t* res, half_t* out, int Ho, int Wo, int N = -1,
-                   const VtOut* vt = nullptr, Stats* so = nullptr) {
+                   const VtOut* vt = nullptr, Stats* so = nullptr, int ldo = 0) {      // ldo > 0: out's row stride (a column block of a wider buffer)
   GemmP p; gemm_defaults(p);
   int C1p = C2 ? C1 : w.cin_pad;  // single-source inputs are stored with the padded channel count
   p.x1 = x1; p.x2 = x2; p.C1 = C1p; p.C2 = C2; p.ldx1 = C1p; p.ldx2 = C2;
   p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.ksize = w.k; p.stride = stride; p.pad = pad; p.ups = ups;
   p.K = w.k * w.k * (C1p + C2); p.w = w.w; p.ldw = p.K;
   p.M = B * Ho * Wo; p.N = N > 0 ? N : w.cout;
-  p.bias = bias; p.res = res; p.ldres = p.N; p.out = out; p.ldo = p.N;
+  p.bias = bias; p.res = res; p.ldres = p.N; p.out = out; p.ldo = ldo > 0 ? ldo : p.N;
   if (vt) { p.outT = vt->outT; p.vt_col0 = vt->col0; p.vt_ld = vt->ld; p.vt_f32 = vt->f32; p.rows_per_batch = vt->rpb; }
   c->ctr.executed_gemm_flops += 2.0 * p.M * p.N * p.K;
   if (so) { p.stats = stats_alloc(c, p.M, p.N); so->p = p.stats; so->rows = 0; }

@@ -71,9 +71,10 @@ static void dino_build(pnpi_ctx* c) {
     v->layers.push_back(L);
   }
 }
-// the tower's own small buffer
+// the row table and the tower's own small buffer
 static void dino_bufs(pnpi_ctx* c, Bump& b) {
   DinoW* v = c->dino;
+  vit_bufs(v, b);
   v->keys16 = (half_t*)b.alloc((size_t)v->max_images * v->T * v->W * sizeof(half_t));
 }
 
@@ -191,7 +192,7 @@ int pnpi_dino_attach(pnpi_ctx* c, const pnpi_dino_config* g, int max_pairs) {
   v->name = "DINO ViT"; v->prefix = "dino.";
   v->cfg = *g; v->max_pairs = max_pairs; v->max_images = 2 * max_pairs; v->W = g->width;
   c->dino = v;
-  return tower_attach(c, v, "pnpi_dino_attach", g->image_size, g->patch, {dino_build, dino_bufs, dino_dry_fwd, dino_free});      // K = 3 patch^2: patch % 8 == 0
+  return vit_attach(c, v, "pnpi_dino_attach", g->image_size, g->patch, {dino_build, dino_bufs, dino_dry_fwd, dino_free});      // K = 3 patch^2: patch % 8 == 0
 }
 
 int pnpi_op_dino_preprocess(pnpi_ctx* c, const uint8_t* img, const uint8_t* mask, int n, int S, int out_size, float* resized_out,

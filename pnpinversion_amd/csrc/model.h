@@ -127,22 +127,25 @@ struct ClipW {
   NormW final_ln;
 };
 
-// What the vision transformers attached to a context share (api_vit.inc): the geometry, the four allocations, the patch embedding, the
-// encoder layers.  Everything a tower owns lives outside the context's own arenas: a context that never attaches one is unchanged.
-struct VitTowerW {
-  const char* name = "";                  // in messages: "CLIP image tower", "DINO ViT"
-  const char* prefix = "";                // of its weight slots' names: "clipv.", "dino."
+// What every network attached to a context owns (api_vit.inc: attach sequence, free, refusals): its allocations live outside the
+// context's own arenas, so a context that never attaches one is unchanged.
+struct TowerW {
+  const char* name = "";                  // in messages: "CLIP image tower", "DINO ViT", "LPIPS SqueezeNet"
+  const char* prefix = "";                // of its weight slots' names: "clipv.", "dino.", "lpips."
   int max_images = 0;
-  int G = 0, NP = 0, T = 0, K = 0, W = 0; // patch grid side, patches, tokens (NP + 1), patch-row length 3 * patch^2 rounded up to 64, width
   Bump arena;                             // weights (own allocation)
   Bump persist, temp;                     // activation workspaces of the forward (swapped into the context while it runs)
-  Bump bufs;                              // small persistent buffers: rows_ident and the tower's own
+  Bump bufs;                              // small persistent buffers
+};
+// What the vision transformers share on top of that: the geometry, the patch embedding, the encoder layers.
+struct VitTowerW : TowerW {
+  int G = 0, NP = 0, T = 0, K = 0, W = 0; // patch grid side, patches, tokens (NP + 1), patch-row length 3 * patch^2 rounded up to 64, width
   half_t* w_patch = nullptr;              // [W][K] patch embedding, (c, ky, kx) columns, pad columns zero
   float* b_patch = nullptr;               // [W], or nullptr: a bias-free patch embedding (CLIP)
   float* cls = nullptr;                   // [W]
   float* pos = nullptr;                   // [T][W]
   std::vector<ClipLayerW> layers;
-  int* rows_ident = nullptr;              // [max_images][4]
+  int* rows_ident = nullptr;              // [max_images][4], first in bufs
 };
 
 // CLIP image tower + the two projections (pnpi_clipv_attach; transformers CLIPModel: vision_model, visual_projection, text_projection).
@@ -169,6 +172,16 @@ struct DinoW : VitTowerW {
   // resize taps per source size (built on the host at first use): idx0 | idx1 [out] ints, lam [out] floats, one allocation each
   struct ResizeTab { int S, out; int* idx; float* lam; };
   std::vector<ResizeTab> tabs;
+};
+
+// SqueezeNet 1.1 features + the seven `lin` layers of LPIPS (pnpi_lpips_attach; torchvision squeezenet1_1, richzhang/PerceptualSimilarity).
+struct FireW { ConvW squeeze, expand1, expand3; };
+struct LpipsW : TowerW {
+  int max_pairs = 0;                      // max_images = 2 * max_pairs
+  half_t* w0 = nullptr; float* b0 = nullptr;   // features.0: [64][27] in (ky, kx, c) columns, [64]
+  FireW fire[8];                          // features.3, 4, 6, 7, 9, 10, 11, 12
+  float* lin[7] = {};                     // lin0 .. lin6 [C_k]
+  int sized_S = 0;                        // the workspaces hold a forward of max_images images of this side (grown on demand)
 };
 
 struct Tensor4 { half_t* p; int B, H, W, C; };
@@ -286,6 +299,8 @@ struct pnpi_ctx {
   ClipVisionW* cv = nullptr;   // pnpi_clipv_attach; nullptr: no image tower
   DinoW* dino = nullptr;       // pnpi_dino_attach; nullptr: no DINO ViT
   float* ss_ws = nullptr; size_t ss_ws_floats = 0;   // norms and partial sums of the self-similarity distance (grown on demand)
+  LpipsW* lpips = nullptr;     // pnpi_lpips_attach; nullptr: no LPIPS network
+  float* lp_ws = nullptr; size_t lp_ws_floats = 0;   // per-workgroup partial sums of the LPIPS tap distance (grown on demand)
   int* rows_ident = nullptr;  // [max(max_rows, 8)][4] identity attention-row table (text encoder)
   int rows_ident_n = 0;
   std::vector<float> ac;

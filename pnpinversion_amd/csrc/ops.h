@@ -149,6 +149,23 @@ int launch_keys_selfsim_mse(const half_t* keys_a, const half_t* keys_b, int n, i
                             hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
+// LPIPS, SqueezeNet (lpips.hip): the first convolution with the metric's preprocessing, ceil-mode max pool, ReLU, the fused tap distance
+// ---------------------------------------------------------------------------------------------------------------
+// img u8 [n][S][S][3] (* mask [n][S][S] 0 / 1, nullable) -> ((u8 / 255) * mask) * 2 - 1 -> (x - shift) / scale -> 3 x 3 stride-2
+// convolution (w fp16 [64][27], (ky, kx, c) columns; bias fp32 [64]; fp32 accumulation) -> ReLU -> out fp16 [n][Ho][Ho][64]
+int lpips_conv1_out(int S);                 // Ho = (S - 3) / 2 + 1
+int launch_lpips_conv1(const uint8_t* img, const uint8_t* mask, int n, int S, const half_t* w, const float* bias, half_t* out, hipStream_t st);
+// MaxPool2d(3, stride 2, ceil_mode = True) on fp16 NHWC [n][H][H][C] -> [n][Ho][Ho][C]; C % 8 == 0, 16-byte aligned; H >= 2
+int maxpool3s2_ceil_out(int H);             // 0: no valid window
+int launch_maxpool3s2_ceil(const half_t* x, int n, int H, int C, half_t* out, hipStream_t st);
+int launch_relu_f16(half_t* x, size_t n, hipStream_t st);      // in place; n % 8 == 0, x 16-byte aligned
+// out[p] (+)= mean over HW of sum_c w_c (a_c / sqrt(1e-8 + |a|^2) - b_c / sqrt(1e-8 + |b|^2))^2; a, b fp16 [n][HW][C],
+// C % 8 == 0, 16-byte aligned; w fp32 [C]; scratch: lpips_layer_scratch_floats(n, HW) floats.  Fixed reduction order, no atomics.
+size_t lpips_layer_scratch_floats(int n, int HW);
+int launch_lpips_layer(const half_t* a, const half_t* b, const float* w, int n, int HW, int C, float* scratch, float* out, int accumulate,
+                       hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------------------
 // Attention
 // ---------------------------------------------------------------------------------------------------------------
 // Key order of a "permuted" V^T (GemmP::vt_perm16 / AttnP::vt_perm): inside every aligned group of 16 tokens the two middle quads are

@@ -180,13 +180,15 @@ class NativeEngine:
         return t.to(device=self.device, dtype=torch.float32).contiguous()
 
     # ---- weights
-    def load_state_dict(self, unet_sd=None, vae_sd=None, chunk_bytes=1 << 30, clip_sd=None, clipv_sd=None, dino_sd=None):
+    def load_state_dict(self, unet_sd=None, vae_sd=None, chunk_bytes=1 << 30, clip_sd=None, clipv_sd=None, dino_sd=None, lpips_sd=None):
         """diffusers-layout state dicts (CPU or GPU tensors, fp32 or fp16); repacked on the device into the fp16 arena.
         clip_sd: transformers CLIPTextModel state dict (optional; only pnpi_text_encode needs it).
         clipv_sd: transformers CLIPModel keys of the image tower and the two projections (after clipv_attach; see load_clipv_state_dict).
-        dino_sd: facebookresearch/dino VisionTransformer keys (after dino_attach; see load_dino_state_dict)."""
+        dino_sd: facebookresearch/dino VisionTransformer keys (after dino_attach; see load_dino_state_dict).
+        lpips_sd: squeezenet1_1 features.* keys and lin{k}.weight (after lpips_attach; see load_lpips_state_dict)."""
         items = []
-        for prefix, sd in (("unet.", unet_sd), ("vae.", vae_sd), ("clip.", clip_sd), ("clipv.", clipv_sd), ("dino.", dino_sd)):
+        for prefix, sd in (("unet.", unet_sd), ("vae.", vae_sd), ("clip.", clip_sd), ("clipv.", clipv_sd), ("dino.", dino_sd),
+                           ("lpips.", lpips_sd)):
             if sd:
                 items += [(prefix + k, v) for k, v in sd.items()]
         batch, keep, size = [], [], 0
@@ -502,6 +504,69 @@ class NativeEngine:
         sim = torch.empty(n, T, T, device=self.device) if want_map else None
         self._call("pnpi_op_keys_selfsim_mse", _p(ka), _p(kb), n, T, D, _p(dist), _p(sim))
         return dist, sim
+
+    # ---- LPIPS (pnpi_lpips_attach and the entry points behind it; lpips.Lpips is the user-facing object)
+    def lpips_attach(self, max_pairs=4):
+        """Attach SqueezeNet 1.1's features and the seven lin layers for up to max_pairs image pairs (2 * max_pairs images) per call."""
+        self._call("pnpi_lpips_attach", int(max_pairs))
+        self.lpips_max_pairs = int(max_pairs)
+
+    def load_lpips_state_dict(self, sd):
+        """torchvision's squeezenet1_1 keys (features.*) and lin{k}.weight (checkpoint.load_lpips_checkpoint, weights.lpips_state_dict)"""
+        self.load_state_dict(lpips_sd=dict(sd))
+
+    @staticmethod
+    def lpips_tap_shape(S, tap):
+        """(map side, channels) of tap 0 .. 6 at image side S: the stride-2 convolution, then ceil-mode 3 x 3 stride-2 pools"""
+        def pool(h):
+            o = (h - 2) // 2 + 1
+            return o - 1 if (o - 1) * 2 >= h else o
+        h = (S - 3) // 2 + 1
+        sides = [h]
+        for _ in range(3):
+            h = pool(h)
+            sides.append(h)
+        from .weights import LPIPS_TAP_CHANNELS
+        return sides[min(tap, 3)], LPIPS_TAP_CHANNELS[tap]
+
+    def lpips_features(self, images, masks=None, tap=0):
+        """-> fp32 [n, H, H, C]: the feature map of tap 0 .. 6 (the outputs of features 1, 4, 7, 9, 10, 11, 12), NHWC"""
+        img, m = self._tower_images(images, masks)
+        H, Cc = self.lpips_tap_shape(img.shape[1], int(tap))
+        out = torch.empty(img.shape[0], H, H, Cc, device=self.device)
+        self._call("pnpi_lpips_features", _p(img), _p(m), img.shape[0], img.shape[1], int(tap), _p(out))
+        return out
+
+    def lpips(self, pred, gt, mask_pred=None, mask_gt=None):
+        """-> fp32 [n]: calculate_lpips per pair, one pass of the network over the 2 n images"""
+        a, ma = self._tower_images(pred, mask_pred)
+        b, mb = self._tower_images(gt, mask_gt)
+        if a.shape != b.shape:
+            raise ValueError("Image shapes should be the same: %s and %s" % (tuple(a.shape), tuple(b.shape)))
+        out = torch.empty(a.shape[0], device=self.device)
+        self._call("pnpi_lpips", _p(a), _p(ma), _p(b), _p(mb), a.shape[0], a.shape[1], _p(out))
+        return out
+
+    def lpips_layer(self, feat_a, feat_b, w):
+        """pnpi_op_lpips_layer on fp16 [n, HW, C] feature maps and fp32 [C] weights -> fp32 [n]"""
+        fa = torch.as_tensor(feat_a).to(self.device, dtype=torch.float16).contiguous()
+        fb = torch.as_tensor(feat_b).to(self.device, dtype=torch.float16).contiguous()
+        wv = self._f32(torch.as_tensor(w))
+        if fa.dim() != 3 or fa.shape != fb.shape or tuple(wv.shape) != (fa.shape[2],):
+            raise ValueError("features must be two [n, HW, C] tensors of one shape and w [C]")
+        out = torch.empty(fa.shape[0], device=self.device)
+        self._call("pnpi_op_lpips_layer", _p(fa), _p(fb), _p(wv), fa.shape[0], fa.shape[1], fa.shape[2], _p(out))
+        return out
+
+    def maxpool3s2_ceil(self, x):
+        """pnpi_op_maxpool3s2_ceil on fp16 NHWC [n, H, H, C] -> fp16 [n, Ho, Ho, C]"""
+        x = torch.as_tensor(x).to(self.device, dtype=torch.float16).contiguous()
+        n, H, _, Cc = x.shape
+        Ho = (H - 2) // 2 + 1
+        Ho -= (Ho - 1) * 2 >= H
+        out = torch.empty(n, Ho, Ho, Cc, dtype=torch.float16, device=self.device)
+        self._call("pnpi_op_maxpool3s2_ceil", _p(x), n, H, Cc, _p(out))
+        return out
 
     def local_blend(self, latents, step_index):
         lat = self._f32(latents)

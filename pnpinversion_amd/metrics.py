@@ -118,3 +118,14 @@ def calculate_structure_distance(img_pred, img_gt, mask_pred=None, mask_gt=None,
     if a.shape != b.shape:
         raise ValueError("Image shapes should be the same.")
     return float(scorer.distance(a[None], b[None], [mask_pred], [mask_gt])[0].item())
+
+
+def calculate_lpips(img_pred, img_gt, mask_pred=None, mask_gt=None, *, scorer):
+    """matrics_calculator.py:324-342: SqueezeNet LPIPS between img_pred * mask_pred and img_gt * mask_gt (each / 255, masked, * 2 - 1),
+    on the device.  scorer: lpips.Lpips (the reference holds its torchmetrics object in the calculator; here the caller passes the
+    scorer).  Masks: None, [S, S] or the [S, S, 3] repeat evaluate.py builds, values 0 / 1."""
+    from .image_batches import rgb
+    a, b = rgb(img_pred), rgb(img_gt)
+    if a.shape != b.shape:
+        raise ValueError("Image shapes should be the same.")
+    return float(scorer.score(a[None], b[None], [mask_pred], [mask_gt])[0].item())

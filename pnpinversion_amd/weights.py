@@ -247,3 +247,29 @@ def dino_state_dict(image_size=224, patch=8, width=768, layers=12, heads=12, int
         _lin(sd, seed, pre + ".mlp.fc2", intermediate, width, gain=0.5)
     _norm(sd, seed, "norm", width)
     return sd
+
+
+# squeezenet1_1().features' Fire blocks: (index, in, squeeze, expand) -- each of expand1x1 / expand3x3 gives `expand` channels
+LPIPS_FIRES = ((3, 64, 16, 64), (4, 128, 16, 64), (6, 128, 32, 128), (7, 256, 32, 128), (9, 256, 48, 192), (10, 384, 48, 192),
+               (11, 384, 64, 256), (12, 512, 64, 256))
+LPIPS_TAP_CHANNELS = (64, 128, 256, 384, 384, 512, 512)       # the outputs of features 1, 4, 7, 9, 10, 11, 12
+
+
+def lpips_state_dict(seed=0):
+    """What lpips.Lpips.load_state_dict takes: torchvision's squeezenet1_1 keys (features.0.*, features.N.{squeeze, expand1x1,
+    expand3x3}.*) and the lpips package's lin layers as lin{k}.weight [1, C, 1, 1], seeded and fp16-representable -- neither file exists
+    offline.  The convolutions are He-scaled (variance 2 / fan_in) so that the ReLU activations neither die nor leave fp16's range over
+    the 17 layers; features.0 sees the ScalingLayer's output (|x| up to 2.7).  The lin weights are non-negative, as the trained ones
+    are (the kernel does not assume it)."""
+    sd = {}
+    he = float(np.sqrt(2.0))
+    _conv(sd, seed, "features.0", 3, 64, 3, gain=he)
+    for idx, cin, sq, ex in LPIPS_FIRES:
+        pre = "features.%d" % idx
+        _conv(sd, seed, pre + ".squeeze", cin, sq, 1, gain=he)
+        _conv(sd, seed, pre + ".expand1x1", sq, ex, 1, gain=he)
+        _conv(sd, seed, pre + ".expand3x3", sq, ex, 3, gain=he)
+    for k, ch in enumerate(LPIPS_TAP_CHANNELS):
+        a = _gen(seed, "lpips.lin%d" % k).uniform(0.0, 1.0, size=(1, ch, 1, 1)).astype(np.float32)
+        sd["lin%d.weight" % k] = torch.from_numpy(_fp16_round(a))
+    return sd
