@@ -81,7 +81,7 @@ def calculate_ssim(img_pred, img_gt, mask_pred=None, mask_gt=None, kernel_size=1
 def panel_report(panel, mask=None):
     """Metrics of one 4-panel output image (instruction | source | reconstruction | edit, each S x S; evaluation/evaluate.py:268-273
     crops the same columns): reconstruction vs source (what an inversion method is judged on), edit vs source on the whole image and,
-    with the PIE-Bench mask (1 = edited region, run_editing_p2p.mask_decode), on the unedited part."""
+    with the PIE-Bench mask (1 = edited region, sweep.mask_decode), on the unedited part."""
     p = np.asarray(panel)
     S = p.shape[0]
     src, rec, edit = p[:, S:2 * S], p[:, 2 * S:3 * S], p[:, 3 * S:4 * S]

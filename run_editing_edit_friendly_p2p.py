@@ -10,18 +10,15 @@ The reference also runs a target-prompt reconstruction pass (:86-89) whose decod
 --batch_size N runs N images per set of launches (pnpi_ef_invert / pnpi_ef_edit with N images); every image gets the noise its sequential
 run would draw -- after setup_seed(1234) the same stream for each."""
 import argparse
-import json
-import os
-import random
 
 import numpy as np
 import torch
 from PIL import Image
 
-from pnpinversion_amd.checkpoint import add_weight_args, resolve_weights
-from pnpinversion_amd.distributed import broadcast_weights, prepare_env, shard_items
+from pnpinversion_amd import sweep
 from pnpinversion_amd.edit_friendly_ddm import inversion_utils as iu
 from pnpinversion_amd.edit_friendly_ddm.ptp_classes import AttentionRefine, AttentionReplace
+from pnpinversion_amd.sweep import mask_decode, setup_seed  # noqa: F401  (mask_decode: part of the reference script's surface, :19-35)
 from pnpinversion_amd.utils.utils import image2latent, latent2image, load_512, txt_draw
 
 image_save_paths = {
@@ -31,26 +28,6 @@ NUM_DDIM_STEPS = 50
 ETA = 1
 SKIP = 12
 ldm_stable = None          # the NativePipeline of main(); edit_image_EF's default
-
-
-def mask_decode(encoded_mask, image_shape=(512, 512)):
-    """run_editing_edit_friendly_p2p.py:19-35"""
-    n = image_shape[0] * image_shape[1]
-    mask = np.zeros(n)
-    runs = np.asarray(encoded_mask, dtype=np.int64).reshape(-1, 2)
-    for start, length in runs:
-        mask[start:start + min(length, n - start)] = 1
-    mask = mask.reshape(image_shape)
-    mask[0, :] = mask[-1, :] = 1
-    mask[:, 0] = mask[:, -1] = 1
-    return mask
-
-
-def setup_seed(seed=1234):
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed_all(seed)
-    np.random.seed(seed)
-    random.seed(seed)
 
 
 def controller_class(prompt_src, prompt_tar):
@@ -101,18 +78,10 @@ def edit_image_EF(edit_method, image_path, prompt_src, prompt_tar, source_guidan
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rerun_exist_images", action="store_true")
-    ap.add_argument("--data_path", type=str, default="data")
-    ap.add_argument("--output_path", type=str, default="output")
-    ap.add_argument("--edit_category_list", nargs="+", type=str, default=[str(i) for i in range(10)])
-    ap.add_argument("--edit_method_list", nargs="+", type=str, default=["edit-friendly-inversion+p2p"])
+    sweep.add_sweep_args(ap, ["edit-friendly-inversion+p2p"])
     ap.add_argument("--batch_size", type=int, default=1, help="images per set of launches and GPU (not in the reference: it edits one by one)")
-    ap.add_argument("--model_config", choices=("sd1", "small64"), default="sd1", help="small64: reduced-width test configuration")
-    add_weight_args(ap)
     args = ap.parse_args(argv)
-    unknown = [m for m in args.edit_method_list if m not in image_save_paths]
-    if unknown:
-        ap.error("unknown edit method(s) %s; this script runs %s" % (unknown, list(image_save_paths)))
+    sweep.check_methods(ap, args, image_save_paths)
     if args.batch_size < 1:
         ap.error("--batch_size must be >= 1")
     return args
@@ -121,54 +90,25 @@ def parse_args(argv=None):
 def main(argv=None):
     global ldm_stable
     args = parse_args(argv)
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    prepare_env()
-    torch.cuda.set_device(local_rank)
-    if world > 1:
-        import torch.distributed as dist
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     from pnpinversion_amd.config import SD1, SMALL64
     from pnpinversion_amd.pipeline import NativePipeline
-    cfg = SD1 if args.model_config == "sd1" else SMALL64
-    unet_sd, vae_sd, clip_sd, tokenizer = resolve_weights(args, cfg, rank)
-    pipe = NativePipeline(cfg, device="cuda:%d" % local_rank, max_unet_rows=4 * args.batch_size, text_encoder="native", tokenizer=tokenizer)
-    if rank == 0:
-        pipe.load_state_dict(unet_sd, vae_sd, clip_sd=clip_sd)
-    if world > 1:
-        broadcast_weights(pipe.engine, src=0)
-    ldm_stable = pipe
-
-    with open(os.path.join(args.data_path, "mapping_file.json")) as f:
-        instructions = json.load(f)
-    work = [(k, v) for k, v in instructions.items() if v["editing_type_id"] in args.edit_category_list]
-    mine = list(shard_items(work, rank, world))
-    for method in args.edit_method_list:
-        todo = []
-        for key, item in mine:
-            src = item["original_prompt"].replace("[", "").replace("]", "")
-            tgt = item["editing_prompt"].replace("[", "").replace("]", "")
-            image_path = os.path.join(args.data_path, "annotation_images", item["image_path"])
-            _ = Image.fromarray(np.uint8(mask_decode(item["mask"])[:, :, None].repeat(3, 2))).convert("L")   # unused, as in the reference
-            out_path = image_path.replace(args.data_path, os.path.join(args.output_path, image_save_paths[method]))
-            if os.path.exists(out_path) and not args.rerun_exist_images:
-                print(f"skip image [{image_path}] with [{method}]")
-                continue
-            todo.append((src, tgt, image_path, out_path))
-        for b0 in range(0, len(todo), args.batch_size):
-            chunk = todo[b0:b0 + args.batch_size]
-            for c in chunk:
-                print(f"editing image [{c[2]}] with [{method}]")
-            setup_seed()
-            panels = edit_images_EF(pipe, [c[2] for c in chunk], [c[0] for c in chunk], [c[1] for c in chunk], source_guidance_scale=1,
-                                    target_guidance_scale=7.5, cross_replace_steps=0.4, self_replace_steps=0.6)
-            for panel, c in zip(panels, chunk):
-                os.makedirs(os.path.dirname(c[3]), exist_ok=True)
-                panel.save(c[3])
-                print("finish")
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    make_pipeline = lambda cfg, device, tokenizer: NativePipeline(cfg, device=device, max_unet_rows=4 * args.batch_size,       # noqa: E731
+                                                                  text_encoder="native", tokenizer=tokenizer)
+    with sweep.session(args, {"sd1": SD1, "small64": SMALL64}, make_pipeline) as s:
+        ldm_stable = s.pipe
+        instructions = sweep.read_mapping(args)
+        for method in args.edit_method_list:
+            todo = sweep.plan(args, instructions, image_save_paths[method], s.rank, s.world, method=method)
+            for b0 in range(0, len(todo), args.batch_size):
+                chunk = todo[b0:b0 + args.batch_size]
+                for _, image_path, _ in chunk:
+                    print(f"editing image [{image_path}] with [{method}]")
+                setup_seed()
+                panels = edit_images_EF(s.pipe, [c[1] for c in chunk], [sweep.clean_prompt(c[0]["original_prompt"]) for c in chunk],
+                                        [sweep.clean_prompt(c[0]["editing_prompt"]) for c in chunk], source_guidance_scale=1,
+                                        target_guidance_scale=7.5, cross_replace_steps=0.4, self_replace_steps=0.6)
+                for panel, c in zip(panels, chunk):
+                    sweep.save_panel(panel, c[2])
 
 
 if __name__ == "__main__":

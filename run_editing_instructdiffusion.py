@@ -13,7 +13,7 @@ import argparse
 import importlib.util
 import os
 
-from pnpinversion_amd.checkpoint import add_weight_args
+from pnpinversion_amd import sweep
 
 
 def _sibling(name):
@@ -24,37 +24,29 @@ def _sibling(name):
     return module
 
 
-sweep = _sibling("run_editing_instructpix2pix")
+ip2p = _sibling("run_editing_instructpix2pix")
 
 image_save_paths = {
     "instruct-diffusion": "instruct-diffusion",
 }
 DEFAULT_CHECKPOINT = "data/checkpoints/v1-5-pruned-emaonly-adaption.ckpt"
 STEPS, CFG_TEXT, CFG_IMAGE = 50, 5.0, 1.25
-assert all(sweep.image_save_paths[m] == folder for m, folder in image_save_paths.items())      # the shared work plan writes to these folders
-plan_work, load_weights = sweep.plan_work, sweep.load_weights
+assert all(ip2p.image_save_paths[m] == folder for m, folder in image_save_paths.items())       # the shared work plan writes to these folders
+plan_work, load_weights = ip2p.plan_work, ip2p.load_weights
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rerun_exist_images", action="store_true")
-    ap.add_argument("--data_path", type=str, default="data")
-    ap.add_argument("--output_path", type=str, default="output")
-    ap.add_argument("--edit_category_list", nargs="+", type=str, default=[str(i) for i in range(10)])
-    ap.add_argument("--edit_method_list", nargs="+", type=str, default=["instruct-diffusion"])
+    sweep.add_sweep_args(ap, ["instruct-diffusion"])
     ap.add_argument("--checkpoint", type=str, default=DEFAULT_CHECKPOINT, help="CompVis-layout .ckpt, as the reference loads it")
     ap.add_argument("--tokenizer_dir", type=str, default=None, help="vocab.json / merges.txt for --checkpoint (a .ckpt holds no vocabulary)")
-    ap.add_argument("--model_config", choices=("sd1", "small64"), default="sd1", help="small64: reduced-width test configuration")
-    add_weight_args(ap)
     args = ap.parse_args(argv)
-    unknown = [m for m in args.edit_method_list if m not in image_save_paths]
-    if unknown:
-        ap.error("unknown edit method(s) %s; this script runs %s" % (unknown, list(image_save_paths)))
+    sweep.check_methods(ap, args, image_save_paths)
     return args
 
 
 def main(argv=None):
-    sweep.main(argv, parse=parse_args, editor_name="InstructDiffusion", scales=(STEPS, CFG_TEXT, CFG_IMAGE))
+    ip2p.main(argv, parse=parse_args, editor_name="InstructDiffusion", scales=(STEPS, CFG_TEXT, CFG_IMAGE))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,6 @@
 mutual-self-attention sampling loop are device-resident libpnpi loops; the attention editor is a kernel-side row table.  Under
 torch.distributed.run the work list is sharded over the ranks exactly like run_editing_p2p.py."""
 import argparse
-import json
 import os
 
 import numpy as np
@@ -16,8 +15,9 @@ from pnpinversion_amd.masactrl.diffuser_utils import MasaCtrlPipeline
 from pnpinversion_amd.masactrl.masactrl import MutualSelfAttentionControl, MutualSelfAttentionControlMask
 from pnpinversion_amd.masactrl.masactrl_utils import AttentionBase, regiter_attention_editor_diffusers
 from pnpinversion_amd.p2p.inversion import DirectInversion
+from pnpinversion_amd import sweep
+from pnpinversion_amd.sweep import mask_decode, setup_seed  # noqa: F401  (same helpers as the reference's copy, :21-46)
 from pnpinversion_amd.utils.utils import load_512, txt_draw
-from run_editing_p2p import mask_decode, setup_seed  # noqa: F401  (same helpers as the reference's copy, :21-46)
 
 
 def load_image(image_path, device):
@@ -113,70 +113,43 @@ def latent_mask(rle, side=64):
     return (np.array(m) > 127).astype(np.uint8)
 
 
+def output_folder(method, mask_guided):
+    """<method> as in the reference; --mask_guided runs go to <method>-mask"""
+    return method + ("-mask" if mask_guided else "")
+
+
 def output_dir(output_path, method, mask_guided):
-    """output/<method> as in the reference; --mask_guided runs go to output/<method>-mask"""
-    return os.path.join(output_path, method + ("-mask" if mask_guided else ""))
+    return os.path.join(output_path, output_folder(method, mask_guided))
 
 
 def build_parser():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rerun_exist_images", action="store_true")
-    ap.add_argument("--data_path", type=str, default="data")
-    ap.add_argument("--output_path", type=str, default="output")
-    ap.add_argument("--edit_category_list", nargs="+", type=str, default=[str(i) for i in range(10)])
-    ap.add_argument("--edit_method_list", nargs="+", type=str, default=["ddim+masactrl", "directinversion+masactrl"])
-    ap.add_argument("--model_config", choices=("sd1", "small64"), default="sd1", help="small64: reduced-width test configuration")
+    sweep.add_sweep_args(ap, ["ddim+masactrl", "directinversion+masactrl"])
     ap.add_argument("--num_ddim_steps", type=int, default=50)
     ap.add_argument("--mask_guided", action="store_true",
                     help="mask-guided MasaCtrl (MutualSelfAttentionControlMask): the item's PIE-Bench mask at 64 x 64 is source and target "
                          "mask; outputs go to <method>-mask.  Not an option of the reference's script.")
-    from pnpinversion_amd.checkpoint import add_weight_args
-    add_weight_args(ap)
     return ap
 
 
 def main(argv=None):
-    from pnpinversion_amd.checkpoint import resolve_weights
     args = build_parser().parse_args(argv)
-    from pnpinversion_amd.distributed import broadcast_weights, shard_items
     from pnpinversion_amd.config import SD1, SMALL64
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local_rank)
-    if world > 1:
-        import torch.distributed as dist
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    cfg = SD1 if args.model_config == "sd1" else SMALL64
-    unet_sd, vae_sd, clip_sd, tokenizer = resolve_weights(args, cfg, rank)     # --checkpoint_dir | --synthetic_weights (loud)
-    pipe = MasaCtrlPipeline(cfg, device="cuda:%d" % local_rank, text_encoder="native", tokenizer=tokenizer)
-    if rank == 0:
-        pipe.load_state_dict(unet_sd, vae_sd, clip_sd=clip_sd)
-    if world > 1:
-        broadcast_weights(pipe.engine, src=0)
-    editor = MasaCtrlEditor(args.edit_method_list, torch.device("cuda", local_rank), num_ddim_steps=args.num_ddim_steps, pipeline=pipe)
-    with open(os.path.join(args.data_path, "mapping_file.json")) as f:
-        instructions = json.load(f)
-    work = [(k, v) for k, v in instructions.items() if v["editing_type_id"] in args.edit_category_list]
-    for key, item in shard_items(work, rank, world):
-        src = item["original_prompt"].replace("[", "").replace("]", "")
-        tgt = item["editing_prompt"].replace("[", "").replace("]", "")
-        image_path = os.path.join(args.data_path, "annotation_images", item["image_path"])
-        for method in args.edit_method_list:
-            out_path = image_path.replace(args.data_path, output_dir(args.output_path, method, args.mask_guided))
-            if os.path.exists(out_path) and not args.rerun_exist_images:
-                print(f"skip image [{image_path}] with [{method}]")
-                continue
-            print(f"editing image [{image_path}] with [{method}]")
-            setup_seed()
-            torch.cuda.empty_cache()
-            kw = dict(mask=latent_mask(item["mask"], cfg.sample_size)) if args.mask_guided else {}
-            edited = editor(method, image_path=image_path, prompt_src=src, prompt_tar=tgt, guidance_scale=7.5, step=4, layper=10, **kw)
-            os.makedirs(os.path.dirname(out_path), exist_ok=True)
-            edited.save(out_path)
-            print("finish")
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    make_pipeline = lambda cfg, device, tokenizer: MasaCtrlPipeline(cfg, device=device, text_encoder="native", tokenizer=tokenizer)  # noqa: E731
+    with sweep.session(args, {"sd1": SD1, "small64": SMALL64}, make_pipeline) as s:
+        editor = MasaCtrlEditor(args.edit_method_list, s.device, num_ddim_steps=args.num_ddim_steps, pipeline=s.pipe)
+        for item, image_path in sweep.shard(args, sweep.read_mapping(args), s.rank, s.world):     # images outside, methods inside
+            for method in args.edit_method_list:
+                out_path = sweep.pending(args, image_path, output_folder(method, args.mask_guided), method=method)
+                if out_path is None:
+                    continue
+                print(f"editing image [{image_path}] with [{method}]")
+                setup_seed()
+                torch.cuda.empty_cache()
+                kw = dict(mask=latent_mask(item["mask"], s.cfg.sample_size)) if args.mask_guided else {}
+                edited = editor(method, image_path=image_path, prompt_src=sweep.clean_prompt(item["original_prompt"]),
+                                prompt_tar=sweep.clean_prompt(item["editing_prompt"]), guidance_scale=7.5, step=4, layper=10, **kw)
+                sweep.save_panel(edited, out_path)
 
 
 if __name__ == "__main__":

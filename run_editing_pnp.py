@@ -9,16 +9,12 @@ reconstruction latents (ddim+pnp): guidance 7.5, feature injection on the first 
 Panel [instruction, source image, reconstruction, edit]; for ddim+pnp the third column is the decoded DDIM reconstruction, for
 directinversion+pnp it is latent2image(inverted_x[1]), as in the reference."""
 import argparse
-import json
-import os
 
 import numpy as np
-import torch
 from PIL import Image
 
-from pnpinversion_amd.checkpoint import add_weight_args, resolve_weights
-from pnpinversion_amd.distributed import broadcast_weights, prepare_env, shard_items
-from run_editing_p2p import mask_decode, setup_seed  # noqa: F401  (mask_decode: part of the reference script's surface)
+from pnpinversion_amd import sweep
+from pnpinversion_amd.sweep import mask_decode, setup_seed  # noqa: F401  (mask_decode: part of the reference script's surface)
 
 image_save_paths = {
     "ddim+pnp": "ddim+pnp",
@@ -29,35 +25,17 @@ NUM_DDIM_STEPS = 50
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rerun_exist_images", action="store_true")
-    ap.add_argument("--data_path", type=str, default="data")
-    ap.add_argument("--output_path", type=str, default="output")
-    ap.add_argument("--edit_category_list", nargs="+", type=str, default=[str(i) for i in range(10)])
-    ap.add_argument("--edit_method_list", nargs="+", type=str, default=["ddim+pnp", "directinversion+pnp"])
-    ap.add_argument("--model_config", choices=("sd1", "small64"), default="sd1", help="small64: reduced-width test configuration")
-    add_weight_args(ap)
+    sweep.add_sweep_args(ap, ["ddim+pnp", "directinversion+pnp"])
     args = ap.parse_args(argv)
-    unknown = [m for m in args.edit_method_list if m not in image_save_paths]
-    if unknown:
-        ap.error("unknown edit method(s) %s; this script runs %s" % (unknown, list(image_save_paths)))
+    sweep.check_methods(ap, args, image_save_paths)
     return args
 
 
 def plan_work(args, instructions, method, rank=0, world=1, log=print):
     """This rank's share of the mapping file for `method`, without what is already on disk (:507-521 + round-robin sharding)
     -> [(original_prompt, editing_prompt, image_path, out_path)]"""
-    work = [(k, v) for k, v in instructions.items() if v["editing_type_id"] in args.edit_category_list]
-    todo = []
-    for key, item in shard_items(work, rank, world):
-        original_prompt = item["original_prompt"].replace("[", "").replace("]", "")
-        editing_prompt = item["editing_prompt"].replace("[", "").replace("]", "")
-        image_path = os.path.join(args.data_path, "annotation_images", item["image_path"])
-        out_path = image_path.replace(args.data_path, os.path.join(args.output_path, image_save_paths[method]))
-        if os.path.exists(out_path) and not args.rerun_exist_images:
-            log(f"skip image [{image_path}] with [{method}]")
-            continue
-        todo.append((original_prompt, editing_prompt, image_path, out_path))
-    return todo
+    return [(sweep.clean_prompt(item["original_prompt"]), sweep.clean_prompt(item["editing_prompt"]), image_path, out_path)
+            for item, image_path, out_path in sweep.plan(args, instructions, image_save_paths[method], rank, world, log, method)]
 
 
 def _u8(img01):
@@ -88,40 +66,22 @@ def edit_image_directinversion_PnP(model, pnp, image_path, prompt_src, prompt_ta
 
 def main(argv=None):
     args = parse_args(argv)
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    prepare_env()
-    torch.cuda.set_device(local_rank)
-    if world > 1:
-        import torch.distributed as dist
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     from pnpinversion_amd.config import SD1, SMALL64
     from pnpinversion_amd.pipeline import NativePipeline
     from pnpinversion_amd.pnp import PNP, Preprocess
-    cfg = SD1 if args.model_config == "sd1" else SMALL64
-    unet_sd, vae_sd, clip_sd, tokenizer = resolve_weights(args, cfg, rank)
-    pipe = NativePipeline(cfg, device="cuda:%d" % local_rank, max_unet_rows=3, text_encoder="native", tokenizer=tokenizer)
-    if rank == 0:
-        pipe.load_state_dict(unet_sd, vae_sd, clip_sd=clip_sd)
-    if world > 1:
-        broadcast_weights(pipe.engine, src=0)
-    model = Preprocess(pipe=pipe)
-    pnp = PNP(pipe=pipe, n_timesteps=NUM_DDIM_STEPS)
-
-    with open(os.path.join(args.data_path, "mapping_file.json")) as f:
-        instructions = json.load(f)
-    for method in args.edit_method_list:
-        for prompt_src, prompt_tar, image_path, out_path in plan_work(args, instructions, method, rank, world):
-            print(f"editing image [{image_path}] with [{method}]")
-            setup_seed()
-            fn = edit_image_ddim_PnP if method == "ddim+pnp" else edit_image_directinversion_PnP
-            edited_image = fn(model, pnp, image_path=image_path, prompt_src=prompt_src, prompt_tar=prompt_tar, guidance_scale=7.5)
-            os.makedirs(os.path.dirname(out_path), exist_ok=True)
-            edited_image.save(out_path)
-            print("finish")
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    make_pipeline = lambda cfg, device, tokenizer: NativePipeline(cfg, device=device, max_unet_rows=3, text_encoder="native",   # noqa: E731
+                                                                  tokenizer=tokenizer)
+    with sweep.session(args, {"sd1": SD1, "small64": SMALL64}, make_pipeline) as s:
+        model = Preprocess(pipe=s.pipe)
+        pnp = PNP(pipe=s.pipe, n_timesteps=NUM_DDIM_STEPS)
+        instructions = sweep.read_mapping(args)
+        for method in args.edit_method_list:
+            for prompt_src, prompt_tar, image_path, out_path in plan_work(args, instructions, method, s.rank, s.world):
+                print(f"editing image [{image_path}] with [{method}]")
+                setup_seed()
+                fn = edit_image_ddim_PnP if method == "ddim+pnp" else edit_image_directinversion_PnP
+                edited_image = fn(model, pnp, image_path=image_path, prompt_src=prompt_src, prompt_tar=prompt_tar, guidance_scale=7.5)
+                sweep.save_panel(edited_image, out_path)
 
 
 if __name__ == "__main__":
